@@ -28,7 +28,8 @@ One step = one full pass of the hot path over the rank's shard, everything on th
        every rank's embeddings requires, at world x the head work per rank.
 value = subgraphs processed by all ranks / max-over-ranks step time.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE short JSON line on rank 0: metric, value, ms_per_step, config, roofline and cpu_baseline in brief (result_line).
+The full result object is written to --details (default bench_details.json) with these extra objects:
   roofline      the structure-channel CSR gather (sgnn_degree_sequence, the kernel BASELINE.json's target names) AS THE PASS RUNS
                 IT (lists of >= 512 entries answered from their membership bitmaps): the bytes that launch reads / its time inside the timed region, peak
                 8 TB/s; streaming_form beside it = the launch that moves SURVEY.md 8(d)'s algorithmic bytes (every neighbour list
@@ -42,6 +43,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with these extra
   cpu_baseline  the oracle (plain C + numpy + torch-CPU restatement of the same algorithm) timed on this box's host cores on a
                 bounded sample (rank 0, N = 1 only; Python stages on worker processes forked before the GPU is initialised), with
                 its calibration against the imported reference (profiles/r06_cpu_calibration.json; round 4: r04_cpu_calibration.json).
+--dump-outputs DIR writes what the last timed step computed (loss, accuracy, the updated parameters) as .npy files, so that
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -116,7 +119,81 @@ def parse():
                          'slower host: 3.4 ms against 2.5)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--cpu-sample', type=int, default=2048)
+    ap.add_argument('--details', metavar='FILE', default='bench_details.json',
+                    help='where the full result object goes (every measurement beside the headline); the stdout line keeps the '
+                         'headline fields only ("": not written)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step handed its caller to DIR/<name>.npy (float32 / '
+                         'float64): loss, accuracy and every parameter after its update -- tables larger than '
+                         'DUMP_SAMPLE_BYTES as a fixed seeded sample of rows, with their row numbers (rank 0 writes)')
     return ap.parse_args()
+
+
+DUMP_SAMPLE_BYTES = 32 << 20         # per sampled table; everything else is written whole (64 MB in all at most)
+DUMP_TOTAL_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, acc, model):
+    """The last timed step's results as .npy files: what a caller of the training step receives (loss, accuracy) and the
+    parameters it updated in place.  A parameter of more than DUMP_SAMPLE_BYTES keeps a sample of its rows drawn with a fixed
+    seed (same arguments -> same rows), written beside it as <name>.sample_rows (float64 row numbers)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {'loss': np.asarray([float(loss)], dtype=np.float64),
+              'accuracy': np.asarray([float(acc)], dtype=np.float64)}
+    for name, p in model.named_parameters():
+        t = p.detach()
+        if t.numel() * 4 > DUMP_SAMPLE_BYTES and t.dim() >= 2:
+            row_bytes = 4 * (t.numel() // t.shape[0])
+            k = min(t.shape[0], max(1, DUMP_SAMPLE_BYTES // row_bytes))
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], k, replace=False))
+            arrays['param.%s.sample_rows' % name] = rows.astype(np.float64)
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+        arrays['param.' + name] = t.float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_TOTAL_BYTES:
+        raise SystemExit('--dump-outputs: %d bytes exceed the %d-byte budget' % (total, DUMP_TOTAL_BYTES))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+# the stdout line: the headline and what the tests / tools read from it.  It stays short (a reader that keeps only the end of
+# the output must still get all of it) and strict JSON; the full result object goes to --details
+LINE_KEYS = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline',
+             'dtype', 'data', 'loss', 'priming_passes_before_warmup', 'first_pass_ms', 'second_pass_ms', 'sequential_ms_per_step',
+             'collectives', 'checksums')
+LINE_CONFIG_KEYS = ('workload', 'subgraphs_per_gpu', 'subgraphs_total', 'schedule')
+LINE_ROOFLINE_KEYS = ('kernel', 'bound', 'achieved', 'peak', 'unit', 'frac', 'traffic', 'algorithmic_bytes_per_launch', 'ms_per_launch')
+LINE_CPU_KEYS = ('value', 'unit', 'cores', 'kind', 'error')
+LINE_MAX_BYTES = 4096                # (without the opt-in SGNN_BENCH_CHECKSUMS lists)
+
+
+def _strict(o):
+    """JSON-safe copy: non-finite floats become null (json.dumps would write NaN / Infinity)."""
+    if isinstance(o, dict):
+        return {k: _strict(v) for k, v in o.items()}
+    if isinstance(o, (list, tuple)):
+        return [_strict(v) for v in o]
+    if isinstance(o, float) and not np.isfinite(o):
+        return None
+    return o
+
+
+def result_line(result, details=None):
+    """The one JSON line bench.py prints: the headline fields of ``result``, the structure-channel roofline and the CPU
+    baseline in short, and the name of the file that holds everything (``details``)."""
+    line = {k: result[k] for k in LINE_KEYS if k in result}
+    line['config'] = {k: result['config'][k] for k in LINE_CONFIG_KEYS if k in result.get('config', {})}
+    if result.get('roofline'):
+        line['roofline'] = {k: result['roofline'].get(k) for k in LINE_ROOFLINE_KEYS}
+    if result.get('cpu_baseline'):
+        cb = result['cpu_baseline']
+        line['cpu_baseline'] = {k: cb[k] for k in LINE_CPU_KEYS if k in cb}
+        if isinstance(cb.get('calibration'), dict):
+            line['cpu_baseline']['calibration_ratio'] = cb['calibration'].get('ratio')
+            line['cpu_baseline']['value_calibrated_to_reference'] = cb['calibration'].get('value_calibrated_to_reference')
+    if details:
+        line['details'] = details
+    return json.dumps(_strict(line), allow_nan=False)
 
 
 def build_inputs(args, rank, world):
@@ -625,6 +702,7 @@ def main():
 
     pipe = pipe_main = hotpath.PassPipeline(model, 'train', shard) if (pipelined and graphed is None) else None
     side_timers = []
+    last_acc = [None]                                            # the latest step's accuracy (--dump-outputs reads it)
 
     def step(timed, sequential=False):
         # ``sequential``: this step in the schedule N > 1 runs by default (the pass prepared after the previous one has trained)
@@ -632,7 +710,7 @@ def main():
         pipe = None if sequential else pipe_main
         if graphed is not None and not sequential:
             timer.mark('start')
-            loss, _acc = graphed.step()                          # two graph launches: this pass's training half, the next pass's preparation
+            loss, last_acc[0] = graphed.step()                   # two graph launches: this pass's training half, the next pass's preparation
             timer.mark('pass(hipGraphs: training half; the next preparation beside it)')
             return timer, loss
         if trainer is not None:
@@ -645,7 +723,7 @@ def main():
                 trainer.install(hotpath.prepare_pass(model, 'train', timer, shard), timer)
             installed = torch.cuda.Event()
             installed.record()
-            loss, _acc = trainer.step()                          # one graph launch: on the device before the host queues anything else
+            loss, last_acc[0] = trainer.step()                   # one graph launch: on the device before the host queues anything else
             timer.mark('training_half(hipGraph)' if not multi else 'forward+backward(hipGraph)')
             if multi:
                 multi_tail(timer)                                # gradient exchange + sharded optimizer: eager (collectives are not recorded),
@@ -668,6 +746,7 @@ def main():
         if replicated:
             batch['label'] = labels_dev                          # the head runs on the gathered global batch
         out = model.training_step(batch, 0)
+        last_acc[0] = out['log']['train_acc']
         timer.mark('forward')
         model.backward(None, out['loss'], None, 0)
         timer.mark('backward')
@@ -765,6 +844,8 @@ def main():
         lt = torch.tensor([loss], device=dev, dtype=torch.float64)
         dist.all_reduce(lt)
         loss = float(lt.item()) / world
+    if args.dump_outputs and rank == 0:                          # before anything below trains the model further
+        dump_outputs(args.dump_outputs, loss, last_acc[0], model)
     stage_n, stage_each = {}, {}
     for tm in timers + side_timers:                              # (passes prepared before the timed region carry no marks)
         for k, v in tm.summary().items():
@@ -1154,7 +1235,15 @@ def main():
                                'params': {k: _ck(p_) for k, p_ in model.named_parameters()},
                                'passes': [{'loss': _ck(l_), 'grads': {k: _ck(g_) for k, g_ in gr_.items()}} for l_, gr_ in kept_passes]}
     if rank == 0:
-        print(json.dumps(result))
+        details = args.details
+        if details:
+            try:
+                with open(details, 'w') as f:
+                    f.write(json.dumps(_strict(result), allow_nan=False) + '\n')
+            except OSError as ex:                    # the details must never hide the headline
+                print('--details: %s not written: %r' % (details, ex), file=sys.stderr)
+                details = None
+        print(result_line(result, details))
     if dist:
         dist.destroy_process_group()
 

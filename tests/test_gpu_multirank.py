@@ -35,6 +35,7 @@ def _bench(ranks, extra, no_dropout=False):
     r = subprocess.run(cmd + SIZE + extra, cwd=REPO, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (cmd + extra, r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith('{')][-1]
+    assert len(line.encode()) < 4096, len(line)                  # the one line must survive a reader that keeps only the end
     return json.loads(line)
 
 
