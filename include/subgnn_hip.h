@@ -844,6 +844,45 @@ int sgnn_reduce_partials(int64_t n_jobs, const float* const* part, const int64_t
                          float* const* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * a19  Node-embedding pre-training (reference prepare_dataset/train_node_emb.py:40-110, model.py:15-36, utils.py:22-56,
+ * preprocess.py:38-60): two graph convolutions over one-hot features -- so layer 1 aggregates a trainable (N, hidden) table --
+ * and link prediction on dot products, full-batch over the whole graph.  All fp32, deterministic, no float atomics.
+ *
+ * sgnn_ne_aggregate replaces PyG's GINConv / GCNConv propagate (model.py:20-27; PyG gcn_norm for the GCN weights):
+ *   out[v] = a_self[v] X[v] + sum_{e = rowptr[v] .. rowptr[v+1]} w[e] X[col[e]] (+ bias), v < n_rows, X and out (n_rows, F),
+ * then relu != 0: max(., 0), then drop_thr != 0: element (v, f) kept iff (draw64(seed, stream_id, v, f) >> 32) >= drop_thr and
+ * scaled by drop_scale, else 0 (model.py:33-34, F.dropout).  a_self / w / bias nullable (1, 1, none).  F a multiple of 4, at most
+ * 512 (else SGNN_ERR_UNSUPPORTED_D).  Rows longer than sgnn_ne_chunk_entries() entries are summed by chunks: the caller lists them
+ * as chunk items (chunk_row[c], first entry chunk_beg[c]; a row's chunks consecutive and in entry order) and as long rows
+ * (long_rows[r], chunks chunk_first[r] .. chunk_first[r+1]); partial holds n_chunks x F floats.  The backward (dX = A^T dOut) is
+ * the same call over the transposed CSR.
+ * sgnn_ne_relu_drop_bwd: dst = out > 0 ? grad * scale : 0 (dst may be grad) -- the gradient through relu -> dropout from the OUTPUT of
+ * that epilogue (an element passed both iff it is positive); n a multiple of 4.
+ * sgnn_ne_negatives replaces torch_geometric.utils.negative_sampling (train_node_emb.py:60,69): pair i takes the first attempt
+ * a < max_attempts of d = draw64(seed, stream_id, item_base + i, a), u = 1 + ((d >> 32) n_ids >> 32), v = 1 + ((d mod 2^32)
+ * n_ids >> 32) with u != v and v not in u's ascending adjacency row col_sorted[rowptr[u] .. rowptr[u+1]); (0, 0) when none is.
+ * sgnn_ne_link_loss replaces utils.el_dot + calc_loss_both (utils.py:22-56): for pairs p < n_pairs (label 1 for p < n_pos, else 0)
+ * s = sigmoid(Z[pu[p]] . Z[pv[p]]) -> s_out, d loss / d dot -> g_out (nullable), loss = mean of
+ * nll(log_softmax(stack(1 - s, s)), y) -> loss[0], reduced in a fixed order; workspace sgnn_ne_link_loss_workspace_bytes().
+ * sgnn_adam_step_l2 replaces torch.optim.Adam(lr, weight_decay) (train_node_emb.py:99): coupled L2 (g + wd p) on one float32
+ * buffer of any length n, 16-byte aligned; step = 1 for the first update.
+ * ------------------------------------------------------------------------------------- */
+int64_t sgnn_ne_chunk_entries(void);
+int sgnn_ne_aggregate(const int64_t* rowptr, const int32_t* col, const float* w, const float* a_self, const float* X,
+                      const float* bias, int64_t n_rows, int64_t F, const int32_t* chunk_row, const int64_t* chunk_beg,
+                      int64_t n_chunks, const int32_t* long_rows, const int64_t* chunk_first, int64_t n_long,
+                      int relu, uint32_t drop_thr, float drop_scale, uint64_t seed, uint64_t stream_id, float* out,
+                      float* partial, void* stream);
+int sgnn_ne_relu_drop_bwd(const float* grad, const float* out, float* dst, int64_t n, float scale, void* stream);
+int sgnn_ne_negatives(const int64_t* rowptr, const int32_t* col_sorted, int64_t n_ids, int64_t n, uint64_t seed,
+                      uint64_t stream_id, int64_t item_base, int max_attempts, int32_t* u_out, int32_t* v_out, void* stream);
+int64_t sgnn_ne_link_loss_workspace_bytes(void);
+int sgnn_ne_link_loss(const float* Z, int64_t F, const int32_t* pu, const int32_t* pv, int64_t n_pairs, int64_t n_pos,
+                      float* s_out, float* g_out, float* loss, void* workspace, int64_t workspace_bytes, void* stream);
+int sgnn_adam_step_l2(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                      float beta2, float eps, float weight_decay, int64_t step, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): streaming copy of n_bytes with 4 or 16 bytes per lane.
  * The rocprofv3 memory-side counters (FETCH_SIZE / WRITE_SIZE) are calibrated on it -- a known byte
  * count in the access width of the CSR gather -- before they are read as HBM traffic of

@@ -1123,8 +1123,10 @@ class SubGNN(nn.Module):
 def dataset_paths(task, embedding_type='gin'):
     """The seven dataset paths train_config.py derives from ``data.task`` (train_config.py:213-230)."""
     t = Path(task)
+    # train_config.py:229-230: the GraphSAINT-trained GCN table is graphsaint_gcn_embeddings.pth
+    emb = 'graphsaint_gcn' if embedding_type == 'graphsaint' else embedding_type
     return dict(graph_path=str(t / 'edge_list.txt'), subgraph_path=str(t / 'subgraphs.pth'),
-                embedding_path=str(t / ('%s_embeddings.pth' % embedding_type)),
+                embedding_path=str(t / ('%s_embeddings.pth' % emb)),
                 similarities_path=str(t / 'similarities/'), shortest_paths_path=str(t / 'shortest_path_matrix.npy'),
                 degree_dict_path=str(t / 'degree_sequence.txt'), ego_graph_path=str(t / 'ego_graphs.txt'))
 

@@ -177,6 +177,15 @@ SIGNATURES = {
     'sgnn_mpn_bwd_edges': (c_int, [ctypes.POINTER(MpnArgs), c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sgnn_mpn_bwd_edges_many': (c_int, [c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sgnn_mpn_bwd_wp_partial': (c_int, [ctypes.POINTER(MpnArgs), c_ptr, c_ptr, c_i64, c_ptr]),
+    'sgnn_ne_chunk_entries': (c_i64, []),
+    'sgnn_ne_aggregate': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64,
+                                  c_int, ctypes.c_uint32, ctypes.c_float, c_u64, c_u64, c_ptr, c_ptr, c_ptr]),
+    'sgnn_ne_relu_drop_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_float, c_ptr]),
+    'sgnn_ne_negatives': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_u64, c_u64, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
+    'sgnn_ne_link_loss_workspace_bytes': (c_i64, []),
+    'sgnn_ne_link_loss': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    'sgnn_adam_step_l2': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                  ctypes.c_float, c_i64, c_ptr]),
 }
 
 ERRORS = {-1: 'SGNN_ERR_BAD_ARG', -2: 'SGNN_ERR_SET_TOO_LARGE', -3: 'SGNN_ERR_NNZ_TOO_LARGE',

@@ -98,6 +98,52 @@ extern "C" int sgnn_adam_step_counted(float* param, float* grad, float* exp_avg,
     return adam_run(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, 0, step_counter, grad_scale, zero_grad, stream);
 }
 
+// ---- Adam with coupled L2 (torch.optim.Adam(weight_decay = wd), the node-embedding trainer's optimiser:
+// reference prepare_dataset/train_node_emb.py:99): g += wd p before the moments, then the rule above.  n any length: the float4
+// body covers n / 4 elements, one extra lane per remaining element.
+__global__ __launch_bounds__(256) void adam_l2_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, int64_t n, float b1, float b2, float eps, float wd,
+                                                      float step_size, float rsqrt_bc2)
+{
+    const int64_t n4 = n / 4;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4 + (n - n4 * 4); i += stride) {
+        if (i < n4) {
+            float4 pp = reinterpret_cast<float4*>(p)[i], gg = reinterpret_cast<const float4*>(g)[i];
+            float4 mm = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
+            float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const float gk = G[k] + wd * P[k];
+                M[k] = M[k] + (1.f - b1) * (gk - M[k]);
+                V[k] = b2 * V[k] + (1.f - b2) * gk * gk;
+                P[k] -= step_size * M[k] / (sqrtf(V[k]) * rsqrt_bc2 + eps);
+            }
+            reinterpret_cast<float4*>(p)[i] = pp; reinterpret_cast<float4*>(m)[i] = mm; reinterpret_cast<float4*>(v)[i] = vv;
+        } else {
+            const int64_t j = n4 * 4 + (i - n4);
+            const float gk = g[j] + wd * p[j];
+            m[j] = m[j] + (1.f - b1) * (gk - m[j]);
+            v[j] = b2 * v[j] + (1.f - b2) * gk * gk;
+            p[j] -= step_size * m[j] / (sqrtf(v[j]) * rsqrt_bc2 + eps);
+        }
+    }
+}
+
+extern "C" int sgnn_adam_step_l2(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                                 float beta2, float eps, float weight_decay, int64_t step, void* stream)
+{
+    if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || step < 1) return SGNN_ERR_BAD_ARG;
+    if ((((uintptr_t)param | (uintptr_t)grad | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) != 0) return SGNN_ERR_BAD_ARG;
+    if (n == 0) return SGNN_OK;
+    const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+    const int64_t work = n / 4 + n % 4;
+    hipLaunchKernelGGL(adam_l2_kernel, dim3(sgnn_grid_for(work, 256)), dim3(256), 0, (hipStream_t)stream, param, grad, exp_avg,
+                       exp_avg_sq, n, beta1, beta2, eps, weight_decay, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)));
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
 // ---- clip_grad_norm_'s coefficient without a pass of library launches over the large gradient ----------------------------
 // torch.nn.utils.clip_grad_norm_ (the caller's gradient clipping, train_config.py: Trainer(gradient_clip_val)): total = 2-norm
 // of all gradients' 2-norms, coefficient = min(1, max_norm / (total + 1e-6)).  The table's gradient (256 MB) took four

@@ -2856,3 +2856,173 @@ def attn_scores(X, U, qW, v, rows_per_batch, half_operands=False):
     recomputes in fp32 either way."""
     return _AttnScores.apply(X.contiguous(), U.contiguous(), qW.contiguous(), v.contiguous().view(-1), int(rows_per_batch),
                              bool(half_operands))
+
+
+# ---------------------------------------------------------------------------------------
+# node-embedding pre-training (train_node_emb.py; reference prepare_dataset/train_node_emb.py + model.py)
+# ---------------------------------------------------------------------------------------
+
+class MessageCSR:
+    """A weighted message graph for sgnn_ne_aggregate: row v lists the sources whose rows are summed into v, with weights w
+    (None: 1) and the self coefficient a_self (float32 per row).  The rows longer than sgnn_ne_chunk_entries() entries are listed
+    once here, as the chunk items the kernel sums on separate wavefronts."""
+
+    def __init__(self, rowptr, col, w, a_self):
+        self.rowptr, self.col, self.w, self.a_self = rowptr, col, w, a_self
+        self.n_rows = rowptr.numel() - 1
+        self.nnz = int(col.numel())
+        chunk = NE_CHUNK()
+        deg = rowptr[1:] - rowptr[:-1]
+        long_rows = torch.nonzero(deg > chunk).view(-1)
+        n_ch = (deg[long_rows] + chunk - 1) // chunk
+        self.long_rows = long_rows.to(torch.int32)
+        self.chunk_first = torch.zeros(long_rows.numel() + 1, dtype=torch.int64, device=rowptr.device)
+        self.chunk_first[1:] = torch.cumsum(n_ch, 0)
+        self.n_chunks = int(self.chunk_first[-1].item()) if long_rows.numel() else 0
+        owner = torch.repeat_interleave(torch.arange(long_rows.numel(), device=rowptr.device), n_ch)
+        self.chunk_row = long_rows[owner].to(torch.int32)
+        self.chunk_beg = rowptr[long_rows][owner] + (torch.arange(self.n_chunks, device=rowptr.device)
+                                                     - self.chunk_first[owner]) * chunk
+        self.max_row = int(deg.max().item()) if deg.numel() else 0
+
+
+@functools.lru_cache(maxsize=None)
+def NE_CHUNK():
+    """Entries per wavefront before the aggregation splits a row (sgnn_ne_chunk_entries)."""
+    return int(_lib.load().sgnn_ne_chunk_entries())
+
+
+def ne_aggregate(csr, X, bias=None, relu=False, dropout=0.0, seed=0, stream_id=0):
+    """out[v] = a_self[v] X[v] + sum_e w[e] X[col[e]] (+ bias), then relu, then dropout with the draw-tape mask of
+    (seed, stream_id): element (v, f) kept iff (draw64(seed, stream_id, v, f) >> 32) >= dropout_threshold(dropout)."""
+    lib = _lib.load()
+    _req(X, torch.float32, 'X')
+    _req(bias, torch.float32, 'bias')
+    if X.dim() != 2 or X.shape[0] != csr.n_rows:
+        raise ValueError('X must be (%d, F)' % csr.n_rows)
+    F = X.shape[1]
+    out = torch.empty_like(X)
+    partial = torch.empty(max(csr.n_chunks, 1) * F, dtype=torch.float32, device=X.device) if csr.n_chunks else None
+    thr = dropout_threshold(dropout)
+    check(lib.sgnn_ne_aggregate(_ptr(csr.rowptr), _ptr(csr.col), _ptr(csr.w), _ptr(csr.a_self), _ptr(X), _ptr(bias), csr.n_rows, F,
+                                _ptr(csr.chunk_row), _ptr(csr.chunk_beg), csr.n_chunks, _ptr(csr.long_rows), _ptr(csr.chunk_first),
+                                csr.long_rows.numel(), 1 if relu else 0, thr, float(1.0 / (1.0 - dropout)) if thr else 1.0,
+                                int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id), _ptr(out), _ptr(partial), _stream()),
+          'sgnn_ne_aggregate')
+    return out
+
+
+def dropout_threshold(p):
+    """The draw-tape dropout rule: an element is dropped iff the high 32 bits of its draw are below int(p 2^32)."""
+    if not 0.0 <= p < 1.0:
+        raise ValueError('dropout must be in [0, 1)')
+    return min(int(p * 4294967296.0), 0xFFFFFFFF)
+
+
+class _GraphConv(torch.autograd.Function):
+    """out = A X (+ bias) [-> relu -> dropout] over the message graph ``fwd``; the backward is the same aggregation over ``bwd``
+    (the transposed graph with the transposed weights) of the gradient taken through the epilogue from the stored output."""
+
+    @staticmethod
+    def forward(ctx, X, bias, fwd, bwd, relu, dropout, seed, stream_id):
+        out = ne_aggregate(fwd, X.contiguous(), bias, relu, dropout, seed, stream_id)
+        ctx.bwd, ctx.relu, ctx.scale = bwd, relu, 1.0 / (1.0 - dropout)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(out if relu else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        g = g.contiguous()
+        if ctx.relu:
+            (out,) = ctx.saved_tensors
+            gp = torch.empty_like(g)
+            check(_lib.load().sgnn_ne_relu_drop_bwd(_ptr(g), _ptr(out), _ptr(gp), g.numel(), float(ctx.scale), _stream()),
+                  'sgnn_ne_relu_drop_bwd')
+            g = gp
+        dX = ne_aggregate(ctx.bwd, g) if ctx.needs_input_grad[0] else None
+        db = column_sum(g) if ctx.has_bias and ctx.needs_input_grad[1] else None
+        return dX, db, None, None, None, None, None, None
+
+
+def graph_conv(X, bias, fwd, bwd, relu=False, dropout=0.0, seed=0, stream_id=0):
+    """One GIN / GCN propagation of the node-embedding model (model.py:15-36) as an autograd op; dropout needs relu (the
+    backward reads the mask off the output)."""
+    if dropout and not relu:
+        raise ValueError('graph_conv: dropout is fused behind relu only')
+    return _GraphConv.apply(X, bias, fwd, bwd, bool(relu), float(dropout), int(seed), int(stream_id))
+
+
+def ne_negatives(g, n, seed, stream_id, item_base=0, max_attempts=64):
+    """n uniform (u, v) node-id pairs, u != v and (u, v) not an edge in either direction (sgnn_ne_negatives) -> (u, v) int32;
+    (0, 0) where max_attempts draws found none."""
+    u = torch.empty(n, dtype=torch.int32, device=g.device)
+    v = torch.empty(n, dtype=torch.int32, device=g.device)
+    check(_lib.load().sgnn_ne_negatives(_ptr(g.rowptr), _ptr(g.col_sorted), g.max_id, n, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                        int(stream_id), int(item_base), int(max_attempts), _ptr(u), _ptr(v), _stream()),
+          'sgnn_ne_negatives')
+    return u, v
+
+
+_NE_LOSS_WS = {}
+
+
+def ne_link_loss(Z, pu, pv, n_pos, want_grad=True):
+    """sgnn_ne_link_loss: -> (loss float32 (1,), s (P,), dloss/ddot (P,) or None); pairs < n_pos are positives."""
+    lib = _lib.load()
+    _req(Z, torch.float32, 'Z')
+    _req(pu, torch.int32, 'pu')
+    _req(pv, torch.int32, 'pv')
+    P = pu.numel()
+    ws = _NE_LOSS_WS.get(Z.device)
+    if ws is None:
+        ws = _NE_LOSS_WS[Z.device] = torch.empty(lib.sgnn_ne_link_loss_workspace_bytes() // 8, dtype=torch.float64, device=Z.device)
+    s = torch.empty(P, dtype=torch.float32, device=Z.device)
+    gd = torch.empty(P, dtype=torch.float32, device=Z.device) if want_grad else None
+    loss = torch.empty(1, dtype=torch.float32, device=Z.device)
+    check(lib.sgnn_ne_link_loss(_ptr(Z), Z.shape[1], _ptr(pu), _ptr(pv), P, int(n_pos), _ptr(s), _ptr(gd), _ptr(loss), _ptr(ws),
+                                ws.numel() * 8, _stream()), 'sgnn_ne_link_loss')
+    return loss, s, gd
+
+
+class _LinkLoss(torch.autograd.Function):
+    """mean nll(log_softmax(stack(1 - s, s)), y), s = sigmoid(z_u . z_v) (utils.py:22-56).  Backward: dZ[u] += g z_v and
+    dZ[v] += g z_u for every scored pair, by sorted atomics-free row sums (scatter_add_rows): the positives with the order the
+    caller sorted once, the negatives sorted here."""
+
+    @staticmethod
+    def forward(ctx, Z, pos_u, pos_v, neg_u, neg_v, pos_sorted):
+        pu, pv = torch.cat([pos_u, neg_u]), torch.cat([pos_v, neg_v])
+        loss, s, gd = ne_link_loss(Z, pu, pv, pos_u.numel(), want_grad=True)
+        ctx.save_for_backward(Z, gd)
+        ctx.pairs = (pos_u, pos_v, neg_u, neg_v)
+        ctx.pos_sorted = pos_sorted
+        ctx.mark_non_differentiable(s)
+        return loss.view(()), s
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_s):
+        Z, gd = ctx.saved_tensors
+        pos_u, pos_v, neg_u, neg_v = ctx.pairs
+        gd = gd * g_loss
+        dZ = torch.zeros_like(Z)
+        n_pos = pos_u.numel()
+        for (u, v, gg, pre) in ((pos_u, pos_v, gd[:n_pos], ctx.pos_sorted), (neg_u, neg_v, gd[n_pos:], None)):
+            if u.numel():
+                scatter_add_rows(dZ, torch.cat([u, v]), G=Z, edge_row=torch.cat([v, u]), c1=torch.cat([gg, gg]), presorted=pre)
+        return dZ, None, None, None, None, None
+
+
+def link_loss(Z, pos_u, pos_v, neg_u, neg_v, pos_sorted=None):
+    """-> (loss, s): the link-prediction loss of the node-embedding trainer.  ``pos_sorted``:
+    sort_edges_by_key(torch.cat([pos_u, pos_v]), Z.shape[0] - 1), kept by a caller whose positives do not change."""
+    return _LinkLoss.apply(Z, pos_u, pos_v, neg_u, neg_v, pos_sorted)
+
+
+def adam_step_l2(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step):
+    """torch.optim.Adam(weight_decay = wd) on one float32 buffer in one pass (sgnn_adam_step_l2): coupled L2."""
+    for t, nm in ((param, 'param'), (grad, 'grad'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
+        _req(t, torch.float32, nm)
+    check(_lib.load().sgnn_adam_step_l2(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), float(lr),
+                                        float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), _stream()),
+          'sgnn_adam_step_l2')

@@ -375,10 +375,16 @@ def generate(prop, seed=42, rng=None, **overrides):
                 identity=identity, rng=rng, n_bins=cfg['n_bins'])
 
 
-def write_dataset(out_dir, prop, seed=42, embed_dim=32, embedding_type='gin', repair_ids=True, **overrides):
+def write_dataset(out_dir, prop, seed=42, embed_dim=32, embedding_type='gin', repair_ids=True, embeddings='random',
+                  **overrides):
     """Generates and writes edge_list.txt, subgraphs.pth (prepare_dataset.py:781-799,822) and
     <type>_embeddings.pth under out_dir.  ``repair_ids``: when the final relabelling moved node ids, write the
-    relabelled subgraphs with labels recomputed on them instead of the reference's stale lists (module docstring)."""
+    relabelled subgraphs with labels recomputed on them instead of the reference's stale lists (module docstring).
+    ``embeddings``: 'random' = an N(0, 1) table of width embed_dim; 'gin' / 'gcn' = pre-trained on the GPU by
+    train_node_emb.generate (default hyper-parameters, output width embed_dim), written under the name SubGNN reads for
+    that conv (gin_embeddings.pth / graphsaint_gcn_embeddings.pth)."""
+    if embeddings not in ('random', 'gin', 'gcn'):
+        raise ValueError("embeddings must be 'random', 'gin' or 'gcn'")
     out = Path(out_dir)
     (out / 'similarities').mkdir(parents=True, exist_ok=True)
     st = generate(prop, seed, **overrides)
@@ -396,8 +402,12 @@ def write_dataset(out_dir, prop, seed=42, embed_dim=32, embedding_type='gin', re
             if len(s) == 0:
                 continue
             f.write('\t'.join(['-'.join(str(v) for v in s), str(lab), names[sp], '\n']))
-    g = torch.Generator().manual_seed(seed + 3)
-    torch.save(torch.randn(G.number_of_nodes(), embed_dim, generator=g), out / ('%s_embeddings.pth' % embedding_type))
+    if embeddings == 'random':
+        g = torch.Generator().manual_seed(seed + 3)
+        torch.save(torch.randn(G.number_of_nodes(), embed_dim, generator=g), out / ('%s_embeddings.pth' % embedding_type))
+    else:
+        from .train_node_emb import generate as pretrain
+        pretrain(out, conv=embeddings, output=embed_dim, seed=seed)
     return out, dict(n_nodes=G.number_of_nodes(), n_edges=G.number_of_edges(), n_subgraphs=len(subs), labels=labels,
                      values=values, ids_repaired=repaired)
 

@@ -157,6 +157,24 @@ def roc_auc(y_true, y_score, multi_class=None):
     return float(np.mean([_binary_auroc(yt == c, ys[:, i]) for i, c in enumerate(classes)]))
 
 
+def average_precision(y_true, y_score):
+    """sklearn.metrics.average_precision_score of one binary problem (the node-embedding trainer's AP, reference
+    prepare_dataset/utils.py:108): scores sorted descending (stable), precision and recall at the LAST entry of every run of
+    equal scores, AP = sum over those thresholds of (R_n - R_{n-1}) P_n.  nan when y_true holds no positive."""
+    import numpy as np
+    yt = np.asarray(y_true).reshape(-1).astype(bool)
+    ys = np.asarray(y_score, dtype=np.float64).reshape(-1)
+    if not yt.any():
+        return float('nan')
+    order = np.argsort(-ys, kind='mergesort')
+    ys, yt = ys[order], yt[order]
+    last = np.r_[np.nonzero(np.diff(ys))[0], ys.size - 1]
+    tps = np.cumsum(yt, dtype=np.float64)[last]
+    precision = tps / (1.0 + last)
+    recall = tps / tps[-1]
+    return float(np.sum(np.diff(np.r_[0.0, recall]) * precision))
+
+
 def calc_f1(logits, labels, avg_type='macro', multilabel_binarizer=None):
     """su.calc_f1 (su:90-105): sklearn's f1_score of the arg-max (multilabel: sigmoid > 0.5) predictions."""
     if multilabel_binarizer is not None:

@@ -19,6 +19,10 @@ STREAM_N_BOR = 6
 STREAM_P_INT = 7
 STREAM_P_EXT = 8
 STREAM_S_PICK = 9
+# node-embedding pre-training (train_node_emb.py): edge split, negative pairs, dropout masks
+STREAM_NE_SPLIT = 10
+STREAM_NE_NEG = 11
+STREAM_NE_DROP = 12
 
 SPLIT_CODE = {'train': 0, 'val': 1, 'test': 2}
 
@@ -30,3 +34,19 @@ def stream_id(kind, split=0, layer=0, epoch=0):
         split = SPLIT_CODE[split]
     assert 0 <= layer < 256 and 0 <= epoch < 65536
     return (kind << 32) | (split << 24) | (epoch << 8) | layer
+
+
+def draw64_np(seed, stream, item, j):
+    """draw64 over numpy arrays of ``item`` / ``j`` (uint64 wrap-around arithmetic): host-side draws of one-time set-up work
+    (the node-embedding trainer's edge split)."""
+    import numpy as np
+    K_STREAM, K_ITEM, K_DRAW = 0x9E3779B97F4A7C15, 0xD1B54A32D192ED03, 0x8CB92BA72F3D8DD7
+
+    def mix(z):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+    with np.errstate(over='ignore'):
+        h0 = mix(np.uint64((seed & MASK64) ^ ((stream * K_STREAM) & MASK64)))
+        h = mix(h0 + np.asarray(item).astype(np.uint64) * np.uint64(K_ITEM))
+        return mix(h + np.asarray(j).astype(np.uint64) * np.uint64(K_DRAW))
