@@ -38,7 +38,7 @@ extern "C" {
 #define SGNN_ERR_LAUNCH         -4   /* hipGetLastError() after a launch */
 #define SGNN_ERR_UNSUPPORTED_D  -5   /* embedding width not supported by the vector path */
 
-#define SGNN_ABI_VERSION 11
+#define SGNN_ABI_VERSION 12
 int sgnn_abi_version(void);
 /* Load the code objects of every translation unit of the library on the current device (one empty launch each on ``stream``):
  * what the first call of each kernel family would otherwise pay, 5-25 ms at a time, inside the reference's one-time
@@ -725,30 +725,16 @@ int sgnn_update_bwd(const float* grad_out, const float* out, const float* x, con
                     void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
- * a18  Adam on one large parameter in one pass (torch.optim.Adam's rule, no weight decay / amsgrad:
- * SubGNN/SubGNN.py:1156-1161), with the caller's clip coefficient (train_config.py: gradient_clip_val) applied on the
- * fly: grad_scale (nullable) is a DEVICE scalar, so the clip needs no host round trip.  step = 1 for the first update.
- * zero_grad != 0: the gradient is zeroed in the same pass (the buffer can be handed out again without a fill).
- * All four arrays float32[n], 16-byte aligned.
+ * a18  Adam on one float32 buffer of any length n in one pass (torch.optim.Adam's rule, no amsgrad: SubGNN/SubGNN.py:1156-1161),
+ * with the gradient term in one of two forms:
+ *   weight_decay == 0: g * grad_scale -- grad_scale (nullable: 1) is the caller's clip coefficient (train_config.py:
+ *     gradient_clip_val) as a DEVICE scalar, so the clip needs no host round trip (dist.ShardedTableAdam's owned slice);
+ *   weight_decay != 0: g + weight_decay * param -- torch.optim.Adam(lr, weight_decay)'s coupled L2 (the node-embedding
+ *     trainer: prepare_dataset/train_node_emb.py:99); grad_scale must then be null.
+ * step = 1 for the first update.  All four arrays float32[n], 16-byte aligned.
  * ------------------------------------------------------------------------------------- */
-/* a18b  The caller's clip_grad_norm_ (train_config.py: Trainer(gradient_clip_val) -> torch.nn.utils.clip_grad_norm_):
- * coefficient = min(1, max_norm / (total + 1e-6)), total = 2-norm over all gradients.  sgnn_grad_sumsq: sums of squares of
- * one large float32 gradient (16-byte aligned) as sgnn_grad_sumsq_partials() per-workgroup values; sgnn_clip_coefficient adds
- * them (any number of such arrays laid end to end) and the squares of other_norms (the small parameters' 2-norms) in a fixed
- * order and writes the DEVICE scalars coef (for sgnn_adam_step's grad_scale) and total_norm (nullable). */
-int64_t sgnn_grad_sumsq_partials(void);
-int sgnn_grad_sumsq(const float* grad, int64_t n, float* partial, void* stream);
-int sgnn_clip_coefficient(const float* partial, int64_t n_partial, const float* other_norms, int64_t n_other,
-                          float max_norm, float* coef, float* total_norm, void* stream);
-
-int sgnn_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                   float beta2, float eps, int64_t step, const float* grad_scale, int zero_grad, void* stream);
-/* The same with the step count in DEVICE memory (int64, starts at 0): incremented on the stream right before the update, read by
- * the update for its bias corrections -- the form a step recorded into a hipGraph replays (a host counter would be frozen at
- * its value at recording time). */
-int sgnn_adam_step_counted(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                           float beta2, float eps, int64_t* step_counter, const float* grad_scale, int zero_grad,
-                           void* stream);
+int sgnn_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, int64_t step, const float* grad_scale, void* stream);
 
 /* a18c  The whole optimizer tail of a step -- clip_grad_norm_ over ALL parameters (train_config.py: Trainer(gradient_clip_val))
  * followed by torch.optim.Adam over all of them (SubGNN/SubGNN.py:1156-1161) -- in two launches per 72 tensors.  The tensor lists
@@ -864,8 +850,7 @@ int sgnn_reduce_partials(int64_t n_jobs, const float* const* part, const int64_t
  * sgnn_ne_link_loss replaces utils.el_dot + calc_loss_both (utils.py:22-56): for pairs p < n_pairs (label 1 for p < n_pos, else 0)
  * s = sigmoid(Z[pu[p]] . Z[pv[p]]) -> s_out, d loss / d dot -> g_out (nullable), loss = mean of
  * nll(log_softmax(stack(1 - s, s)), y) -> loss[0], reduced in a fixed order; workspace sgnn_ne_link_loss_workspace_bytes().
- * sgnn_adam_step_l2 replaces torch.optim.Adam(lr, weight_decay) (train_node_emb.py:99): coupled L2 (g + wd p) on one float32
- * buffer of any length n, 16-byte aligned; step = 1 for the first update.
+ * The optimiser, torch.optim.Adam(lr, weight_decay) (train_node_emb.py:99), is sgnn_adam_step with weight_decay (a18).
  * ------------------------------------------------------------------------------------- */
 int64_t sgnn_ne_chunk_entries(void);
 int sgnn_ne_aggregate(const int64_t* rowptr, const int32_t* col, const float* w, const float* a_self, const float* X,
@@ -879,8 +864,6 @@ int sgnn_ne_negatives(const int64_t* rowptr, const int32_t* col_sorted, int64_t 
 int64_t sgnn_ne_link_loss_workspace_bytes(void);
 int sgnn_ne_link_loss(const float* Z, int64_t F, const int32_t* pu, const int32_t* pv, int64_t n_pairs, int64_t n_pos,
                       float* s_out, float* g_out, float* loss, void* workspace, int64_t workspace_bytes, void* stream);
-int sgnn_adam_step_l2(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1,
-                      float beta2, float eps, float weight_decay, int64_t step, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * Measurement aid (no reference counterpart): streaming copy of n_bytes with 4 or 16 bytes per lane.

@@ -100,9 +100,6 @@ SIGNATURES = {
     'sgnn_masked_sum_slots_fwd': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr]),
     'sgnn_masked_sum_slots_bwd': (c_int, [c_ptr, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_readout_sum_fwd': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr]),
-    'sgnn_grad_sumsq_partials': (c_i64, []),
-    'sgnn_grad_sumsq': (c_int, [c_ptr, c_i64, c_ptr, c_ptr]),
-    'sgnn_clip_coefficient': (c_int, [c_ptr, c_i64, c_ptr, c_i64, ctypes.c_float, c_ptr, c_ptr, c_ptr]),
     'sgnn_first_occurrence_mask': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     'sgnn_filter_sets': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sgnn_pack_rows_count': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
@@ -150,9 +147,7 @@ SIGNATURES = {
     'sgnn_mpn_bwd_shared_det_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64]),
     'sgnn_mpn_bwd_shared_det': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_adam_step': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                               c_i64, c_ptr, c_int, c_ptr]),
-    'sgnn_adam_step_counted': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                       ctypes.c_float, c_ptr, c_ptr, c_int, c_ptr]),
+                               ctypes.c_float, c_i64, c_ptr, c_ptr]),
     'sgnn_optim_partials': (c_i64, [c_ptr, c_i64]),
     'sgnn_optim_sumsq': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sgnn_optim_count': (c_int, [c_ptr, c_ptr, c_i64, c_ptr]),
@@ -184,8 +179,6 @@ SIGNATURES = {
     'sgnn_ne_negatives': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_u64, c_u64, c_i64, c_int, c_ptr, c_ptr, c_ptr]),
     'sgnn_ne_link_loss_workspace_bytes': (c_i64, []),
     'sgnn_ne_link_loss': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
-    'sgnn_adam_step_l2': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
-                                  ctypes.c_float, c_i64, c_ptr]),
 }
 
 ERRORS = {-1: 'SGNN_ERR_BAD_ARG', -2: 'SGNN_ERR_SET_TOO_LARGE', -3: 'SGNN_ERR_NNZ_TOO_LARGE',
@@ -214,7 +207,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the header and the library disagree
         fn.restype = res
         fn.argtypes = args
-    if lib.sgnn_abi_version() != 11:
+    if lib.sgnn_abi_version() != 12:
         raise SubgnnHipError('ABI version mismatch')
     _lib = lib
     return lib

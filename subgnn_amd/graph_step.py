@@ -82,10 +82,11 @@ class CapturedTrainStep:
         self.model, self.opt, self.B, self.clip, self.split = model, optimizer, int(batch_size), clip, split
         self.idx = torch.zeros(self.B, dtype=torch.int64, device=model.device)
         self._token = self._anchor_token()
-        if hasattr(optimizer, 'param_groups'):
+        if hasattr(optimizer, 'capturable'):                       # optim.ClipAdam: its step counts must live on the device
+            if not optimizer.capturable:
+                raise ValueError('CapturedTrainStep needs an optimizer whose step count is device-resident (ClipAdam(capturable=True))')
+        else:
             make_capturable(optimizer)
-        elif not getattr(optimizer, 'capturable', False):          # optim.ClipAdam: its step counts must live on the device
-            raise ValueError('CapturedTrainStep needs an optimizer whose step count is device-resident (ClipAdam(capturable=True))')
         self.graph, self.loss, self.acc = None, None, None
         self._warm_left = warmup
 

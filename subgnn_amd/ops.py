@@ -1770,21 +1770,15 @@ def update_chunks_max_rows():
     return int(_lib.load().sgnn_update_fwd_chunks_max_rows())
 
 
-def adam_step(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, step, grad_scale=None, zero_grad=False, step_counter=None):
-    """One Adam update of a large float32 parameter in one pass (sgnn_adam_step); ``grad_scale``: device scalar.
-    ``step_counter``: int64 (1,) device tensor that replaces the host count ``step`` (incremented on the stream before the
-    update: the form a recorded step replays)."""
+def adam_step(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, step, grad_scale=None, weight_decay=0.0):
+    """One Adam update of a float32 buffer in one pass (sgnn_adam_step).  The gradient enters as ``grad * grad_scale``
+    (``grad_scale``: a (1,) device scalar, the clip coefficient) or, with ``weight_decay``, as ``grad + weight_decay * param``
+    (torch.optim.Adam's coupled L2); not both."""
     for t, nm in ((param, 'param'), (grad, 'grad'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq'), (grad_scale, 'grad_scale')):
         _req(t, torch.float32, nm)
-    if step_counter is not None:
-        _req(step_counter, torch.int64, 'step_counter')
-        check(_lib.load().sgnn_adam_step_counted(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), float(lr),
-                                                 float(betas[0]), float(betas[1]), float(eps), _ptr(step_counter), _ptr(grad_scale),
-                                                 1 if zero_grad else 0, _stream()), 'sgnn_adam_step_counted')
-        return
     check(_lib.load().sgnn_adam_step(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), float(lr),
-                                     float(betas[0]), float(betas[1]), float(eps), int(step), _ptr(grad_scale),
-                                     1 if zero_grad else 0, _stream()), 'sgnn_adam_step')
+                                     float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                                     _ptr(grad_scale), _stream()), 'sgnn_adam_step')
 
 
 class OptimTail:
@@ -1872,23 +1866,6 @@ class OptimTail:
                                   _ptr(partial), n_partial,
                                   float(max_norm) if partial is not None else 0.0, _ptr(out), st), 'sgnn_optim_adam')
         return out
-
-
-def clip_coefficient(big_grads, small_grads, max_norm):
-    """clip_grad_norm_'s coefficient min(1, max_norm / (total + 1e-6)) as a (1,) device tensor: the large gradients are
-    reduced by sgnn_grad_sumsq (one launch each), the small ones by one multi-tensor norm."""
-    lib = _lib.load()
-    dev = (big_grads + small_grads)[0].device
-    P = int(lib.sgnn_grad_sumsq_partials())
-    partial = torch.empty(max(len(big_grads), 1) * P, dtype=torch.float32, device=dev)
-    for i, g in enumerate(big_grads):
-        _req(g, torch.float32, 'gradient')
-        check(lib.sgnn_grad_sumsq(_ptr(g), g.numel(), ctypes.c_void_p(partial.data_ptr() + 4 * i * P), _stream()), 'sgnn_grad_sumsq')
-    other = torch.stack(torch._foreach_norm(small_grads)).float() if small_grads else None
-    coef = torch.empty(1, dtype=torch.float32, device=dev)
-    check(lib.sgnn_clip_coefficient(_ptr(partial), len(big_grads) * P, _ptr(other), other.numel() if other is not None else 0,
-                                    float(max_norm), _ptr(coef), None, _stream()), 'sgnn_clip_coefficient')
-    return coef
 
 
 _ZEROS = {}
@@ -3018,11 +2995,3 @@ def link_loss(Z, pos_u, pos_v, neg_u, neg_v, pos_sorted=None):
     sort_edges_by_key(torch.cat([pos_u, pos_v]), Z.shape[0] - 1), kept by a caller whose positives do not change."""
     return _LinkLoss.apply(Z, pos_u, pos_v, neg_u, neg_v, pos_sorted)
 
-
-def adam_step_l2(param, grad, exp_avg, exp_avg_sq, lr, betas, eps, weight_decay, step):
-    """torch.optim.Adam(weight_decay = wd) on one float32 buffer in one pass (sgnn_adam_step_l2): coupled L2."""
-    for t, nm in ((param, 'param'), (grad, 'grad'), (exp_avg, 'exp_avg'), (exp_avg_sq, 'exp_avg_sq')):
-        _req(t, torch.float32, nm)
-    check(_lib.load().sgnn_adam_step_l2(_ptr(param), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), param.numel(), float(lr),
-                                        float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step), _stream()),
-          'sgnn_adam_step_l2')

@@ -215,7 +215,7 @@ class Trainer:
         self.t += 1
         with torch.no_grad():
             for p, (m, v) in zip(self.params, self.state):
-                ops.adam_step_l2(p, p.grad.contiguous(), m, v, self.lr, BETAS, ADAM_EPS, self.wd, self.t)
+                ops.adam_step(p, p.grad.contiguous(), m, v, self.lr, BETAS, ADAM_EPS, self.t, weight_decay=self.wd)
         self.last_negatives = (nu, nv)
         return loss.detach(), Z.detach()
 

@@ -712,7 +712,7 @@ def test_clip_adam_fused_tail_many_tensors(capturable):
     4 bytes past a 16-byte boundary (scalar path), parameters whose gradient is missing on some steps (torch.optim.Adam
     skips them and their step counts fall behind: host counts and device counts alike), against clip_grad_norm_ +
     torch.optim.Adam; the reported total norm against clip_grad_norm_'s; then make_eager() (device counts -> host counts)
-    and two more steps.  Also ClipAdam(fuse_tail=False), the library-call form, gives the same parameters."""
+    and two more steps."""
     from subgnn_amd import optim
     g = torch.Generator().manual_seed(11)
     sizes = [1, 2, 3, 5, 64, 127, 1000, 4096, 4097, 70001] + [int(x) for x in torch.randint(1, 3000, (140,), generator=g)]
@@ -730,29 +730,27 @@ def test_clip_adam_fused_tail_many_tensors(capturable):
             else:
                 out.append(torch.nn.Parameter(t.clone().to(DEV)))
         return out
-    ref, got, lib_form = make(), make(), make()
+    ref, got = make(), make()
     o_ref = torch.optim.Adam(ref, lr=0.01)
     o_got = optim.ClipAdam(got, lr=0.01, max_norm=0.7, big_bytes=70001 * 4, capturable=capturable)
-    o_lib = optim.ClipAdam(lib_form, lr=0.01, max_norm=0.7, big_bytes=70001 * 4, capturable=capturable, fuse_tail=False)
-    assert o_got.tail is not None and o_got.small_opt is None and len(o_got.big) == 1 and o_lib.tail is None
+    assert len(o_got.big) == 1
     for it in range(6):
         if it == 4:
-            o_got.make_eager(); o_lib.make_eager()
+            o_got.make_eager()
             assert o_got.counters is None
         grads = [torch.randn(n, generator=g).to(DEV) * (3.0 if it % 2 else 0.05) for n in sizes]
-        for ps in (ref, got, lib_form):
+        for ps in (ref, got):
             for i, (p, gr) in enumerate(zip(ps, grads)):
                 p.grad = None if (i % 7 == 3 and it in (1, 2)) or (i == 9 and it == 3) else gr.clone()
         total = torch.nn.utils.clip_grad_norm_(ref, 0.7)
-        o_ref.step(); o_got.step(); o_lib.step()
+        o_ref.step(); o_got.step()
         coef, norm = o_got.last_clip.tolist()
         assert abs(norm - float(total)) <= 1e-5 * float(total), (norm, float(total))
         assert abs(coef - min(1.0, 0.7 / (float(total) + 1e-6))) <= 1e-6
-        for opt in (o_ref, o_got, o_lib):
+        for opt in (o_ref, o_got):
             opt.zero_grad()
-        for k, (a, b, c) in enumerate(zip(got, ref, lib_form)):
+        for k, (a, b) in enumerate(zip(got, ref)):
             assert_close(a.detach(), b.detach(), 'fused tail step %d parameter %d (%d elements)' % (it, k, sizes[k]), norm_tol=2e-6)
-            assert_close(c.detach(), b.detach(), 'library form step %d parameter %d' % (it, k), norm_tol=2e-6)
     steps = [o_got.state[id(p)]['step'] for p in got]
     assert steps[0] == 6 and steps[3] == 4 and steps[9] == 5, steps[:12]
 
@@ -794,12 +792,13 @@ def test_clip_adam_skips_untouched_table_rows_bit_exactly(D):
     assert torch.equal(models[0][0][~touched.to(DEV)].cpu(), init[0][~touched])    # untouched rows: the initial bits
 
 
-@pytest.mark.parametrize('capturable,fuse_tail', [(False, True), (True, True), (False, False)])
-def test_clip_adam_checkpoint_round_trip_and_param_groups(capturable, fuse_tail):
+@pytest.mark.parametrize('capturable', [False, True])
+def test_clip_adam_checkpoint_round_trip_and_param_groups(capturable):
     """ClipAdam has torch's optimizer surface: ``param_groups[0]['lr']`` written by a scheduler is what the next
     step uses; ``state_dict`` / ``load_state_dict`` carry moments, step counts and the row-skip bytes, so that a restored
     optimizer continues bit for bit -- and a checkpoint WITHOUT the row-skip bytes (moments restored from elsewhere) does too
-    (rows with a non-zero moment are marked seen on load: a skipped row would otherwise stop decaying)."""
+    (rows with a non-zero moment are marked seen on load: a skipped row would otherwise stop decaying).  A checkpoint that keeps
+    the small parameters' moments in a torch optimizer's state dict (``'small'``) is refused, not half restored."""
     from subgnn_amd import optim
     g = torch.Generator().manual_seed(5)
     rows, D = 3001, 32
@@ -807,7 +806,7 @@ def test_clip_adam_checkpoint_round_trip_and_param_groups(capturable, fuse_tail)
 
     def fresh():
         ps = [torch.nn.Parameter(t.clone().to(DEV)) for t in init]
-        return ps, optim.ClipAdam(ps, lr=0.01, max_norm=0.5, big_bytes=rows * D * 4, capturable=capturable, fuse_tail=fuse_tail)
+        return ps, optim.ClipAdam(ps, lr=0.01, max_norm=0.5, big_bytes=rows * D * 4, capturable=capturable)
 
     def grads(it):
         gg = torch.Generator().manual_seed(100 + it)
@@ -839,7 +838,26 @@ def test_clip_adam_checkpoint_round_trip_and_param_groups(capturable, fuse_tail)
         c.load_state_dict(sd2)
         run(c_ps, c, range(3, 5))
         for p, q in zip(c_ps, a_ps):
-            assert torch.equal(p.detach(), q.detach()), (capturable, fuse_tail, strip)
+            assert torch.equal(p.detach(), q.detach()), (capturable, strip)
+    _, d = fresh()
+    torch_sd = torch.optim.Adam(b_ps[1:], lr=0.01).state_dict()
+    with pytest.raises(ValueError, match='small'):
+        d.load_state_dict({'state': sd['state'], 'param_groups': sd['param_groups'], 'small': torch_sd})
+
+
+@pytest.mark.parametrize('odd', ['float64', 'non-contiguous'])
+def test_clip_adam_refuses_parameters_the_fused_tail_cannot_step(odd):
+    """One float64 or non-contiguous parameter among CUDA float32 ones: ``accelerate`` returns the torch optimizer untouched
+    (the trainer then clips with clip_grad_norm_) and ClipAdam refuses the list."""
+    from subgnn_amd import optim
+    odd_t = torch.randn(64, 9, dtype=torch.float64, device=DEV) if odd == 'float64' else torch.randn(9, 64, device=DEV).t()
+    ps = [torch.nn.Parameter(torch.randn(300, 64, device=DEV)), torch.nn.Parameter(odd_t)]
+    assert ps[1].dtype == torch.float64 or not ps[1].is_contiguous()
+    adam = torch.optim.Adam(ps, lr=0.01)
+    assert optim.accelerate(adam, max_norm=0.5) is adam
+    with pytest.raises(ValueError):
+        optim.ClipAdam(ps, lr=0.01, max_norm=0.5)
+    assert isinstance(optim.accelerate(torch.optim.Adam(ps[:1], lr=0.01), max_norm=0.5), optim.ClipAdam)
 
 
 def test_clip_adam_follows_a_parameter_whose_storage_was_replaced():

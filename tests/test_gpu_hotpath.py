@@ -355,9 +355,11 @@ def test_training_half_replayed_from_a_hipgraph_trains_like_the_eager_step(name,
     """hotpath.CapturedTraining: the training half (training_step -> backward -> ClipAdam) recorded into a hipGraph on
     the second pass and replayed, every later pass copied into the recording's tensors (install_pass_static) -- losses
     and parameters equal the eager prepare-then-train schedule bit for bit over 5 passes (clip + Adam with device-side
-    step counts; without dropout: a replayed graph draws its masks from its own Philox offsets)."""
+    step counts; without dropout: a replayed graph draws its masks from its own Philox offsets).  Neither recording takes
+    a ClipAdam with host step counts."""
     from conftest import load_golden
     from subgnn_amd import hotpath, optim
+    from subgnn_amd.graph_step import CapturedTrainStep
     golden = load_golden(name)
     (seq, cap) = _models(golden, tmp_path, {'lin_dropout': 0.0, 'lstm_dropout': 0.0})
     cap.load_state_dict(seq.state_dict())
@@ -397,6 +399,8 @@ def test_training_half_replayed_from_a_hipgraph_trains_like_the_eager_step(name,
         assert torch.equal(a, b), n1
     with pytest.raises(ValueError):
         hotpath.CapturedTraining(cap, optim.ClipAdam(cap.parameters(), lr), 'train')      # a host step count cannot be replayed
+    with pytest.raises(ValueError):
+        CapturedTrainStep(cap, optim.ClipAdam(cap.parameters(), lr), 4)
 
 
 @pytest.mark.parametrize('name,big_bytes', [('density', 1024), ('density', 1 << 30)])

@@ -168,19 +168,32 @@ def test_link_loss_and_gradient(F):
     assert_close(Zg.grad, Zr.grad, 'dZ')
 
 
-def test_adam_l2_matches_torch():
-    from subgnn_amd import ops
+@pytest.mark.parametrize('n', [10008, 10007])
+@pytest.mark.parametrize('scaled', [False, True])
+@pytest.mark.parametrize('wd', [0.0, 5e-4])
+def test_adam_step_matches_torch(wd, scaled, n):
+    """ops.adam_step (sgnn_adam_step) == torch.optim.Adam(weight_decay = wd) over five steps, in both gradient forms: coupled
+    L2 (the node-embedding trainer) and the gradient times a device scalar (dist.ShardedTableAdam's clip coefficient; torch
+    gets the gradient multiplied first), on a length that is a multiple of 4 and on one that is not.  Both forms at once are
+    refused."""
+    from subgnn_amd import ops, _lib
     gen = torch.Generator(device=DEV).manual_seed(2)
-    p0 = torch.randn(10007, device=DEV, generator=gen)
+    p0 = torch.randn(n, device=DEV, generator=gen)
     p, m, v = p0.clone(), torch.zeros_like(p0), torch.zeros_like(p0)
     q = p0.clone().requires_grad_(True)
-    opt = torch.optim.Adam([q], lr=5e-3, weight_decay=5e-4)
+    opt = torch.optim.Adam([q], lr=5e-3, weight_decay=wd)
+    scale = torch.full((1,), 0.37, device=DEV) if scaled else None
+    if scaled and wd:
+        with pytest.raises(_lib.SubgnnHipError):
+            ops.adam_step(p, torch.zeros_like(p), m, v, 5e-3, (0.9, 0.999), 1e-8, 1, grad_scale=scale, weight_decay=wd)
+        assert torch.equal(p, p0)
+        return
     for t in range(1, 6):
-        grad = torch.randn(10007, device=DEV, generator=gen) * 0.01
-        ops.adam_step_l2(p, grad, m, v, 5e-3, (0.9, 0.999), 1e-8, 5e-4, t)
-        q.grad = grad.clone()
+        grad = torch.randn(n, device=DEV, generator=gen) * 0.01
+        ops.adam_step(p, grad, m, v, 5e-3, (0.9, 0.999), 1e-8, t, grad_scale=scale, weight_decay=wd)
+        q.grad = grad * scale if scaled else grad.clone()
         opt.step()
-    assert_close(p, q.detach(), 'Adam(weight_decay)', tol=1e-5)
+    assert_close(p, q.detach(), 'Adam(weight_decay=%g, scaled=%s, n=%d)' % (wd, scaled, n), tol=1e-5)
 
 
 @pytest.mark.parametrize('conv', ['gin', 'gcn'])

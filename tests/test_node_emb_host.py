@@ -153,10 +153,10 @@ def test_node_emb_kernels_use_no_scratch_and_spill_nothing():
     from subgnn_amd import build
     build.build(verbose=False)
     ks = [k for o in ('node_emb.o', 'optim.o') for k in KR.kernels(os.path.join(build.LIBDIR, o))
-          if k['demangled'].startswith(('ne_', 'void ne_', 'adam_l2'))]
+          if k['demangled'].startswith(('ne_', 'void ne_', 'void adam_step_kernel'))]
     names = ' '.join(k['demangled'] for k in ks)
     for want in ('ne_aggregate_kernel', 'ne_aggregate_finish_kernel', 'ne_negatives_kernel', 'ne_link_loss_kernel',
-                 'ne_loss_finish_kernel', 'ne_relu_drop_bwd_kernel', 'adam_l2_kernel'):
+                 'ne_loss_finish_kernel', 'ne_relu_drop_bwd_kernel', 'adam_step_kernel<true>', 'adam_step_kernel<false>'):
         assert want in names, want
     for k in ks:
         assert k['private_segment_fixed_size'] == 0, k['demangled'][:80]

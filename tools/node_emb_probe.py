@@ -69,7 +69,7 @@ def main():
         T = tr.params[0]
         gT, mT, vT = torch.zeros_like(T), torch.zeros_like(T), torch.zeros_like(T)
         Tc = T.detach().clone()
-        r['adam_table'] = dict(ms=timed(lambda: ops.adam_step_l2(Tc, gT, mT, vT, 1e-3, (0.9, 0.999), 1e-8, 5e-4, 1), args.reps),
+        r['adam_table'] = dict(ms=timed(lambda: ops.adam_step(Tc, gT, mT, vT, 1e-3, (0.9, 0.999), 1e-8, 1, weight_decay=5e-4), args.reps),
                                gbytes=T.numel() * 4 * 7 / 1e9)
         del Tc, gT, mT, vT, X
         ep = [0]
