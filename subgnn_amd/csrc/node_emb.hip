@@ -289,7 +289,8 @@ extern "C" int sgnn_ne_negatives(const int64_t* rowptr, const int32_t* col_sorte
 
 // ---- link loss ----------------------------------------------------------------------------------------------------------------
 // pairs [0, n_pos) have label 1, the rest label 0.  s = sigmoid(z_u . z_v); the reference's term is -log_softmax(1 - s, s)[y]
-// = lse - x_y with lse = log(e^(1-s) + e^s); d term / d s = 2 (q - y), q = sigmoid(2 s - 1); d / d dot = that * s (1 - s).
+// = lse - x_y with lse = log(e^(1-s) + e^s); d term / d s = 2 (q - y), q = sigmoid(2 s - 1); d / d dot = that * s (1 - s), with
+// 1 - s taken as sigmoid(-dot): 1.f - s keeps only an absolute ulp of 1 (no digit at all once s rounds to 1, dot above ~17).
 // grad[p] = inv_n * d term / d dot; loss = inv_n * sum of the terms (block partials in double, added in block order).
 #define NE_LOSS_BLOCKS_MAX 4096
 template <int L, int C>
@@ -321,14 +322,14 @@ __global__ __launch_bounds__(64 * NE_WAVES) void ne_link_loss_kernel(const float
         for (int off = L / 2; off > 0; off >>= 1) d += __shfl_xor(d, off);
         double term = 0.0;
         if (p < n_pairs && li == 0) {
-            const float s = 1.f / (1.f + expf(-d));
+            const float s = 1.f / (1.f + expf(-d)), sn = 1.f / (1.f + expf(d));      // sigmoid(d), sigmoid(-d) = 1 - s
             const float y = p < n_pos ? 1.f : 0.f;
             const float q = 1.f / (1.f + expf(1.f - 2.f * s));
             const float m = fmaxf(s, 1.f - s);
             const float lse = m + log1pf(expf(-fabsf(2.f * s - 1.f)));
             term = (double)(lse - (p < n_pos ? s : 1.f - s));
             s_out[p] = s;
-            if (g_out) g_out[p] = (float)(inv_n * (double)(2.f * (q - y) * s * (1.f - s)));
+            if (g_out) g_out[p] = (float)(inv_n * (double)(2.f * (q - y) * s * sn));
         }
         if (li == 0) terms[wave * G + g] = term;
         __syncthreads();

@@ -146,7 +146,9 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
             __syncthreads();
         }
         const float total = (float)sqrt(shd[0]);
-        gs = fminf(max_norm / (total + 1e-6f), 1.f);
+        // a NaN norm (a NaN gradient anywhere) gives a NaN coefficient, as torch's clamp(max_norm / (total + 1e-6), max=1)
+        // does, so every parameter turns NaN as under clip_grad_norm_ (fminf would return 1 and step the others unclipped)
+        gs = total != total ? total : fminf(max_norm / (total + 1e-6f), 1.f);
         if (coef_out && b == 0 && threadIdx.x == 0) { coef_out[0] = gs; coef_out[1] = total; }
     }
     const double st = counters ? (double)counters[T.slot[t]] : (double)host_step;
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
                     const bool nz = gg[u].x != 0.f || gg[u].y != 0.f || gg[u].z != 0.f || gg[u].w != 0.f;
                     any[u] = (__ballot(nz) & rowmask) != 0ull;
                     was[u] = in[u] ? seen[idx[u] >> sh] != 0 : false;
-                    act[u] = in[u] && (any[u] || was[u]);
+                    act[u] = in[u] && (any[u] || was[u] || gs != gs);        // a NaN coefficient poisons every row
                 }
                 float4 pp[U], mm[U], vv[U];
 #pragma unroll

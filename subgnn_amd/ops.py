@@ -1069,6 +1069,7 @@ def sort_edges_by_key(keys, max_key):
     return sk, order
 
 
+SCATTER_MAX_D = 256                    # row width of sgnn_scatter_add_rows_sorted (64 lanes x 4 columns); wider: SGNN_ERR_UNSUPPORTED_D
 SCATTER_TOGETHER_BELOW = 1 << 16       # edges: shorter lists into a tapped table wait for the step's other lists (one sort, one scatter)
 
 
@@ -1814,6 +1815,17 @@ class OptimTail:
         parameters of the list (those of ``which`` advance).  Returns the (2,) device tensor [coefficient, total norm] when
         clipping, else None."""
         lib = _lib.load()
+        empty = [j for j, p_i in enumerate(which) if self.numels[p_i] == 0]
+        if empty:
+            # an empty parameter has nothing to clip or update (and its data_ptr() is 0): it stays out of the launches, and only
+            # its step count advances, as torch.optim.Adam's does
+            if step_counters is not None:
+                _req(step_counters, torch.int64, 'step_counters')
+                slots = np.asarray([which[j] for j in empty], dtype=np.int64)
+                check(lib.sgnn_optim_count(_ptr(step_counters), slots.ctypes.data, len(empty), _stream()), 'sgnn_optim_count')
+            keep = [j for j in range(len(which)) if self.numels[which[j]] != 0]
+            which, grads = [which[j] for j in keep], [grads[j] for j in keep]
+            steps = [steps[j] for j in keep] if steps is not None else None
         k = len(which)
         if k == 0:
             return None
@@ -2984,9 +2996,21 @@ class _LinkLoss(torch.autograd.Function):
         gd = gd * g_loss
         dZ = torch.zeros_like(Z)
         n_pos = pos_u.numel()
+        D = Z.shape[1]
         for (u, v, gg, pre) in ((pos_u, pos_v, gd[:n_pos], ctx.pos_sorted), (neg_u, neg_v, gd[n_pos:], None)):
-            if u.numel():
-                scatter_add_rows(dZ, torch.cat([u, v]), G=Z, edge_row=torch.cat([v, u]), c1=torch.cat([gg, gg]), presorted=pre)
+            if not u.numel():
+                continue
+            keys, rows, c1 = torch.cat([u, v]), torch.cat([v, u]), torch.cat([gg, gg])
+            if D <= SCATTER_MAX_D:
+                scatter_add_rows(dZ, keys, G=Z, edge_row=rows, c1=c1, presorted=pre)
+                continue
+            # wider than the scatter kernel's rows (output 260..512): one sort, column blocks of SCATTER_MAX_D scattered in turn
+            pre = pre if pre is not None else sort_edges_by_key(keys, Z.shape[0] - 1)
+            for a in range(0, D, SCATTER_MAX_D):
+                Zc = Z[:, a:a + SCATTER_MAX_D].contiguous()
+                dZc = dZ[:, a:a + SCATTER_MAX_D].contiguous()
+                scatter_add_rows(dZc, keys, G=Zc, edge_row=rows, c1=c1, presorted=pre)
+                dZ[:, a:a + SCATTER_MAX_D] = dZc
         return dZ, None, None, None, None, None
 
 

@@ -2,7 +2,8 @@
 -> clip_grad_norm_, then SubGNN.configure_optimizers' torch.optim.Adam, SubGNN/SubGNN.py:1156-1161), over every parameter in two
 launches (ops.OptimTail: sgnn_optim_sumsq, sgnn_optim_adam) instead of torch's multi-tensor norm, multiply and fused Adam
 around a chunked pass over the (N+1, D) embedding table.  Same update rule, same clipping rule (coefficient = min(1, max_norm /
-(total_norm + 1e-6)) over ALL parameters); the coefficient stays a device scalar, so the step has no host round trip."""
+(total_norm + 1e-6)) over ALL parameters, NaN when the norm is NaN, as torch's clamp leaves it); the coefficient stays a device
+scalar, so the step has no host round trip."""
 import torch
 
 from . import ops
@@ -15,7 +16,8 @@ def fusable(params):
 
 
 class ClipAdam:
-    """``step()`` = clip_grad_norm_(params, max_norm) followed by Adam(params, lr).step();  ``zero_grad()`` as usual.
+    """``step()`` = clip_grad_norm_(params, max_norm) followed by Adam(params, lr).step(), non-finite gradients included (a NaN
+    anywhere makes every parameter NaN, as there);  ``zero_grad()`` as usual.
     After ``step()`` the gradient of a large parameter is gone (``p.grad is None``): its buffer, zeroed by the update
     kernel, hangs on the parameter (``ops.release_zeroed``) and becomes the next backward's accumulator -- a caller that
     kept a reference to ``p.grad`` across ``step()`` holds that recycled buffer, not the old gradient.  ``release()``

@@ -196,22 +196,23 @@ def test_adam_step_matches_torch(wd, scaled, n):
     assert_close(p, q.detach(), 'Adam(weight_decay=%g, scaled=%s, n=%d)' % (wd, scaled, n), tol=1e-5)
 
 
+@pytest.mark.parametrize('hidden, output', [(64, 32), (260, 20), (512, 100)])     # (the ragged and <64, 2> forms in one step)
 @pytest.mark.parametrize('conv', ['gin', 'gcn'])
 @pytest.mark.parametrize('direction', ['reference', 'both'])
-def test_one_training_step_against_float64(conv, direction):
+def test_one_training_step_against_float64(conv, direction, hidden, output):
     from oracle.tape import draw64_np
     from subgnn_amd import ops, tape
     from subgnn_amd.train_node_emb import Messages, Trainer, edge_split, BETAS, ADAM_EPS
     g, _ = hub_graph()
     m = Messages(g, conv, direction)
-    tr = Trainer(g, m, edge_split(m.pos_u.numel(), 3), conv, 64, 32, 1e-3, 5e-4, 0.4, 3)
+    tr = Trainer(g, m, edge_split(m.pos_u.numel(), 3), conv, hidden, output, 1e-3, 5e-4, 0.4, 3)
     p0 = [p.detach().double().clone() for p in tr.params]
     tr.step(0)
     grads = [p.grad.detach() for p in tr.params]
     nu, nv = tr.last_negatives
     # float64 replica given the same negatives and masks
     A = _sparse(m.fwd, m.a_self).to_dense()
-    n, hid = A.shape[0], 64
+    n, hid = A.shape[0], hidden
     v, f = np.meshgrid(np.arange(n, dtype=np.uint64), np.arange(hid, dtype=np.uint64), indexing='ij')
     keep = (draw64_np(3, tr.stream(tape.STREAM_NE_DROP, epoch=0), v, f) >> np.uint64(32)) >= np.uint64(ops.dropout_threshold(0.4))
     mask = torch.from_numpy(keep).to(DEV).double() / 0.6
