@@ -100,22 +100,35 @@ class ClipAdam:
                     p.grad.zero_()
 
     # -- checkpointing (torch.optim.Optimizer's surface: what a Lightning-style caller saves and restores) ----------------------
-    def state_dict(self):
-        """Moments, step counts and the row-skip bytes of every parameter, by position in ``param_groups[0]['params']`` (as
-        torch keys optimizer state).  Device step counters are read back (one host round trip)."""
+    def state_refs(self):
+        """``state_dict``'s structure holding the LIVE tensors: no copy and no read-back -- a device step count is a 0-d view
+        of the counters (what checkpoint.Snapshot copies on the device when a trainer keeps an epoch)."""
         pos = {id(p): i for i, p in enumerate(self.param_groups[0]['params'])}
-        counts = self.counters.tolist() if self.counters is not None else None
         state = {}
         for k, p in enumerate(self.all):
             st = self.state[id(p)]
-            ent = {'step': int(counts[k] if counts is not None else st['step']),
-                   'exp_avg': st['exp_avg'].detach().clone(), 'exp_avg_sq': st['exp_avg_sq'].detach().clone()}
+            ent = {'step': self.counters[k] if self.counters is not None else int(st['step']),
+                   'exp_avg': st['exp_avg'], 'exp_avg_sq': st['exp_avg_sq']}
             if k in self.tail.seen:
-                ent['rows_seen'] = self.tail.seen[k].detach().clone()
+                ent['rows_seen'] = self.tail.seen[k]
             state[pos[id(p)]] = ent
         group = {k: v for k, v in self.param_groups[0].items() if k != 'params'}
         group['params'] = list(range(len(self.param_groups[0]['params'])))
         return {'state': state, 'param_groups': [group]}
+
+    def state_dict(self):
+        """Moments, step counts and the row-skip bytes of every parameter, by position in ``param_groups[0]['params']`` (as
+        torch keys optimizer state).  Device step counters are read back (one host round trip)."""
+        sd = self.state_refs()
+        counts = self.counters.tolist() if self.counters is not None else None
+        pos = {id(p): i for i, p in enumerate(self.param_groups[0]['params'])}
+        for k, p in enumerate(self.all):
+            ent = sd['state'][pos[id(p)]]
+            ent['step'] = int(counts[k]) if counts is not None else ent['step']
+            for name in ('exp_avg', 'exp_avg_sq', 'rows_seen'):
+                if name in ent:
+                    ent[name] = ent[name].detach().clone()
+        return sd
 
     def load_state_dict(self, sd):
         """Inverse of ``state_dict``.  A checkpoint without the row-skip bytes (moments restored from elsewhere) marks every row

@@ -220,15 +220,18 @@ def time_steps(model, opt, hp, steps, warmup, graph, count=False):
     return ms, float(loss.detach()), n_k
 
 
-def time_epochs(model, hp, epochs=4):
+def time_epochs(model, hp, epochs=4, trainer_kw=None):
     """Whole EPOCHS of the reference's loop (train_config.py:156-186 / SubGNN.py:350-464) on a prepared model, as
     train_config.Trainer runs them: replayed training steps, the validation steps, validation_epoch_end (metrics,
     init_all_embeddings, anchor resample when hparams ask for it) and any re-recording -> dict: wall ms per epoch (mean over
-    the epochs after the first, which also pays the eager warm-up steps and the recordings) and where it goes."""
+    the epochs after the first, which also pays the eager warm-up steps and the recordings) and where it goes.
+    ``trainer_kw``: more Trainer arguments (checkpoint_dir / checkpoint_k: the epoch then includes the snapshot of a kept
+    epoch, also reported on its own with the write at the end of fit)."""
     import time
     from .train_config import Trainer
     import gc
-    tr = Trainer(epochs, hp.get('grad_clip', 0.0), log=lambda *a, **k: None, hip_graph_step=bool(hp.get('hip_graph_step', True)))
+    tr = Trainer(epochs, hp.get('grad_clip', 0.0), log=lambda *a, **k: None, hip_graph_step=bool(hp.get('hip_graph_step', True)),
+                 **(trainer_kw or {}))
     tr.phase_times = []
     # (Trainer.fit freezes the heap after prepare_data: a full collection over the few million container objects the loaded
     # dataset left behind costs tens of ms when it happens.  The 50-80 ms stalls of single epochs -- 22 / 78 / 22 / 78 ms on the
@@ -241,6 +244,8 @@ def time_epochs(model, hp, epochs=4):
     wall = time.perf_counter() - t0
     later = tr.phase_times[2:] or tr.phase_times[1:] or tr.phase_times      # (epoch 0: warm-up steps + the training recording; epoch 1 may
     keys = ('train_steps_s', 'validation_steps_s', 'validation_epoch_end_s')  #  still record the validation forward of a one-batch split)
+    if tr.checkpoint_k > 0:
+        keys += ('checkpoint_s',)
     # the MEDIAN epoch (every epoch is listed beside it): in a long-lived process single epochs stall by tens of ms for reasons
     # outside the loop (allocator growth after an empty_cache, a collector pass) -- the mean of four epochs was 17 / 17 / 90 / 95 ms
     order = sorted(later, key=lambda r: sum(r.get(k, 0.0) for k in keys))
@@ -259,7 +264,9 @@ def time_epochs(model, hp, epochs=4):
             'recordings_after_the_first_epoch': sum(r.get('recordings', 0) for r in later),
             'resample_anchor_patches': bool(hp.get('resample_anchor_patches', False)),
             'every_epoch_ms': [{k[:-2]: round(1e3 * r.get(k, 0.0), 2) for k in keys} for r in tr.phase_times],
-            'monitor_last': tr.history[-1] if tr.history else None}
+            'monitor_last': tr.history[-1] if tr.history else None,
+            **({'checkpoint_ms_of_kept_epochs': [round(1e3 * r['checkpoint_s'], 3) for r in tr.phase_times if r.get('checkpoint_kept')],
+                'checkpoint_write_s': round(tr.checkpoint_write_s, 4)} if tr.checkpoint_k > 0 else {})}
 
 
 def bench_config(name, steps=30, warmup=5, deterministic=True, root=None, count=True, also_atomics=False, epochs=0):

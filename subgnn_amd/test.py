@@ -5,6 +5,10 @@ the seed, SubGNN/test.py:63-70 -> train.py), run the test split, collect ``test_
 ``test_acc``, ``test_auroc`` (SubGNN/test.py:84-86); then write means / standard deviations and the
 per-seed lists to ``experiment_results.json`` with the reference's keys (SubGNN/test.py:88-101).
 Seeds are 0..n-1, or random in [0, 10^6] with ``-random_seeds`` (SubGNN/test.py:65).
+
+``-checkpoint_k k`` (k >= 1) keeps each seed's k best epochs by the monitored metric in ``version_<i>`` and tests the best of
+them: the reference's protocol (ModelCheckpoint(save_top_k=1), train.py:327-334,389-409).  The default, 0, tests the last
+epoch's weights.  ``-no_train`` tests each ``version_<i>``'s best ``epoch*.ckpt`` again without training (test.py:73-82).
 """
 import argparse
 import copy
@@ -14,12 +18,17 @@ from pathlib import Path
 
 import numpy as np
 
-from . import config
+from . import checkpoint, config
 from .train_config import read_json, train_model
 
 
-def run_seeds(run_config, n_seeds=10, random_seeds=False, results_dir=None, log=print):
-    """Returns the experiment_results dict of SubGNN/test.py:52-57."""
+def run_seeds(run_config, n_seeds=10, random_seeds=False, results_dir=None, log=print, checkpoint_k=0, no_train=False):
+    """Returns the experiment_results dict of SubGNN/test.py:52-57.  ``checkpoint_k`` / ``no_train``: see the module's doc."""
+    if (checkpoint_k or no_train) and results_dir is None:
+        raise ValueError('checkpoints need a results_dir')
+    opt_cfg = run_config.get('optuna', {})
+    monitor = opt_cfg.get('monitor_metric', 'val_micro_f1')
+    mode = 'max' if opt_cfg.get('opt_direction', 'maximize') == 'maximize' else 'min'
     exp = {"test_acc_mean": 0, "test_acc_sd": 0, "test_micro_f1_mean": 0, "test_micro_f1_sd": 0,
            "test_auroc_mean": 0, "test_auroc_sd": 0, "test_acc": [], "test_micro_f1": [], "test_auroc": [],
            "call": {"task": run_config['data']['task'], "n_seeds": n_seeds, "random_seeds": bool(random_seeds)}}
@@ -29,8 +38,16 @@ def run_seeds(run_config, n_seeds=10, random_seeds=False, results_dir=None, log=
         cfg = copy.deepcopy(run_config)
         cfg['hyperparams_fix']['seed'] = seed
         out = Path(results_dir) / ('version_%d' % rnd) if results_dir is not None else None
-        _, model, trainer = train_model(cfg, results_dir=out, log=lambda *a: None)
-        trainer.test(model)
+        if no_train:
+            name = checkpoint.best_checkpoint(out, monitor, mode)
+            if name is None:
+                raise FileNotFoundError('no epoch*.ckpt in %s' % (out,))
+            _, model, _ = train_model(cfg, restore_path=out, restore_name=name, no_train=True, log=lambda *a: None)
+        elif checkpoint_k:
+            _, model, _ = train_model(cfg, results_dir=out, log=lambda *a: None, checkpoint_k=checkpoint_k, run_test=True)
+        else:
+            _, model, trainer = train_model(cfg, results_dir=out, log=lambda *a: None)
+            trainer.test(model)
         res = model.test_results
         for k in ('test_micro_f1', 'test_acc', 'test_auroc'):
             exp[k].append(float(res[k]))
@@ -53,11 +70,13 @@ def main(argv=None):
     ap.add_argument('-results_dir', type=str, default='tensorboard_test/sg')
     ap.add_argument('-n_seeds', type=int, default=10)
     ap.add_argument('-random_seeds', action='store_true')
+    ap.add_argument('-checkpoint_k', type=int, default=0, help='test each seed from its best of k kept epochs (0: the last epoch)')
+    ap.add_argument('-no_train', action='store_true', help="test each version_<i>'s best epoch*.ckpt without training")
     args = ap.parse_args(argv)
     if args.project_root:
         config.PROJECT_ROOT = Path(args.project_root)
     return run_seeds(read_json(args.config_path), args.n_seeds, args.random_seeds,
-                     Path(config.PROJECT_ROOT) / args.results_dir)
+                     Path(config.PROJECT_ROOT) / args.results_dir, checkpoint_k=args.checkpoint_k, no_train=args.no_train)
 
 
 if __name__ == '__main__':

@@ -30,7 +30,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import config
+from . import checkpoint, config
 from .SubGNN import SubGNN, dataset_paths
 from .optim import ClipAdam, accelerate
 
@@ -80,9 +80,10 @@ def get_hyperparams(run_config, trial):
     return hp
 
 
-def build_model(run_config, trial=None):
-    trial = trial or FixedTrial()
-    hp = get_hyperparams(run_config, trial)
+def build_model(run_config, trial=None, hp=None):
+    """``hp``: the hyper-parameters themselves (a restored run's hyperparams.json, train.py:233-237) instead of the config's."""
+    if hp is None:
+        hp = get_hyperparams(run_config, trial or FixedTrial())
     if 'seed' in hp:
         torch.manual_seed(hp['seed'])
         np.random.seed(hp['seed'])
@@ -98,9 +99,17 @@ class Trainer:
     gradient clipping, validation every epoch, best-by-monitor bookkeeping."""
 
     def __init__(self, max_epochs, gradient_clip_val=0.0, monitor='val_micro_f1', mode='max', log=print,
-                 hip_graph_step=True):
+                 hip_graph_step=True, checkpoint_dir=None, checkpoint_k=0):
         self.max_epochs, self.clip, self.monitor, self.mode, self.log = max_epochs, gradient_clip_val, monitor, mode, log
         self.best, self.history = None, []
+        # checkpoint_k >= 1: the k best epochs by ``monitor`` (checkpoint.TopK, PL 0.7.1's rule) are kept as device copies and
+        # written to ``checkpoint_dir`` with last.ckpt (the resume state) when fit returns; 0 writes nothing
+        self.checkpoint_dir = Path(checkpoint_dir) if checkpoint_dir is not None else None
+        self.checkpoint_k = int(checkpoint_k)
+        if self.checkpoint_k > 0 and self.checkpoint_dir is None:
+            raise ValueError('checkpoint_k > 0 needs a checkpoint_dir')
+        self.top_k = checkpoint.TopK(self.checkpoint_k, mode)
+        self.global_step = 0
         # Full batches replay a recorded step (graph_step.CapturedTrainStep) unless hparams['hip_graph_step'] is False: at the
         # reference's batch sizes the eager step is bound by the host's ~250 launches (3.5-11.5 ms against 1.3-4.6 ms replayed,
         # profiles/r03_bench_standin_*.json).  A short last batch runs eagerly; a model whose step cannot be recorded (an
@@ -166,11 +175,29 @@ class Trainer:
             lo += n
         return outs
 
-    def fit(self, model, prepared=False):
+    def fit(self, model, prepared=False, resume_from=None):
         """``prepared``: the caller has already run prepare_data (or hotpath.prepare_sparse for graphs whose dense structures
-        cannot exist)."""
+        cannot exist).  ``resume_from``: a last.ckpt written by a fit with checkpoint_k >= 1 -- training continues at its next
+        epoch, bit for bit the run it was written by (the weights, the optimizer, the anchor draw, the random generators, the
+        head's dropout state and this trainer's bookkeeping are restored; the step is recorded again here)."""
+        if resume_from is not None and checkpoint.resume_blocker(model):
+            raise ValueError(checkpoint.resume_blocker(model))
         if not prepared:
             model.prepare_data()
+        resume = None
+        if resume_from is not None:
+            resume = checkpoint.load(resume_from)
+            self._resumed_from = resume_from
+            checkpoint.check_resumable(model, resume)
+            st = resume[checkpoint.RESUME_KEY]
+            if st['hip_graph_step'] and not self.hip_graph_step:
+                raise ValueError('cannot resume bit for bit: the checkpoint was trained with recorded steps (unpadded eager '
+                                 'batches sum in another order); resume with hip_graph_step=True')
+            self.hip_graph_step = bool(st['hip_graph_step'])     # (a run that fell back to eager steps continues eagerly)
+            if model.hparams.get('resample_anchor_patches') and model.__dict__.get('_resample_epoch', 0) != st['resample_epoch']:
+                model.__dict__['_resample_epoch'] = st['resample_epoch']
+                model._prepare_anchors_only()
+            checkpoint.load_checkpoint(model, resume)
         if model.hparams.get('gc_freeze', True):
             # everything prepare_data left behind (the loaded dataset: subgraph lists, the graph's containers) lives as long as the
             # run: moved out of the cyclic collector's sight, so that a full collection does not walk a few million long-lived
@@ -181,13 +208,17 @@ class Trainer:
         # plain Adam over CUDA parameters (what configure_optimizers returns) becomes optim.ClipAdam: same update and clipping
         # rule, the embedding table in one HIP pass, the clip coefficient a device scalar (optim.accelerate)
         opt = accelerate(model.configure_optimizers(), self.clip, capturable=self.hip_graph_step)
+        start = 0
+        if resume is not None:
+            checkpoint.check_resumable(model, resume, opt)
+            start = self._restore(model, opt, resume)
         captured = None
         if self.hip_graph_step:
             from .graph_step import CapturedTrainStep, StepNotRecordable, make_capturable, make_eager
             if not isinstance(opt, ClipAdam):
                 make_capturable(opt)
         import time
-        for epoch in range(self.max_epochs):
+        for epoch in range(start, self.max_epochs):
             rec = None
             if self.phase_times is not None:
                 rec = {'replayed_steps': 0, 'eager_steps': 0, 'recordings': 0}
@@ -235,15 +266,132 @@ class Trainer:
                 t_ph = self._phase(rec, 'validation_steps_s', t_ph)
                 if rec is not None:
                     rec['validation_batches'] = len(outs)
+                drawn = model.__dict__.get('_resample_epoch', 0)      # (the anchor draw this epoch was validated with)
                 res = model.validation_epoch_end(outs)
                 t_ph = self._phase(rec, 'validation_epoch_end_s', t_ph)
             val = float(res['log'][self.monitor])
             if self.best is None or (val > self.best if self.mode == 'max' else val < self.best):
                 self.best = val
+            self.global_step += len(losses)
+            if self.checkpoint_k > 0:
+                kept = self._keep(model, opt, epoch, val, res['log'], drawn)
+                if rec is not None:
+                    rec['checkpoint_kept'] = kept
+                    t_ph = self._phase(rec, 'checkpoint_s', t_ph)
             tl = float(torch.stack(losses).mean()) if losses else float('nan')
             self.history.append({'epoch': epoch, 'train_loss': tl, 'val_loss': float(res['avg_val_loss']), self.monitor: val})
             self.log('epoch %d  train_loss %.4f  val_loss %.4f  %s %.4f' % (epoch, tl, float(res['avg_val_loss']), self.monitor, val))
+        if self.checkpoint_k > 0:
+            self._write(model, opt, max(start, self.max_epochs))
         return self
+
+    # -- checkpoints (checkpoint.py) ------------------------------------------------------------------------------------------
+    def _state_tensors(self, model, opt):
+        """The live tensors a kept epoch copies -- the model's state_dict, then the optimizer's state -- with the structures
+        that name them.  Looked up once per fit (and again after a fall-back to eager steps replaces the step counters)."""
+        key = (id(model), id(opt), self.hip_graph_step)
+        if self.__dict__.get('_ck_key') != key:
+            sd = model.state_dict()
+            refs = checkpoint.optimizer_state_refs(opt)
+            self._ck_refs = (list(sd), refs, list(sd.values()) + checkpoint._leaves(refs, []))
+            self._ck_key = key
+        keys, refs, src = self._ck_refs
+        if not self.hip_graph_step:                              # (host step counts: read now, they are not in ``src``)
+            refs = checkpoint.optimizer_state_refs(opt)
+        return keys, refs, src
+
+    def _keep(self, model, opt, epoch, value, logs, drawn):
+        enters, out = self.top_k.offer(epoch, value)
+        if not enters:
+            return False
+        if out is not None:
+            self.top_k.entries.remove(out)
+            if out['slot'] is None:                              # written by an earlier fit of this run (a resumed one)
+                self.__dict__.setdefault('_ck_stale', []).append(out['file'])
+        slots = self.__dict__.setdefault('_ck_slots', [])
+        held = {e['slot'] for e in self.top_k.entries}
+        free = next((i for i in range(len(slots)) if i not in held), None)
+        if free is None:
+            slots.append(checkpoint.Snapshot())
+            free = len(slots) - 1
+        keys, refs, src = self._state_tensors(model, opt)
+        slots[free].capture(src, {'epoch': epoch, 'global_step': self.global_step, 'keys': keys, 'refs': refs,
+                                  'resample_epoch': drawn})
+        self.top_k.entries.append({'epoch': epoch, 'value': value, 'file': checkpoint.checkpoint_name(epoch, self.monitor, logs),
+                                   'slot': free})
+        return True
+
+    def _info(self, value, resample_epoch):
+        return {'monitor': self.monitor, 'mode': self.mode, 'value': value, 'resample_epoch': resample_epoch}
+
+    def _write(self, model, opt, next_epoch):
+        """The kept epochs' files and last.ckpt (the run's state now), written when fit returns."""
+        import time
+        t0 = time.perf_counter()
+        d = self.checkpoint_dir
+        d.mkdir(parents=True, exist_ok=True)
+        slots = self.__dict__.get('_ck_slots', [])
+        for e in self.top_k.entries:
+            if e['slot'] is None:
+                continue
+            snap = slots[e['slot']]
+            keys, refs, meta = snap.meta['keys'], snap.meta['refs'], snap.meta
+            n = len(keys)
+            checkpoint.save({'epoch': meta['epoch'], 'global_step': meta['global_step'],
+                             'state_dict': {k: t.cpu() for k, t in zip(keys, snap.bufs[:n])},
+                             'optimizer_states': [checkpoint._optimizer_for_file(opt, refs, snap.bufs[n:])],
+                             checkpoint.INFO_KEY: self._info(e['value'], meta['resample_epoch'])}, d / e['file'])
+            e['slot'] = None                                     # (on disk now)
+        for f in self.__dict__.pop('_ck_stale', []):
+            if (d / f).exists() and f not in {e['file'] for e in self.top_k.entries}:
+                (d / f).unlink()
+        self.__dict__.pop('_ck_slots', None)
+        dev = model.node_embeddings.weight.device
+        head = model.__dict__.get('_head_rng')
+        resume = {'next_epoch': int(next_epoch), 'optimizer': checkpoint.optimizer_kind(opt), 'hip_graph_step': self.hip_graph_step,
+                  'generators': checkpoint.generator_states(dev), 'head_rng': head.cpu() if head is not None else None,
+                  'resample_epoch': int(model.__dict__.get('_resample_epoch', 0)),
+                  'metric_scores': list(model.metric_scores), 'history': list(self.history), 'best': self.best,
+                  'top_k': [dict(e) for e in self.top_k.entries], 'k': self.checkpoint_k, 'monitor': self.monitor,
+                  'mode': self.mode}
+        checkpoint.save({'epoch': int(next_epoch) - 1, 'global_step': self.global_step,
+                         'state_dict': checkpoint.to_cpu(model.state_dict()), 'optimizer_states': [checkpoint.to_cpu(opt.state_dict())],
+                         checkpoint.RESUME_KEY: resume}, d / checkpoint.LAST)
+        self.checkpoint_write_s = time.perf_counter() - t0
+
+    def _restore(self, model, opt, ck):
+        """The resume half of ``fit`` after the weights: optimizer, bookkeeping, generators.  -> the epoch to continue at."""
+        st = ck[checkpoint.RESUME_KEY]
+        if st['monitor'] != self.monitor or st['mode'] != self.mode:
+            raise ValueError('cannot resume: the checkpoint monitors %s (%s), this trainer %s (%s)' % (
+                st['monitor'], st['mode'], self.monitor, self.mode))
+        if self.checkpoint_k == 0:                               # (a resumed run checkpoints as the run it continues did)
+            self.checkpoint_k, self.top_k = int(st['k']), checkpoint.TopK(st['k'], self.mode)
+            if self.checkpoint_dir is None:
+                self.checkpoint_dir = Path(self.__dict__['_resumed_from']).parent
+        opt.load_state_dict(ck['optimizer_states'][0])
+        dev = model.node_embeddings.weight.device
+        if st['head_rng'] is not None:
+            model.__dict__['_head_rng'] = st['head_rng'].to(dev)
+        model.metric_scores[:] = st['metric_scores']
+        self.history, self.best, self.global_step = list(st['history']), st['best'], int(ck['global_step'])
+        self.top_k.entries = []
+        for e in sorted(st['top_k'], key=lambda e: e['epoch']):     # (already on disk: a smaller k keeps the best of them)
+            enters, out = self.top_k.offer(e['epoch'], e['value'])
+            if out is not None:
+                self.top_k.entries.remove(out)
+                self.__dict__.setdefault('_ck_stale', []).append(out['file'])
+            if enters:
+                self.top_k.entries.append(dict(e, slot=None))
+            elif self.checkpoint_k > 0:
+                self.__dict__.setdefault('_ck_stale', []).append(e['file'])
+        checkpoint.set_generator_states(st['generators'], dev)
+        return int(st['next_epoch'])
+
+    def best_checkpoint_path(self):
+        """The file of the best kept epoch (ties: the earliest), or None."""
+        b = self.top_k.best()
+        return self.checkpoint_dir / b['file'] if b is not None else None
 
     def test(self, model):
         model.eval()
@@ -252,36 +400,95 @@ class Trainer:
             return model.test_epoch_end(outs)
 
 
-def train_model(run_config, trial=None, results_dir=None, log=print):
-    model, hp = build_model(run_config, trial)
+def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_k=0, restore_path=None, restore_name=None,
+                no_train=False, run_test=False, resume=False, max_epochs=None):
+    """train.py's train_model (train.py:375-420) for one run.
+    ``checkpoint_k``: keep the k best epochs by the monitored metric in ``results_dir`` (ModelCheckpoint, train.py:327-334).
+    ``restore_path``: hyper-parameters from ``restore_path/hyperparams.json`` (``max_epochs`` overrides them); with
+    ``restore_name`` the weights of that checkpoint are loaded after prepare_data; ``resume`` continues from
+    ``restore_path/last.ckpt`` bit for bit.  ``no_train``: test the restored model without training (train.py:392-411).
+    ``run_test``: after training, test the best checkpoint (the last epoch when nothing was checkpointed) and write
+    ``test_results.json``.  -> (best monitored value, model, trainer)."""
+    hp = None
+    if restore_path is not None:
+        hp = json.loads((Path(restore_path) / 'hyperparams.json').read_text(), object_pairs_hook=OrderedDict)
+        if results_dir is None and not no_train:
+            results_dir = restore_path
+    elif resume or restore_name is not None:
+        raise ValueError('resume / restore_name need restore_path')
+    if max_epochs:
+        hp = hp if hp is not None else get_hyperparams(run_config, trial or FixedTrial())
+        hp['max_epochs'] = int(max_epochs)
+    model, hp = build_model(run_config, trial, hp)
     opt_cfg = run_config.get('optuna', {})
     monitor = opt_cfg.get('monitor_metric', 'val_micro_f1')
     mode = 'max' if opt_cfg.get('opt_direction', 'maximize') == 'maximize' else 'min'
     trainer = Trainer(hp['max_epochs'], hp.get('grad_clip', 0.0), monitor, mode, log,
-                      hip_graph_step=bool(hp.get('hip_graph_step', True)))
-    if results_dir is not None:
+                      hip_graph_step=bool(hp.get('hip_graph_step', True)), checkpoint_dir=results_dir,
+                      checkpoint_k=0 if no_train else checkpoint_k)
+    if results_dir is not None and not no_train:
         Path(results_dir).mkdir(parents=True, exist_ok=True)
         with open(Path(results_dir) / 'hyperparams.json', 'w') as f:
             json.dump({k: v for k, v in hp.items()}, f, indent=2, default=str)
-    trainer.fit(model)
-    scores = {k: (float(v) if hasattr(v, '__float__') else v) for k, v in model.metric_scores[-1].items()}
-    if results_dir is not None:
-        with open(Path(results_dir) / 'final_metric_scores.json', 'w') as f:
-            json.dump(scores, f, indent=2)
+    prepared = False
+    if restore_name is not None:
+        model.prepare_data()
+        prepared = True
+        checkpoint.load_checkpoint(model, Path(restore_path) / restore_name)
+    if not no_train:
+        trainer.fit(model, prepared=prepared, resume_from=Path(restore_path) / checkpoint.LAST if resume else None)
+    if no_train or run_test:
+        if not prepared and no_train:
+            model.prepare_data()
+        best_file = trainer.best_checkpoint_path() if not no_train else None
+        if best_file is not None:
+            checkpoint.load_checkpoint(model, best_file)
+        trainer.test(model)
+        out = results_dir if results_dir is not None else restore_path
+        if out is not None:
+            with open(Path(out) / 'test_results.json', 'w') as f:
+                json.dump({k: float(v) for k, v in model.test_results.items()}, f, indent=2)
+    if model.metric_scores:
+        scores = {k: (float(v) if hasattr(v, '__float__') else v) for k, v in model.metric_scores[-1].items()}
+        if results_dir is not None:
+            with open(Path(results_dir) / 'final_metric_scores.json', 'w') as f:
+                json.dump(scores, f, indent=2)
     return trainer.best, model, trainer
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Train SubGNN on MI355X from a reference-format config.json')
     ap.add_argument('-config_path', type=str, required=True)
     ap.add_argument('-project_root', type=str, default=None, help='overrides subgnn_amd.config.PROJECT_ROOT')
     ap.add_argument('-results_dir', type=str, default=None)
+    ap.add_argument('-max_epochs', type=int, default=None, help='overrides the hyper-parameters (a restored run\'s too)')
+    ap.add_argument('-checkpoint_k', type=int, default=0, help='keep the k best epochs by the monitored metric (0: none)')
+    ap.add_argument('-restoreModelPath', type=str, default=None, help='directory of a run: its hyperparams.json is used')
+    ap.add_argument('-restoreModelName', type=str, default=None, help='checkpoint file in -restoreModelPath to load')
+    ap.add_argument('-noTrain', action='store_true', help='test the restored model without training')
+    ap.add_argument('-runTest', action='store_true', help='test after training (the best checkpoint) -> test_results.json')
+    ap.add_argument('-resume', action='store_true', help='continue the run in -restoreModelPath from its last.ckpt')
     args = ap.parse_args(argv)
+    if (args.resume or args.restoreModelName or args.noTrain) and not args.restoreModelPath:
+        ap.error('-resume, -restoreModelName and -noTrain need -restoreModelPath')
+    if args.noTrain and not args.restoreModelName:
+        ap.error('-noTrain needs -restoreModelName')
+    if args.resume and (args.noTrain or args.restoreModelName):
+        ap.error('-resume restores last.ckpt: it takes neither -restoreModelName nor -noTrain')
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if args.project_root:
         config.PROJECT_ROOT = Path(args.project_root)
     run_config = read_json(args.config_path)
-    best, model, trainer = train_model(run_config, results_dir=args.results_dir)
-    print('best %s: %.4f' % (trainer.monitor, best))
+    best, model, trainer = train_model(run_config, results_dir=args.results_dir, checkpoint_k=args.checkpoint_k,
+                                       restore_path=args.restoreModelPath, restore_name=args.restoreModelName,
+                                       no_train=args.noTrain, run_test=args.runTest, resume=args.resume,
+                                       max_epochs=args.max_epochs)
+    if best is not None:
+        print('best %s: %.4f' % (trainer.monitor, best))
     return best
 
 
