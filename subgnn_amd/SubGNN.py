@@ -14,6 +14,7 @@ the loss are torch modules (MIOpen / rocBLAS).  Randomness is the draw tape keye
 ``hparams['seed']`` (subgnn_amd.tape).
 """
 import json
+import os
 from pathlib import Path
 
 import numpy as np
@@ -109,6 +110,20 @@ class _DeviceLoader:
     def __iter__(self):
         for idx in self.index_batches():
             yield self.m.make_batch(self.split, idx)
+
+
+def _save_npy(fname, arr):
+    """np.save(fname, arr) through a temporary name in the same directory and os.replace: a concurrent reader (search
+    trials sharing a similarity directory) sees the whole file or none.  The bytes are np.save's."""
+    fname = Path(fname)
+    tmp = fname.with_name('.%s.%d.tmp' % (fname.name, os.getpid()))
+    try:
+        with open(tmp, 'wb') as f:
+            np.save(f, arr)
+        os.replace(tmp, fname)
+    finally:
+        if tmp.exists():
+            tmp.unlink()
 
 
 class SubGNN(nn.Module):
@@ -350,12 +365,12 @@ class SubGNN(nn.Module):
             t = torch.from_numpy(np.load(fname, allow_pickle=True))
             return t.to(self.device) if dtype is None else t.to(self.device, dtype)
         t = compute()
-        np.save(fname, t.detach().cpu().numpy())
+        _save_npy(fname, t.detach().cpu().numpy())
         return t
 
     def initialize_border_sets(self, fname, cc_ids, radius, ego_graph_dict=None):
         t = subgraph_utils.border_sets(self.networkx_graph, cc_ids, radius, ego_dict_mode=ego_graph_dict is not None)
-        np.save(fname, t.cpu().numpy())
+        _save_npy(fname, t.cpu().numpy())
         return t
 
     def get_border_sets(self, split):
@@ -379,7 +394,7 @@ class SubGNN(nn.Module):
         S, C, L = cc_ids.shape
         sets = ops.Ragged.from_padded(cc_ids.reshape(S * C, L))
         sims = ops.sp_similarity_dense(shortest_paths, sets).view(S, C, -1)
-        np.save(fname, sims.cpu().numpy())
+        _save_npy(fname, sims.cpu().numpy())
         return sims
 
     def compute_structure_patch_similarities(self, degree_dict, fname, internal, cc_ids, sim_path=None,
@@ -393,7 +408,7 @@ class SubGNN(nn.Module):
         a_sets, a_seq = gamma.degree_sequences(g, self.structure_anchors, internal, use_dict)
         c_sets, c_seq = gamma.degree_sequences(g, cc_ids.reshape(S * C, L), internal, use_dict)
         sims = gamma.dtw_similarity_matrix(c_sets, c_seq, a_sets, a_seq, self.hparams['dtw_tie_order']).view(S, C, -1)
-        np.save(fname, sims.cpu().numpy())
+        _save_npy(fname, sims.cpu().numpy())
         return sims
 
     def get_similarities(self, split):

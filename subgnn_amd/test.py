@@ -6,6 +6,9 @@ the seed, SubGNN/test.py:63-70 -> train.py), run the test split, collect ``test_
 per-seed lists to ``experiment_results.json`` with the reference's keys (SubGNN/test.py:88-101).
 Seeds are 0..n-1, or random in [0, 10^6] with ``-random_seeds`` (SubGNN/test.py:65).
 
+``-restoreModelPath DIR`` (the reference's flag) takes the hyper-parameters from ``DIR/hyperparams.json`` -- a search
+trial's directory, e.g. the best trial of ``study_results.json`` -- and the dataset from ``-config_path``.
+
 ``-checkpoint_k k`` (k >= 1) keeps each seed's k best epochs by the monitored metric in ``version_<i>`` and tests the best of
 them: the reference's protocol (ModelCheckpoint(save_top_k=1), train.py:327-334,389-409).  The default, 0, tests the last
 epoch's weights.  ``-no_train`` tests each ``version_<i>``'s best ``epoch*.ckpt`` again without training (test.py:73-82).
@@ -18,8 +21,18 @@ from pathlib import Path
 
 import numpy as np
 
+from collections import OrderedDict
+
 from . import checkpoint, config
 from .train_config import read_json, train_model
+
+
+def restored_config(run_config, restore_path):
+    """``run_config`` with the hyper-parameters of ``restore_path/hyperparams.json`` fixed and nothing searched."""
+    cfg = copy.deepcopy(run_config)
+    cfg['hyperparams_fix'] = json.loads((Path(restore_path) / 'hyperparams.json').read_text(), object_pairs_hook=OrderedDict)
+    cfg['hyperparams_optuna'] = {}
+    return cfg
 
 
 def run_seeds(run_config, n_seeds=10, random_seeds=False, results_dir=None, log=print, checkpoint_k=0, no_train=False):
@@ -63,7 +76,7 @@ def run_seeds(run_config, n_seeds=10, random_seeds=False, results_dir=None, log=
     return exp
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Train and test SubGNN on MI355X for several seeds')
     ap.add_argument('-config_path', type=str, required=True, help='reference-format config.json')
     ap.add_argument('-project_root', type=str, default=None)
@@ -72,10 +85,19 @@ def main(argv=None):
     ap.add_argument('-random_seeds', action='store_true')
     ap.add_argument('-checkpoint_k', type=int, default=0, help='test each seed from its best of k kept epochs (0: the last epoch)')
     ap.add_argument('-no_train', action='store_true', help="test each version_<i>'s best epoch*.ckpt without training")
-    args = ap.parse_args(argv)
+    ap.add_argument('-restoreModelPath', type=str, default=None,
+                    help='directory whose hyperparams.json is used (a search trial); the dataset comes from -config_path')
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if args.project_root:
         config.PROJECT_ROOT = Path(args.project_root)
-    return run_seeds(read_json(args.config_path), args.n_seeds, args.random_seeds,
+    run_config = read_json(args.config_path)
+    if args.restoreModelPath:
+        run_config = restored_config(run_config, args.restoreModelPath)
+    return run_seeds(run_config, args.n_seeds, args.random_seeds,
                      Path(config.PROJECT_ROOT) / args.results_dir, checkpoint_k=args.checkpoint_k, no_train=args.no_train)
 
 

@@ -17,8 +17,9 @@ and torch, so the drop-in module can be exercised end to end on the GPU box:
   -> final_metric_scores.json from model.metric_scores[-1]          :189-193
   -> return the monitored metric                                    :196-200
 
-There is no hyper-parameter search here: a ``FixedTrial`` answers every ``suggest_*`` call with the
-first categorical choice / the lower bound (or a value supplied by the caller).
+A single run answers every ``suggest_*`` call with a ``FixedTrial``: the first categorical choice / the lower bound (or
+a value supplied by the caller).  ``-search`` runs the study instead (``subgnn_amd.search``: samplers, median pruning,
+concurrent trial processes).
 """
 import argparse
 import json
@@ -58,10 +59,10 @@ class FixedTrial:
     def suggest_categorical(self, name, choices):
         return self._pick(name, choices[0])
 
-    def suggest_float(self, name, low, high, **kw):
+    def suggest_float(self, name, low, high, *a, **kw):         # (*a: suggest_discrete_uniform's q, a positional step)
         return self._pick(name, float(low))
 
-    def suggest_int(self, name, low, high, **kw):
+    def suggest_int(self, name, low, high, *a, **kw):
         return self._pick(name, int(low))
 
     suggest_uniform = suggest_loguniform = suggest_discrete_uniform = suggest_float
@@ -80,8 +81,9 @@ def get_hyperparams(run_config, trial):
     return hp
 
 
-def build_model(run_config, trial=None, hp=None):
-    """``hp``: the hyper-parameters themselves (a restored run's hyperparams.json, train.py:233-237) instead of the config's."""
+def build_model(run_config, trial=None, hp=None, similarities_subdir=None):
+    """``hp``: the hyper-parameters themselves (a restored run's hyperparams.json, train.py:233-237) instead of the config's.
+    ``similarities_subdir``: the similarity cache lives in that subdirectory of the dataset's (a search trial's)."""
     if hp is None:
         hp = get_hyperparams(run_config, trial or FixedTrial())
     if 'seed' in hp:
@@ -91,6 +93,8 @@ def build_model(run_config, trial=None, hp=None):
         if torch.cuda.is_available():
             torch.cuda.manual_seed_all(hp['seed'])
     paths = dataset_paths(run_config['data']['task'], hp.get('embedding_type', 'gin'))
+    if similarities_subdir is not None:
+        paths['similarities_path'] = str(Path(paths['similarities_path']) / similarities_subdir)
     return SubGNN(hp, **paths), hp
 
 
@@ -175,11 +179,13 @@ class Trainer:
             lo += n
         return outs
 
-    def fit(self, model, prepared=False, resume_from=None):
+    def fit(self, model, prepared=False, resume_from=None, epoch_callback=None):
         """``prepared``: the caller has already run prepare_data (or hotpath.prepare_sparse for graphs whose dense structures
         cannot exist).  ``resume_from``: a last.ckpt written by a fit with checkpoint_k >= 1 -- training continues at its next
         epoch, bit for bit the run it was written by (the weights, the optimizer, the anchor draw, the random generators, the
-        head's dropout state and this trainer's bookkeeping are restored; the step is recorded again here)."""
+        head's dropout state and this trainer's bookkeeping are restored; the step is recorded again here).
+        ``epoch_callback(epoch, monitored value)``: called after each epoch's validation (and checkpoint bookkeeping); a true
+        return stops training after that epoch (a pruned search trial) -- last.ckpt then names the next epoch to run."""
         if resume_from is not None and checkpoint.resume_blocker(model):
             raise ValueError(checkpoint.resume_blocker(model))
         if not prepared:
@@ -218,6 +224,8 @@ class Trainer:
             if not isinstance(opt, ClipAdam):
                 make_capturable(opt)
         import time
+        next_epoch = max(start, self.max_epochs)
+        self.stopped_epoch = None
         for epoch in range(start, self.max_epochs):
             rec = None
             if self.phase_times is not None:
@@ -281,8 +289,12 @@ class Trainer:
             tl = float(torch.stack(losses).mean()) if losses else float('nan')
             self.history.append({'epoch': epoch, 'train_loss': tl, 'val_loss': float(res['avg_val_loss']), self.monitor: val})
             self.log('epoch %d  train_loss %.4f  val_loss %.4f  %s %.4f' % (epoch, tl, float(res['avg_val_loss']), self.monitor, val))
+            if epoch_callback is not None and epoch_callback(epoch, val):
+                self.stopped_epoch = next_epoch = epoch + 1
+                self.log('stopped after epoch %d by the epoch callback' % epoch)
+                break
         if self.checkpoint_k > 0:
-            self._write(model, opt, max(start, self.max_epochs))
+            self._write(model, opt, next_epoch)
         return self
 
     # -- checkpoints (checkpoint.py) ------------------------------------------------------------------------------------------
@@ -401,14 +413,15 @@ class Trainer:
 
 
 def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_k=0, restore_path=None, restore_name=None,
-                no_train=False, run_test=False, resume=False, max_epochs=None):
+                no_train=False, run_test=False, resume=False, max_epochs=None, epoch_callback=None, similarities_subdir=None):
     """train.py's train_model (train.py:375-420) for one run.
     ``checkpoint_k``: keep the k best epochs by the monitored metric in ``results_dir`` (ModelCheckpoint, train.py:327-334).
     ``restore_path``: hyper-parameters from ``restore_path/hyperparams.json`` (``max_epochs`` overrides them); with
     ``restore_name`` the weights of that checkpoint are loaded after prepare_data; ``resume`` continues from
     ``restore_path/last.ckpt`` bit for bit.  ``no_train``: test the restored model without training (train.py:392-411).
     ``run_test``: after training, test the best checkpoint (the last epoch when nothing was checkpointed) and write
-    ``test_results.json``.  -> (best monitored value, model, trainer)."""
+    ``test_results.json``.  ``epoch_callback``: Trainer.fit's; ``similarities_subdir``: build_model's (both for a search trial).
+    -> (best monitored value, model, trainer)."""
     hp = None
     if restore_path is not None:
         hp = json.loads((Path(restore_path) / 'hyperparams.json').read_text(), object_pairs_hook=OrderedDict)
@@ -419,7 +432,7 @@ def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_
     if max_epochs:
         hp = hp if hp is not None else get_hyperparams(run_config, trial or FixedTrial())
         hp['max_epochs'] = int(max_epochs)
-    model, hp = build_model(run_config, trial, hp)
+    model, hp = build_model(run_config, trial, hp, similarities_subdir=similarities_subdir)
     opt_cfg = run_config.get('optuna', {})
     monitor = opt_cfg.get('monitor_metric', 'val_micro_f1')
     mode = 'max' if opt_cfg.get('opt_direction', 'maximize') == 'maximize' else 'min'
@@ -436,7 +449,8 @@ def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_
         prepared = True
         checkpoint.load_checkpoint(model, Path(restore_path) / restore_name)
     if not no_train:
-        trainer.fit(model, prepared=prepared, resume_from=Path(restore_path) / checkpoint.LAST if resume else None)
+        trainer.fit(model, prepared=prepared, resume_from=Path(restore_path) / checkpoint.LAST if resume else None,
+                    epoch_callback=epoch_callback)
     if no_train or run_test:
         if not prepared and no_train:
             model.prepare_data()
@@ -462,13 +476,23 @@ def parse_args(argv=None):
     ap.add_argument('-project_root', type=str, default=None, help='overrides subgnn_amd.config.PROJECT_ROOT')
     ap.add_argument('-results_dir', type=str, default=None)
     ap.add_argument('-max_epochs', type=int, default=None, help='overrides the hyper-parameters (a restored run\'s too)')
-    ap.add_argument('-checkpoint_k', type=int, default=0, help='keep the k best epochs by the monitored metric (0: none)')
+    ap.add_argument('-checkpoint_k', type=int, default=None,
+                    help='keep the k best epochs by the monitored metric (default 0: none; 3 per trial with -search)')
     ap.add_argument('-restoreModelPath', type=str, default=None, help='directory of a run: its hyperparams.json is used')
     ap.add_argument('-restoreModelName', type=str, default=None, help='checkpoint file in -restoreModelPath to load')
     ap.add_argument('-noTrain', action='store_true', help='test the restored model without training')
     ap.add_argument('-runTest', action='store_true', help='test after training (the best checkpoint) -> test_results.json')
     ap.add_argument('-resume', action='store_true', help='continue the run in -restoreModelPath from its last.ckpt')
+    ap.add_argument('-search', action='store_true', help='run the hyper-parameter study (subgnn_amd.search) instead of one run')
+    from .search import add_search_args
+    add_search_args(ap)
     args = ap.parse_args(argv)
+    if args.search and (args.restoreModelPath or args.results_dir or args.max_epochs or args.runTest):
+        ap.error('-search takes none of -restoreModelPath, -results_dir, -max_epochs, -runTest')
+    if not args.search and (args.study_path or args.n_workers is not None):
+        ap.error('-study_path and -n_workers need -search')
+    if args.checkpoint_k is None:
+        args.checkpoint_k = 3 if args.search else 0
     if (args.resume or args.restoreModelName or args.noTrain) and not args.restoreModelPath:
         ap.error('-resume, -restoreModelName and -noTrain need -restoreModelPath')
     if args.noTrain and not args.restoreModelName:
@@ -480,6 +504,12 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.search:
+        from . import search
+        rc = search.main_from_args(args)
+        if rc:
+            raise SystemExit(rc)
+        return None
     if args.project_root:
         config.PROJECT_ROOT = Path(args.project_root)
     run_config = read_json(args.config_path)
