@@ -17,7 +17,8 @@ reads them, all on the GPU:
 
 The result plugs into SubGNN.forward through the per-edge similarity dict (see
 SubGNN._run_mpn_layer_fused).  Values are identical to what the dense path would gather from
-its slabs (tests/test_gpu_hotpath.py).
+its slabs (tests/test_gpu_hotpath.py).  The recorded passes (CapturedTraining, GraphedPasses) capture through
+graph_step.record and train with one body, ``train_half``.
 """
 import time
 
@@ -26,6 +27,7 @@ import collections
 import torch
 
 from . import ops, tape, gamma, subgraph_utils
+from .graph_step import record, recording_key
 from . import anchor_patch_samplers as aps
 
 MAX_PINT_BYTES = 16 << 30          # hop table (max_id+1) x (#distinct P-internal anchors) uint8 kept in HBM
@@ -899,7 +901,7 @@ def install_pass_static(model, st, timer=None):
 
 class CapturedTraining:
     """The training half of a pass -- component embeddings, the three channels, head, loss, backward, gradient clipping,
-    Adam (SubGNN.training_step -> backward -> optim.ClipAdam.step) -- recorded once into a hipGraph and replayed per pass.
+    Adam (``train_half``) -- recorded once into a hipGraph and replayed per pass.
     ~150 launches become one: the host needs ~0.1 ms instead of ~4 to queue them, so that under PassPipeline the training
     kernels of pass k are on the device BEFORE the host starts queueing the preparation of pass k + 1 (queued behind the
     preparation they started 4 ms late and ran into the DTW launch, which shares a CU with nothing).
@@ -907,9 +909,9 @@ class CapturedTraining:
         trainer = CapturedTraining(model, ClipAdam(..., capturable=True))
         per pass:  trainer.install(prepared_state);  loss, acc = trainer.step()
 
-    ``install`` keeps the recording's addresses valid (install_pass_static); a shape change records again.  The first
-    ``warmup`` steps run eagerly (lazy initialisations must not land in the recording).  Same kernels, same order, same
-    arithmetic as the eager step: losses and parameters are bit-equal (tests/test_gpu_hotpath.py)."""
+    ``install`` keeps the recording's addresses valid (install_pass_static); a shape change or a new learning rate records
+    again.  The first ``warmup`` steps run eagerly (lazy initialisations must not land in the recording).  Same kernels, same
+    order, same arithmetic as the eager step: losses and parameters are bit-equal (tests/test_gpu_hotpath.py)."""
 
     def __init__(self, model, optimizer, split='train', warmup=2):
         """``optimizer`` None: the recording ends with the backward pass -- the data-parallel form, whose gradient exchange and
@@ -927,6 +929,7 @@ class CapturedTraining:
         self.graph, self.loss, self.acc = None, None, None
         self._warm_left = int(warmup)
         self._installed = False
+        self._lrs = None
         self.recordings = 0
         self.last_changed = None
 
@@ -941,13 +944,7 @@ class CapturedTraining:
             self.last_changed = changed
 
     def _body(self):
-        m = self.model
-        out = m.training_step(full_split_batch(m, self.split), 0)
-        m.backward(None, out['loss'], None, 0)
-        if self.opt is not None:
-            self.opt.step()
-            self.opt.zero_grad(set_to_none=True)
-        return out['loss'].detach(), out['log']['train_acc'].detach()
+        return train_half(self.model, self.opt, self.split)
 
     def step(self):
         """-> (loss, accuracy): the recording's static outputs once it exists (clone to keep past the next step)."""
@@ -956,21 +953,15 @@ class CapturedTraining:
             sync()                               # (a sharded optimizer's all-gather of the table: the training half reads it)
         if self.opt is None and any(p.grad is not None for p in self.model.parameters()):
             raise RuntimeError('CapturedTraining without an optimizer: the caller must set the gradients to None after its update')
+        lrs = recording_key(self.model, self.opt)[1]
+        if lrs != self._lrs:
+            self.graph = None                    # (the recorded launches carry the learning rate: record again)
         if self.graph is None:
             if self._warm_left > 0:
                 self._warm_left -= 1
                 return self._body()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            try:
-                with torch.cuda.graph(g):
-                    self.loss, self.acc = self._body()
-            except Exception:
-                from .graph_step import abandon_capture
-                self.loss = self.acc = None
-                abandon_capture(self.model, self.opt)      # (buffers of the dead capture must not reach an eager step)
-                raise
-            self.graph = g
+            self.graph, (self.loss, self.acc) = record(self.model, self.opt, self._body)
+            self._lrs = lrs
             self.recordings += 1
             if self.opt is None:
                 self.static_grads = [(p, p.grad) for p in self.model.parameters() if p.grad is not None]
@@ -985,7 +976,7 @@ class CapturedTraining:
 class GraphedPasses:
     """BOTH halves of a pass replayed from hipGraphs, two slots: the sampling + similarity half (prepare_pass: ~130 launches
     on two streams) recorded into one graph that writes the pass's tensors at FIXED addresses, the training half
-    (CapturedTraining's body: ~135 launches) recorded into a second graph that reads exactly those addresses -- nothing is
+    (``train_half``: ~135 launches) recorded into a second graph that reads exactly those addresses -- nothing is
     installed or copied between them (CapturedTraining alone copies every pass into its recording's tensors: 0.7 ms of a 3.5 ms
     pass at shard size).  Two such pairs alternate, so that slot B's preparation replays on a second stream while slot A
     trains:
@@ -997,9 +988,10 @@ class GraphedPasses:
     host's ~265 launches) 4.7 ms eager -> 3.5 ms with the training half recorded -> see DESIGN 4 for this form.  Same kernels,
     same order, same arithmetic as prepare_pass + install_pass + the eager step: losses and parameters are bit-equal
     (tests/test_gpu_hotpath.py).  What a recording cannot contain -- a host round trip (torch.unique of the P-internal
-    anchors of multi-component subgraphs), collectives -- raises at record time; the caller falls back to PassPipeline.
+    anchors of multi-component subgraphs), collectives -- raises StepNotRecordable at record time; the caller falls back to
+    PassPipeline.
     The hinted position-channel searches are verified after every replay (status in pinned memory); one that ran out of
-    levels raises the hint and both slots are recorded again."""
+    levels raises the hint and both slots are recorded again, as they are after a change of the learning rate."""
 
     class _Slot:
         def __init__(self):
@@ -1020,47 +1012,48 @@ class GraphedPasses:
         if int(warmup) < 2:
             raise ValueError('GraphedPasses needs two eager passes before it records (the second one runs the kernels the first one chose)')
         self._warm_left = int(warmup)
+        self._lrs = None
         self.recordings = 0
 
     def _body(self):
-        m = self.model
-        out = m.training_step(full_split_batch(m, self.split), 0)
-        m.backward(None, out['loss'], None, 0)
-        self.opt.step()
-        self.opt.zero_grad(set_to_none=True)
-        return out['loss'].detach(), out['log']['train_acc'].detach()
+        return train_half(self.model, self.opt, self.split)
 
     def _record(self, i):
         """Slot i: record its preparation, run it once (a capture executes nothing), make its tensors the model's, record the
         training half on them."""
-        slot = self._Slot()
-        pool = self.model.__dict__.setdefault('_bfs_status_pool', [])
-        while len(pool) < 4 * max(1, int(self.model.hparams['n_layers'])):      # pinned buffers the recorded searches will take
+        m, slot = self.model, self._Slot()
+        pool = m.__dict__.setdefault('_bfs_status_pool', [])
+        while len(pool) < 4 * max(1, int(m.hparams['n_layers'])):      # pinned buffers the recorded searches will take
             pool.append(torch.empty(4, dtype=torch.int32).pin_memory())
-        torch.cuda.synchronize()
-        _settle_dtw_grouping(self.model, self.split, wait=True)     # (the recording keeps whatever kernels this decides on)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            slot.state = prepare_pass(self.model, self.split)
-        slot.prep = g
-        slot.checks = list(slot.state.bfs_checks)
-        g.replay()
-        torch.cuda.synchronize()
+        held = list(pool)
+        _settle_dtw_grouping(m, self.split, wait=True)     # (the recording keeps whatever kernels this decides on)
+        self._lrs = recording_key(m, self.opt)[1]
         try:
-            install_pass(self.model, slot.state)             # (verifies the searches of the replay above)
-        except BfsLevelsExhausted:
-            release_checks(self.model, slot.checks)
-            return self._record(i)                           # (the hint is the cap now: this happens at most once)
-        slot.state.bfs_checks = list(slot.checks)
-        g2 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g2):
-            slot.loss, slot.acc = self._body()
-        slot.train = g2
+            slot.prep, slot.state = record(m, self.opt, lambda: prepare_pass(m, self.split))
+            slot.checks = list(slot.state.bfs_checks)
+            slot.prep.replay()
+            torch.cuda.synchronize()
+            install_pass(m, slot.state)                      # (verifies the searches of the replay above)
+            slot.state.bfs_checks = list(slot.checks)
+            slot.train, (slot.loss, slot.acc) = record(m, self.opt, self._body)
+        except Exception as ex:
+            pool[:] = held                                   # every status buffer the dropped recording took (release_checks)
+            if isinstance(ex, BfsLevelsExhausted):
+                return self._record(i)                       # (the hint is the cap now: this happens at most once)
+            raise
         slot.prepared = True                                  # the replay above IS this slot's next pass
         slot.prep_done.record()
         self.slots[i] = slot
         self.recordings += 1
         return slot
+
+    def _drop_slots(self):
+        """Record both slots again (deeper searches, a new learning rate): their pinned status buffers return to the pool."""
+        torch.cuda.synchronize()
+        for sl in self.slots:
+            if sl is not None:
+                release_checks(self.model, sl.checks)
+        self.slots = [None, None]
 
     def step(self):
         """One pass -> (loss, accuracy): the recording's static outputs (clone to keep past the slot's next use)."""
@@ -1075,6 +1068,8 @@ class GraphedPasses:
             # decided form eagerly (its first call indexes with a mask: not recordable)
             _settle_dtw_grouping(self.model, self.split, wait=True)
             return out
+        if recording_key(self.model, self.opt)[1] != self._lrs and any(sl is not None for sl in self.slots):
+            self._drop_slots()                                 # (the recorded launches carry the learning rate)
         i = self.k & 1
         main = torch.cuda.current_stream()
         slot = self.slots[i] or self._record(i)
@@ -1086,11 +1081,7 @@ class GraphedPasses:
         try:
             _verify_bfs(self.model, slot.state, keep=True)
         except BfsLevelsExhausted:
-            torch.cuda.synchronize()
-            for sl in self.slots:                              # the dropped recordings' pinned status buffers return to the pool
-                if sl is not None:
-                    release_checks(self.model, sl.checks)
-            self.slots = [None, None]                          # deeper searches from now on: record again
+            self._drop_slots()                                 # deeper searches from now on: record again
             return self.step()
         slot.train.replay()
         slot.train_done.record(main)
@@ -1128,6 +1119,18 @@ def _whole_split_index(model, S):
         idx._sgnn_identity = S
         memo[S] = idx
     return memo[S]
+
+
+def train_half(model, optimizer, split):
+    """The training half of a full-split pass, eager or recorded (CapturedTraining, GraphedPasses) -> (loss, accuracy),
+    detached: training_step -> backward -> optimizer step -> zero_grad.  (Not the order of the batch step,
+    graph_step.train_step: each order is what its callers compare against.)  ``optimizer`` None: forward + backward only."""
+    out = model.training_step(full_split_batch(model, split), 0)
+    model.backward(None, out['loss'], None, 0)
+    if optimizer is not None:
+        optimizer.step()
+        optimizer.zero_grad(set_to_none=True)
+    return out['loss'].detach(), out['log']['train_acc'].detach()
 
 
 def full_split_batch(model, split):

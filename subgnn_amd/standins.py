@@ -183,23 +183,15 @@ def time_steps(model, opt, hp, steps, warmup, graph, count=False):
                 if idx.numel() == B:
                     yield idx
     it = index_batches()
-    from .optim import ClipAdam
-    own_clip = isinstance(opt, ClipAdam)                     # (clips inside its step: train_config.Trainer does the same)
+    from .graph_step import CapturedTrainStep, train_step
     if graph:
-        from .graph_step import CapturedTrainStep
-        cap = CapturedTrainStep(model, opt, B, 0.0 if own_clip else hp['grad_clip'])
+        cap = CapturedTrainStep(model, opt, B, hp['grad_clip'])
 
         def step():
             return cap.replay(next(it))[0]
     else:
         def step():
-            out = model.training_step(model.make_batch('train', next(it)), 0)
-            opt.zero_grad(set_to_none=True)
-            model.backward(None, out['loss'], opt, 0)
-            if not own_clip:
-                torch.nn.utils.clip_grad_norm_(model.parameters(), hp['grad_clip'])
-            opt.step()
-            return out['loss']
+            return train_step(model, opt, model.make_batch('train', next(it)), hp['grad_clip'])[0]
     for _ in range(warmup):
         step()
     # ``steps`` steps, timed in up to five equal blocks, the MEDIAN block reported: the boxes of this pool hold the device for

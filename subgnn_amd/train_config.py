@@ -33,7 +33,8 @@ import torch
 
 from . import checkpoint, config
 from .SubGNN import SubGNN, dataset_paths
-from .optim import ClipAdam, accelerate
+from .graph_step import CapturedEvalStep, CapturedTrainStep, StepNotRecordable, make_capturable, make_eager, train_step
+from .optim import accelerate
 
 
 def read_json(fname):
@@ -135,13 +136,7 @@ class Trainer:
         return t1
 
     def _eager_step(self, model, opt, batch, bi):
-        out = model.training_step(batch, bi)
-        opt.zero_grad(set_to_none=True)
-        model.backward(self, out['loss'], opt, 0)
-        if self.clip and self.clip > 0 and not isinstance(opt, ClipAdam):      # (ClipAdam clips inside its step)
-            torch.nn.utils.clip_grad_norm_(model.parameters(), self.clip)
-        opt.step()
-        return out['loss'].detach()
+        return train_step(model, opt, batch, self.clip)[0]
 
     def _validation_outputs(self, model):
         """[validation_step(batch) for batch in val_dataloader] (train_config.py:156-186 via PL's validation loop).  With
@@ -152,7 +147,6 @@ class Trainer:
         loader = model.val_dataloader()
         if not self.hip_graph_step or len(loader) == 0:
             return [model.validation_step(b, i) for i, b in enumerate(loader)]
-        from .graph_step import CapturedEvalStep, StepNotRecordable
         cap = self.__dict__.get('_captured_eval')
         if cap is None or cap.model is not model or cap.stale() or cap.B != min(loader.bs, loader.n):
             cap = self.__dict__['_captured_eval'] = CapturedEvalStep(model, min(loader.bs, loader.n), 'val', warmup=1)
@@ -220,9 +214,7 @@ class Trainer:
             start = self._restore(model, opt, resume)
         captured = None
         if self.hip_graph_step:
-            from .graph_step import CapturedTrainStep, StepNotRecordable, make_capturable, make_eager
-            if not isinstance(opt, ClipAdam):
-                make_capturable(opt)
+            make_capturable(opt)
         import time
         next_epoch = max(start, self.max_epochs)
         self.stopped_epoch = None
@@ -240,8 +232,7 @@ class Trainer:
                 # full batches replay the recorded step (graph_step.py); a ragged last batch, or
                 # anchors resampled at the end of the previous epoch, fall back / record again
                 if captured is None or captured.stale():
-                    captured = CapturedTrainStep(model, opt, loader.bs, 0.0 if isinstance(opt, ClipAdam) else self.clip,
-                                                 warmup=3 if captured is None else 0)
+                    captured = CapturedTrainStep(model, opt, loader.bs, self.clip, warmup=3 if captured is None else 0)
                     if rec is not None:
                         rec['recordings'] += 1
                 for bi, idx in enumerate(loader.index_batches()):
@@ -257,7 +248,7 @@ class Trainer:
                             # are the ones hip_graph_step=False would have run
                             self.log('hip_graph_step: the training step could not be recorded (%s); training eagerly' % (ex,))
                             self.hip_graph_step = False
-                            opt.make_eager() if isinstance(opt, ClipAdam) else make_eager(opt)
+                            make_eager(opt)
                             torch.cuda.synchronize()
                     losses.append(self._eager_step(model, opt, model.make_batch('train', idx), bi))
                     if rec is not None:

@@ -103,6 +103,14 @@ def test_recording_goes_stale_when_prepared_tensors_are_replaced(tiny, tmp_path)
     assert not cap.stale()
     m.prepare_data()                         # every prepared tensor is a new object now
     assert cap.stale()
+    # a learning rate reaches the recorded launches as a host float: a new one makes the recording stale, for torch's Adam
+    # and for ClipAdam alike
+    from subgnn_amd import optim
+    for opt in (m.configure_optimizers(), optim.ClipAdam(m.parameters(), 0.01, max_norm=1.0, capturable=True)):
+        cap = CapturedTrainStep(m, opt, 4, 1.0)
+        assert not cap.stale()
+        opt.param_groups[0]['lr'] *= 0.5
+        assert cap.stale()
 
 
 def test_training_step_is_bit_reproducible(tiny, tmp_path):

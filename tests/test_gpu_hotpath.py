@@ -355,8 +355,8 @@ def test_training_half_replayed_from_a_hipgraph_trains_like_the_eager_step(name,
     """hotpath.CapturedTraining: the training half (training_step -> backward -> ClipAdam) recorded into a hipGraph on
     the second pass and replayed, every later pass copied into the recording's tensors (install_pass_static) -- losses
     and parameters equal the eager prepare-then-train schedule bit for bit over 5 passes (clip + Adam with device-side
-    step counts; without dropout: a replayed graph draws its masks from its own Philox offsets).  Neither recording takes
-    a ClipAdam with host step counts."""
+    step counts; without dropout: a replayed graph draws its masks from its own Philox offsets).  A new learning rate after
+    pass 3 records again (the launches carry it).  Neither recording takes a ClipAdam with host step counts."""
     from conftest import load_golden
     from subgnn_amd import hotpath, optim
     from subgnn_amd.graph_step import CapturedTrainStep
@@ -370,6 +370,8 @@ def test_training_half_replayed_from_a_hipgraph_trains_like_the_eager_step(name,
     assert (len(o_cap.big) > 0) == (big_bytes < (1 << 30))
     want = []
     for k in range(5):
+        if k == 3:
+            o_seq.lr = 0.5 * lr
         hotpath.prepare_sparse(seq, 'train')
         out = seq.training_step(hotpath.full_split_batch(seq, 'train'), 0)
         out['loss'].backward()
@@ -382,6 +384,9 @@ def test_training_half_replayed_from_a_hipgraph_trains_like_the_eager_step(name,
         pipe = hotpath.PassPipeline(cap, 'train')
         pipe.start()
     for k in range(5):
+        if k == 3:
+            assert trainer.recordings == 1, trainer.last_changed
+            o_cap.param_groups[0]['lr'] = 0.5 * lr
         if pipelined:
             pipe.install(installer=trainer.install)
             ev = torch.cuda.Event()
@@ -393,7 +398,7 @@ def test_training_half_replayed_from_a_hipgraph_trains_like_the_eager_step(name,
             loss, acc = trainer.step()
         got.append(float(loss))
     torch.cuda.synchronize()
-    assert trainer.recordings == 1 and trainer.graph is not None, trainer.last_changed
+    assert trainer.recordings == 2 and trainer.graph is not None, trainer.last_changed
     assert got == want
     for (n1, a), (_, b) in zip(seq.named_parameters(), cap.named_parameters()):
         assert torch.equal(a, b), n1
@@ -408,7 +413,8 @@ def test_both_halves_replayed_from_hipgraphs_train_like_the_eager_passes(name, b
     """hotpath.GraphedPasses: the sampling + similarity half AND the training half of a pass recorded into hipGraphs, two
     alternating slots (slot B's preparation replays on a second stream while slot A trains), nothing installed or copied
     between the halves -- losses and parameters equal the eager prepare-then-train schedule bit for bit over 9 passes
-    (two eager warm-up passes, one recording per slot, five replayed passes)."""
+    (two eager warm-up passes, one recording per slot, two replayed passes; then a new learning rate, which records both
+    slots again, and three more passes)."""
     from conftest import load_golden
     from subgnn_amd import hotpath, optim
     golden = load_golden(name)
@@ -420,6 +426,8 @@ def test_both_halves_replayed_from_hipgraphs_train_like_the_eager_passes(name, b
     o_cap = optim.ClipAdam(cap.parameters(), lr, max_norm=clip, big_bytes=big_bytes, capturable=True)
     want = []
     for k in range(9):
+        if k == 6:
+            o_seq.lr = 0.5 * lr
         hotpath.prepare_sparse(seq, 'train')
         out = seq.training_step(hotpath.full_split_batch(seq, 'train'), 0)
         out['loss'].backward()
@@ -429,15 +437,92 @@ def test_both_halves_replayed_from_hipgraphs_train_like_the_eager_passes(name, b
     passes = hotpath.GraphedPasses(cap, o_cap, 'train', warmup=2)
     got = []
     for k in range(9):
+        if k == 6:
+            assert passes.recordings == 2
+            o_cap.lr = 0.5 * lr
         loss, acc = passes.step()
         got.append(float(loss))
     torch.cuda.synchronize()
-    assert passes.recordings == 2 and all(s is not None for s in passes.slots)
+    assert passes.recordings == 4 and all(s is not None for s in passes.slots)
     assert got == want
     for (n1, a), (_, b) in zip(seq.named_parameters(), cap.named_parameters()):
         assert torch.equal(a, b), n1
     with pytest.raises(ValueError):
         hotpath.GraphedPasses(cap, optim.ClipAdam(cap.parameters(), lr), 'train')
+
+
+@pytest.mark.parametrize('recorder', ['CapturedTrainStep', 'CapturedEvalStep', 'CapturedTraining', 'GraphedPasses'])
+def test_a_failed_recording_leaves_nothing_behind(recorder, tmp_path, monkeypatch):
+    """Every recorder captures through graph_step.record: an exception inside the capture (here a plain RuntimeError raised
+    after the real forward while the stream captures -- no HIP error) reaches the caller as StepNotRecordable, and nothing of
+    the dead capture is left: no gradient on a parameter, no queued layer body, every pinned BFS status buffer back in the
+    pool (GraphedPasses, whose training half is the capture that fails).  An eager pass then trains normally."""
+    from conftest import load_golden
+    from subgnn_amd import hotpath, ops, optim
+    from subgnn_amd.SubGNN import SubGNN
+    from subgnn_amd.graph_step import CapturedEvalStep, CapturedTrainStep, StepNotRecordable
+    golden = load_golden('density')
+    m, _ = _models(golden, tmp_path, {'lin_dropout': 0.0, 'lstm_dropout': 0.0})
+    m.train()
+    opt = optim.ClipAdam(m.parameters(), 0.01, max_norm=0.5, big_bytes=1024, capturable=True)
+    name = '_forward_batch' if recorder == 'CapturedEvalStep' else 'training_step'
+    real = getattr(SubGNN, name)
+
+    def not_recordable(self, *a):
+        out = real(self, *a)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('not recordable')
+        return out
+    monkeypatch.setattr(SubGNN, name, not_recordable)
+    pool = m.__dict__.setdefault('_bfs_status_pool', [])
+    held = None
+    idx = torch.arange(4)
+    if recorder == 'CapturedTrainStep':
+        hotpath.prepare_sparse(m, 'train')
+        cap = CapturedTrainStep(m, opt, idx.numel(), warmup=1)
+        cap.replay(idx)
+        with pytest.raises(StepNotRecordable):
+            cap.replay(idx)
+    elif recorder == 'CapturedEvalStep':
+        hotpath.prepare_sparse(m, 'train')
+        m.eval()
+        with torch.no_grad():
+            cap = CapturedEvalStep(m, idx.numel(), 'train', warmup=1)
+            cap.replay(idx)
+            with pytest.raises(StepNotRecordable):
+                cap.replay(idx)
+        m.train()
+    elif recorder == 'CapturedTraining':
+        trainer = hotpath.CapturedTraining(m, opt, 'train', warmup=1)
+        trainer.install(hotpath.prepare_pass(m, 'train'))
+        trainer.step()
+        trainer.install(hotpath.prepare_pass(m, 'train'))
+        with pytest.raises(StepNotRecordable):
+            trainer.step()
+        assert trainer.graph is None and trainer.recordings == 0
+    else:
+        passes = hotpath.GraphedPasses(m, opt, 'train', warmup=2)
+        passes.step()
+        passes.step()
+        held = list(pool)
+        with pytest.raises(StepNotRecordable):
+            passes.step()
+        assert passes.slots == [None, None] and passes.recordings == 0
+    torch.cuda.synchronize()
+    assert all(p.grad is None for p in m.parameters())
+    assert ops.lazy_mpn_pending() == 0
+    if held is not None:
+        # (the recording tops the pool up to four buffers per layer before it starts)
+        assert len(pool) == max(len(held), 4 * m.hparams['n_layers'])
+        assert all(any(h is x for x in pool) for h in held)
+    monkeypatch.undo()
+    hotpath.prepare_sparse(m, 'train')
+    out = m.training_step(hotpath.full_split_batch(m, 'train'), 0)
+    out['loss'].backward()
+    opt.step()
+    opt.zero_grad(set_to_none=True)
+    assert torch.isfinite(out['loss'])
+    assert all(bool(torch.isfinite(p).all()) for p in m.parameters())
 
 
 @pytest.mark.parametrize('tie', [1, 2])
