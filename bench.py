@@ -29,7 +29,9 @@ One step = one full pass of the hot path over the rank's shard, everything on th
 value = subgraphs processed by all ranks / max-over-ranks step time.
 
 Prints ONE short JSON line on rank 0: metric, value, ms_per_step, config, roofline and cpu_baseline in brief (result_line).
-The full result object is written to --details (default bench_details.json) with these extra objects:
+The full result object is written to --details (default bench_details.json).  A plain run only sets up, primes, warms up, times
+the --steps steps, writes --dump-outputs and prints the line; --full also measures, after the timed steps, these extra objects
+(and the north_star exchange of ``collectives`` at N > 1):
   roofline      the structure-channel CSR gather (sgnn_degree_sequence, the kernel BASELINE.json's target names) AS THE PASS RUNS
                 IT (lists of >= 512 entries answered from their membership bitmaps): the bytes that launch reads / its time inside the timed region, peak
                 8 TB/s; streaming_form beside it = the launch that moves SURVEY.md 8(d)'s algorithmic bytes (every neighbour list
@@ -108,16 +110,21 @@ def parse():
     ap.add_argument('--embed', type=int, default=64)
     ap.add_argument('--embedding-dtype', choices=['fp32', 'fp16'], default='fp32',
                     help="fp16: the fused kernels read an IEEE-half copy of the embedding table (fp32 accumulate, fp32 master)")
+    ap.add_argument('--full', action='store_true',
+                    help='measure everything beside the headline too: the rooflines, the N>1 north_star exchange, and at N=1 the '
+                         'extras, the projection and the CPU baseline (without it a run sets up, warms up, times the steps, '
+                         'dumps its outputs if asked and prints the line)')
     ap.add_argument('--no-extras', action='store_true',
-                    help='N=1: skip what is measured beside the headline in the same run -- the sequential two-stream schedule (what N>1 '
-                         'runs by default: the projection is computed from it), the live 6 250-subgraph strong-scaling shard, and the '
-                         'batch-sized training steps of the BASELINE configs[0,1,2,4] stand-ins (the ``configs`` object)')
+                    help='with --full, N=1: skip what is measured beside the headline in the same run -- the sequential two-stream '
+                         'schedule (what N>1 runs by default: the projection is computed from it), the live 6 250-subgraph '
+                         'strong-scaling shard, and the batch-sized training steps of the BASELINE configs[0,1,2,4] stand-ins (the '
+                         '``configs`` object)')
     ap.add_argument('--extras-budget-s', type=float, default=100.0, help='wall-clock budget of the stand-in configurations')
     ap.add_argument('--strong-rank-only', type=int, default=-1, metavar='RANK',
                     help='print ONLY the strong_rank8 object of this rank of 8 (the N = 1 line embeds it: measured in a fresh child '
                          'process, as a real rank is its own process -- inside the long-lived bench process the same loop is bound by a '
                          'slower host: 3.4 ms against 2.5)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-sample', type=int, default=2048)
     ap.add_argument('--details', metavar='FILE', default='bench_details.json',
                     help='where the full result object goes (every measurement beside the headline); the stdout line keeps the '
@@ -531,6 +538,179 @@ def strong_rank_only(args):
     print(json.dumps(line))
 
 
+def measure_rooflines(args, model, g, rowptr, hp, stage_ms, stage_each, elapsed, S, rank):
+    """--full: the roofline of the structure-channel CSR gather and of the other HBM-class kernels of the pass, priced from
+    launches of their own after the timed steps (``stage_ms`` / ``stage_each``: the timed passes' stage times), and the
+    committed counters of the longest kernel -> the ``roofline``, ``rooflines`` and ``longest_kernel`` objects."""
+    from subgnn_amd import ops, hotpath
+    n = args.nodes
+    # ---- roofline of the structure-channel CSR gather, measured live ------------------------
+    cc_ids = model.train_cc_ids
+    Sx, C, Lc = cc_ids.shape
+    cc_sets = ops.Ragged.from_padded(cc_ids.reshape(Sx * C, Lc))
+    set_lists = cc_sets.to_lists()
+    alg_bytes = degseq_algorithmic_bytes(rowptr, set_lists)                      # SURVEY 8(d): every list read in full
+    ds_bits = g.hub_tables() is not None                                          # (the lists of >= 512 entries have membership bitmaps)
+    alg_bytes_search = degseq_algorithmic_bytes(rowptr, set_lists, search='bits' if ds_bits else True)   # what the shipped launch reads
+    reps = 20
+    ds_order = model._degseq_order['train']
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def back_to_back(**kw):
+        ops.degree_sequence(g, cc_sets, order=ds_order, **kw)
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps):
+            ops.degree_sequence(g, cc_sets, order=ds_order, **kw)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps
+    # The roofline figure is a bandwidth, so it is taken on the launch that MOVES the algorithmic bytes: the
+    # streaming form of the kernel (every neighbour list read in full; sgnn_degree_sequence without the
+    # row-sorted CSR), 20 launches back to back on the launching stream.  The shipped launch (lists of
+    # >= 512 entries binary-searched for the set's members: same results, fewer bytes) is timed inside the
+    # timed region by the 'degree_sequences' stage events and priced with its own byte count.
+    ds_ms_stream = back_to_back(search_long_lists=False)
+    ds_ms_b2b = back_to_back()
+    # in the timed region the launch shares the chip with the other stream's kernels (the training half of the pass before):
+    # its event-to-event time there varies from pass to pass with what it happens to run beside (0.21-0.26 ms typically, the
+    # odd pass twice that) -- the figure is the MEDIAN over the timed passes, the mean and the extremes are reported beside it
+    ds_each = sorted(stage_each.get('degree_sequences', []))
+    ds_ms = (ds_each[len(ds_each) // 2] if len(ds_each) % 2 else 0.5 * (ds_each[len(ds_each) // 2 - 1] + ds_each[len(ds_each) // 2])) \
+        if ds_each else ds_ms_b2b
+    achieved = alg_bytes / (ds_ms_stream * 1e-3) / 1e9
+
+    # ---- the other HBM-class kernels of the pass, same recipe: SURVEY 8(d) bytes / live HIP-event time / 8 TB/s --------------
+    from subgnn_amd import tape as _tape
+
+    def timed(fn, reps_=10):
+        fn()
+        torch.cuda.synchronize()
+        e0.record()
+        for _ in range(reps_):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps_
+    deg_np = np.diff(rowptr)
+    list_bytes = int(sum(int((16 + 4 * deg_np[np.asarray(s_, dtype=np.int64)].astype(np.int64)).sum()) for s_ in set_lists))
+    n_members = int(sum(len(s_) for s_ in set_lists))
+    rooflines = []
+    if hp['use_neighborhood']:
+        k1_seed, k1_stream = int(hp.get('seed', 0)), _tape.stream_id(_tape.STREAM_N_BOR, 'train', 0)
+        _, _, k1_counts = ops.khop_border_sample(g, cc_sets, hp['neigh_sample_border_size'], hp['n_anchor_patches_N_out'], k1_seed, k1_stream)
+        k1_ms = timed(lambda: ops.khop_border_sample(g, cc_sets, hp['neigh_sample_border_size'], hp['n_anchor_patches_N_out'],
+                                                     k1_seed, k1_stream, width=model._border_width.get(('train', hp['neigh_sample_border_size'], cc_sets.n, 1))))
+        # 8(d) a8, k = 1: the frontier's lists + 4 (|CC| + |border|).  The kernel never writes the border (the draw is a rank query
+        # on the bitmap): achieved / frac price what it has to READ (lists + members); the formula with the border the reference
+        # materialises is beside it
+        k1_bytes = list_bytes + 4 * n_members
+        k1_bytes_8d = k1_bytes + 4 * int(k1_counts.sum())
+        rooflines.append({'kernel': 'khop1_sample_kernel<false> (sgnn_khop_border_sample: one-hop border + N-border draw, a8 + a4)',
+                          'bound': 'hbm', 'algorithmic_bytes_per_launch': k1_bytes, 'ms_per_launch': k1_ms,
+                          'achieved': k1_bytes / (k1_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                          'frac': k1_bytes / (k1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                          'survey_8d_bytes_with_the_border_written': k1_bytes_8d,
+                          'frac_on_survey_8d_bytes': k1_bytes_8d / (k1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                          'stage_ms_in_timed_region': stage_ms.get('border_bfs+N_anchors'),
+                          'note': 'issue- and barrier-bound on one 1024-thread workgroup per CU around a 125 KB LDS bitmap (r04 counters: 26 % of wave-cycles issuing, 57 % waiting; r05: its load phase runs at the fabric\'s rate, DESIGN 4), '
+                                  'not memory-bound; the lists come from L2 / Infinity Cache (the CSR is 88 MB)'})
+    if hp['use_position']:
+        src = model.anchors_pos_ext[0].to(torch.int32).contiguous()
+        nlev = hotpath._bfs_levels(model, ('P_out', 'train', 0), hp.get('max_bfs_hops', 32))
+        _, st_ = ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=nlev, want_status=True)
+        levels = int(st_[0]) + 1
+        bfs_ms = timed(lambda: ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=nlev))
+        words = (src.numel() + 63) // 64
+        nnz_dir = int(rowptr[-1])
+        # the bit-parallel search reads, per level and 64-source word, every node's row pointers and neighbour list once;
+        # 8(d) a9 as worded (one BFS per source: sum over visited nodes of 16 + 4 deg) would be n_sources x (16 N + 4 E)
+        bfs_bytes = levels * words * (16 * n + 4 * nnz_dir) + 4 * cc_sets.n * src.numel()
+        rooflines.append({'kernel': 'msbfs_* (sgnn_bfs_min_hops_to_sets: position-channel multi-source BFS + min over members, a9 sparse form)',
+                          'bound': 'hbm', 'algorithmic_bytes_per_launch': bfs_bytes, 'ms_per_launch': bfs_ms,
+                          'achieved': bfs_bytes / (bfs_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                          'frac': bfs_bytes / (bfs_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                          'levels': levels, 'source_words': words, 'sources': int(src.numel()),
+                          'per_source_8d_bytes': int(src.numel()) * (16 * n + 4 * nnz_dir),
+                          'note': 'all kernels of one search (init, expand / commit per level, set reduce) between two events; bytes = levels x '
+                                  'words x (16 N + 4 E): the pull levels gather a 32-byte row per edge out of 128-byte lines (DESIGN 4)'})
+    traffic = traffic_src = hbm_frac = traffic_shipped = None
+    out_of_cache = None
+    tf = next((f_ for f_ in (os.path.join(REPO, 'profiles', t_ + '_degseq_traffic.json') for t_ in ('r06', 'r05', 'r04', 'r02')) if os.path.exists(f_)), None)
+    tf_name = 'profiles/' + os.path.basename(tf) if tf else None
+    if tf:
+        # PMC passes cannot run inside this process; these are the committed rocprofv3 measurements
+        # (tools/run_hbm_probe.sh: separate --pmc passes, FETCH_SIZE calibrated on a copy of known size)
+        with open(tf) as f:
+            tj = json.load(f)
+        if args.nodes == 1_000_000 and S == 50_000 and args.m == 10 and rank == 0:
+            traffic = tj['benchmark_graph']['streaming']['memory_side_bytes_per_launch']
+            traffic_shipped = tj['benchmark_graph']['shipped_search']['memory_side_bytes_per_launch']
+            traffic_src = tf_name + ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; ' \
+                          'FETCH_SIZE x2 per the 4 B/lane calibration copy)'
+            hbm_frac = traffic / (ds_ms_stream * 1e-3) / 1e9 / HBM_PEAK_GBS
+        out_of_cache = {'graph': tj['out_of_cache']['bfs_sets']['graph'], 'csr_bytes': tj['out_of_cache']['bfs_sets']['csr_bytes'],
+                        'source': tf_name + ' (committed measurement, not re-run here)'}
+        for fam, c in tj['out_of_cache'].items():
+            out_of_cache[fam] = {form: {k: c[form][k] for k in ('ms_per_launch', 'algorithmic_frac_of_8TBs',
+                                                                'memory_side_frac_of_8TBs', 'traffic_over_algorithmic')}
+                                 for form in ('streaming', 'shipped_search')}
+    # the kernel that dominates the pass by TIME is not an HBM kernel: the DTW launch is bound by fp64 vector issue.  Its
+    # counters are a committed measurement (tools/run_dtw_pmc.sh), quoted beside the roofline of the HBM-class kernel.
+    longest = None
+    pj = next((f_ for f_ in (os.path.join(REPO, 'profiles', t_ + '_dtw_pmc.json') for t_ in ('r05', 'r04', 'r03')) if os.path.exists(f_)), None)
+    if pj:
+        pm = json.load(open(pj))
+        kk = [k for k in pm if 'dtw_similarity' in k]
+        if kk and stage_ms.get('dtw'):
+            c = pm[kk[0]]
+            wps = int(c.get('wavefronts_per_simd', 3))
+            longest = {'kernel': kk[0].split('(')[0], 'bound': 'fp64 vector issue (not HBM, not MFMA)',
+                       'share_of_step': round(stage_ms['dtw'] / (1e3 * elapsed / args.steps), 3),
+                       'simd_valu_busy': round(c.get('simd_valu_busy_from_grbm', min(1.0, wps * c['frac_wave_cycles_valu_active'])), 3),
+                       'wave_cycles': {'issuing': round(c['frac_wave_cycles_issuing'], 3),
+                                       'waiting_on_memory_or_barrier': round(c['frac_wave_cycles_waiting_waitcnt_or_barrier'], 3),
+                                       'issue_stalled': round(c['frac_wave_cycles_issue_stalled'], 3)},
+                       'valu_instructions_per_64_pairs': round(c['valu_instructions_per_64_pairs']),
+                       'source': 'profiles/' + os.path.basename(pj) + ' (rocprofv3 --pmc, committed measurement of the external-side launch; '
+                                 '%d wavefronts per SIMD; SIMD busy = 4 x SQ_ACTIVE_INST_VALU / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs))' % wps}
+    return {
+        # the kernel BASELINE.json's target names, as the pass RUNS it (lists of >= 512 entries binary-searched, not streamed):
+        # its own bytes / its time inside the timed region.  The streaming form (every list read in full: the launch that moves
+        # SURVEY 8(d)'s bytes) is beside it as streaming_form -- that is the figure the >= 40 % target is quoted on.
+        'roofline': {'kernel': ('degseq_wave_kernel<true, false, true> (sgnn_degree_sequence_hub_bitmaps: structure-channel CSR gather as '
+                                'the pass runs it; lists of >= %d entries answered from their membership bitmaps)' % DS_SEARCH) if ds_bits else
+                               ('degseq_wave_kernel<true, false, true> (sgnn_degree_sequence_sorted_rows: structure-channel CSR gather as '
+                                'the pass runs it; lists of >= %d entries searched)' % DS_SEARCH),
+                     'bound': 'hbm', 'achieved': alg_bytes_search / (ds_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
+                     'frac': alg_bytes_search / (ds_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                     # BASELINE.json's target (>= 40 % of the HBM roofline on the structure-channel CSR gather) is quoted on SURVEY 8(d)'s
+                     # algorithmic bytes: the figure of the launch that moves them (streaming_form below), repeated here at the top level
+                     'frac_of_roofline_on_survey_8d_bytes(streaming_form)': achieved / HBM_PEAK_GBS,
+                     'traffic': traffic_shipped, 'traffic_source': traffic_src,
+                     'algorithmic_bytes_per_launch': alg_bytes_search, 'ms_per_launch': ds_ms,
+                     'ms_per_launch_is': 'median over the %d timed passes of the HIP-event time of the launch on its stream' % len(ds_each),
+                     'ms_per_launch_mean_min_max': [round(sum(ds_each) / len(ds_each), 4), round(ds_each[0], 4), round(ds_each[-1], 4)] if ds_each else None,
+                     'ms_per_launch_back_to_back': ds_ms_b2b, 'sets_per_launch': cc_sets.n,
+                     'survey_8d_bytes_per_launch': alg_bytes,
+                     'survey_8d_bytes_over_this_time_GBs': alg_bytes / (ds_ms * 1e-3) / 1e9,
+                     'speedup_vs_streaming': ds_ms_stream / ds_ms,
+                     'streaming_form': {'kernel': 'degseq_wave_kernel<true, false, false> (every neighbour list streamed: moves SURVEY 8(d)\'s bytes)',
+                                        'achieved': achieved, 'frac': achieved / HBM_PEAK_GBS, 'ms_per_launch': ds_ms_stream,
+                                        'algorithmic_bytes_per_launch': alg_bytes, 'traffic': traffic, 'hbm_frac': hbm_frac,
+                                        'in_the_timed_pass': False},
+                     'out_of_cache': out_of_cache,
+                     'note': 'achieved = the bytes THIS launch reads (a list of >= 512 entries: 16 + 4 |S| -- one word of its membership bitmap per '
+                             'member, round 6; rounds 3-5 searched it: 16 + 4 min(deg, (floor(log2 deg) + 2) |S|)) / its time '
+                             'inside the timed region: it is latency-bound, and faster than the form that streams SURVEY 8(d)\'s bytes '
+                             '(survey_8d_bytes_over_this_time_GBs exceeds the peak: the launch does not move them).  streaming_form: 8(d) bytes / '
+                             'time of the launch that streams them, 20 launches back to back after the timed region (HIP events); on the '
+                             'benchmark graph an ON-DIE rate -- the CSR (88 MB) fits the 256 MiB Infinity Cache: hbm_frac = memory-side '
+                             'counter traffic over the same time.  out_of_cache: the same kernel on BA n=8M m=16 (CSR 1.09 GB)'},
+        'rooflines': rooflines,
+        'longest_kernel': longest}
+
+
 def main():
     args = parse()
     if args.strong_rank_only >= 0:
@@ -546,7 +726,7 @@ def main():
     early = None
     if world == 1 and 'RANK' not in os.environ:
         early = build_inputs(args, 0, 1)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 from oracle import cpu_baseline
                 cpu_baseline.start_pool(early[0], early[1])
@@ -865,9 +1045,15 @@ def main():
             print('step', i, {k: round(v, 3) for k, v in tm.summary().items()}, file=sys.stderr)
             print('     host', {k: round(v, 3) for k, v in tm.host_summary().items()}, file=sys.stderr)
 
-    # ---- N > 1: what crossed the links, and north_star's exchange timed in this very run ---------------------------
+    # ---- N > 1: what crossed the links, and (--full) north_star's exchange timed in this very run -------------------
     collectives = None
     if multi:
+        collectives = {
+            'rccl_ranks': dist.get_world_size(), 'backend': dist.get_backend(),
+            'per_step_ms': {k[5:]: round(v, 3) for k, v in stage_ms.items() if k.startswith('coll_')},
+            'table_all_gather_wait_ms': round(stage_ms.get('table_all_gather_wait', 0.0), 3),
+            'table_bytes': int(table.numel() * 4)}
+    if multi and args.full:
         # "RCCL all-gather of per-channel embeddings over xGMI" (BASELINE.json north_star): the (components, hid_dim) fp32
         # embeddings of this rank's shard gathered from every rank -- the collective the replicated head consumes inside
         # the step (--head replicated); with the default sharded head nothing needs it, so it is timed here on its own,
@@ -886,153 +1072,21 @@ def main():
         dist.all_reduce(ns, op=dist.ReduceOp.MAX)
         ns_ms = float(ns.item())
         per_rank = rows * model.hid_dim * 4
-        collectives = {
-            'rccl_ranks': dist.get_world_size(), 'backend': dist.get_backend(),
-            'per_step_ms': {k[5:]: round(v, 3) for k, v in stage_ms.items() if k.startswith('coll_')},
-            'table_all_gather_wait_ms': round(stage_ms.get('table_all_gather_wait', 0.0), 3),
-            'table_bytes': int(table.numel() * 4),
-            'north_star_exchange': {
-                'what': 'all-gather of the per-component channel embeddings (rows_per_rank, hid_dim) fp32 from every rank '
-                        '(dist.all_gather_rows: what dist.gather_rows_replicated issues for the replicated head)',
-                'rows_per_rank': rows, 'hid_dim': int(model.hid_dim), 'bytes_per_rank': per_rank,
-                'gathered_rows': int(gathered.shape[0]), 'ms': round(ns_ms, 3),
-                'algbw_GBs': round(per_rank * (world - 1) / (ns_ms * 1e-3) / 1e9, 1) if ns_ms > 0 else None,
-                'inside_the_timed_step': bool(replicated)}}
+        collectives['north_star_exchange'] = {
+            'what': 'all-gather of the per-component channel embeddings (rows_per_rank, hid_dim) fp32 from every rank '
+                    '(dist.all_gather_rows: what dist.gather_rows_replicated issues for the replicated head)',
+            'rows_per_rank': rows, 'hid_dim': int(model.hid_dim), 'bytes_per_rank': per_rank,
+            'gathered_rows': int(gathered.shape[0]), 'ms': round(ns_ms, 3),
+            'algbw_GBs': round(per_rank * (world - 1) / (ns_ms * 1e-3) / 1e9, 1) if ns_ms > 0 else None,
+            'inside_the_timed_step': bool(replicated)}
         del x, gathered
 
-    # ---- roofline of the structure-channel CSR gather, measured live ------------------------
-    cc_ids = model.train_cc_ids
-    Sx, C, Lc = cc_ids.shape
-    cc_sets = ops.Ragged.from_padded(cc_ids.reshape(Sx * C, Lc))
-    set_lists = cc_sets.to_lists()
-    alg_bytes = degseq_algorithmic_bytes(rowptr, set_lists)                      # every list read in full
-    ds_bits = g.hub_tables() is not None                                          # (the lists of >= 512 entries have membership bitmaps)
-    alg_bytes_search = degseq_algorithmic_bytes(rowptr, set_lists, search='bits' if ds_bits else True)   # what the shipped launch reads
-    reps = 20
-    ds_order = model._degseq_order['train']
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    # ---- --full: roofline of the structure-channel CSR gather and the other HBM-class kernels, measured live ------------------
+    figures = measure_rooflines(args, model, g, rowptr, hp, stage_ms, stage_each, elapsed, S, rank) if args.full else {}
 
-    def back_to_back(**kw):
-        ops.degree_sequence(g, cc_sets, order=ds_order, **kw)
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(reps):
-            ops.degree_sequence(g, cc_sets, order=ds_order, **kw)
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / reps
-    # The roofline figure is a bandwidth, so it is taken on the launch that MOVES the algorithmic bytes: the
-    # streaming form of the kernel (every neighbour list read in full; sgnn_degree_sequence without the
-    # row-sorted CSR), 20 launches back to back on the launching stream.  The shipped launch (lists of
-    # >= 512 entries binary-searched for the set's members: same results, fewer bytes) is timed inside the
-    # timed region by the 'degree_sequences' stage events and priced with its own byte count.
-    ds_ms_stream = back_to_back(search_long_lists=False)
-    ds_ms_b2b = back_to_back()
-    # in the timed region the launch shares the chip with the other stream's kernels (the training half of the pass before):
-    # its event-to-event time there varies from pass to pass with what it happens to run beside (0.21-0.26 ms typically, the
-    # odd pass twice that) -- the figure is the MEDIAN over the timed passes, the mean and the extremes are reported beside it
-    ds_each = sorted(stage_each.get('degree_sequences', []))
-    ds_ms = (ds_each[len(ds_each) // 2] if len(ds_each) % 2 else 0.5 * (ds_each[len(ds_each) // 2 - 1] + ds_each[len(ds_each) // 2])) \
-        if ds_each else ds_ms_b2b
-    achieved = alg_bytes / (ds_ms_stream * 1e-3) / 1e9
-
-    # ---- the other HBM-class kernels of the pass, same recipe: SURVEY 8(d) bytes / live HIP-event time / 8 TB/s --------------
-    from subgnn_amd import tape as _tape
-
-    def timed(fn, reps_=10):
-        fn()
-        torch.cuda.synchronize()
-        e0.record()
-        for _ in range(reps_):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / reps_
-    deg_np = np.diff(rowptr)
-    list_bytes = int(sum(int((16 + 4 * deg_np[np.asarray(s_, dtype=np.int64)].astype(np.int64)).sum()) for s_ in set_lists))
-    n_members = int(sum(len(s_) for s_ in set_lists))
-    rooflines = []
-    if hp['use_neighborhood']:
-        k1_seed, k1_stream = int(hp.get('seed', 0)), _tape.stream_id(_tape.STREAM_N_BOR, 'train', 0)
-        _, _, k1_counts = ops.khop_border_sample(g, cc_sets, hp['neigh_sample_border_size'], hp['n_anchor_patches_N_out'], k1_seed, k1_stream)
-        k1_ms = timed(lambda: ops.khop_border_sample(g, cc_sets, hp['neigh_sample_border_size'], hp['n_anchor_patches_N_out'],
-                                                     k1_seed, k1_stream, width=model._border_width.get(('train', hp['neigh_sample_border_size'], cc_sets.n, 1))))
-        # 8(d) a8, k = 1: the frontier's lists + 4 (|CC| + |border|).  The kernel never writes the border (the draw is a rank query
-        # on the bitmap): achieved / frac price what it has to READ (lists + members); the formula with the border the reference
-        # materialises is beside it
-        k1_bytes = list_bytes + 4 * n_members
-        k1_bytes_8d = k1_bytes + 4 * int(k1_counts.sum())
-        rooflines.append({'kernel': 'khop1_sample_kernel<false> (sgnn_khop_border_sample: one-hop border + N-border draw, a8 + a4)',
-                          'bound': 'hbm', 'algorithmic_bytes_per_launch': k1_bytes, 'ms_per_launch': k1_ms,
-                          'achieved': k1_bytes / (k1_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                          'frac': k1_bytes / (k1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                          'survey_8d_bytes_with_the_border_written': k1_bytes_8d,
-                          'frac_on_survey_8d_bytes': k1_bytes_8d / (k1_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                          'stage_ms_in_timed_region': stage_ms.get('border_bfs+N_anchors'),
-                          'note': 'issue- and barrier-bound on one 1024-thread workgroup per CU around a 125 KB LDS bitmap (r04 counters: 26 % of wave-cycles issuing, 57 % waiting; r05: its load phase runs at the fabric\'s rate, DESIGN 4), '
-                                  'not memory-bound; the lists come from L2 / Infinity Cache (the CSR is 88 MB)'})
-    if hp['use_position']:
-        src = model.anchors_pos_ext[0].to(torch.int32).contiguous()
-        nlev = hotpath._bfs_levels(model, ('P_out', 'train', 0), hp.get('max_bfs_hops', 32))
-        _, st_ = ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=nlev, want_status=True)
-        levels = int(st_[0]) + 1
-        bfs_ms = timed(lambda: ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=nlev))
-        words = (src.numel() + 63) // 64
-        nnz_dir = int(rowptr[-1])
-        # the bit-parallel search reads, per level and 64-source word, every node's row pointers and neighbour list once;
-        # 8(d) a9 as worded (one BFS per source: sum over visited nodes of 16 + 4 deg) would be n_sources x (16 N + 4 E)
-        bfs_bytes = levels * words * (16 * n + 4 * nnz_dir) + 4 * cc_sets.n * src.numel()
-        rooflines.append({'kernel': 'msbfs_* (sgnn_bfs_min_hops_to_sets: position-channel multi-source BFS + min over members, a9 sparse form)',
-                          'bound': 'hbm', 'algorithmic_bytes_per_launch': bfs_bytes, 'ms_per_launch': bfs_ms,
-                          'achieved': bfs_bytes / (bfs_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                          'frac': bfs_bytes / (bfs_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                          'levels': levels, 'source_words': words, 'sources': int(src.numel()),
-                          'per_source_8d_bytes': int(src.numel()) * (16 * n + 4 * nnz_dir),
-                          'note': 'all kernels of one search (init, expand / commit per level, set reduce) between two events; bytes = levels x '
-                                  'words x (16 N + 4 E): the pull levels gather a 32-byte row per edge out of 128-byte lines (DESIGN 4)'})
-    traffic = traffic_src = hbm_frac = traffic_shipped = None
-    out_of_cache = None
-    tf = next((f_ for f_ in (os.path.join(REPO, 'profiles', t_ + '_degseq_traffic.json') for t_ in ('r06', 'r05', 'r04', 'r02')) if os.path.exists(f_)), None)
-    tf_name = 'profiles/' + os.path.basename(tf) if tf else None
-    if tf:
-        # PMC passes cannot run inside this process; these are the committed rocprofv3 measurements
-        # (tools/run_hbm_probe.sh: separate --pmc passes, FETCH_SIZE calibrated on a copy of known size)
-        with open(tf) as f:
-            tj = json.load(f)
-        if args.nodes == 1_000_000 and S == 50_000 and args.m == 10 and rank == 0:
-            traffic = tj['benchmark_graph']['streaming']['memory_side_bytes_per_launch']
-            traffic_shipped = tj['benchmark_graph']['shipped_search']['memory_side_bytes_per_launch']
-            traffic_src = tf_name + ' (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; ' \
-                          'FETCH_SIZE x2 per the 4 B/lane calibration copy)'
-            hbm_frac = traffic / (ds_ms_stream * 1e-3) / 1e9 / HBM_PEAK_GBS
-        out_of_cache = {'graph': tj['out_of_cache']['bfs_sets']['graph'], 'csr_bytes': tj['out_of_cache']['bfs_sets']['csr_bytes'],
-                        'source': tf_name + ' (committed measurement, not re-run here)'}
-        for fam, c in tj['out_of_cache'].items():
-            out_of_cache[fam] = {form: {k: c[form][k] for k in ('ms_per_launch', 'algorithmic_frac_of_8TBs',
-                                                                'memory_side_frac_of_8TBs', 'traffic_over_algorithmic')}
-                                 for form in ('streaming', 'shipped_search')}
-    # the kernel that dominates the pass by TIME is not an HBM kernel: the DTW launch is bound by fp64 vector issue.  Its
-    # counters are a committed measurement (tools/run_dtw_pmc.sh), quoted beside the roofline of the HBM-class kernel.
-    longest = None
-    pj = next((f_ for f_ in (os.path.join(REPO, 'profiles', t_ + '_dtw_pmc.json') for t_ in ('r05', 'r04', 'r03')) if os.path.exists(f_)), None)
-    if pj:
-        pm = json.load(open(pj))
-        kk = [k for k in pm if 'dtw_similarity' in k]
-        if kk and stage_ms.get('dtw'):
-            c = pm[kk[0]]
-            wps = int(c.get('wavefronts_per_simd', 3))
-            longest = {'kernel': kk[0].split('(')[0], 'bound': 'fp64 vector issue (not HBM, not MFMA)',
-                       'share_of_step': round(stage_ms['dtw'] / (1e3 * elapsed / args.steps), 3),
-                       'simd_valu_busy': round(c.get('simd_valu_busy_from_grbm', min(1.0, wps * c['frac_wave_cycles_valu_active'])), 3),
-                       'wave_cycles': {'issuing': round(c['frac_wave_cycles_issuing'], 3),
-                                       'waiting_on_memory_or_barrier': round(c['frac_wave_cycles_waiting_waitcnt_or_barrier'], 3),
-                                       'issue_stalled': round(c['frac_wave_cycles_issue_stalled'], 3)},
-                       'valu_instructions_per_64_pairs': round(c['valu_instructions_per_64_pairs']),
-                       'source': 'profiles/' + os.path.basename(pj) + ' (rocprofv3 --pmc, committed measurement of the external-side launch; '
-                                 '%d wavefronts per SIMD; SIMD busy = 4 x SQ_ACTIVE_INST_VALU / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs))' % wps}
-    # ---- N = 1: measured beside the headline, in this process -----------------------------------------
+    # ---- --full, N = 1: measured beside the headline, in this process ----------------------------------
     sequential_ms = shard_line = strong_line = configs_obj = pool_reuse_ms = None
-    if world == 1 and not args.no_extras and graphed is None:
+    if args.full and world == 1 and not args.no_extras and graphed is None:
         # (1) the schedule `--gpus 8` runs by default: sequential passes, two-stream preparation -- what projection.weak_* uses
         for _ in range(2):
             step(False, sequential=True)
@@ -1146,40 +1200,7 @@ def main():
                                    'reduce-scatter / all-gather of the embedding table)' % world) if not replicated else
                                   ('dp%d (subgraph shards; RCCL all-gather of the channel embeddings into a replicated head, '
                                    'all-reduce of channel gradients, reduce-scatter / all-gather of the embedding table)' % world)},
-        # the kernel BASELINE.json's target names, as the pass RUNS it (lists of >= 512 entries binary-searched, not streamed):
-        # its own bytes / its time inside the timed region.  The streaming form (every list read in full: the launch that moves
-        # SURVEY 8(d)'s bytes) is beside it as streaming_form -- that is the figure the >= 40 % target is quoted on.
-        'roofline': {'kernel': ('degseq_wave_kernel<true, false, true> (sgnn_degree_sequence_hub_bitmaps: structure-channel CSR gather as '
-                                'the pass runs it; lists of >= %d entries answered from their membership bitmaps)' % DS_SEARCH) if ds_bits else
-                               ('degseq_wave_kernel<true, false, true> (sgnn_degree_sequence_sorted_rows: structure-channel CSR gather as '
-                                'the pass runs it; lists of >= %d entries searched)' % DS_SEARCH),
-                     'bound': 'hbm', 'achieved': alg_bytes_search / (ds_ms * 1e-3) / 1e9, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
-                     'frac': alg_bytes_search / (ds_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     # BASELINE.json's target (>= 40 % of the HBM roofline on the structure-channel CSR gather) is quoted on SURVEY 8(d)'s
-                     # algorithmic bytes: the figure of the launch that moves them (streaming_form below), repeated here at the top level
-                     'frac_of_roofline_on_survey_8d_bytes(streaming_form)': achieved / HBM_PEAK_GBS,
-                     'traffic': traffic_shipped, 'traffic_source': traffic_src,
-                     'algorithmic_bytes_per_launch': alg_bytes_search, 'ms_per_launch': ds_ms,
-                     'ms_per_launch_is': 'median over the %d timed passes of the HIP-event time of the launch on its stream' % len(ds_each),
-                     'ms_per_launch_mean_min_max': [round(sum(ds_each) / len(ds_each), 4), round(ds_each[0], 4), round(ds_each[-1], 4)] if ds_each else None,
-                     'ms_per_launch_back_to_back': ds_ms_b2b, 'sets_per_launch': cc_sets.n,
-                     'survey_8d_bytes_per_launch': alg_bytes,
-                     'survey_8d_bytes_over_this_time_GBs': alg_bytes / (ds_ms * 1e-3) / 1e9,
-                     'speedup_vs_streaming': ds_ms_stream / ds_ms,
-                     'streaming_form': {'kernel': 'degseq_wave_kernel<true, false, false> (every neighbour list streamed: moves SURVEY 8(d)\'s bytes)',
-                                        'achieved': achieved, 'frac': achieved / HBM_PEAK_GBS, 'ms_per_launch': ds_ms_stream,
-                                        'algorithmic_bytes_per_launch': alg_bytes, 'traffic': traffic, 'hbm_frac': hbm_frac,
-                                        'in_the_timed_pass': False},
-                     'out_of_cache': out_of_cache,
-                     'note': 'achieved = the bytes THIS launch reads (a list of >= 512 entries: 16 + 4 |S| -- one word of its membership bitmap per '
-                             'member, round 6; rounds 3-5 searched it: 16 + 4 min(deg, (floor(log2 deg) + 2) |S|)) / its time '
-                             'inside the timed region: it is latency-bound, and faster than the form that streams SURVEY 8(d)\'s bytes '
-                             '(survey_8d_bytes_over_this_time_GBs exceeds the peak: the launch does not move them).  streaming_form: 8(d) bytes / '
-                             'time of the launch that streams them, 20 launches back to back after the timed region (HIP events); on the '
-                             'benchmark graph an ON-DIE rate -- the CSR (88 MB) fits the 256 MiB Infinity Cache: hbm_frac = memory-side '
-                             'counter traffic over the same time.  out_of_cache: the same kernel on BA n=8M m=16 (CSR 1.09 GB)'},
-        'rooflines': rooflines,
-        'longest_kernel': longest,
+        **figures,
         'collectives': collectives,
         'stages_ms': {k: round(v, 3) for k, v in stage_ms.items()},
         'stages_note': ('HIP-event time per stage on the stream it runs on; ' + ('pipelined: the preparation stages (components ... dtw) of later passes '
@@ -1197,7 +1218,7 @@ def main():
         # BLAS handles, the torch kernels of the preparation)
         'warm_up_ms_at_construction': round(1e3 * getattr(model, 'warm_up_s', 0.0), 1),
     }
-    if world == 1 and args.scaling == 'weak':
+    if args.full and world == 1 and args.scaling == 'weak':
         result['projection'] = projection(args, result, model, S, sequential_ms, shard_line, strong_line)
     if sequential_ms is not None:
         result['sequential_ms_per_step'] = round(sequential_ms, 3)
@@ -1214,7 +1235,7 @@ def main():
         result['strong_rank8'] = strong_line
     if configs_obj is not None:
         result['configs'] = configs_obj
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             from oracle import cpu_baseline
             result['cpu_baseline'] = cpu_baseline.run(rowptr, col, subs, hp, emb.cpu(), labels, args.cpu_sample, S)

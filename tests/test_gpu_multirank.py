@@ -41,7 +41,7 @@ def _bench(ranks, extra, no_dropout=False):
 
 @pytest.mark.parametrize('scaling,head', [('weak', 'sharded'), ('strong', 'replicated')])
 def test_two_rank_bench_runs_pipelined(scaling, head):
-    d = _bench(2, ['--steps', '2', '--warmup', '1', '--scaling', scaling, '--head', head, '--pipeline-multi'])
+    d = _bench(2, ['--steps', '2', '--warmup', '1', '--scaling', scaling, '--head', head, '--pipeline-multi', '--full'])   # (--full: the north_star exchange)
     assert d['n_gpus'] == 2 and d['scaling'] == scaling
     assert d['collectives']['rccl_ranks'] == 2 and d['collectives']['backend'] == 'gloo'
     assert d['config']['subgraphs_total'] == (4000 if scaling == 'weak' else 2000)
