@@ -769,6 +769,17 @@ int sgnn_optim_adam(float* const* params, float* const* grads, float* const* exp
                     float eps, const int64_t* steps, const int64_t* step_counters, const int64_t* counter_slots,
                     const int64_t* row_lens, unsigned char* const* row_seen,
                     const float* partial, int64_t n_partial, float max_norm, float* coef_out, void* stream);
+/*   sgnn_optim_adam_lr_table(...)           sgnn_optim_adam with the learning rate read on the device: lr_table (DEVICE float[lr_len],
+ *                                           lr_len >= 1) in place of lr.  The update of step s (the step count the tensor reads
+ *                                           above) takes lr_table[min(s, lr_len) - 1]: a range test's schedule replays from one
+ *                                           recording; lr_len = 1 is a constant rate on the device.  Same arithmetic as the host
+ *                                           float: a table holding lr gives sgnn_optim_adam's result bit for bit. */
+int sgnn_optim_adam_lr_table(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                             const int64_t* numels, const int32_t* zero_grad, int64_t n_tensors, const float* lr_table,
+                             int64_t lr_len, float beta1, float beta2, float eps, const int64_t* steps,
+                             const int64_t* step_counters, const int64_t* counter_slots, const int64_t* row_lens,
+                             unsigned char* const* row_seen, const float* partial, int64_t n_partial, float max_norm,
+                             float* coef_out, void* stream);
 
 
 /* A batch's rows of up to sgnn_gather_rows_many_max() per-split tensors in ONE launch (the row gathers of _pad_collate,

@@ -142,6 +142,13 @@ class Snapshot:
                 torch._foreach_copy_([self.bufs[i] for i in idx], [src[i] for i in idx])
         self.meta = dict(meta)
 
+    def restore(self, dst):
+        """The captured values back into ``dst`` (the tensors ``capture`` was given, or tensors of the same shapes): the same
+        multi-tensor copies the other way, in place, so a recording that reads ``dst`` sees them."""
+        with torch.no_grad():
+            for idx in self.groups:
+                torch._foreach_copy_([dst[i] for i in idx], [self.bufs[i] for i in idx])
+
 
 # -- files --------------------------------------------------------------------------------------------------------------------
 def save(obj, path):

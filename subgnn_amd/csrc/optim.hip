@@ -131,7 +131,8 @@ __global__ __launch_bounds__(256) void optim_sumsq_kernel(const OptTensors T, fl
 #endif
 __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, const float* __restrict__ partial, int n_partial, float max_norm,
                                                          float* __restrict__ coef_out, float lr, float b1, float b2, float eps,
-                                                         long long host_step, const int64_t* __restrict__ counters)
+                                                         long long host_step, const int64_t* __restrict__ counters,
+                                                         const float* __restrict__ lr_table, long long lr_len)
 {
     __shared__ double shd[256];
     const int b = blockIdx.x, t = opt_find(T, b), nb = T.blk[t + 1] - T.blk[t];
@@ -151,8 +152,12 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
         gs = total != total ? total : fminf(max_norm / (total + 1e-6f), 1.f);
         if (coef_out && b == 0 && threadIdx.x == 0) { coef_out[0] = gs; coef_out[1] = total; }
     }
-    const double st = counters ? (double)counters[T.slot[t]] : (double)host_step;
-    const float step_size = (float)((double)lr / (1.0 - pow((double)b1, st)));
+    const long long s = counters ? (long long)counters[T.slot[t]] : host_step;
+    const double st = (double)s;
+    // a learning-rate table on the device (a range test's schedule): step s takes entry min(s, lr_len) - 1, so one recording
+    // replays every rate; the same double arithmetic as the host float, so a table of float(lr) is bit-identical to it
+    const float lr_s = lr_table ? lr_table[(s < lr_len ? (s > 1 ? s : 1) : lr_len) - 1] : lr;
+    const float step_size = (float)((double)lr_s / (1.0 - pow((double)b1, st)));
     const float rsqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, st)));
     float* __restrict__ p = T.p[t]; float* __restrict__ g = T.g[t]; float* __restrict__ m = T.m[t]; float* __restrict__ v = T.v[t];
     const int64_t n = T.n[t];
@@ -312,11 +317,11 @@ extern "C" int sgnn_optim_count(int64_t* step_counters, const int64_t* counter_s
     return SGNN_OK;
 }
 
-extern "C" int sgnn_optim_adam(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
-                               const int64_t* numels, const int32_t* zero_grad, int64_t n_tensors, float lr, float beta1, float beta2,
-                               float eps, const int64_t* steps, const int64_t* step_counters, const int64_t* counter_slots,
-                               const int64_t* row_lens, unsigned char* const* row_seen,
-                               const float* partial, int64_t n_partial, float max_norm, float* coef_out, void* stream)
+static int optim_adam(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                      const int64_t* numels, const int32_t* zero_grad, int64_t n_tensors, float lr, const float* lr_table,
+                      int64_t lr_len, float beta1, float beta2, float eps, const int64_t* steps, const int64_t* step_counters,
+                      const int64_t* counter_slots, const int64_t* row_lens, unsigned char* const* row_seen,
+                      const float* partial, int64_t n_partial, float max_norm, float* coef_out, void* stream)
 {
     if (n_tensors < 0 || (n_tensors && (!params || !grads || !exp_avg || !exp_avg_sq || !numels))) return SGNN_ERR_BAD_ARG;
     if ((steps == nullptr) == (step_counters == nullptr) && n_tensors) return SGNN_ERR_BAD_ARG;      // exactly one of the two
@@ -339,12 +344,35 @@ extern "C" int sgnn_optim_adam(float* const* params, float* const* grads, float*
             T.rows_t = (int)(i - from); T.row_lanes = (int)(D / 4); T.seen = row_seen[i];
         }
         hipLaunchKernelGGL(optim_adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, T, partial, (int)n_partial, max_norm,
-                           first ? coef_out : nullptr, lr, beta1, beta2, eps, (long long)(steps ? steps[from] : 0), step_counters);
+                           first ? coef_out : nullptr, lr, beta1, beta2, eps, (long long)(steps ? steps[from] : 0), step_counters,
+                           lr_table, (long long)lr_len);
         SGNN_CHECK_LAUNCH();
         first = false;
         from = to;
     }
     return SGNN_OK;
+}
+
+extern "C" int sgnn_optim_adam(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                               const int64_t* numels, const int32_t* zero_grad, int64_t n_tensors, float lr, float beta1, float beta2,
+                               float eps, const int64_t* steps, const int64_t* step_counters, const int64_t* counter_slots,
+                               const int64_t* row_lens, unsigned char* const* row_seen,
+                               const float* partial, int64_t n_partial, float max_norm, float* coef_out, void* stream)
+{
+    return optim_adam(params, grads, exp_avg, exp_avg_sq, numels, zero_grad, n_tensors, lr, nullptr, 0, beta1, beta2, eps, steps,
+                      step_counters, counter_slots, row_lens, row_seen, partial, n_partial, max_norm, coef_out, stream);
+}
+
+extern "C" int sgnn_optim_adam_lr_table(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                        const int64_t* numels, const int32_t* zero_grad, int64_t n_tensors, const float* lr_table,
+                                        int64_t lr_len, float beta1, float beta2, float eps, const int64_t* steps,
+                                        const int64_t* step_counters, const int64_t* counter_slots, const int64_t* row_lens,
+                                        unsigned char* const* row_seen, const float* partial, int64_t n_partial, float max_norm,
+                                        float* coef_out, void* stream)
+{
+    if (!lr_table || lr_len < 1 || (((uintptr_t)lr_table) & 3)) return SGNN_ERR_BAD_ARG;
+    return optim_adam(params, grads, exp_avg, exp_avg_sq, numels, zero_grad, n_tensors, 0.f, lr_table, lr_len, beta1, beta2, eps,
+                      steps, step_counters, counter_slots, row_lens, row_seen, partial, n_partial, max_norm, coef_out, stream);
 }
 
 SGNN_DEFINE_WARM(optim)

@@ -100,7 +100,9 @@ def recording_key(model, optimizer=None):
     """What a recording depends on -> (the model's preparation generation, the learning rate of every param group).  Every
     code path that replaces a tensor a recording reads (prepare_data / prepare_test_data, hotpath.prepare_sparse, the anchor
     resample, the structure column lists) bumps the generation (SubGNN._bump_generation); object ids would miss the
-    similarity tensors and can be reused after garbage collection.  A learning rate reaches the launches as a host float."""
+    similarity tensors and can be reused after garbage collection.  A learning rate reaches the launches as a host float;
+    a ClipAdam ``lr_schedule`` is device memory the replays read, and is not part of the key (no read-back, no new recording
+    as the schedule advances)."""
     lrs = () if optimizer is None else tuple(float(g['lr']) for g in optimizer.param_groups)
     return model.__dict__.get('_prep_generation', 0), lrs
 

@@ -1809,11 +1809,12 @@ class OptimTail:
                 self.seen[i] = torch.zeros(p.shape[0], dtype=torch.uint8, device=p.device)
                 self.row_len[i], self.seen_ptr[i] = D, self.seen[i].data_ptr()
 
-    def step(self, which, grads, lr, betas, eps, max_norm, steps=None, step_counters=None):
+    def step(self, which, grads, lr, betas, eps, max_norm, steps=None, step_counters=None, lr_table=None):
         """``which``: indices (ascending) of the parameters that have a gradient this step, ``grads`` theirs (float32,
         contiguous).  ``steps``: host step numbers per listed parameter -- or ``step_counters``: int64 device tensor over ALL
-        parameters of the list (those of ``which`` advance).  Returns the (2,) device tensor [coefficient, total norm] when
-        clipping, else None."""
+        parameters of the list (those of ``which`` advance).  ``lr_table``: a float32 device tensor read in place of ``lr`` --
+        step s takes entry min(s, len) - 1 (sgnn_optim_adam_lr_table).  Returns the (2,) device tensor [coefficient, total
+        norm] when clipping, else None."""
         lib = _lib.load()
         empty = [j for j, p_i in enumerate(which) if self.numels[p_i] == 0]
         if empty:
@@ -1871,12 +1872,17 @@ class OptimTail:
         elif counters is not None:
             check(lib.sgnn_optim_count(counters, slots, k, st), 'sgnn_optim_count')
         host_steps = None if counters is not None else np.asarray(steps, dtype=np.int64)
-        check(lib.sgnn_optim_adam(p_ptr.ctypes.data, g_ptr.ctypes.data, m_ptr.ctypes.data, v_ptr.ctypes.data, numels.ctypes.data,
-                                  zero.ctypes.data, k, float(lr), float(betas[0]), float(betas[1]), float(eps),
-                                  host_steps.ctypes.data if host_steps is not None else None, counters, slots,
-                                  row_len.ctypes.data if self.seen else None, seen_ptr.ctypes.data if self.seen else None,
-                                  _ptr(partial), n_partial,
-                                  float(max_norm) if partial is not None else 0.0, _ptr(out), st), 'sgnn_optim_adam')
+        tail = (float(betas[0]), float(betas[1]), float(eps), host_steps.ctypes.data if host_steps is not None else None, counters,
+                slots, row_len.ctypes.data if self.seen else None, seen_ptr.ctypes.data if self.seen else None, _ptr(partial),
+                n_partial, float(max_norm) if partial is not None else 0.0, _ptr(out), st)
+        head = (p_ptr.ctypes.data, g_ptr.ctypes.data, m_ptr.ctypes.data, v_ptr.ctypes.data, numels.ctypes.data, zero.ctypes.data, k)
+        if lr_table is None:
+            check(lib.sgnn_optim_adam(*head, float(lr), *tail), 'sgnn_optim_adam')
+        else:
+            _req(lr_table, torch.float32, 'lr_table')
+            if lr_table.numel() < 1 or lr_table.device != dev:
+                raise ValueError('lr_table must be a non-empty float32 tensor on the parameters\' device')
+            check(lib.sgnn_optim_adam_lr_table(*head, _ptr(lr_table), lr_table.numel(), *tail), 'sgnn_optim_adam_lr_table')
         return out
 
 

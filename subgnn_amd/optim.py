@@ -21,10 +21,14 @@ class ClipAdam:
     After ``step()`` the gradient of a large parameter is gone (``p.grad is None``): its buffer, zeroed by the update
     kernel, hangs on the parameter (``ops.release_zeroed``) and becomes the next backward's accumulator -- a caller that
     kept a reference to ``p.grad`` across ``step()`` holds that recycled buffer, not the old gradient.  ``release()``
-    drops the kept buffers."""
+    drops the kept buffers.
+    ``lr_schedule``: a float32 CUDA tensor of learning rates read ON THE DEVICE in place of ``lr`` -- step s (the parameters'
+    step count) takes ``lr_schedule[min(s, len) - 1]`` (sgnn_optim_adam_lr_table), so a recorded step replays a changing rate
+    (lr_find's range test) and the rate never enters the recording key.  All parameters it steps must share one step count:
+    an eager step that would update tensors of different counts raises."""
 
     def __init__(self, params, lr, max_norm=None, betas=(0.9, 0.999), eps=1e-8, big_bytes=16 << 20, capturable=False,
-                 skip_untouched_rows=True):
+                 skip_untouched_rows=True, lr_schedule=None):
         params = [p for p in params if p.requires_grad]
         if not fusable(params):
             raise ValueError('ClipAdam needs a non-empty list of float32, contiguous CUDA parameters on one device')
@@ -48,6 +52,12 @@ class ClipAdam:
         self.capturable = bool(capturable)
         self.counters = torch.zeros(len(self.all), dtype=torch.int64, device=params[0].device) if self.capturable else None
         self.last_clip = None                                   # (2,) device tensor [coefficient, total norm] of the last step
+        if lr_schedule is not None and not (torch.is_tensor(lr_schedule) and lr_schedule.is_cuda and lr_schedule.dim() == 1
+                                            and lr_schedule.dtype == torch.float32 and lr_schedule.numel() >= 1
+                                            and lr_schedule.is_contiguous() and lr_schedule.device == params[0].device):
+            raise ValueError("ClipAdam's lr_schedule must be a non-empty, contiguous 1-D float32 tensor on the parameters' device")
+        self.lr_schedule = lr_schedule
+        self._sched_which = None                                # the parameters a scheduled step updates (device step counts)
 
     @property
     def lr(self):
@@ -71,13 +81,21 @@ class ClipAdam:
             return
         steps = None
         if self.counters is None:
-            steps = []
-            for i in which:
-                st = self.state[id(self.all[i])]
-                st['step'] += 1
-                steps.append(st['step'])
+            steps = [self.state[id(self.all[i])]['step'] + 1 for i in which]
+            if self.lr_schedule is not None and len(set(steps)) > 1:
+                raise ValueError('a scheduled ClipAdam step would update tensors at different step counts %s: the learning-rate '
+                                 'table has one position for all of them' % sorted(set(steps)))
+            for i, n in zip(which, steps):
+                self.state[id(self.all[i])]['step'] = n
+        elif self.lr_schedule is not None:
+            # (device counts are not read back: the counts stay equal while every step updates the same parameters)
+            if self._sched_which is None:
+                self._sched_which = tuple(which)
+            elif tuple(which) != self._sched_which:
+                raise ValueError('a scheduled ClipAdam step would update another set of parameters than its first step: their '
+                                 'step counts would part and the learning-rate table has one position for all of them')
         self.last_clip = self.tail.step(which, grads, self.lr, self.betas, self.eps, self.max_norm, steps=steps,
-                                        step_counters=self.counters)
+                                        step_counters=self.counters, lr_table=self.lr_schedule)
         for i, g, take in zip(which, grads, takes):
             p = self.all[i]
             if self.tail.zero[i] and take:                      # (the kernel zeroed the gradient it consumed)
@@ -172,14 +190,27 @@ class ClipAdam:
 TRAINER_BIG_BYTES = 6 << 20        # the embedding table of the stand-ins (7.5-30 MB), not their per-split component embeddings (4.6 MB each)
 
 
-def accelerate(optimizer, max_norm=None, capturable=False, big_bytes=TRAINER_BIG_BYTES):
+def accelerate(optimizer, max_norm=None, capturable=False, big_bytes=TRAINER_BIG_BYTES, lr_schedule=None):
     """What ``train_config.Trainer`` steps with: the optimizer ``configure_optimizers`` returned when it is anything but a plain
     ``torch.optim.Adam`` over float32, contiguous CUDA parameters on one device (``fusable``) -- else a ClipAdam with the same
     learning rate, betas and eps that also applies the trainer's ``gradient_clip_val`` (so the caller must NOT clip again): clip
     and Adam over every parameter in two launches, the clip coefficient a device scalar, the gradient of the embedding table
     (and of any other parameter of at least ``big_bytes``) zeroed in the update and its untouched rows skipped -- at a batch
     of 64 torch's chunked multi-tensor Adam over a 9 MB table and the ten small launches of ``clip_grad_norm_`` were ~140 us of
-    a 1.5 ms step (PPI-BP stand-in).  Same update rule (tests/test_gpu_float.py::test_clip_adam_matches_torch)."""
+    a 1.5 ms step (PPI-BP stand-in).  Same update rule (tests/test_gpu_float.py::test_clip_adam_matches_torch).
+    ``lr_schedule``: ClipAdam's device learning-rate table (lr_find); an optimizer that would stay torch's cannot read one and
+    raises."""
+    if lr_schedule is not None:
+        out = _accelerate(optimizer, max_norm, capturable, big_bytes, lr_schedule)
+        if not isinstance(out, ClipAdam) or out is optimizer:
+            raise ValueError('a learning-rate schedule on the device needs a plain torch.optim.Adam over float32, contiguous CUDA '
+                             'parameters on one device (what accelerate turns into ClipAdam); configure_optimizers returned %s'
+                             % type(optimizer).__name__)
+        return out
+    return _accelerate(optimizer, max_norm, capturable, big_bytes, None)
+
+
+def _accelerate(optimizer, max_norm, capturable, big_bytes, lr_schedule):
     if isinstance(optimizer, ClipAdam):
         return optimizer
     if type(optimizer) is not torch.optim.Adam or len(optimizer.param_groups) != 1 or len(optimizer.state) != 0:
@@ -191,4 +222,4 @@ def accelerate(optimizer, max_norm=None, capturable=False, big_bytes=TRAINER_BIG
     if not fusable(params) or torch.is_tensor(g['lr']):
         return optimizer
     return ClipAdam(params, g['lr'], max_norm=(max_norm if max_norm and max_norm > 0 else None), betas=g['betas'], eps=g['eps'],
-                    big_bytes=big_bytes, capturable=capturable)
+                    big_bytes=big_bytes, capturable=capturable, lr_schedule=lr_schedule)

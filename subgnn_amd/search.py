@@ -558,9 +558,10 @@ class StudyFailed(RuntimeError):
 
 
 def run_study(run_config, study_dir, n_workers=None, checkpoint_k=3, project_root=None, trial_fn=None, log=print,
-              poll_s=0.2):
+              poll_s=0.2, auto_lr_find=False):
     """Run ``opt_n_trials`` more trials of the study in ``study_dir`` with ``n_workers`` worker processes.
     ``trial_fn``: 'module:function' run in the workers instead of the training trial (host tests).
+    ``auto_lr_find``: the trials honour their ``auto_lr_find`` hyper-parameter (train_config.train_model's).
     -> the study_results dict; raises StudyFailed when a trial failed or a worker died."""
     from . import config
     opt = run_config.get('optuna', {})
@@ -576,7 +577,7 @@ def run_study(run_config, study_dir, n_workers=None, checkpoint_k=3, project_roo
     storage.check_study(direction, monitor, sampler_name)
     inv = storage.begin_invocation(int(opt.get('opt_n_trials', 1)))
     args = {'run_config': run_config, 'study_dir': str(study_dir), 'invocation': inv, 'n_workers': n_workers,
-            'checkpoint_k': int(checkpoint_k), 'trial_fn': trial_fn,
+            'checkpoint_k': int(checkpoint_k), 'trial_fn': trial_fn, 'auto_lr_find': bool(auto_lr_find),
             'project_root': str(Path(project_root if project_root is not None else config.PROJECT_ROOT).resolve()),
             'sys_path': [p for p in sys.path if p]}
     prelude = ('import json, sys; a = json.loads(sys.argv[1]); sys.path[:0] = a["sys_path"]; '
@@ -632,8 +633,9 @@ def run_study(run_config, study_dir, n_workers=None, checkpoint_k=3, project_roo
 class TrialContext:
     """What a trial function gets: its number, parameters, merged hyper-parameters and directory, and ``report``."""
 
-    def __init__(self, storage, number, params, run_config, study_dir, checkpoint_k, pruning, direction, log):
-        self.storage, self.number, self.params = storage, number, params
+    def __init__(self, storage, number, params, run_config, study_dir, checkpoint_k, pruning, direction, log,
+                 auto_lr_find=False):
+        self.storage, self.number, self.params, self.auto_lr_find = storage, number, params, bool(auto_lr_find)
         self.run_config, self.checkpoint_k, self.pruning, self.direction, self.log = \
             run_config, checkpoint_k, pruning, direction, log
         self.hp = merged_hyperparams(run_config, params)
@@ -655,7 +657,7 @@ def train_trial(ctx):
     from .train_config import FixedTrial, train_model
     best, model, trainer = train_model(ctx.run_config, trial=FixedTrial(ctx.params), results_dir=ctx.dir, log=ctx.log,
                                        checkpoint_k=ctx.checkpoint_k, epoch_callback=ctx.report,
-                                       similarities_subdir='search_' + cache_key(ctx.hp))
+                                       similarities_subdir='search_' + cache_key(ctx.hp), auto_lr_find=ctx.auto_lr_find)
     del model, trainer
     return best
 
@@ -689,7 +691,8 @@ def worker_main(a):
             return 0
         number, params = got
         log('trial %d: %s' % (number, json.dumps(params)))
-        ctx = TrialContext(storage, number, params, run_config, study_dir, a['checkpoint_k'], pruning, direction, log)
+        ctx = TrialContext(storage, number, params, run_config, study_dir, a['checkpoint_k'], pruning, direction, log,
+                           auto_lr_find=a.get('auto_lr_find', False))
         cuda = torch.cuda.is_available() and torch.cuda.is_initialized()
         if cuda:
             torch.cuda.reset_peak_memory_stats()
@@ -729,6 +732,7 @@ def parse_args(argv=None):
     ap.add_argument('-config_path', type=str, required=True)
     ap.add_argument('-project_root', type=str, default=None, help='overrides subgnn_amd.config.PROJECT_ROOT')
     ap.add_argument('-checkpoint_k', type=int, default=3, help='epochs kept per trial by the monitored metric')
+    ap.add_argument('-auto_lr_find', action='store_true', help="the trials honour their auto_lr_find hyper-parameter")
     add_search_args(ap)
     ap.add_argument('-trial_fn', type=str, default=None, help=argparse.SUPPRESS)    # module:function instead of training (tests)
     return ap.parse_args(argv)
@@ -744,7 +748,7 @@ def main_from_args(args):
     k = 3 if args.checkpoint_k is None else args.checkpoint_k
     try:
         res = run_study(run_config, study_dir, n_workers=args.n_workers, checkpoint_k=k,
-                        trial_fn=getattr(args, 'trial_fn', None))
+                        trial_fn=getattr(args, 'trial_fn', None), auto_lr_find=getattr(args, 'auto_lr_find', False))
     except StudyFailed as ex:
         print('study failed: %s' % ex, file=sys.stderr)
         return 1

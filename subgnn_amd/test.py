@@ -35,8 +35,10 @@ def restored_config(run_config, restore_path):
     return cfg
 
 
-def run_seeds(run_config, n_seeds=10, random_seeds=False, results_dir=None, log=print, checkpoint_k=0, no_train=False):
-    """Returns the experiment_results dict of SubGNN/test.py:52-57.  ``checkpoint_k`` / ``no_train``: see the module's doc."""
+def run_seeds(run_config, n_seeds=10, random_seeds=False, results_dir=None, log=print, checkpoint_k=0, no_train=False,
+              auto_lr_find=False):
+    """Returns the experiment_results dict of SubGNN/test.py:52-57.  ``checkpoint_k`` / ``no_train``: see the module's doc;
+    ``auto_lr_find``: each seed's training honours the hyper-parameter (train_config.train_model's)."""
     if (checkpoint_k or no_train) and results_dir is None:
         raise ValueError('checkpoints need a results_dir')
     opt_cfg = run_config.get('optuna', {})
@@ -57,9 +59,10 @@ def run_seeds(run_config, n_seeds=10, random_seeds=False, results_dir=None, log=
                 raise FileNotFoundError('no epoch*.ckpt in %s' % (out,))
             _, model, _ = train_model(cfg, restore_path=out, restore_name=name, no_train=True, log=lambda *a: None)
         elif checkpoint_k:
-            _, model, _ = train_model(cfg, results_dir=out, log=lambda *a: None, checkpoint_k=checkpoint_k, run_test=True)
+            _, model, _ = train_model(cfg, results_dir=out, log=lambda *a: None, checkpoint_k=checkpoint_k, run_test=True,
+                                      auto_lr_find=auto_lr_find)
         else:
-            _, model, trainer = train_model(cfg, results_dir=out, log=lambda *a: None)
+            _, model, trainer = train_model(cfg, results_dir=out, log=lambda *a: None, auto_lr_find=auto_lr_find)
             trainer.test(model)
         res = model.test_results
         for k in ('test_micro_f1', 'test_acc', 'test_auroc'):
@@ -85,6 +88,8 @@ def parse_args(argv=None):
     ap.add_argument('-random_seeds', action='store_true')
     ap.add_argument('-checkpoint_k', type=int, default=0, help='test each seed from its best of k kept epochs (0: the last epoch)')
     ap.add_argument('-no_train', action='store_true', help="test each version_<i>'s best epoch*.ckpt without training")
+    ap.add_argument('-auto_lr_find', action='store_true',
+                    help='honour the hyper-parameter auto_lr_find: a learning-rate range test before each seed trains')
     ap.add_argument('-restoreModelPath', type=str, default=None,
                     help='directory whose hyperparams.json is used (a search trial); the dataset comes from -config_path')
     return ap.parse_args(argv)
@@ -98,7 +103,8 @@ def main(argv=None):
     if args.restoreModelPath:
         run_config = restored_config(run_config, args.restoreModelPath)
     return run_seeds(run_config, args.n_seeds, args.random_seeds,
-                     Path(config.PROJECT_ROOT) / args.results_dir, checkpoint_k=args.checkpoint_k, no_train=args.no_train)
+                     Path(config.PROJECT_ROOT) / args.results_dir, checkpoint_k=args.checkpoint_k, no_train=args.no_train,
+                     auto_lr_find=args.auto_lr_find)
 
 
 if __name__ == '__main__':

@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import checkpoint, config
+from . import lr_find as range_test
 from .SubGNN import SubGNN, dataset_paths
 from .graph_step import CapturedEvalStep, CapturedTrainStep, StepNotRecordable, make_capturable, make_eager, train_step
 from .optim import accelerate
@@ -104,8 +105,11 @@ class Trainer:
     gradient clipping, validation every epoch, best-by-monitor bookkeeping."""
 
     def __init__(self, max_epochs, gradient_clip_val=0.0, monitor='val_micro_f1', mode='max', log=print,
-                 hip_graph_step=True, checkpoint_dir=None, checkpoint_k=0):
+                 hip_graph_step=True, checkpoint_dir=None, checkpoint_k=0, auto_lr_find=False):
         self.max_epochs, self.clip, self.monitor, self.mode, self.log = max_epochs, gradient_clip_val, monitor, mode, log
+        # auto_lr_find (pl.Trainer's): True or the name of a hyper-parameter -- a fresh fit runs ``lr_find`` first and trains at
+        # its suggestion (subgnn_amd/lr_find.py); the finder's result stays on ``lr_finder``
+        self.auto_lr_find, self.lr_finder, self.lr_finder_configured = auto_lr_find, None, None
         self.best, self.history = None, []
         # checkpoint_k >= 1: the k best epochs by ``monitor`` (checkpoint.TopK, PL 0.7.1's rule) are kept as device copies and
         # written to ``checkpoint_dir`` with last.ckpt (the resume state) when fit returns; 0 writes nothing
@@ -134,6 +138,24 @@ class Trainer:
         t1 = time.perf_counter()
         rec[name] = rec.get(name, 0.0) + (t1 - t0)
         return t1
+
+    def lr_find(self, model, min_lr=1e-8, max_lr=1.0, num_training=100, mode='exponential', early_stop_threshold=4.0):
+        """pl.Trainer.lr_find: a learning-rate range test with this trainer's step and clip -> lr_find.LRFinder (``results``,
+        ``suggestion()``).  The model is left as it was (subgnn_amd/lr_find.py)."""
+        return range_test.run(self, model, min_lr, max_lr, num_training, mode, early_stop_threshold)
+
+    def _find_lr(self, model):
+        """Trainer(auto_lr_find): the suggestion becomes the hyper-parameter ``configure_optimizers`` reads; without one the
+        configured rate stays."""
+        key = range_test.lr_key(model.hparams, self.auto_lr_find)
+        self.lr_finder_configured = model.hparams[key]
+        self.lr_finder = self.lr_find(model)
+        lr = self.lr_finder.suggestion()
+        if lr is None:
+            self.log('lr_find: no suggestion after %d steps; keeping %s = %s' % (self.lr_finder.steps, key, model.hparams[key]))
+        else:
+            model.hparams[key] = lr
+            self.log('learning rate set to %s' % (lr,))
 
     def _eager_step(self, model, opt, batch, bi):
         return train_step(model, opt, batch, self.clip)[0]
@@ -198,6 +220,8 @@ class Trainer:
                 model.__dict__['_resample_epoch'] = st['resample_epoch']
                 model._prepare_anchors_only()
             checkpoint.load_checkpoint(model, resume)
+        elif self.auto_lr_find:
+            self._find_lr(model)
         if model.hparams.get('gc_freeze', True):
             # everything prepare_data left behind (the loaded dataset: subgraph lists, the graph's containers) lives as long as the
             # run: moved out of the cyclic collector's sight, so that a full collection does not walk a few million long-lived
@@ -212,6 +236,8 @@ class Trainer:
         if resume is not None:
             checkpoint.check_resumable(model, resume, opt)
             start = self._restore(model, opt, resume)
+            if self.auto_lr_find:                                # (the rate the interrupted fit found is the optimizer's)
+                model.hparams[range_test.lr_key(model.hparams, self.auto_lr_find)] = float(opt.param_groups[0]['lr'])
         captured = None
         if self.hip_graph_step:
             make_capturable(opt)
@@ -404,7 +430,8 @@ class Trainer:
 
 
 def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_k=0, restore_path=None, restore_name=None,
-                no_train=False, run_test=False, resume=False, max_epochs=None, epoch_callback=None, similarities_subdir=None):
+                no_train=False, run_test=False, resume=False, max_epochs=None, epoch_callback=None, similarities_subdir=None,
+                auto_lr_find=False):
     """train.py's train_model (train.py:375-420) for one run.
     ``checkpoint_k``: keep the k best epochs by the monitored metric in ``results_dir`` (ModelCheckpoint, train.py:327-334).
     ``restore_path``: hyper-parameters from ``restore_path/hyperparams.json`` (``max_epochs`` overrides them); with
@@ -412,6 +439,9 @@ def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_
     ``restore_path/last.ckpt`` bit for bit.  ``no_train``: test the restored model without training (train.py:392-411).
     ``run_test``: after training, test the best checkpoint (the last epoch when nothing was checkpointed) and write
     ``test_results.json``.  ``epoch_callback``: Trainer.fit's; ``similarities_subdir``: build_model's (both for a search trial).
+    ``auto_lr_find``: honour the hyper-parameter ``auto_lr_find`` (Trainer(auto_lr_find=hp['auto_lr_find']), train.py:297-298);
+    when the finder ran, ``lr_find.json`` records it.  hyperparams.json keeps the configured rate (written before fit, as the
+    reference does); the checkpoints' optimizer state holds the found one.
     -> (best monitored value, model, trainer)."""
     hp = None
     if restore_path is not None:
@@ -429,7 +459,8 @@ def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_
     mode = 'max' if opt_cfg.get('opt_direction', 'maximize') == 'maximize' else 'min'
     trainer = Trainer(hp['max_epochs'], hp.get('grad_clip', 0.0), monitor, mode, log,
                       hip_graph_step=bool(hp.get('hip_graph_step', True)), checkpoint_dir=results_dir,
-                      checkpoint_k=0 if no_train else checkpoint_k)
+                      checkpoint_k=0 if no_train else checkpoint_k,
+                      auto_lr_find=hp.get('auto_lr_find', False) if auto_lr_find else False)
     if results_dir is not None and not no_train:
         Path(results_dir).mkdir(parents=True, exist_ok=True)
         with open(Path(results_dir) / 'hyperparams.json', 'w') as f:
@@ -442,6 +473,9 @@ def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_
     if not no_train:
         trainer.fit(model, prepared=prepared, resume_from=Path(restore_path) / checkpoint.LAST if resume else None,
                     epoch_callback=epoch_callback)
+        if trainer.lr_finder is not None and results_dir is not None:
+            with open(Path(results_dir) / 'lr_find.json', 'w') as f:
+                json.dump(trainer.lr_finder.summary(trainer.lr_finder_configured), f, indent=2)
     if no_train or run_test:
         if not prepared and no_train:
             model.prepare_data()
@@ -475,6 +509,8 @@ def parse_args(argv=None):
     ap.add_argument('-runTest', action='store_true', help='test after training (the best checkpoint) -> test_results.json')
     ap.add_argument('-resume', action='store_true', help='continue the run in -restoreModelPath from its last.ckpt')
     ap.add_argument('-search', action='store_true', help='run the hyper-parameter study (subgnn_amd.search) instead of one run')
+    ap.add_argument('-auto_lr_find', action='store_true',
+                    help="honour the hyper-parameter auto_lr_find: a learning-rate range test before training (lr_find.json)")
     from .search import add_search_args
     add_search_args(ap)
     args = ap.parse_args(argv)
@@ -507,7 +543,7 @@ def main(argv=None):
     best, model, trainer = train_model(run_config, results_dir=args.results_dir, checkpoint_k=args.checkpoint_k,
                                        restore_path=args.restoreModelPath, restore_name=args.restoreModelName,
                                        no_train=args.noTrain, run_test=args.runTest, resume=args.resume,
-                                       max_epochs=args.max_epochs)
+                                       max_epochs=args.max_epochs, auto_lr_find=args.auto_lr_find)
     if best is not None:
         print('best %s: %.4f' % (trainer.monitor, best))
     return best
