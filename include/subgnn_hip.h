@@ -397,6 +397,27 @@ int sgnn_dtw_similarity_live(const int64_t* x_ptr, const int32_t* x_val, int64_t
                              void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * a11x Structure similarity with the EXACT distance: 1 / (1 + DTW(x, y, dist=calc_dist)), the minimum over all warp
+ * paths of the whole grid -- what fastdtw approximates (hparams['structure_similarity_fn'] = 'dtw_exact').
+ *   D[i][j] = min(D[i-1][j], D[i][j-1], D[i-1][j-1]) + calc_dist(x[i], y[j])
+ * The value does not depend on a predecessor rule, so there is no tie_order.  Everything else is as for
+ * sgnn_dtw_similarity: same x / y / out conventions, fp64 DP, out = float(1 / (1 + d)), rows with an empty x are PAD, and
+ * so is every pair of an empty y row (what sgnn_dtw_similarity writes for one); x_order and x_live_range mean the same.
+ * kernel: 0 = pick by size (x rows of at most 32 entries: the register-resident kernel), 1 = the general kernel (the
+ * lane's column in the workspace) whatever the size -- same values, bit for bit.
+ * workspace: sgnn_dtw_exact_workspace_bytes(n_x, max_x_len, n_y, max_y_len) bytes (any content).
+ * ------------------------------------------------------------------------------------- */
+int64_t sgnn_dtw_exact_workspace_bytes(int64_t n_x, int64_t max_x_len, int64_t n_y, int64_t max_y_len);
+int sgnn_dtw_exact_similarity(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len,
+                              const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                              int kernel, const int32_t* x_order, float* out, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+int sgnn_dtw_exact_similarity_live(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len,
+                                   const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                                   int kernel, const int32_t* x_order, const int64_t* x_live_range, float* out,
+                                   void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * a12  CC embedding initialisation: sum or max of member node embeddings.
  * Replaces SubGNN.initialize_cc_embeddings (SubGNN/SubGNN.py:609-622).  E: (n_emb_rows, D) f32.
  * aggregator 0 = sum, 1 = max.  For max, a row shorter than padded_len also competes with the

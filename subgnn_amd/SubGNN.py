@@ -399,15 +399,17 @@ class SubGNN(nn.Module):
 
     def compute_structure_patch_similarities(self, degree_dict, fname, internal, cc_ids, sim_path=None,
                                              dataset_type=None, border_set=None):
-        """S.py:783-833: (S, C, n_patches) = 1/(1+fastdtw(deg seq of CC, deg seq of anchor))."""
-        if self.hparams['structure_similarity_fn'] != 'dtw':
+        """S.py:783-833: (S, C, n_patches) = 1/(1+fastdtw(deg seq of CC, deg seq of anchor)); with
+        structure_similarity_fn = 'dtw_exact' the exact DTW distance stands in fastdtw's place."""
+        fn = self.hparams['structure_similarity_fn']
+        if fn not in ops.DTW_FNS:
             raise NotImplementedError
         S, C, L = cc_ids.shape
         g = self.networkx_graph
         use_dict = g.full_degree is not None
         a_sets, a_seq = gamma.degree_sequences(g, self.structure_anchors, internal, use_dict)
         c_sets, c_seq = gamma.degree_sequences(g, cc_ids.reshape(S * C, L), internal, use_dict)
-        sims = gamma.dtw_similarity_matrix(c_sets, c_seq, a_sets, a_seq, self.hparams['dtw_tie_order']).view(S, C, -1)
+        sims = gamma.dtw_similarity_matrix(c_sets, c_seq, a_sets, a_seq, self.hparams['dtw_tie_order'], fn=fn).view(S, C, -1)
         _save_npy(fname, sims.cpu().numpy())
         return sims
 

@@ -19,6 +19,7 @@ extern "C" int sgnn_warm_graph_sets(void*);
 extern "C" int sgnn_warm_samplers(void*);
 extern "C" int sgnn_warm_similarity(void*);
 extern "C" int sgnn_warm_dtw(void*);
+extern "C" int sgnn_warm_dtw_exact(void*);
 extern "C" int sgnn_warm_embed(void*);
 extern "C" int sgnn_warm_mpn(void*);
 extern "C" int sgnn_warm_attention(void*);
@@ -39,6 +40,7 @@ extern "C" int sgnn_warm_up(void* stream)
     bad += sgnn_warm_samplers(stream) != 0;
     bad += sgnn_warm_similarity(stream) != 0;
     bad += sgnn_warm_dtw(stream) != 0;
+    bad += sgnn_warm_dtw_exact(stream) != 0;
     bad += sgnn_warm_embed(stream) != 0;
     bad += sgnn_warm_mpn(stream) != 0;
     bad += sgnn_warm_attention(stream) != 0;

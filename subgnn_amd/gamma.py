@@ -28,22 +28,25 @@ def get_degree_sequence(graph, nodes, degree_dict=None, internal=True):
     return vals[:n].cpu().tolist()
 
 
-def dtw_similarity_matrix(cc_sets, cc_seq, anchor_sets, anchor_seq, tie_order=None):
+def dtw_similarity_matrix(cc_sets, cc_seq, anchor_sets, anchor_seq, tie_order=None, fn='dtw'):
     """1/(1+fastdtw(cc, anchor, radius=1, dist=calc_dist)) for all pairs (gamma.py:51-59,
-    SubGNN.py:811-822) -> (n_cc_rows, n_anchors) float32, empty (padded) rows = PAD."""
+    SubGNN.py:811-822) -> (n_cc_rows, n_anchors) float32, empty (padded) rows = PAD.
+    ``fn`` = 'dtw_exact': the exact DTW distance in fastdtw's place (no ``tie_order``)."""
     return ops.dtw_similarity(cc_sets.ptr, cc_seq, max(cc_sets.max_len, 1),
-                              anchor_sets.ptr, anchor_seq, max(anchor_sets.max_len, 1), tie_order)
+                              anchor_sets.ptr, anchor_seq, max(anchor_sets.max_len, 1), tie_order, fn=fn)
 
 
-def calc_dtw(graph_device, component_degree, patch_degree, tie_order=None):
-    """gamma.calc_dtw for one pair of python lists (convenience; the hot path is batched)."""
+def calc_dtw(graph_device, component_degree, patch_degree, tie_order=None, fn='dtw'):
+    """gamma.calc_dtw for one pair of python lists (convenience; the hot path is batched).  ``fn`` as in ops.dtw_similarity."""
+    if fn not in ops.DTW_FNS:
+        raise ValueError('structure similarity function %r' % (fn,))
     dev = graph_device
     x = ops.Ragged.from_lists([list(component_degree)], dev)
     y = ops.Ragged.from_lists([list(patch_degree)], dev)
     if len(component_degree) == 0:
         return 1.0          # fastdtw of an empty series costs 0 (see DESIGN.md, DTW)
     out = ops.dtw_similarity(x.ptr, x.nodes, max(len(component_degree), 1), y.ptr, y.nodes, max(len(patch_degree), 1),
-                             tie_order)
+                             tie_order, fn=fn)
     return float(out[0, 0].item())
 
 

@@ -915,9 +915,15 @@ def distinct_rows_ready(pending, wait=False):
     return float(int(host[0])) / n
 
 
+DTW_FNS = ('dtw', 'dtw_exact')          # values of hparams['structure_similarity_fn'] the library computes
+
+
 def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, order_rows=True, dedupe=True, order=None,
-                   _live=None, x_prep=None, kernel=0):
+                   _live=None, x_prep=None, kernel=0, fn='dtw'):
     """1/(1+fastdtw) for all (x row, y row) pairs -> (n_x, n_y) float32; empty x rows -> PAD.
+    ``fn``: hparams['structure_similarity_fn'] -- 'dtw' = fastdtw(radius=1), 'dtw_exact' = the exact DTW distance over the
+    whole grid (sgnn_dtw_exact_similarity; ``tie_order`` is ignored: a minimum over warp paths has no predecessor rule).
+    Everything below serves both.
     ``dedupe``: identical x rows (sorted degree sequences of small components repeat a lot: 50k BFS
     components of the benchmark have 2.7k distinct internal sequences) are computed once and the
     result rows gathered back.  ``order_rows``: process the x rows sorted by (length, coarse series) so
@@ -927,6 +933,8 @@ def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, ord
     the series the kernel reads are always this call's ``x_val``.
     ``kernel``: 0 = pick by size, 1 = the general (workspace-resident) kernel; same values.
     ``tie_order``: fastdtw's predecessor rule (0 / 1 / 2); None = config.DTW_TIE_ORDER, the product's default."""
+    if fn not in DTW_FNS:
+        raise ValueError('structure similarity function %r: one of %s' % (fn, ', '.join(map(repr, DTW_FNS))))
     if tie_order is None:
         from .config import DTW_TIE_ORDER as tie_order
     tie_order = int(tie_order)
@@ -951,7 +959,7 @@ def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, ord
             uval = torch.zeros(x_val.numel() + 1, dtype=torch.int32, device=x_ptr.device)
             uval.scatter_(0, dst_e, x_val)
             out_u = dtw_similarity(uptr, uval, max_x, y_ptr, y_val, max_y, tie_order, order_rows, dedupe=False, order=order,
-                                   _live=live, x_prep=x_prep.setdefault('grouped', {}), kernel=kernel)
+                                   _live=live, x_prep=x_prep.setdefault('grouped', {}), kernel=kernel, fn=fn)
             return out_u.index_select(0, rep)
         # no host round trip: every row keeps its slot, the rows that repeat an earlier one are given
         # length 0 (their pairs exit at once -- sorted by length they fill whole wavefronts) and read
@@ -983,7 +991,8 @@ def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, ord
                 dst_e = torch.cat([dst_e, dst_e.new_full((x_val.numel() - dst_e.numel(),), x_val.numel())])
             x_prep['dedupe_entry_dst'] = dst_e
         out_u = dtw_similarity(uptr, uval, max_x, y_ptr, y_val, max_y, tie_order, order_rows, dedupe=False, order=order,
-                               _live=live, x_prep=x_prep.setdefault('grouped', {}) if x_prep is not None else None, kernel=kernel)
+                               _live=live, x_prep=x_prep.setdefault('grouped', {}) if x_prep is not None else None, kernel=kernel,
+                               fn=fn)
         return out_u.index_select(0, rep)
     lib = _lib.load()
     for t, nm in ((x_ptr, 'x_ptr'), (y_ptr, 'y_ptr')):
@@ -1007,6 +1016,18 @@ def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, ord
             order = torch.argsort(key).to(torch.int32).contiguous()
             if x_prep is not None:
                 x_prep['order'] = order
+    if fn == 'dtw_exact':
+        wsb = lib.sgnn_dtw_exact_workspace_bytes(nx, max_x, ny, max_y)
+        ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=x_ptr.device)
+        if _live is not None and order is not None:
+            check(lib.sgnn_dtw_exact_similarity_live(_ptr(x_ptr), _ptr(x_val), nx, max_x, _ptr(y_ptr), _ptr(y_val), ny, max_y,
+                                                     int(kernel), _ptr(order), _ptr(_live), _ptr(out), _ptr(ws), wsb, _stream()),
+                  'sgnn_dtw_exact_similarity_live')
+            return out
+        check(lib.sgnn_dtw_exact_similarity(_ptr(x_ptr), _ptr(x_val), nx, max_x, _ptr(y_ptr), _ptr(y_val), ny, max_y,
+                                            int(kernel), _ptr(order), _ptr(out), _ptr(ws), wsb, _stream()),
+              'sgnn_dtw_exact_similarity')
+        return out
     wsb = lib.sgnn_dtw_workspace_bytes(nx, max_x, ny, max_y)
     ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=x_ptr.device)
     if _live is not None and order is not None:
