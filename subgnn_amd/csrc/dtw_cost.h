@@ -12,7 +12,8 @@ __device__ static inline double dtw_cost(double a, double b) {            // gam
 // q = RN(q0 + rem * r) is the correctly rounded quotient mx / mn when r = RN(1 / mn) (Markstein's
 // division step; it can only fail for divisors whose significand is all ones, and mn is a small
 // dyadic rational here).  tests/test_oracle_integer.py::test_reciprocal_division_is_exact runs the
-// identity exhaustively over the integer range and on 10^7 random dyadic pairs on the CPU.
+// identity on the CPU (oracle/division_check.c): exhaustively for integers up to 3000, and on random samples -- 10^7 pairs
+// (x + 1) / 2^L with x < 2^22, L <= 7, and 10^7 pairs v + 1 with v a mean of 2^L int32 values up to 2^31 - 1, L <= 15.
 __device__ __forceinline__ double dtw_cost_rcp(double a1, double ra, double b1, double rb) {
     // max / min with ONE division step (round 5; rounds 2-4 formed both quotients and took the larger: 8 fp64 instructions, this
     // is 7, and every one of them issues at half rate on gfx950): mx = max(a1, b1), mn = min(a1, b1), and the correctly rounded

@@ -211,17 +211,21 @@ def test_neighbourhood_anchor_law():
 
 
 def test_reciprocal_division_is_exact():
-    """The register DTW kernel divides by multiplying with a correctly rounded reciprocal plus one
-    fma correction (similarity.hip dtw_cost_rcp); on the operands it can meet that IS the IEEE
-    quotient the reference's `/` produces (gamma.py:51-52) -- checked here on the CPU, exhaustively
-    for integers up to 3000 and on 10^7 random dyadic rationals."""
+    """The register DTW kernels divide by multiplying with a correctly rounded reciprocal plus one fma correction
+    (csrc/dtw_cost.h dtw_cost_rcp); on the operands they can meet that IS the IEEE quotient the reference's `/` produces
+    (gamma.py:51-52) -- checked here on the CPU (oracle/division_check.c): exhaustively for integers up to 3000; on 10^7
+    random pairs (x + 1) / 2^L with x < 2^22, L <= 7; and on 10^7 random pairs v + 1 where v is a mean of 2^L int32 values,
+    L <= 15 (a series is halved at most DTW_MAX_LEVELS - 1 times), v up to 2^22 - 1 .. 2^31 - 1 -- what the boundary sweep
+    of tests/test_gpu_dtw_paths.py feeds the kernels.  The random parts are samples, not proofs (4 x 10^8 pairs of the
+    third kind run once by hand: no failure); the counts keep the test under a second."""
     import os
     import subprocess
     here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'oracle')
     subprocess.check_call(['make', '-s', '-C', here, '_build/division_check'])
-    out = subprocess.run([os.path.join(here, '_build', 'division_check'), '3000', '10000000'], capture_output=True,
+    out = subprocess.run([os.path.join(here, '_build', 'division_check'), '3000', '10000000', '10000000'], capture_output=True,
                          text=True)
     assert out.returncode == 0 and 'bad 0' in out.stdout, out.stdout + out.stderr
+    assert 'checked %d\n' % (3000 * 3001 // 2 + 2 * 10 ** 7) in out.stdout, out.stdout         # all three parts ran
 
 
 
@@ -293,6 +297,16 @@ def test_fastdtw_tie_orders_bound_exact_dtw():
         for i in range(0, 300, 7):
             for j in range(0, 300, 11):
                 assert got[i, j] == np.float32(FD.calc_dtw(xs[i], ys[j], t))
+    # sorted rows such as the ones above hold no pair that tells rule 2 from rule 1 (tests/test_dtw_paths_host.py has the
+    # comparison of the two oracles on pairs that do); the bound holds on those as well: four mined pairs per cell of
+    # tests/golden/dtw_rules.npz on which the two rules' similarities differ
+    import dtw_cases
+    for cell in dtw_cases.load_rule_cells():
+        for i, j in np.argwhere(cell.sims[1] != cell.sims[2])[:4]:
+            x, y = cell.xs[i], cell.ys[j]
+            exact = FD.exact_dtw(x, y, FD.calc_dist)
+            costs = [FD.fastdtw(x, y, 1, FD.calc_dist, t)[0] for t in (0, 1, 2)]
+            assert all(c >= exact for c in costs) and costs[1] != costs[2], (cell.name, int(i), int(j))
 
 
 def test_c_bfs_min_hops_matches_the_apsp_golden(tiny):
