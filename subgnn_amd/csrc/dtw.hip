@@ -283,7 +283,7 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_similarity_kernel(
             result = WD(prow + (ly - 1));
             if (lev == 0) break;
             // backtrack: column range of the path per row of THIS level
-            for (int q = 0; q < lx; ++q) FL(hc, q) = ((-1) << 16) | 0xffff;     // last = -1, first = 65535
+            for (int q = 0; q < lx; ++q) FL(hc, q) = (int32_t)((0xffffu << 16) | 0xffffu);     // last = -1, first = 65535
             int i = lx - 1, j = ly - 1;
             while (i >= 0 && j >= 0) {
                 const int fl = FL(hc, i);
@@ -338,15 +338,6 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_similarity_kernel(
 // path in LDS for the next finer level.  The finest level -- more than half of all cells -- is never
 // backtracked: it neither tracks nor stores predecessors, and takes one add instead of three.
 #define DTW_R 32
-#ifndef DTW_OLD_COARSE
-#define DTW_OLD_COARSE 0          // 1: the coarse levels of rounds 1-3 (one column array, 2-bit codes at fixed positions) for every instantiation
-#endif
-#ifndef DTW_NO_ROW_MAJOR
-#define DTW_NO_ROW_MAJOR 0        // 1: round 4's coarse levels (a word of predecessor bits per column in LDS, cell-by-cell back-trace) also for levels of <= 32 columns
-#endif
-#ifndef DTW_COARSE_ONE_SIZE
-#define DTW_COARSE_ONE_SIZE 0     // 1: every coarse level runs the RMAX / 2-row instantiation (rounds 4-5)
-#endif
 #ifndef DTW_MINB12
 #define DTW_MINB12 3            // resident 256-thread blocks per CU the 12-row kernel is compiled for
 #endif
@@ -356,6 +347,7 @@ __global__ __launch_bounds__(DTW_THREADS) void dtw_similarity_kernel(
 #ifndef DTW_MINB20
 #define DTW_MINB20 3            // 168 registers: 3 wavefronts per SIMD (5.46 -> 4.65 ms on the benchmark's external side)
 #endif
+#define DTW_EMPTY 1             // a lane's window word hi << 16 | lo of a row pair it has no cells in: lo = 1, hi = 0
 
 #ifdef DTW_PROBE_COUNT
 // Measurement build (tools/dtw_budget.py): what the register kernel executes per level, for the per-level instruction budget.
@@ -375,8 +367,22 @@ __device__ __forceinline__ unsigned long long dtw_probe_wave_sum(unsigned long l
     return v;
 }
 #define DTW_COUNT(LEV, WHAT, V) do { if ((threadIdx.x & 63) == 0) atomicAdd(&g_dtw_counts[(LEV) & 7][WHAT], (unsigned long long)(V)); } while (0)
+#define DTW_COUNT_LANE(LEV, WHAT, V) atomicAdd(&g_dtw_counts[(LEV) & 7][WHAT], (unsigned long long)(V))       // every lane's own
+// what a level function counts before its sweep: the wavefront-level, the cells of the lanes' own windows, the lanes with a pair
+template <int P>
+__device__ __forceinline__ void dtw_probe_windows(const int32_t (&lohi)[P], bool act, int lx, int lev)
+{
+    unsigned long long own = 0;
+    for (int p = 0; p < P; ++p)
+        if (lohi[p] != DTW_EMPTY) own += (unsigned long long)(((uint32_t)lohi[p] >> 16) - (lohi[p] & 0xffff) + 1) * (2 * p + 1 < lx ? 2 : 1);
+    own = dtw_probe_wave_sum(own);
+    const unsigned long long lanes = dtw_probe_wave_sum(act ? 1ull : 0ull);
+    DTW_COUNT(lev, 0, 1); DTW_COUNT(lev, 2, own); DTW_COUNT(lev, 6, lanes);
+}
 #else
 #define DTW_COUNT(LEV, WHAT, V) do { } while (0)
+#define DTW_COUNT_LANE(LEV, WHAT, V) do { (void)(V); } while (0)
+template <int P> __device__ __forceinline__ void dtw_probe_windows(const int32_t (&)[P], bool, int, int) { }
 #endif
 
 typedef unsigned short dtw_us2 __attribute__((ext_vector_type(2)));
@@ -398,27 +404,21 @@ __device__ __forceinline__ uint32_t dtw_wave_pkmax(uint32_t v) {
     return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-// One level of the register-resident DP for a wavefront, unrolled over RR (even) rows = RR / 2 row pairs.
+// ---- the parts every level function of the register kernel starts with ---------------------------------------------------
 // fl: this lane's column of the workgroup's LDS table (stride DTW_THREADS words) holding the coarser
 // path's first | last << 16 column per row.  act: the lane has a pair and this level exists for it;
 // inactive lanes run along with empty windows.  ly / lyc are wave-uniform (one anchor per wavefront).
-// Predecessor codes of a non-finest level go to wl (LDS) when WLDS, else to the global scratch wq.
-template <int RR, int TIE, bool WLDS, bool FINEST>
-__device__ __forceinline__ double dtw_wave_level(
-    int32_t* __restrict__ fl, const double* __restrict__ xcol, const double* __restrict__ xrcol, int64_t n_x,
-    const double* __restrict__ ycol, const double* __restrict__ yrcol, bool act,
-    int lx, int ly, int lxc, int lyc, bool coarsest, uint32_t* __restrict__ wl, uint32_t* __restrict__ wq, int64_t NT, int lev = 0)
-{
-    static_assert(RR % 2 == 0 && RR <= 32, "rows come in pairs");
-    constexpr int P = RR / 2;
 #define FLQ(q) fl[(q) * DTW_THREADS]
-    const double INF = __longlong_as_double(0x7ff0000000000000ll);
-    const int32_t EMPTY = 1;                                  // lo = 1, hi = 0
+
+// This lane's window per row pair (lohi: hi << 16 | lo, or DTW_EMPTY) and the hull of the 64 lanes' windows (wave-uniform).
+template <int P>
+__device__ __forceinline__ void dtw_wave_windows(int32_t* __restrict__ fl, bool act, int lx, int ly, int lxc, int lyc,
+                                                 bool coarsest, int32_t (&lohi)[P], uint32_t (&hull)[P])
+{
     // ---- this lane's window per row pair (rows 2p and 2p+1 share coarse row p) ----
-    int32_t lohi[P];
     if (coarsest) {
 #pragma unroll
-        for (int p = 0; p < P; ++p) lohi[p] = (act && 2 * p < lx) ? ((ly - 1) << 16) : EMPTY;
+        for (int p = 0; p < P; ++p) lohi[p] = (act && 2 * p < lx) ? ((ly - 1) << 16) : DTW_EMPTY;
     } else {
         int prev_lo = 0;
 #pragma unroll
@@ -433,49 +433,109 @@ __device__ __forceinline__ double dtw_wave_level(
             if (lo < 0) lo = 0;
             if (hi > ly - 1) hi = ly - 1;
             int32_t v = (hi << 16) | lo;
-            if (hi < lo || 2 * p >= lx || !act) v = EMPTY; else prev_lo = lo;
+            if (hi < lo || 2 * p >= lx || !act) v = DTW_EMPTY; else prev_lo = lo;
             lohi[p] = v;
         }
     }
     // ---- hull of the 64 lanes' windows per row pair: (0x7fff - lo) << 16 | (hi + 1), both halves maximised ----
-    uint32_t hull[P];
 #pragma unroll
     for (int p = 0; p < P; ++p) {
         const uint32_t lo = lohi[p] & 0xffff, hi = (uint32_t)lohi[p] >> 16;
-        hull[p] = dtw_wave_pkmax(lohi[p] == EMPTY ? 0u : (((0x7fffu - lo) << 16) | (hi + 1)));
+        hull[p] = dtw_wave_pkmax(lohi[p] == DTW_EMPTY ? 0u : (((0x7fffu - lo) << 16) | (hi + 1)));
     }
-#ifdef DTW_PROBE_COUNT
-    {
-        unsigned long long own = 0;
-        for (int p = 0; p < P; ++p)
-            if (lohi[p] != EMPTY) own += (unsigned long long)(((uint32_t)lohi[p] >> 16) - (lohi[p] & 0xffff) + 1) * (2 * p + 1 < lx ? 2 : 1);
-        own = dtw_probe_wave_sum(own);
-        const unsigned long long lanes = dtw_probe_wave_sum(act ? 1ull : 0ull);
-        DTW_COUNT(lev, 0, 1); DTW_COUNT(lev, 2, own); DTW_COUNT(lev, 6, lanes);
+}
+
+// The level's x rows (value + 1, and the reciprocal) into the registers xp1[] / xr[]; INIT sets row i of the DP's column
+// array(s) to +inf.  This one and DTW_BACKTRACE_CELLS are macros, not functions like the parts around them: the compiler
+// optimises a helper function on its own before it inlines it, and what it makes of these two does not come out as it does
+// inside the level function -- as a function the loads of all rows come first and their additions after them (20 more vector
+// registers in the 12-row kernel, spills in the 20- and the 32-row one), and the back-trace takes one more move per row.
+#define DTW_LOAD_ROWS(INIT)                                                                                          \
+    _Pragma("unroll")                                                                                                \
+    for (int i = 0; i < RR; ++i) {                                                                                   \
+        const int64_t ic = i < lx ? i : 0;                                   /* rows past the series repeat row 0: nobody reads them, */ \
+        xp1[i] = xcol[ic * n_x] + 1.0;                                       /* and all loads of the level are in flight together */ \
+        xr[i] = xrcol[ic * n_x];                                                                                     \
+        INIT;                                                                                                        \
+    }
+
+// Column c's entry of the table the column loop reads with v_readlane: the row pairs the column touches in the hull, as a bit
+// mask (pairs [ra, rb1)) | ra << 16, and with LAST_ROW the column's last row 2 rb1 - 1 in bits 27..31 (where the column's word
+// of predecessor bits keeps it).  0: no lane holds this column (cannot happen for real series).
+template <int P, bool LAST_ROW>
+__device__ __forceinline__ uint32_t dtw_column_pairs(const uint32_t (&hull)[P], uint32_t c)
+{
+    uint32_t ra = P, rb1 = 0;
+#pragma unroll
+    for (int p = P - 1; p >= 0; --p) ra = ((hull[p] & 0xffffu) > c) ? (uint32_t)p : ra;              // hi >= c
+#pragma unroll
+    for (int p = 0; p < P; ++p) rb1 = (hull[p] != 0u && (0x7fffu - (hull[p] >> 16)) <= c) ? (uint32_t)(p + 1) : rb1;
+    return rb1 > ra ? ((((1u << rb1) - 1u) & ~((1u << ra) - 1u)) | (ra << 16) | (LAST_ROW ? (2u * rb1 - 1u) << 27 : 0u)) : 0u;
+}
+
+// Cell-by-cell back-trace through the per-column words of predecessor bits (wl: LDS when WLDS, else the global scratch wq);
+// records the path's column range per row in fl.  The path enters a row at its LAST column and leaves it at its first, and
+// it visits every row: one LDS write per row when the path leaves it (no initialisation, no read-modify-write per step), and
+// the column's word is fetched when the column changes.  Row i's step in a column's word: FIXED: the 2-bit code
+// (0 = (i-1,j), 1 = (i,j-1), 2 = (i-1,j-1)) at bits 2 i; else the two compare bits of the tie rule (see dtw_shift_in) at
+// 2 (last_row - i), with the column's last row in bits 27..31.
+#ifdef DTW_PROBE_NO_BACKTRACK
+#define DTW_BACKTRACE_CELLS(FIXED)
+#else
+#define DTW_BACKTRACE_CELLS(FIXED)                                                                                   \
+    {                                                                                                                \
+        int i = lx - 1, j = ly - 1;                                                                                  \
+        int last = j;                                                                                                \
+        uint32_t word = WLDS ? wl[j * DTW_THREADS] : wq[(int64_t)j * NT];                                            \
+        unsigned long long bt_steps = 0;                                     /* (DTW_PROBE_COUNT only) */             \
+        while (i >= 0 && j >= 0) {                                                                                   \
+            ++bt_steps;                                                                                              \
+            int d;                                                                                                   \
+            if constexpr (FIXED) d = (int)((word >> (2 * i)) & 3);                                                   \
+            else {                                                                                                   \
+                const int sh = 2 * ((int)(word >> 27) - i);                                                          \
+                const uint32_t b = (word >> sh) & 3u;                        /* first bit << 1 | second bit */        \
+                if (TIE == 0) d = (b & 2u) ? 0 : ((b & 1u) ? 1 : 2);                                                 \
+                else d = (b & 2u) ? 2 : ((b & 1u) ? 0 : 1);                                                          \
+            }                                                                                                        \
+            if (d != 1) {                                                    /* the path leaves row i here, at column j */ \
+                FLQ(i) = (last << 16) | j;                                                                           \
+                --i;                                                                                                 \
+            }                                                                                                        \
+            if (d != 0) {                                                                                            \
+                --j;                                                                                                 \
+                if (j >= 0) word = WLDS ? wl[j * DTW_THREADS] : wq[(int64_t)j * NT];                                 \
+            }                                                                                                        \
+            if (d != 1) last = j;                                            /* ... and enters the row above at column j (or j - 1) */ \
+        }                                                                                                            \
+        /* (a path that runs off the first column inside a row -- only possible through a window's edge -- leaves that row open) */ \
+        if (i >= 0 && j < 0) FLQ(i) = (last << 16) | 0;                                                              \
+        DTW_COUNT_LANE(lev, 5, bt_steps);                                                                            \
     }
 #endif
+
+// One level of the register-resident DP for a wavefront, unrolled over RR (even) rows = RR / 2 row pairs: one column array,
+// 2-bit predecessor codes at fixed positions.  The finest level of every instantiation, and the coarse levels of the 32-row one.
+// Predecessor codes of a non-finest level go to wl (LDS) when WLDS, else to the global scratch wq.
+template <int RR, int TIE, bool WLDS, bool FINEST>
+__device__ __forceinline__ double dtw_wave_level(
+    int32_t* __restrict__ fl, const double* __restrict__ xcol, const double* __restrict__ xrcol, int64_t n_x,
+    const double* __restrict__ ycol, const double* __restrict__ yrcol, bool act,
+    int lx, int ly, int lxc, int lyc, bool coarsest, uint32_t* __restrict__ wl, uint32_t* __restrict__ wq, int64_t NT, int lev = 0)
+{
+    static_assert(RR % 2 == 0 && RR <= 32, "rows come in pairs");
+    constexpr int P = RR / 2;
+    const double INF = __longlong_as_double(0x7ff0000000000000ll);
+    int32_t lohi[P];
+    uint32_t hull[P];
+    dtw_wave_windows<P>(fl, act, lx, ly, lxc, lyc, coarsest, lohi, hull);
+    dtw_probe_windows<P>(lohi, act, lx, lev);
     double xp1[RR], xr[RR], col[RR];
-#pragma unroll
-    for (int i = 0; i < RR; ++i) {
-        const int64_t ic = i < lx ? i : 0;                                   // rows past the series repeat row 0: nobody reads them,
-        xp1[i] = xcol[ic * n_x] + 1.0;                                       // and all loads of the level are in flight together
-        xr[i] = xrcol[ic * n_x];
-        col[i] = INF;
-    }
+    DTW_LOAD_ROWS(col[i] = INF)
     const int lane = threadIdx.x & 63;
     uint32_t prev_am = 0;                                                    // the previous column's row-pair mask
     for (int jc = 0; jc < ly; jc += 64) {
-        // lane c: the row pairs column jc + c touches in the hull, as a bit mask (pairs [ra, rb1)) | ra << 16
-        uint32_t tab;
-        {
-            const uint32_t c = (uint32_t)(jc + lane);
-            uint32_t ra = P, rb1 = 0;
-#pragma unroll
-            for (int p = P - 1; p >= 0; --p) ra = ((hull[p] & 0xffffu) > c) ? (uint32_t)p : ra;              // hi >= c
-#pragma unroll
-            for (int p = 0; p < P; ++p) rb1 = (hull[p] != 0u && (0x7fffu - (hull[p] >> 16)) <= c) ? (uint32_t)(p + 1) : rb1;
-            tab = rb1 > ra ? ((((1u << rb1) - 1u) & ~((1u << ra) - 1u)) | (ra << 16)) : 0u;
-        }
+        const uint32_t tab = dtw_column_pairs<P, false>(hull, (uint32_t)(jc + lane));       // lane c: column jc + c
         const int jend = jc + 64 < ly ? jc + 64 : ly;
         double y_next = ycol[jc], yr_next = yrcol[jc];
         for (int j = jc; j < jend; ++j) {
@@ -590,61 +650,43 @@ __device__ __forceinline__ double dtw_wave_level(
     double result = 0.0;
 #pragma unroll
     for (int i = 0; i < RR; ++i) if (i == lx - 1) result = col[i];
-    if (FINEST || !act) return result;
-#ifdef DTW_PROBE_NO_BACKTRACK
+    if (FINEST || !act) return result;                                       // the finest level is never backtracked
+    DTW_BACKTRACE_CELLS(true)
     return result;
-#endif
-    // backtrack through the predecessor codes; record the path's column range per row.  The path enters a row at its
-    // LAST column and leaves it at its first, and it visits every row: one LDS write per row when the path leaves it (no
-    // initialisation, no read-modify-write per step), and the column's word of codes is fetched when the column changes
-    int i = lx - 1, j = ly - 1;
-    int last = j;
-    uint32_t word = WLDS ? wl[j * DTW_THREADS] : wq[(int64_t)j * NT];
-#ifdef DTW_PROBE_COUNT
-    unsigned long long bt_steps = 0;
-#endif
-    while (i >= 0 && j >= 0) {
-#ifdef DTW_PROBE_COUNT
-        ++bt_steps;
-#endif
-        const int d = (int)((word >> (2 * i)) & 3);
-        if (d != 1) {                                                        // the path leaves row i here, at column j
-            FLQ(i) = (last << 16) | j;
-            --i;
-        }
-        if (d != 0) {
-            --j;
-            if (j >= 0) word = WLDS ? wl[j * DTW_THREADS] : wq[(int64_t)j * NT];
-        }
-        if (d != 1) last = j;                                                // ... and enters the row above at column j (or j - 1)
-    }
-    // (a path that runs off the first column inside a row -- only possible through a window's edge -- leaves that row open)
-    if (i >= 0 && j < 0) FLQ(i) = (last << 16) | 0;
-#ifdef DTW_PROBE_COUNT
-    atomicAdd(&g_dtw_counts[lev & 7][5], bt_steps);
-#endif
-    return result;
-#undef FLQ
 }
 
-// ---- coarse levels, round 4: two column arrays + predecessor bits shifted in through the carry ----------------------------
-// The levels that are backtracked paid ~23 vector instructions per cell where the finest level pays 12 (ISA count): per row pair
-// three v_mov_b64 (a cell's old value had to be copied out of the row's register before the new one went in: it is the next
-// row's diagonal) and per cell two v_cndmask + an OR (+ v_mov of the shifted constants) to turn two compare masks into a 2-bit
-// code at the row's fixed position of the column's word.  Here
+// ---- coarse levels of the 12- and 20-row instantiations: two column arrays + predecessor bits shifted in through the carry ----
+// With one column array and fixed-position codes (dtw_wave_level) the levels that are backtracked paid ~23 vector instructions
+// per cell where the finest level pays 12 (ISA count): per row pair three v_mov_b64 (a cell's old value had to be copied out of
+// the row's register before the new one went in: it is the next row's diagonal) and per cell two v_cndmask + an OR (+ v_mov of
+// the shifted constants) to turn two compare masks into a 2-bit code at the row's fixed position of the column's word.  Here
 //   * the DP keeps TWO column arrays, read (column j - 1) and written (column j) alternately -- a cell reads up = cur[i - 1],
 //     left = prev[i], diagonal = prev[i - 1] and writes cur[i]: no copies; the column loop is unrolled by two so that the
 //     arrays keep static registers.  A row is evaluated over one contiguous column interval and both of its registers are +inf
 //     before it, so prev[] of a row that joins the sweep in this column is +inf by itself; the entry pair's row above (not
 //     part of this column, nor of any later one) is made +inf in cur[] and -- unless it was evaluated in the previous
 //     column -- in prev[];
-//   * the two compare masks of a cell (wave-wide lane masks in scalar registers) are shifted into the lane's word through the
-//     carry input of v_addc_co_u32 (word = 2 word + bit): two instructions per cell.  The bits of the rows a column evaluated
-//     follow each other in evaluation order, the last row in the lowest two bits; the column's last row number (wave-uniform)
-//     sits in bits 27..31, so the back-trace finds row i's bits at 2 (last_row - i).  Needs 2 RR <= 27: the levels of the
-//     12- and 20-row instantiations (6 / 10 rows); the 32-row one keeps the fixed-position words.
+//   * the two compare masks of a cell (wave-wide lane masks in scalar registers) are shifted into a word of the lane through the
+//     carry input of v_addc_co_u32 (word = 2 word + bit): two instructions per cell.
 // Bits per tie rule (first, second): 0: (c_up == min, c_left == min); 1: (c_diag == min, c_up == min); 2: (diag <= up && diag
 // <= left, up <= left) on the predecessor costs -- decoded only along the path.
+// Where the bits go, and how the path is walked back through them, comes in two forms:
+//   * !ROW_MAJOR: one word per COLUMN, written to LDS / the global scratch.  The bits of the rows a column evaluated follow each
+//     other in evaluation order, the last row in the lowest two bits; the column's last row number (wave-uniform) sits in bits
+//     27..31, so the cell-by-cell back-trace finds row i's bits at 2 (last_row - i).  Needs 2 RR <= 27: the levels of the 12- and
+//     20-row instantiations (6 / 10 rows); the 32-row one keeps the fixed-position words;
+//   * ROW_MAJOR: two words per ROW, kept in registers, and a back-trace of one step per row.  The cell-by-cell walk takes ~45
+//     dependent steps per pair over the three coarse levels of the benchmark (26 + 13 + 6), each a chain of ~20 vector
+//     instructions around an LDS read whose address depends on the step before -- a per-lane serial loop inside a kernel whose
+//     every other part runs in lockstep.  With each row keeping the two compare masks of its cells, one bit per evaluated column
+//     (no per-column word, no LDS store), and a row being evaluated over one contiguous column interval -- its pair's hull
+//     [ulo, uhi], wave-uniform -- column j's bit sits at position uhi - j.  The warp path visits every row, from the last to the
+//     first, and inside a row it can only move LEFT: the cells it crosses in row i are a run of "left" codes that starts at the
+//     column it entered the row.  With the row's bits in a register that run is a count of trailing ones -- shift, complement,
+//     find-first-set -- and the code at the run's end says whether the path goes up or diagonally.  The back-trace is a loop
+//     over ROWS, unrolled (all lanes are in the same row at the same time; only the column differs), ~12 vector instructions
+//     per row and no memory access but the row's (first, last) write.  Needs a level of at most 32 columns (anchor series of
+//     up to 65 entries).  Same predecessor rule, same path, same windows for the finer level: bit-identical to the other form.
 __device__ __forceinline__ uint32_t dtw_shift_in(uint32_t word, uint64_t lane_mask)
 {
 #if defined(__gfx950__) || defined(__gfx942__) || defined(__gfx90a__)
@@ -653,374 +695,152 @@ __device__ __forceinline__ uint32_t dtw_shift_in(uint32_t word, uint64_t lane_ma
     asm("v_addc_co_u32_e64 %0, vcc, %1, %1, %2" : "=v"(out) : "v"(word), "s"(lane_mask) : "vcc");
     return out;
 #elif defined(__HIP_DEVICE_COMPILE__)
-#error "dtw_shift_in: hand-written gfx9 wave64 instruction -- build with -DDTW_OLD_COARSE=1 for another target"
+#error "dtw_shift_in: hand-written instruction in the gfx9 family's wave64 encoding (gfx90a, gfx942, gfx950)"
 #else
     return 2u * word + (uint32_t)(lane_mask & 1u);              // host pass of the single-source compile: never executed
 #endif
 }
 
-template <int RR, int TIE, bool WLDS>
-__device__ __forceinline__ void dtw_wave_level_pp(
+template <int RR, int TIE, bool WLDS, bool ROW_MAJOR>
+__device__ __forceinline__ void dtw_wave_level_2col(
     int32_t* __restrict__ fl, const double* __restrict__ xcol, const double* __restrict__ xrcol, int64_t n_x,
     const double* __restrict__ ycol, const double* __restrict__ yrcol, bool act,
     int lx, int ly, int lxc, int lyc, bool coarsest, uint32_t* __restrict__ wl, uint32_t* __restrict__ wq, int64_t NT, int lev = 0)
 {
-    static_assert(RR % 2 == 0 && 2 * RR <= 27, "two bits per row below the row number");
+    static_assert(RR % 2 == 0 && (ROW_MAJOR ? RR <= 16 : 2 * RR <= 27),
+                  "rows come in pairs; two words of bits per row, or two bits per row below the row number in a column's word");
     constexpr int P = RR / 2;
-#define FLQ(q) fl[(q) * DTW_THREADS]
     const double INF = __longlong_as_double(0x7ff0000000000000ll);
-    const int32_t EMPTY = 1;
     int32_t lohi[P];
-    if (coarsest) {
-#pragma unroll
-        for (int p = 0; p < P; ++p) lohi[p] = (act && 2 * p < lx) ? ((ly - 1) << 16) : EMPTY;
-    } else {
-        int prev_lo = 0;
-#pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const int ca = p - 1 < 0 ? 0 : p - 1;
-            const int cb = p + 1;
-            const int firstc = FLQ(ca) & 0xffff;
-            const int lastc = (cb < lxc) ? (FLQ(cb < P ? cb : P - 1) >> 16) : (lyc - 1);
-            int lo = 2 * (firstc - 1);
-            int hi = 2 * (lastc + 1) + 1;
-            if (lo < prev_lo) lo = prev_lo;
-            if (lo < 0) lo = 0;
-            if (hi > ly - 1) hi = ly - 1;
-            int32_t v = (hi << 16) | lo;
-            if (hi < lo || 2 * p >= lx || !act) v = EMPTY; else prev_lo = lo;
-            lohi[p] = v;
-        }
-    }
     uint32_t hull[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const uint32_t lo = lohi[p] & 0xffff, hi = (uint32_t)lohi[p] >> 16;
-        hull[p] = dtw_wave_pkmax(lohi[p] == EMPTY ? 0u : (((0x7fffu - lo) << 16) | (hi + 1)));
-    }
-#ifdef DTW_PROBE_COUNT
-    {
-        unsigned long long own = 0;
-        for (int p = 0; p < P; ++p)
-            if (lohi[p] != EMPTY) own += (unsigned long long)(((uint32_t)lohi[p] >> 16) - (lohi[p] & 0xffff) + 1) * (2 * p + 1 < lx ? 2 : 1);
-        own = dtw_probe_wave_sum(own);
-        const unsigned long long lanes = dtw_probe_wave_sum(act ? 1ull : 0ull);
-        DTW_COUNT(lev, 0, 1); DTW_COUNT(lev, 2, own); DTW_COUNT(lev, 6, lanes);
-    }
-#endif
+    dtw_wave_windows<P>(fl, act, lx, ly, lxc, lyc, coarsest, lohi, hull);
+    dtw_probe_windows<P>(lohi, act, lx, lev);
     double xp1[RR], xr[RR], cA[RR], cB[RR];
-#pragma unroll
-    for (int i = 0; i < RR; ++i) {
-        const int64_t ic = i < lx ? i : 0;
-        xp1[i] = xcol[ic * n_x] + 1.0;
-        xr[i] = xrcol[ic * n_x];
-        cA[i] = INF;
-        cB[i] = INF;
-    }
+    [[maybe_unused]] uint32_t mA[RR], mB[RR];                                // ROW_MAJOR: the rows' bits: first / second compare mask of every cell
+    DTW_LOAD_ROWS(cA[i] = INF; cB[i] = INF; if constexpr (ROW_MAJOR) { mA[i] = 0u; mB[i] = 0u; })
     const int lane = threadIdx.x & 63;
     uint32_t prev_am = 0;
-    for (int jc = 0; jc < ly; jc += 64) {
-        uint32_t tab;
-        {
-            const uint32_t c = (uint32_t)(jc + lane);
-            uint32_t ra = P, rb1 = 0;
-#pragma unroll
-            for (int p = P - 1; p >= 0; --p) ra = ((hull[p] & 0xffffu) > c) ? (uint32_t)p : ra;
-#pragma unroll
-            for (int p = 0; p < P; ++p) rb1 = (hull[p] != 0u && (0x7fffu - (hull[p] >> 16)) <= c) ? (uint32_t)(p + 1) : rb1;
-            // pairs [ra, rb1) as a mask | ra << 16 | the column's last row 2 rb1 - 1, already at its place in the word (bits 27..31)
-            tab = rb1 > ra ? ((((1u << rb1) - 1u) & ~((1u << ra) - 1u)) | (ra << 16) | ((2u * rb1 - 1u) << 27)) : 0u;
+#define DTW2_IN(K) { const int lo_ = lohi[(K) < P ? (K) : 0] & 0xffff, hi_ = lohi[(K) < P ? (K) : 0] >> 16; in_ = J_ >= lo_ && J_ <= hi_; }
+#define DTW2_COST(I) dtw_mask_cost(in_, dtw_cost_rcp(xp1[(I) < RR ? (I) : 0], xr[(I) < RR ? (I) : 0], yp1, yr))
+    // one cell of row ROW: UPV / LEFT / DIAG are the three predecessors' values, OUT the register the cell's value goes into
+#define DTW2_CELL(UPV, LEFT, DIAG, DT, OUT, ROW)                                                                     \
+        {                                                                                                            \
+            const double c_up = (UPV) + (DT), c_left = (LEFT) + (DT), c_diag = (DIAG) + (DT);                        \
+            /* rule 2 picks on the predecessors' values: only the cell's value is needed of the sums, and rounding */ \
+            /* is monotone -- the smallest rounded sum is the rounded sum of the smallest predecessor: 1 add, not 3 */ \
+            /* (and "diagonal <= up and diagonal <= left" is ONE compare against min(up, left), which the value needs anyway) */ \
+            const double m1_ = fmin((UPV), (LEFT));                                                                  \
+            const double mv = TIE == 2 ? fmin(m1_, (DIAG)) + (DT) : fmin(fmin(c_up, c_left), c_diag);                \
+            const bool first_ = TIE == 0 ? c_up == mv : (TIE == 1 ? c_diag == mv : (DIAG) <= m1_);                   \
+            const bool second_ = TIE == 0 ? c_left == mv : (TIE == 1 ? c_up == mv : (UPV) <= (LEFT));                \
+            if constexpr (ROW_MAJOR) {                                                                               \
+                mA[ROW] = dtw_shift_in(mA[ROW], __ballot(first_));                                                   \
+                mB[ROW] = dtw_shift_in(mB[ROW], __ballot(second_));                                                  \
+            } else {                                                                                                 \
+                word = dtw_shift_in(word, __ballot(first_));                                                         \
+                word = dtw_shift_in(word, __ballot(second_));                                                        \
+            }                                                                                                        \
+            (OUT) = mv;                                                                                              \
         }
-        const int jend = jc + 64 < ly ? jc + 64 : ly;
-        double y_next = ycol[jc], yr_next = yrcol[jc];
-#define DTWP_IN(K) { const int lo_ = lohi[(K) < P ? (K) : 0] & 0xffff, hi_ = lohi[(K) < P ? (K) : 0] >> 16; in_ = J_ >= lo_ && J_ <= hi_; }
-#define DTWP_COST(I) dtw_mask_cost(in_, dtw_cost_rcp(xp1[(I) < RR ? (I) : 0], xr[(I) < RR ? (I) : 0], yp1, yr))
-        // one cell: UPV / LEFT / DIAG are the three predecessors' values, OUT the register the cell's value goes into
-#define DTWP_CELL(UPV, LEFT, DIAG, DT, OUT)                                                                          \
-            {                                                                                                        \
-                const double c_up = (UPV) + (DT), c_left = (LEFT) + (DT), c_diag = (DIAG) + (DT);                    \
-                /* rule 2 picks on the predecessors' values: only the cell's value is needed of the sums, and rounding */ \
-                /* is monotone -- the smallest rounded sum is the rounded sum of the smallest predecessor: 1 add, not 3 */ \
-                /* (and "diagonal <= up and diagonal <= left" is ONE compare against min(up, left), which the value needs anyway) */ \
-                const double m1_ = fmin((UPV), (LEFT));                                                              \
-                const double mv = TIE == 2 ? fmin(m1_, (DIAG)) + (DT) : fmin(fmin(c_up, c_left), c_diag);            \
-                if (TIE == 0) { word = dtw_shift_in(word, __ballot(c_up == mv)); word = dtw_shift_in(word, __ballot(c_left == mv)); } \
-                else if (TIE == 1) { word = dtw_shift_in(word, __ballot(c_diag == mv)); word = dtw_shift_in(word, __ballot(c_up == mv)); } \
-                else { word = dtw_shift_in(word, __ballot((DIAG) <= m1_));                                           \
-                       word = dtw_shift_in(word, __ballot((UPV) <= (LEFT))); }                                      \
-                (OUT) = mv;                                                                                          \
-            }
-#define DTWP_PAIR(K, PREV, CUR)                                                                                      \
-            if ((K) < P && (am & (1u << (K)))) {                                                                     \
-                constexpr int a_ = 2 * (K) < RR ? 2 * (K) : 0, b_ = 2 * (K) + 1 < RR ? 2 * (K) + 1 : 0;              \
-                constexpr int u_ = (2 * (K) - 1) >= 0 && (2 * (K) - 1) < RR ? (2 * (K) - 1) : 0;                     \
-                bool in_;                                                                                            \
-                DTWP_IN(K)                                                                                           \
-                const double dt0_ = DTWP_COST(2 * (K));                                                              \
-                const double dt1_ = DTWP_COST(2 * (K) + 1);                                                          \
-                if ((K) == 0) {                                                                                      \
-                    const double diag0_ = (J_ == 0) ? 0.0 : INF;             /* virtual origin D[-1][-1] = 0 */       \
-                    DTWP_CELL(INF, PREV[a_], diag0_, dt0_, CUR[a_])                                                  \
-                } else {                                                                                             \
-                    if (ra == (K)) {                                         /* the row above is not part of this column */ \
-                        CUR[u_] = INF;                                                                               \
-                        if (!carry) PREV[u_] = INF;                                                                  \
-                        asm volatile("" ::: "memory");                       /* keeps this a branch */               \
-                    }                                                                                                \
-                    DTWP_CELL(CUR[u_], PREV[a_], PREV[u_], dt0_, CUR[a_])                                            \
+#define DTW2_PAIR(K, PREV, CUR)                                                                                      \
+        if ((K) < P && (am & (1u << (K)))) {                                                                         \
+            constexpr int a_ = 2 * (K) < RR ? 2 * (K) : 0, b_ = 2 * (K) + 1 < RR ? 2 * (K) + 1 : 0;                  \
+            constexpr int u_ = (2 * (K) - 1) >= 0 && (2 * (K) - 1) < RR ? (2 * (K) - 1) : 0;                         \
+            bool in_;                                                                                                \
+            DTW2_IN(K)                                                                                               \
+            const double dt0_ = DTW2_COST(2 * (K));                                                                  \
+            const double dt1_ = DTW2_COST(2 * (K) + 1);                                                              \
+            if ((K) == 0) {                                                                                          \
+                const double diag0_ = (J_ == 0) ? 0.0 : INF;                 /* virtual origin D[-1][-1] = 0 */       \
+                DTW2_CELL(INF, PREV[a_], diag0_, dt0_, CUR[a_], a_)                                                  \
+            } else {                                                                                                 \
+                if (ra == (K)) {                                             /* the row above is not part of this column */ \
+                    CUR[u_] = INF;                                                                                   \
+                    if (!carry) PREV[u_] = INF;                                                                      \
+                    asm volatile("" ::: "memory");                           /* keeps this a branch */               \
                 }                                                                                                    \
-                DTWP_CELL(CUR[a_], PREV[b_], PREV[a_], dt1_, CUR[b_])                                                \
-            }
-#define DTWP_COLUMN(JJ, PREV, CUR)                                                                                   \
-            {                                                                                                        \
-                const int J_ = (JJ);                                                                                 \
-                const double yp1 = y_next + 1.0, yr = yr_next;                                                       \
-                if (J_ + 1 < ly) { y_next = ycol[J_ + 1]; yr_next = yrcol[J_ + 1]; }                                 \
-                const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)tab, J_ - jc);                           \
-                const uint32_t am = t & 0xffffu;                                                                     \
-                const int ra = (int)((t >> 16) & 0x7ffu);                                                            \
-                DTW_COUNT(lev, 1, 2 * __builtin_popcount(am)); DTW_COUNT(lev, 3, 1); DTW_COUNT(lev, 4, __builtin_popcount(am)); \
-                const bool carry = ra > 0 && ((prev_am >> (ra - 1)) & 1u);                                           \
-                prev_am = am;                                                                                        \
-                uint32_t word = 0;                                                                                   \
-                DTWP_PAIR(0, PREV, CUR) DTWP_PAIR(1, PREV, CUR) DTWP_PAIR(2, PREV, CUR) DTWP_PAIR(3, PREV, CUR)      \
-                DTWP_PAIR(4, PREV, CUR) DTWP_PAIR(5, PREV, CUR)                                                      \
+                DTW2_CELL(CUR[u_], PREV[a_], PREV[u_], dt0_, CUR[a_], a_)                                            \
+            }                                                                                                        \
+            DTW2_CELL(CUR[a_], PREV[b_], PREV[a_], dt1_, CUR[b_], b_)                                                \
+        }
+#define DTW2_COLUMN(JJ, PREV, CUR)                                                                                   \
+        {                                                                                                            \
+            const int J_ = (JJ);                                                                                     \
+            const double yp1 = y_next + 1.0, yr = yr_next;                                                           \
+            if (J_ + 1 < ly) { y_next = ycol[J_ + 1]; yr_next = yrcol[J_ + 1]; }                                     \
+            const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)tab, J_ - jc);                               \
+            const uint32_t am = t & 0xffffu;                                                                         \
+            const int ra = (int)((t >> 16) & 0x7ffu);                                                                \
+            DTW_COUNT(lev, 1, 2 * __builtin_popcount(am)); DTW_COUNT(lev, 3, 1); DTW_COUNT(lev, 4, __builtin_popcount(am)); \
+            const bool carry = ra > 0 && ((prev_am >> (ra - 1)) & 1u);                                               \
+            prev_am = am;                                                                                            \
+            [[maybe_unused]] uint32_t word = 0;                                                                      \
+            DTW2_PAIR(0, PREV, CUR) DTW2_PAIR(1, PREV, CUR) DTW2_PAIR(2, PREV, CUR) DTW2_PAIR(3, PREV, CUR)          \
+            DTW2_PAIR(4, PREV, CUR) DTW2_PAIR(5, PREV, CUR) DTW2_PAIR(6, PREV, CUR) DTW2_PAIR(7, PREV, CUR)          \
+            if constexpr (!ROW_MAJOR) {                                                                              \
                 word |= t & 0xf8000000u;                                     /* the column's last row */             \
                 if (WLDS) wl[J_ * DTW_THREADS] = word; else wq[(int64_t)J_ * NT] = word;                             \
-            }
-        int j = jc;
-        for (; j + 1 < jend; j += 2) {
-            DTWP_COLUMN(j, cB, cA)
-            DTWP_COLUMN(j + 1, cA, cB)
+            }                                                                                                        \
         }
-        if (j < jend) DTWP_COLUMN(j, cB, cA)
-#undef DTWP_IN
-#undef DTWP_COST
-#undef DTWP_CELL
-#undef DTWP_PAIR
-#undef DTWP_COLUMN
-    }
-    if (!act) return;
-#ifdef DTW_PROBE_NO_BACKTRACK
-    return;
-#endif
-    int i = lx - 1, j = ly - 1;
-    int last = j;
-    uint32_t word = WLDS ? wl[j * DTW_THREADS] : wq[(int64_t)j * NT];
-#ifdef DTW_PROBE_COUNT
-    unsigned long long bt_steps = 0;
-#endif
-    while (i >= 0 && j >= 0) {
-#ifdef DTW_PROBE_COUNT
-        ++bt_steps;
-#endif
-        const int sh = 2 * ((int)(word >> 27) - i);
-        const uint32_t b = (word >> sh) & 3u;                                // first bit << 1 | second bit
-        int d;
-        if (TIE == 0) d = (b & 2u) ? 0 : ((b & 1u) ? 1 : 2);
-        else d = (b & 2u) ? 2 : ((b & 1u) ? 0 : 1);
-        if (d != 1) {
-            FLQ(i) = (last << 16) | j;
-            --i;
+    // the columns [JC, JEND) that one table of the hull serves (64 columns, one per lane).  A ROW_MAJOR level has at most 32
+    // columns: one table, written without the loop over tables (as a loop of one pass the level's start is scheduled differently)
+#define DTW2_CHUNK(JC, JEND)                                                                                         \
+        {                                                                                                            \
+            const int jc = (JC), jend = (JEND);                                                                      \
+            const uint32_t tab = dtw_column_pairs<P, !ROW_MAJOR>(hull, (uint32_t)(jc + lane));                       \
+            double y_next = ycol[jc], yr_next = yrcol[jc];                                                           \
+            int j = jc;                                                                                              \
+            for (; j + 1 < jend; j += 2) {                                                                           \
+                DTW2_COLUMN(j, cB, cA)                                                                               \
+                DTW2_COLUMN(j + 1, cA, cB)                                                                           \
+            }                                                                                                        \
+            if (j < jend) DTW2_COLUMN(j, cB, cA)                                                                     \
         }
-        if (d != 0) {
-            --j;
-            if (j >= 0) word = WLDS ? wl[j * DTW_THREADS] : wq[(int64_t)j * NT];
-        }
-        if (d != 1) last = j;
-    }
-    if (i >= 0 && j < 0) FLQ(i) = (last << 16) | 0;
-#ifdef DTW_PROBE_COUNT
-    atomicAdd(&g_dtw_counts[lev & 7][5], bt_steps);
-#endif
-#undef FLQ
-}
-
-// ---- coarse levels, round 5: predecessor bits kept ROW-major in registers, the back-trace one step per ROW ------------------
-// Round 4's levels wrote one word of predecessor bits per column to LDS and walked the path back cell by cell: ~45 dependent
-// steps per pair over the three coarse levels of the benchmark (26 + 13 + 6), each a chain of ~20 vector instructions around an
-// LDS read whose address depends on the step before -- a per-lane serial loop inside a kernel whose every other part runs in
-// lockstep.  Here
-//   * each ROW keeps two 32-bit words (the two compare masks of its cells, one bit per evaluated column, shifted in through the
-//     carry exactly as before -- still two instructions per cell, no per-column word, no LDS store).  A row is evaluated over
-//     one contiguous column interval -- its pair's hull [ulo, uhi], wave-uniform -- so column j's bit sits at position uhi - j.
-//     Needs a level of at most 32 columns (anchor series of up to 65 entries); longer ones keep dtw_wave_level_pp;
-//   * the warp path visits every row, from the last to the first, and inside a row it can only move LEFT: the cells it crosses
-//     in row i are a run of "left" codes that starts at the column it entered the row.  With the row's bits in a register that
-//     run is a count of trailing ones -- shift, complement, find-first-set -- and the code at the run's end says whether the
-//     path goes up or diagonally.  The back-trace is a loop over ROWS, unrolled (all lanes are in the same row at the same
-//     time; only the column differs), ~12 vector instructions per row and no memory access but the row's (first, last) write.
-// Same predecessor rule, same path, same windows for the finer level: bit-identical to the cell-by-cell walk.
-template <int RR, int TIE>
-__device__ __forceinline__ void dtw_wave_level_rm(
-    int32_t* __restrict__ fl, const double* __restrict__ xcol, const double* __restrict__ xrcol, int64_t n_x,
-    const double* __restrict__ ycol, const double* __restrict__ yrcol, bool act,
-    int lx, int ly, int lxc, int lyc, bool coarsest, int lev = 0)
-{
-    static_assert(RR % 2 == 0 && RR <= 16, "rows come in pairs; two words of bits per row");
-    constexpr int P = RR / 2;
-#define FLQ(q) fl[(q) * DTW_THREADS]
-    const double INF = __longlong_as_double(0x7ff0000000000000ll);
-    const int32_t EMPTY = 1;
-    int32_t lohi[P];
-    if (coarsest) {
-#pragma unroll
-        for (int p = 0; p < P; ++p) lohi[p] = (act && 2 * p < lx) ? ((ly - 1) << 16) : EMPTY;
+    if constexpr (ROW_MAJOR) DTW2_CHUNK(0, ly)
+    else for (int jc0 = 0; jc0 < ly; jc0 += 64) DTW2_CHUNK(jc0, jc0 + 64 < ly ? jc0 + 64 : ly)
+#undef DTW2_CHUNK
+#undef DTW2_IN
+#undef DTW2_COST
+#undef DTW2_CELL
+#undef DTW2_PAIR
+#undef DTW2_COLUMN
+    if constexpr (!ROW_MAJOR) {
+        if (!act) return;
+        DTW_BACKTRACE_CELLS(false)
     } else {
-        int prev_lo = 0;
+#ifndef DTW_PROBE_NO_BACKTRACK
+        // ---- back-trace, one step per row --------------------------------------------------------------------------------
+        int j = act ? ly - 1 : -1;                                           // the column the path enters the current row at
 #pragma unroll
-        for (int p = 0; p < P; ++p) {
-            const int ca = p - 1 < 0 ? 0 : p - 1;
-            const int cb = p + 1;
-            const int firstc = FLQ(ca) & 0xffff;
-            const int lastc = (cb < lxc) ? (FLQ(cb < P ? cb : P - 1) >> 16) : (lyc - 1);
-            int lo = 2 * (firstc - 1);
-            int hi = 2 * (lastc + 1) + 1;
-            if (lo < prev_lo) lo = prev_lo;
-            if (lo < 0) lo = 0;
-            if (hi > ly - 1) hi = ly - 1;
-            int32_t v = (hi << 16) | lo;
-            if (hi < lo || 2 * p >= lx || !act) v = EMPTY; else prev_lo = lo;
-            lohi[p] = v;
+        for (int i = RR - 1; i >= 0; --i) {
+            const uint32_t h = hull[i >> 1];
+            const int uhi = (int)(h & 0xffffu) - 1, ulo = 0x7fff - (int)(h >> 16);   // the row's evaluated columns (wave-uniform)
+            if (i < lx && j >= 0) {
+                const int pos = uhi - j;                                     // column j's bit
+                const uint32_t valid = (uhi - ulo + 1) >= 32 ? ~0u : ((1u << (uhi - ulo + 1)) - 1u);
+                const uint32_t A = mA[i], B = mB[i];
+                // the cells whose predecessor is (i, j - 1): rule 0: not up, left; rules 1 / 2: neither first nor second
+                const uint32_t is_left = (TIE == 0 ? (~A & B) : (~A & ~B)) & valid;
+                const uint32_t tl = (pos >= 0 && pos < 32) ? (is_left >> pos) : 0u;
+                int run = __ffs((int)~tl) - 1;                               // trailing ones (tl has a zero: bit 31 - pos at the latest ... see valid)
+                if (run < 0) run = 32;
+                if (run > j) run = j;                                        // (a run into column 0 ends there)
+                const int first = j - run;
+                FLQ(i) = (j << 16) | first;
+                const int p2 = pos + run;
+                const uint32_t a2 = (p2 >= 0 && p2 < 32) ? ((A >> p2) & 1u) : 0u, b2 = (p2 >= 0 && p2 < 32) ? ((B >> p2) & 1u) : 0u;
+                // at the run's end: up, diagonal -- or still left, when the run was cut at column 0: the path ends in this row
+                const bool up = TIE == 0 ? (a2 != 0u) : (a2 == 0u && b2 != 0u);
+                const bool left_still = TIE == 0 ? (a2 == 0u && b2 != 0u) : (a2 == 0u && b2 == 0u);
+                j = left_still ? -1 : (up ? first : first - 1);
+            }
         }
-    }
-    uint32_t hull[P];
-#pragma unroll
-    for (int p = 0; p < P; ++p) {
-        const uint32_t lo = lohi[p] & 0xffff, hi = (uint32_t)lohi[p] >> 16;
-        hull[p] = dtw_wave_pkmax(lohi[p] == EMPTY ? 0u : (((0x7fffu - lo) << 16) | (hi + 1)));
-    }
-#ifdef DTW_PROBE_COUNT
-    {
-        unsigned long long own = 0;
-        for (int p = 0; p < P; ++p)
-            if (lohi[p] != EMPTY) own += (unsigned long long)(((uint32_t)lohi[p] >> 16) - (lohi[p] & 0xffff) + 1) * (2 * p + 1 < lx ? 2 : 1);
-        own = dtw_probe_wave_sum(own);
-        const unsigned long long lanes = dtw_probe_wave_sum(act ? 1ull : 0ull);
-        DTW_COUNT(lev, 0, 1); DTW_COUNT(lev, 2, own); DTW_COUNT(lev, 6, lanes);
-    }
 #endif
-    double xp1[RR], xr[RR], cA[RR], cB[RR];
-    uint32_t mA[RR], mB[RR];                                                 // the rows' bits: first / second compare mask of every cell
-#pragma unroll
-    for (int i = 0; i < RR; ++i) {
-        const int64_t ic = i < lx ? i : 0;
-        xp1[i] = xcol[ic * n_x] + 1.0;
-        xr[i] = xrcol[ic * n_x];
-        cA[i] = INF;
-        cB[i] = INF;
-        mA[i] = 0u;
-        mB[i] = 0u;
     }
-    const int lane = threadIdx.x & 63;
-    uint32_t prev_am = 0;
-    {                                                                        // (at most 32 columns: one table)
-        uint32_t tab;
-        {
-            const uint32_t c = (uint32_t)lane;
-            uint32_t ra = P, rb1 = 0;
-#pragma unroll
-            for (int p = P - 1; p >= 0; --p) ra = ((hull[p] & 0xffffu) > c) ? (uint32_t)p : ra;
-#pragma unroll
-            for (int p = 0; p < P; ++p) rb1 = (hull[p] != 0u && (0x7fffu - (hull[p] >> 16)) <= c) ? (uint32_t)(p + 1) : rb1;
-            tab = rb1 > ra ? ((((1u << rb1) - 1u) & ~((1u << ra) - 1u)) | (ra << 16)) : 0u;
-        }
-        double y_next = ycol[0], yr_next = yrcol[0];
-#define DTWR_IN(K) { const int lo_ = lohi[(K) < P ? (K) : 0] & 0xffff, hi_ = lohi[(K) < P ? (K) : 0] >> 16; in_ = J_ >= lo_ && J_ <= hi_; }
-#define DTWR_COST(I) dtw_mask_cost(in_, dtw_cost_rcp(xp1[(I) < RR ? (I) : 0], xr[(I) < RR ? (I) : 0], yp1, yr))
-        // one cell of row ROW: UPV / LEFT / DIAG are the three predecessors' values, OUT the register the cell's value goes into
-#define DTWR_CELL(UPV, LEFT, DIAG, DT, OUT, ROW)                                                                     \
-            {                                                                                                        \
-                const double c_up = (UPV) + (DT), c_left = (LEFT) + (DT), c_diag = (DIAG) + (DT);                    \
-                /* rule 2 picks on the predecessors' values: only the cell's value is needed of the sums, and rounding */ \
-                /* is monotone -- the smallest rounded sum is the rounded sum of the smallest predecessor: 1 add, not 3 */ \
-                /* (and "diagonal <= up and diagonal <= left" is ONE compare against min(up, left), which the value needs anyway) */ \
-                const double m1_ = fmin((UPV), (LEFT));                                                              \
-                const double mv = TIE == 2 ? fmin(m1_, (DIAG)) + (DT) : fmin(fmin(c_up, c_left), c_diag);            \
-                if (TIE == 0) { mA[ROW] = dtw_shift_in(mA[ROW], __ballot(c_up == mv)); mB[ROW] = dtw_shift_in(mB[ROW], __ballot(c_left == mv)); } \
-                else if (TIE == 1) { mA[ROW] = dtw_shift_in(mA[ROW], __ballot(c_diag == mv)); mB[ROW] = dtw_shift_in(mB[ROW], __ballot(c_up == mv)); } \
-                else { mA[ROW] = dtw_shift_in(mA[ROW], __ballot((DIAG) <= m1_));                                     \
-                       mB[ROW] = dtw_shift_in(mB[ROW], __ballot((UPV) <= (LEFT))); }                                 \
-                (OUT) = mv;                                                                                          \
-            }
-#define DTWR_PAIR(K, PREV, CUR)                                                                                      \
-            if ((K) < P && (am & (1u << (K)))) {                                                                     \
-                constexpr int a_ = 2 * (K) < RR ? 2 * (K) : 0, b_ = 2 * (K) + 1 < RR ? 2 * (K) + 1 : 0;              \
-                constexpr int u_ = (2 * (K) - 1) >= 0 && (2 * (K) - 1) < RR ? (2 * (K) - 1) : 0;                     \
-                bool in_;                                                                                            \
-                DTWR_IN(K)                                                                                           \
-                const double dt0_ = DTWR_COST(2 * (K));                                                              \
-                const double dt1_ = DTWR_COST(2 * (K) + 1);                                                          \
-                if ((K) == 0) {                                                                                      \
-                    const double diag0_ = (J_ == 0) ? 0.0 : INF;             /* virtual origin D[-1][-1] = 0 */       \
-                    DTWR_CELL(INF, PREV[a_], diag0_, dt0_, CUR[a_], a_)                                              \
-                } else {                                                                                             \
-                    if (ra == (K)) {                                         /* the row above is not part of this column */ \
-                        CUR[u_] = INF;                                                                               \
-                        if (!carry) PREV[u_] = INF;                                                                  \
-                        asm volatile("" ::: "memory");                       /* keeps this a branch */               \
-                    }                                                                                                \
-                    DTWR_CELL(CUR[u_], PREV[a_], PREV[u_], dt0_, CUR[a_], a_)                                        \
-                }                                                                                                    \
-                DTWR_CELL(CUR[a_], PREV[b_], PREV[a_], dt1_, CUR[b_], b_)                                            \
-            }
-#define DTWR_COLUMN(JJ, PREV, CUR)                                                                                   \
-            {                                                                                                        \
-                const int J_ = (JJ);                                                                                 \
-                const double yp1 = y_next + 1.0, yr = yr_next;                                                       \
-                if (J_ + 1 < ly) { y_next = ycol[J_ + 1]; yr_next = yrcol[J_ + 1]; }                                 \
-                const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)tab, J_);                                \
-                const uint32_t am = t & 0xffffu;                                                                     \
-                const int ra = (int)((t >> 16) & 0x7ffu);                                                            \
-                DTW_COUNT(lev, 1, 2 * __builtin_popcount(am)); DTW_COUNT(lev, 3, 1); DTW_COUNT(lev, 4, __builtin_popcount(am)); \
-                const bool carry = ra > 0 && ((prev_am >> (ra - 1)) & 1u);                                           \
-                prev_am = am;                                                                                        \
-                DTWR_PAIR(0, PREV, CUR) DTWR_PAIR(1, PREV, CUR) DTWR_PAIR(2, PREV, CUR) DTWR_PAIR(3, PREV, CUR)      \
-                DTWR_PAIR(4, PREV, CUR) DTWR_PAIR(5, PREV, CUR) DTWR_PAIR(6, PREV, CUR) DTWR_PAIR(7, PREV, CUR)      \
-            }
-        int j = 0;
-        for (; j + 1 < ly; j += 2) {
-            DTWR_COLUMN(j, cB, cA)
-            DTWR_COLUMN(j + 1, cA, cB)
-        }
-        if (j < ly) DTWR_COLUMN(j, cB, cA)
-#undef DTWR_IN
-#undef DTWR_COST
-#undef DTWR_CELL
-#undef DTWR_PAIR
-#undef DTWR_COLUMN
-    }
-#ifdef DTW_PROBE_NO_BACKTRACK
-    return;
-#endif
-    // ---- back-trace, one step per row ------------------------------------------------------------------------------------
-    int j = act ? ly - 1 : -1;                                               // the column the path enters the current row at
-#pragma unroll
-    for (int i = RR - 1; i >= 0; --i) {
-        const uint32_t h = hull[i >> 1];
-        const int uhi = (int)(h & 0xffffu) - 1, ulo = 0x7fff - (int)(h >> 16);       // the row's evaluated columns (wave-uniform)
-        if (i < lx && j >= 0) {
-            const int pos = uhi - j;                                         // column j's bit
-            const uint32_t valid = (uhi - ulo + 1) >= 32 ? ~0u : ((1u << (uhi - ulo + 1)) - 1u);
-            const uint32_t A = mA[i], B = mB[i];
-            // the cells whose predecessor is (i, j - 1): rule 0: not up, left; rules 1 / 2: neither first nor second
-            const uint32_t is_left = (TIE == 0 ? (~A & B) : (~A & ~B)) & valid;
-            const uint32_t tl = (pos >= 0 && pos < 32) ? (is_left >> pos) : 0u;
-            int run = __ffs((int)~tl) - 1;                                   // trailing ones (tl has a zero: bit 31 - pos at the latest ... see valid)
-            if (run < 0) run = 32;
-            if (run > j) run = j;                                            // (a run into column 0 ends there)
-            const int first = j - run;
-            FLQ(i) = (j << 16) | first;
-            const int p2 = pos + run;
-            const uint32_t a2 = (p2 >= 0 && p2 < 32) ? ((A >> p2) & 1u) : 0u, b2 = (p2 >= 0 && p2 < 32) ? ((B >> p2) & 1u) : 0u;
-            // at the run's end: up, diagonal -- or still left, when the run was cut at column 0: the path ends in this row
-            const bool up = TIE == 0 ? (a2 != 0u) : (a2 == 0u && b2 != 0u);
-            const bool left_still = TIE == 0 ? (a2 == 0u && b2 != 0u) : (a2 == 0u && b2 == 0u);
-            j = left_still ? -1 : (up ? first : first - 1);
-        }
-    }
-#undef FLQ
 }
+#undef FLQ
+#undef DTW_LOAD_ROWS
+#undef DTW_BACKTRACE_CELLS
 
 // RMAX = rows the instantiation can hold (12 / 20 / 32): the register budget -- and with it the
 // number of resident wavefronts that hide the fp64 dependency chains -- follows the longest
@@ -1086,10 +906,10 @@ __global__ __launch_bounds__(DTW_THREADS, MINB) void dtw_similarity_reg_kernel(
             if (lev == 0)
                 result = dtw_wave_level<RMAX, TIE, WLDS, true>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc,
                                                                coarsest, wl, w, NT, lev);
-            else if constexpr (2 * RH <= 27 && !DTW_OLD_COARSE) {
+            else if constexpr (2 * RH <= 27) {
                 // (wave-uniform: one anchor per wavefront.  Only in the instantiation whose words sit in LDS -- anchor series of up to
                 // 96 entries: the other one serves longer series, whose first coarse level has more than 32 columns anyway)
-                if (WLDS && ly <= 32 && !DTW_NO_ROW_MAJOR) {
+                if (WLDS && ly <= 32) {
                     // Level lev of a series of <= RMAX entries has <= RMAX >> lev rows: the second coarse level and the ones
                     // below it get instantiations of their own size (round 6).  Everything per row of the level function is
                     // unrolled over its row count -- loading the series, clearing two column arrays and two bit rows, the
@@ -1097,15 +917,15 @@ __global__ __launch_bounds__(DTW_THREADS, MINB) void dtw_similarity_reg_kernel(
                     // 5-row level of a 20-entry series paid ~500 vector instructions each for rows they do not have.
                     constexpr int R2 = (((RMAX >> 2) + 1) & ~1) < 2 ? 2 : (((RMAX >> 2) + 1) & ~1);
                     constexpr int R3 = (((RMAX >> 3) + 1) & ~1) < 2 ? 2 : (((RMAX >> 3) + 1) & ~1);
-                    if (DTW_COARSE_ONE_SIZE || lev == 1)
-                        dtw_wave_level_rm<RH, TIE>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc, coarsest, lev);
+                    if (lev == 1)
+                        dtw_wave_level_2col<RH, TIE, WLDS, true>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc, coarsest, wl, w, NT, lev);
                     else if (lev == 2)
-                        dtw_wave_level_rm<R2, TIE>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc, coarsest, lev);
+                        dtw_wave_level_2col<R2, TIE, WLDS, true>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc, coarsest, wl, w, NT, lev);
                     else
-                        dtw_wave_level_rm<R3, TIE>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc, coarsest, lev);
+                        dtw_wave_level_2col<R3, TIE, WLDS, true>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc, coarsest, wl, w, NT, lev);
                 }
                 else
-                    dtw_wave_level_pp<RH, TIE, WLDS>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc, coarsest, wl, w, NT, lev);
+                    dtw_wave_level_2col<RH, TIE, WLDS, false>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc, coarsest, wl, w, NT, lev);
             }
             else
                 dtw_wave_level<RH, TIE, WLDS, false>(fl, xcol, xrcol, n_x, ycol, yrcol, act, lx, ly, lxc, lyc, coarsest,
@@ -1133,9 +953,6 @@ __global__ void dtw_order_keys_kernel(const int64_t* __restrict__ x_ptr, const i
 #define DTW_KEY_STEPS 4.f       // log-scale steps per octave.  Round 5, cells a wavefront evaluates on the finest level (tools/dtw_budget.py; a
 #endif                          // lane's own window: 346.2) and the external side: 2 / 4 / 8 / 16 steps: 435.9 / 425.6 / 438.6 / 463.1 cells, 3.90 / 3.88 / 3.97 / 4.08 ms;
                                 // components in reverse (largest degrees first) 581 cells, middle-out 480: the ascending order stays
-#ifndef DTW_KEY_ORDER
-#define DTW_KEY_ORDER 0
-#endif
     auto q8 = [](float v) { const int q = (int)lrintf(DTW_KEY_STEPS * log2f(1.f + (v < 0.f ? 0.f : v))); return (int64_t)(q > 255 ? 255 : q); };
     const int64_t n2 = len / 4;
     if (n2 == 0) {
@@ -1145,10 +962,7 @@ __global__ void dtw_order_keys_kernel(const int64_t* __restrict__ x_ptr, const i
         for (int64_t f = 0; f < nf; ++f) {
             const int64_t g = b + 4 * ((f * n2) / nf);
             const float v = 0.25f * ((float)x_val[g] + (float)x_val[g + 1] + (float)x_val[g + 2] + (float)x_val[g + 3]);
-            int64_t slot = f;                                        // significance of component f (0 = most significant)
-            if (DTW_KEY_ORDER == 1) slot = nf - 1 - f;               // the largest degrees first
-            else if (DTW_KEY_ORDER == 2) { const int64_t mid = nf / 2; const int64_t dlt = f - mid; slot = dlt == 0 ? 0 : (dlt > 0 ? 2 * dlt - 1 : -2 * dlt); if (slot >= nf) slot = nf - 1; }   // middle out
-            key |= q8(v) << (40 - 8 * slot);
+            key |= q8(v) << (40 - 8 * f);                            // component 0 is the most significant
         }
     }
     keys[i] = key;

@@ -39,7 +39,8 @@ def n_levels(lx, ly):
 
 
 def _chunks(ly):
-    """``for (jc = 0; jc < ly; jc += 64)`` in every level function: 1, 2 or 3+ chunks of the hull table."""
+    """``for (jc = 0; jc < ly; jc += 64)`` in the level functions (the row-major form has one table: at most 32 columns): 1, 2
+    or 3+ chunks of the hull table."""
     c = (ly + 63) // 64
     return '3+' if c >= 3 else str(c)
 
@@ -50,11 +51,11 @@ def level_form(rmax, wlds, lev, ly):
     if lev == 0:
         return 'finest'                                  # if (lev == 0) dtw_wave_level<RMAX, TIE, WLDS, true>
     rh = ((rmax // 2) + 1) & ~1                          # constexpr int RH = ((RMAX / 2) + 1) & ~1
-    if not 2 * rh <= 27:                                 # else if constexpr (2 * RH <= 27 && !DTW_OLD_COARSE) ... else
+    if not 2 * rh <= 27:                                 # else if constexpr (2 * RH <= 27) ... else
         return 'coarse32'                                #     dtw_wave_level<RH, TIE, WLDS, false>   (RMAX 32: RH 16)
-    if wlds and ly <= 32:                                # if (WLDS && ly <= 32 && !DTW_NO_ROW_MAJOR)
+    if wlds and ly <= 32:                                # if (WLDS && ly <= 32): dtw_wave_level_2col<RH / R2 / R3, TIE, WLDS, true>
         return 'rm-RH' if lev == 1 else ('rm-R2' if lev == 2 else 'rm-R3')      # lev == 1 / lev == 2 / else
-    return 'pp-lds' if wlds else 'pp-global'             # else dtw_wave_level_pp<RH, TIE, WLDS>
+    return 'pp-lds' if wlds else 'pp-global'             # else dtw_wave_level_2col<RH, TIE, WLDS, false>
 
 
 def pair_labels(max_x, max_y, kernel, ly, lx):
