@@ -617,6 +617,21 @@ int sgnn_cross_entropy_fwd(const float* logits, const int64_t* labels, int64_t B
 int sgnn_cross_entropy_bwd(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss,
                            int64_t B, int64_t K, float* grad_logits, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Multi-label loss and accuracy of a training step in one pass over the logits: nn.BCEWithLogitsLoss() (mean over all B x K
+ * elements, SubGNN/SubGNN.py:133) and the exact-match accuracy the step logs (subgraph_utils.calc_accuracy with a binarizer,
+ * SubGNN/subgraph_utils.py:108-124: a row counts when sigmoid(x) > 0.5 equals the target in every column).
+ * logits: (B, K) float, targets: (B, K) int64 indicator matrix (non-zero counts as 1), any K.  loss, accuracy: one float each
+ * (accuracy nullable).  The prediction is the float32 expression 1 / (1 + exp(-x)) > 0.5, as torch.sigmoid(x) > 0.5.
+ * grad_logits = (sigmoid(x) - y) * grad_loss[0] / (B K), the sigmoid evaluated without overflow.  Nothing is saved between the
+ * two calls.  workspace: sgnn_bce_logits_workspace_bytes(B) bytes.  Partial sums are added in a fixed order: bit-reproducible.
+ * ------------------------------------------------------------------------------------- */
+int64_t sgnn_bce_logits_workspace_bytes(int64_t B);
+int sgnn_bce_logits_fwd(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
+                        void* workspace, int64_t workspace_bytes, void* stream);
+int sgnn_bce_logits_bwd(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K,
+                        float* grad_logits, void* stream);
+
 /* Column sums of a row-major matrix x (R rows of A floats, row stride ld): out[a] = sum_r x[r, a] -- the bias gradients of the
  * head's Linear layers over a shard's rows (autograd of SubGNN/SubGNN.py:304-312).  Row-block partials added in block order:
  * bit-reproducible.  workspace: sgnn_column_sum_workspace_bytes. */
@@ -842,6 +857,19 @@ int sgnn_head_bwd(const float* logits, const float* lse, const int64_t* labels, 
                   const float* grad_logits, const float* rows, const float* a1, const float* a2, const float* W2,
                   const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial,
                   void* stream);
+
+/* The same head in multi-label mode (nn.BCEWithLogitsLoss, SubGNN/SubGNN.py:133; exact-match accuracy, SubGNN/subgraph_utils.py:
+ * 108-124): kernels of their own, so the single-label launches above carry nothing for it.  targets: (B, K) int64 indicator
+ * matrix (non-zero counts as 1, not nullable).  out = [sum of the element losses / (B K), rows whose K predictions
+ * (1 / (1 + exp(-x)) > 0.5 in float32) all equal their targets / B, B K].  No lse: the backward recomputes
+ * dlogits = (sigmoid(x) - y) grad_loss[0] / rows[0] (+ grad_logits, nullable) from the logits; rows = out + 2.  Workspace, ticket,
+ * partials, summation order, dropout masks and the {seed, step} state are those of sgnn_head_fwd / sgnn_head_bwd. */
+int sgnn_head_fwd_ml(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                     const float* W3, const float* b3, const int64_t* targets, float p, int64_t* rng, float* a1, float* a2,
+                     float* logits, float* out, void* workspace, int64_t workspace_bytes, void* stream);
+int sgnn_head_bwd_ml(const float* logits, const int64_t* targets, const float* grad_loss, const float* grad_logits,
+                     const float* rows, const float* a1, const float* a2, const float* W2, const float* W3, int64_t B,
+                     int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream);
 
 /* A^T B for tall operands (the weight gradients of Linear / LSTM layers: outputs of a few thousand elements contracted over
  * thousands of rows -- a library GEMM runs them on a handful of workgroups): job k contracts A[k] (R[k], M[k]) with B[k]

@@ -869,10 +869,12 @@ class SubGNN(nn.Module):
 
     def _head(self, subgraph_embedding):
         """S.py:304-312.  One fused launch behind the first layer's GEMM (ops.fused_head: csrc/head.hip) when the widths fit;
-        with the step's labels at hand (training_step leaves them in ``_head_labels``) the same launch computes the loss and
-        the accuracy and leaves them in ``_head_result``."""
+        with the step's labels at hand (training_step leaves them in ``_head_labels``; the (B, K) indicator matrix of a
+        multi-label step in ``_head_targets``) the same launch computes the loss and the accuracy and leaves them in
+        ``_head_result``."""
         hp = self.hparams
         labels = self.__dict__.pop('_head_labels', None)
+        targets = self.__dict__.pop('_head_targets', None)
         x = subgraph_embedding
         if (hp.get('fused_forward', True) and hp.get('fused_head', True) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
                 and x.shape[0] > 0 and ops.head_supported(self.lin.out_features, self.lin2.out_features, self.lin3.out_features)
@@ -880,8 +882,12 @@ class SubGNN(nn.Module):
             p = float(self.lin_dropout.p) if self.training else 0.0
             if labels is not None and (labels.dim() != 1 or labels.shape[0] != x.shape[0] or labels.dtype != torch.int64):
                 labels = None
-            logits, loss, acc = ops.fused_head(x, self.lin, self.lin2, self.lin3, labels, p, self._dropout_rng() if p > 0 else None)
-            if labels is not None:
+            if targets is not None and (targets.dim() != 2 or targets.shape[0] != x.shape[0] or targets.dtype != torch.int64
+                                        or targets.shape[1] != self.lin3.out_features):
+                targets = None
+            logits, loss, acc = ops.fused_head(x, self.lin, self.lin2, self.lin3, labels, p, self._dropout_rng() if p > 0 else None,
+                                               targets=targets)
+            if labels is not None or targets is not None:
                 self.__dict__['_head_result'] = (loss, acc)
             return logits
         h = self.lin_dropout(F.relu(ops.linear(subgraph_embedding, self.lin.weight, self.lin.bias)))
@@ -908,16 +914,28 @@ class SubGNN(nn.Module):
         labels = train_batch['label'].squeeze(-1)
         fusable = not self.multilabel and labels.is_cuda and labels.dim() == 1 and type(self.loss) is nn.CrossEntropyLoss \
             and self.hparams.get('fused_forward', True)
+        # multi-label (HPO-NEURO): BCE with logits + exact-match accuracy in the head's launch too, straight from the int64 (B, K)
+        # indicator matrix the split keeps on the device; hparams['fused_multilabel_loss'] = False is the library path
+        fusable_ml = self.multilabel and labels.is_cuda and labels.dim() == 2 and labels.dtype == torch.int64 \
+            and labels.shape[1] == self.lin3.out_features and type(self.loss) is nn.BCEWithLogitsLoss \
+            and self.hparams.get('fused_forward', True) and self.hparams.get('fused_multilabel_loss', True)
         self.__dict__.pop('_head_result', None)
         if fusable:
             self.__dict__['_head_labels'] = labels          # the head computes loss + accuracy in its own launch (_head)
+        elif fusable_ml:
+            self.__dict__['_head_targets'] = labels
         try:
             logits = self._forward_batch('train', train_batch)
         finally:
             self.__dict__.pop('_head_labels', None)
+            self.__dict__.pop('_head_targets', None)
         done = self.__dict__.pop('_head_result', None)
         if done is not None:
             loss, acc = done
+            return {'loss': loss, 'log': {'train_loss': loss, 'train_acc': acc}}
+        if fusable_ml and logits.is_cuda and logits.dtype == torch.float32 and logits.shape == labels.shape:
+            # a head the fused kernel does not take (widths above 128, K above 32, fused_head: false): one pass over the logits
+            loss, acc = ops.bce_with_logits_and_accuracy(logits, labels)
             return {'loss': loss, 'log': {'train_loss': loss, 'train_acc': acc}}
         if not self.multilabel and logits.is_cuda and logits.dim() == 2 and labels.dim() == 1 and logits.dtype == torch.float32 \
                 and type(self.loss) is nn.CrossEntropyLoss and self.hparams.get('fused_forward', True):

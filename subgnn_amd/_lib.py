@@ -117,6 +117,9 @@ SIGNATURES = {
     'sgnn_cross_entropy_workspace_bytes': (c_i64, [c_i64]),
     'sgnn_cross_entropy_fwd': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_cross_entropy_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    'sgnn_bce_logits_workspace_bytes': (c_i64, [c_i64]),
+    'sgnn_bce_logits_fwd': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    'sgnn_bce_logits_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
     'sgnn_column_sum_workspace_bytes': (c_i64, [c_i64, c_i64]),
     'sgnn_column_sum': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_readout_sum_bwd_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64]),
@@ -142,6 +145,10 @@ SIGNATURES = {
                               c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_head_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64,
                               ctypes.c_float, c_ptr, c_ptr, c_ptr]),
+    'sgnn_head_fwd_ml': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float, c_ptr, c_ptr, c_ptr,
+                                 c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
+    'sgnn_head_bwd_ml': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64,
+                                 ctypes.c_float, c_ptr, c_ptr, c_ptr]),
     'sgnn_contract_rows_max_jobs': (c_i64, []),
     'sgnn_contract_rows_blocks': (c_i64, [c_i64, c_i64, c_i64]),
     'sgnn_contract_rows_partial': (c_int, [c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),

@@ -20,6 +20,13 @@
 // memory and is advanced by the forward kernel's last workgroup, so a step replayed from a hipGraph draws fresh masks; what
 // the backward needs of a mask is in the saved activations (a == 0 <=> dropped or not activated).  p = 0 touches no random
 // state at all.
+//
+// Multi-label mode (HPO-NEURO: nn.BCEWithLogitsLoss, SubGNN.py:133, and the exact-match accuracy of su:108-124): the same two
+// bodies instantiated with ML = 1 as kernels of their own (head_fwd_ml_kernel, head_bwd_ml_kernel<NB>) -- the single-label
+// launches carry no argument and no branch for it.  `labels` is then the int64 (B, K) 0/1 indicator matrix (non-zero counts as
+// 1), a row's loss the sum over k of max(x, 0) - x y + log1p(exp(-|x|)), a row a hit when 1 / (1 + exp(-x)) > 0.5 (float32, as
+// torch.sigmoid(x) > 0.5 evaluates it: NOT x > 0) equals y in every column; out = [sum / (B K), hits / B, B K].  Nothing is saved
+// for the backward (no lse): dlogits = (sigmoid(x) - y) g / (B K) is recomputed from the logits.
 #include "common.h"
 
 #define HEAD_RB 32
@@ -61,7 +68,16 @@ __device__ __forceinline__ float head_dot4(const float4 a, const float4 b, float
     acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc); acc = fmaf(a.z, b.z, acc); return fmaf(a.w, b.w, acc);
 }
 
-__global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const HeadFwd A)
+// sigmoid that cannot overflow: exp of a non-positive argument only
+__device__ __forceinline__ float head_sigmoid(float x)
+{
+    if (x >= 0.f) return 1.f / (1.f + expf(-x));
+    const float e = expf(x);
+    return e / (1.f + e);
+}
+
+template <int ML>
+__device__ __forceinline__ void head_fwd_body(const HeadFwd A)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H1 = A.H1, H2 = A.H2, K = A.K, tid = threadIdx.x;
@@ -150,7 +166,21 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const HeadFwd A)
             lgs[idx] = acc;
         }
         __syncthreads();
-        if (A.labels && tid < nr) {
+        if (ML) {
+            if (A.labels && tid < nr) {
+                const float* x = lgs + tid * K;
+                const int64_t* y = A.labels + (row0 + tid) * K;
+                float l = 0.f;
+                bool all = true;
+                for (int k = 0; k < K; ++k) {
+                    const float v = x[k];
+                    const bool t = y[k] != 0;
+                    l += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
+                    all = all && ((1.f / (1.f + expf(-v)) > 0.5f) == t);           // torch.sigmoid(x) > 0.5 in float32
+                }
+                loss += l; hit += all ? 1.f : 0.f; cnt += (float)K;
+            }
+        } else if (A.labels && tid < nr) {
             const float* x = lgs + tid * K;
             float m = x[0];
             int am = 0;
@@ -184,7 +214,14 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const HeadFwd A)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); h += __shfl_xor(h, o, 64); n += __shfl_xor(n, o, 64); }
     if (tid == 0) {
-        if (A.labels) {
+        if (ML) {
+            if (A.labels) {
+                const float bk = (float)(A.B * (int64_t)K);                        // (not the sum of the counts: exact past 2^24 too)
+                A.out[0] = a / bk;
+                A.out[1] = h / (float)A.B;
+                A.out[2] = bk;
+            }
+        } else if (A.labels) {
             A.out[0] = a / n;                            // every row ignored: 0 / 0 = NaN, as the library gives
             A.out[1] = h / (float)A.B;
             A.out[2] = n;
@@ -195,12 +232,15 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const HeadFwd A)
     }
 }
 
+__global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const HeadFwd A) { head_fwd_body<0>(A); }
+__global__ __launch_bounds__(HEAD_THREADS) void head_fwd_ml_kernel(const HeadFwd A) { head_fwd_body<1>(A); }
+
 // partial layout of one workgroup: [gW3 (K H2) | gb3 (K) | gW2 (H2 H1) | gb2 (H2) | gb1 (H1)]
 __host__ __device__ static inline int64_t head_partial_floats(int H1, int H2, int K) { return (int64_t)K * H2 + K + (int64_t)H2 * H1 + H2 + H1; }
 
 // NB: 4 x 4 blocks of gW2 a thread keeps in registers (1: up to 64 x 64 weights, 2: 128 x 64, 4: 128 x 128)
-template <int NB>
-__global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(const HeadBwd A)
+template <int NB, int ML>
+__device__ __forceinline__ void head_bwd_body(const HeadBwd A)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H1 = A.H1, H2 = A.H2, K = A.K, tid = threadIdx.x;
@@ -241,7 +281,10 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(const HeadBwd A)
         for (int idx = tid; idx < nr * K; idx += HEAD_THREADS) {
             const int r = idx / K, c = idx - r * K;
             float v = 0.f;
-            if (A.labels && A.g_loss) {
+            if (ML) {
+                if (A.labels && A.g_loss)
+                    v = (head_sigmoid(A.logits[row0 * K + idx]) - (A.labels[row0 * K + idx] != 0 ? 1.f : 0.f)) * gscale;
+            } else if (A.labels && A.g_loss) {
                 const int64_t y = A.labels[row0 + r];
                 if (y >= 0 && y < K) v = (expf(A.logits[row0 * K + idx] - A.lse[row0 + r]) - (c == (int)y ? 1.f : 0.f)) * gscale;
             }
@@ -342,6 +385,9 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(const HeadBwd A)
         }
     }
 }
+
+template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(const HeadBwd A) { head_bwd_body<NB, 0>(A); }
+template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_ml_kernel(const HeadBwd A) { head_bwd_body<NB, 1>(A); }
 
 // ---- A^T B for tall operands: partial sums over row blocks (fp32 MFMA) ----------------------------------------------------------
 // part[blk][m][n] = sum over the block's rows r of A[r][m] B[r][n].  blockIdx.x = row block (four wavefronts of `wr` rows each),
@@ -498,13 +544,14 @@ static int head_set_lds(const void* kernel, size_t bytes)
     return 0;
 }
 
-extern "C" int sgnn_head_fwd(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
-                             const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1, float* a2,
-                             float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream)
+// ml: `labels` is the (B, K) indicator matrix and the launch is head_fwd_ml_kernel (no lse)
+static int head_fwd_launch(bool ml, const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                           const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1, float* a2,
+                           float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream)
 {
     if (!z1 || !W2 || !W3 || !a1 || !a2 || !logits || B < 1 || !(p >= 0.f && p < 1.f)) return SGNN_ERR_BAD_ARG;
     if (!sgnn_head_supported(H1, H2, K)) return SGNN_ERR_UNSUPPORTED_D;
-    if (labels && (!lse || !out)) return SGNN_ERR_BAD_ARG;
+    if (labels && ((!ml && !lse) || !out)) return SGNN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < sgnn_head_fwd_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
     HeadFwd A;
     A.z1 = z1; A.W2 = W2; A.b2 = b2; A.W3 = W3; A.b3 = b3; A.labels = labels; A.rng = (p > 0.f) ? rng : nullptr;
@@ -515,8 +562,58 @@ extern "C" int sgnn_head_fwd(const float* z1, int64_t B, int64_t H1, int64_t H2,
     A.ticket = (unsigned*)((char*)workspace + 3 * nb * 4);
     const int64_t H1p = (H1 + 3) & ~3ll, H2p = (H2 + 3) & ~3ll, H2e = (H2 + 1) & ~1ll;
     const size_t lds = (size_t)(H2e * (H1p + 4) + K * (H2p + 4) + HEAD_RB * (H1p + H2p + K)) * 4;
-    if (head_set_lds((const void*)head_fwd_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
-    hipLaunchKernelGGL(head_fwd_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A);
+    if (ml) {
+        if (head_set_lds((const void*)head_fwd_ml_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
+        hipLaunchKernelGGL(head_fwd_ml_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A);
+    } else {
+        if (head_set_lds((const void*)head_fwd_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
+        hipLaunchKernelGGL(head_fwd_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A);
+    }
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
+extern "C" int sgnn_head_fwd(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                             const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1, float* a2,
+                             float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    return head_fwd_launch(false, z1, B, H1, H2, K, W2, b2, W3, b3, labels, p, rng, a1, a2, logits, lse, out, workspace, workspace_bytes,
+                           stream);
+}
+
+extern "C" int sgnn_head_fwd_ml(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                                const float* W3, const float* b3, const int64_t* targets, float p, int64_t* rng, float* a1, float* a2,
+                                float* logits, float* out, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (!targets) return SGNN_ERR_BAD_ARG;
+    return head_fwd_launch(true, z1, B, H1, H2, K, W2, b2, W3, b3, targets, p, rng, a1, a2, logits, nullptr, out, workspace,
+                           workspace_bytes, stream);
+}
+
+static int head_bwd_launch(bool ml, const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,
+                           const float* grad_logits, const float* rows, const float* a1, const float* a2, const float* W2,
+                           const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial,
+                           void* stream)
+{
+    if (!a1 || !a2 || !W2 || !W3 || !dz1 || !partial || B < 1 || !(p >= 0.f && p < 1.f)) return SGNN_ERR_BAD_ARG;
+    if (!sgnn_head_supported(H1, H2, K)) return SGNN_ERR_UNSUPPORTED_D;
+    if (grad_loss && (!labels || !logits || (!ml && !lse) || !rows)) return SGNN_ERR_BAD_ARG;
+    HeadBwd A;
+    A.logits = logits; A.lse = lse; A.labels = labels; A.g_loss = grad_loss; A.g_logits = grad_logits; A.rows = rows;
+    A.a1 = a1; A.a2 = a2; A.W2 = W2; A.W3 = W3; A.B = B; A.H1 = (int)H1; A.H2 = (int)H2; A.K = (int)K;
+    A.scale = 1.f / (1.f - p);
+    A.dz1 = dz1; A.partial = partial;
+    const int64_t H1p = (H1 + 3) & ~3ll, H2p = (H2 + 3) & ~3ll, H1e = (H1 + 1) & ~1ll;
+    const size_t lds = (size_t)(H1e * (H2p + 4) + K * H2p + HEAD_RB * (K + 2 * H2p + 2 * H1p)) * 4;
+    const int64_t nblocks = (H2p / 4) * (H1p / 4);
+#define HEAD_BWD(KERNEL, NB) do { if (head_set_lds((const void*)KERNEL<NB>, lds) != 0) return SGNN_ERR_LAUNCH; \
+                                  hipLaunchKernelGGL(KERNEL<NB>, dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A); } while (0)
+    if (ml) {
+        if (nblocks <= HEAD_THREADS) HEAD_BWD(head_bwd_ml_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD(head_bwd_ml_kernel, 2); else HEAD_BWD(head_bwd_ml_kernel, 4);
+    } else {
+        if (nblocks <= HEAD_THREADS) HEAD_BWD(head_bwd_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD(head_bwd_kernel, 2); else HEAD_BWD(head_bwd_kernel, 4);
+    }
+#undef HEAD_BWD
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
@@ -526,23 +623,15 @@ extern "C" int sgnn_head_bwd(const float* logits, const float* lse, const int64_
                              const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial,
                              void* stream)
 {
-    if (!a1 || !a2 || !W2 || !W3 || !dz1 || !partial || B < 1 || !(p >= 0.f && p < 1.f)) return SGNN_ERR_BAD_ARG;
-    if (!sgnn_head_supported(H1, H2, K)) return SGNN_ERR_UNSUPPORTED_D;
-    if (grad_loss && (!labels || !logits || !lse || !rows)) return SGNN_ERR_BAD_ARG;
-    HeadBwd A;
-    A.logits = logits; A.lse = lse; A.labels = labels; A.g_loss = grad_loss; A.g_logits = grad_logits; A.rows = rows;
-    A.a1 = a1; A.a2 = a2; A.W2 = W2; A.W3 = W3; A.B = B; A.H1 = (int)H1; A.H2 = (int)H2; A.K = (int)K;
-    A.scale = 1.f / (1.f - p);
-    A.dz1 = dz1; A.partial = partial;
-    const int64_t H1p = (H1 + 3) & ~3ll, H2p = (H2 + 3) & ~3ll, H1e = (H1 + 1) & ~1ll;
-    const size_t lds = (size_t)(H1e * (H2p + 4) + K * H2p + HEAD_RB * (K + 2 * H2p + 2 * H1p)) * 4;
-    const int64_t nblocks = (H2p / 4) * (H1p / 4);
-#define HEAD_BWD(NB) do { if (head_set_lds((const void*)head_bwd_kernel<NB>, lds) != 0) return SGNN_ERR_LAUNCH; \
-                          hipLaunchKernelGGL(head_bwd_kernel<NB>, dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A); } while (0)
-    if (nblocks <= HEAD_THREADS) HEAD_BWD(1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD(2); else HEAD_BWD(4);
-#undef HEAD_BWD
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
+    return head_bwd_launch(false, logits, lse, labels, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K, p, dz1, partial, stream);
+}
+
+extern "C" int sgnn_head_bwd_ml(const float* logits, const int64_t* targets, const float* grad_loss, const float* grad_logits,
+                                const float* rows, const float* a1, const float* a2, const float* W2, const float* W3, int64_t B,
+                                int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream)
+{
+    return head_bwd_launch(true, logits, nullptr, targets, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K, p, dz1, partial,
+                           stream);
 }
 
 // rows per wavefront of a job: enough row blocks that blocks x output tiles fill the chip twice (~512 workgroups), no more -- every

@@ -110,4 +110,97 @@ extern "C" int sgnn_cross_entropy_bwd(const float* logits, const int64_t* labels
     return SGNN_OK;
 }
 
+// ---- multi-label: nn.BCEWithLogitsLoss() (mean over B x K, SubGNN.py:133 with several labels per subgraph) + the exact-match
+// accuracy of su:108-124, for any K.  targets: int64 (B, K) indicator matrix, non-zero counts as 1.  A thread walks its row in k
+// order: l = max(x, 0) - x y + log1p(exp(-|x|)); the row is a hit when 1 / (1 + exp(-x)) > 0.5 (float32, as torch.sigmoid(x) >
+// 0.5 evaluates it -- not x > 0) equals y in every column.  Same partials and the same fixed order as the single-label pair.
+__global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets, int64_t B,
+                                                      int32_t K, float* __restrict__ partial_loss, float* __restrict__ partial_hits)
+{
+    __shared__ float sh_l[256], sh_h[256];
+    const int64_t r = blockIdx.x * 256ll + threadIdx.x;
+    float loss = 0.f, hit = 0.f;
+    if (r < B) {
+        const float* x = logits + r * K;
+        const int64_t* y = targets + r * K;
+        bool all = true;
+        for (int32_t k = 0; k < K; ++k) {
+            const float v = x[k];
+            const bool t = y[k] != 0;
+            loss += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
+            all = all && ((1.f / (1.f + expf(-v)) > 0.5f) == t);
+        }
+        hit = all ? 1.f : 0.f;
+    }
+    sh_l[threadIdx.x] = loss;
+    sh_h[threadIdx.x] = hit;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        float a = (sh_l[threadIdx.x] + sh_l[threadIdx.x + 64]) + (sh_l[threadIdx.x + 128] + sh_l[threadIdx.x + 192]);
+        float h = (sh_h[threadIdx.x] + sh_h[threadIdx.x + 64]) + (sh_h[threadIdx.x + 128] + sh_h[threadIdx.x + 192]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); h += __shfl_xor(h, o, 64); }
+        if (threadIdx.x == 0) { partial_loss[blockIdx.x] = a; partial_hits[blockIdx.x] = h; }
+    }
+}
+
+__global__ __launch_bounds__(64) void bce_finish_kernel(const float* __restrict__ partial_loss, const float* __restrict__ partial_hits,
+                                                        int64_t nblk, int64_t B, int64_t K, float* __restrict__ loss,
+                                                        float* __restrict__ accuracy)
+{
+    float a = 0.f, h = 0.f;
+    for (int64_t k = threadIdx.x; k < nblk; k += 64) { a += partial_loss[k]; h += partial_hits[k]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); h += __shfl_xor(h, o, 64); }
+    if (threadIdx.x == 0) {
+        loss[0] = a / (float)(B * K);
+        if (accuracy) accuracy[0] = h / (float)B;
+    }
+}
+
+// d loss / d logits[r, k] = (sigmoid(x) - y) * grad_loss / (B K); the sigmoid takes exp of a non-positive argument only
+__global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                      const float* __restrict__ grad_loss, int64_t n, float* __restrict__ grad_logits)
+{
+    const int64_t t = blockIdx.x * 256ll + threadIdx.x;
+    if (t >= n) return;
+    const float x = logits[t], e = expf(-fabsf(x));
+    const float sig = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    grad_logits[t] = (sig - (targets[t] != 0 ? 1.f : 0.f)) * (grad_loss[0] / (float)n);
+}
+
+extern "C" int64_t sgnn_bce_logits_workspace_bytes(int64_t B)
+{
+    if (B < 0) return -1;
+    return 2 * ce_blocks(B) * (int64_t)sizeof(float) + 16;
+}
+
+extern "C" int sgnn_bce_logits_fwd(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
+                                   void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (!logits || !targets || !loss || B < 1 || K < 1 || K > 0x7fffffff || B > (int64_t)0x7fffffffffffffffll / K) return SGNN_ERR_BAD_ARG;
+    if (!workspace || workspace_bytes < sgnn_bce_logits_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
+    const int64_t nblk = ce_blocks(B);
+    if (nblk > 0x7fffffff) return SGNN_ERR_BAD_ARG;
+    float* pl = (float*)workspace;
+    float* ph = pl + nblk;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(bce_fwd_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, pl, ph);
+    SGNN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(bce_finish_kernel, dim3(1), dim3(64), 0, st, pl, ph, nblk, B, K, loss, accuracy);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
+extern "C" int sgnn_bce_logits_bwd(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K,
+                                   float* grad_logits, void* stream)
+{
+    if (!logits || !targets || !grad_loss || !grad_logits || B < 1 || K < 1 || B > (int64_t)0x7fffffffffffffffll / K) return SGNN_ERR_BAD_ARG;
+    if ((B * K + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
+    hipLaunchKernelGGL(bce_bwd_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, targets,
+                       grad_loss, B * K, grad_logits);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
 SGNN_DEFINE_WARM(loss)

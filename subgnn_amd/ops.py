@@ -2292,6 +2292,47 @@ def cross_entropy_with_accuracy(logits, labels):
     return _CrossEntropy.apply(logits.contiguous(), labels.contiguous())
 
 
+class _BCEWithLogits(torch.autograd.Function):
+    """(mean binary cross entropy, exact-match accuracy) of logits (B, K) against an int64 (B, K) indicator matrix
+    (sgnn_bce_logits_fwd / _bwd).  Nothing but the two inputs is saved: the backward recomputes the sigmoid."""
+
+    @staticmethod
+    def forward(ctx, logits, targets):
+        lib = _lib.load()
+        _req(logits, torch.float32, 'logits')
+        _req(targets, torch.int64, 'targets')
+        if logits.dim() != 2 or targets.shape != logits.shape or logits.numel() == 0:
+            raise ValueError('bce_with_logits_and_accuracy: logits %s and targets %s must be the same non-empty (B, K)'
+                             % (tuple(logits.shape), tuple(targets.shape)))
+        B, K = logits.shape
+        res = torch.empty(2, dtype=torch.float32, device=logits.device)
+        wsb = lib.sgnn_bce_logits_workspace_bytes(B)
+        ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=logits.device)
+        check(lib.sgnn_bce_logits_fwd(_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb,
+                                      _stream()), 'sgnn_bce_logits_fwd')
+        ctx.save_for_backward(logits, targets)
+        loss, acc = res[0], res[1:2]
+        ctx.mark_non_differentiable(acc)
+        return loss, acc
+
+    @staticmethod
+    def backward(ctx, g_loss, _g_acc):
+        lib = _lib.load()
+        logits, targets = ctx.saved_tensors
+        B, K = logits.shape
+        g = torch.empty_like(logits)
+        check(lib.sgnn_bce_logits_bwd(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K, _ptr(g),
+                                      _stream()), 'sgnn_bce_logits_bwd')
+        return g, None
+
+
+def bce_with_logits_and_accuracy(logits, targets):
+    """nn.BCEWithLogitsLoss()(logits, targets.float()) and the exact-match accuracy calc_accuracy logs for a multi-label batch
+    (every sigmoid(x) > 0.5 of a row equal to its target) -> (0-d loss, (1,) accuracy) in one pass.  ``targets``: int64 (B, K)
+    indicator matrix, as the data loader keeps it (no float copy is made); any K."""
+    return _BCEWithLogits.apply(logits.contiguous(), targets.contiguous())
+
+
 # ---------------------------------------------------------------------------------------
 # the MLP head + loss of a step (csrc/head.hip)
 # ---------------------------------------------------------------------------------------
@@ -2398,7 +2439,7 @@ class _FusedHead(torch.autograd.Function):
     every weight and bias gradient of the head.  9 + 22 launches -> 2 + 4."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, W3, b3, labels, p, rng):
+    def forward(ctx, x, W1, b1, W2, b2, W3, b3, labels, p, rng, ml):
         lib = _lib.load()
         for t, nm in ((x, 'x'), (W1, 'W1'), (b1, 'b1'), (W2, 'W2'), (b2, 'b2'), (W3, 'W3'), (b3, 'b3')):
             _req(t, torch.float32, nm)
@@ -2406,18 +2447,25 @@ class _FusedHead(torch.autograd.Function):
         _req(rng, torch.int64, 'rng')
         B, H1, H2, K = x.shape[0], W1.shape[0], W2.shape[0], W3.shape[0]
         dev = x.device
+        if ml and (labels is None or tuple(labels.shape) != (B, K)):
+            raise ValueError('fused_head: targets must be an int64 (%d, %d) indicator matrix' % (B, K))
         z1 = torch.addmm(b1, x, W1.t()) if b1 is not None else x @ W1.t()
         a1 = torch.empty((B, H1), dtype=torch.float32, device=dev)
         a2 = torch.empty((B, H2), dtype=torch.float32, device=dev)
         logits = torch.empty((B, K), dtype=torch.float32, device=dev)
-        lse = torch.empty(B + 1, dtype=torch.float32, device=dev) if labels is not None else None
+        lse = torch.empty(B + 1, dtype=torch.float32, device=dev) if (labels is not None and not ml) else None
         out = torch.empty(3, dtype=torch.float32, device=dev) if labels is not None else None
         ws = _head_workspace(dev, B)
-        check(lib.sgnn_head_fwd(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p), _ptr(rng),
-                                _ptr(a1), _ptr(a2), _ptr(logits), _ptr(lse), _ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
-              'sgnn_head_fwd')
+        if ml:                                               # multi-label: ``labels`` is the (B, K) indicator matrix; no lse
+            check(lib.sgnn_head_fwd_ml(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p), _ptr(rng),
+                                       _ptr(a1), _ptr(a2), _ptr(logits), _ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
+                  'sgnn_head_fwd_ml')
+        else:
+            check(lib.sgnn_head_fwd(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p), _ptr(rng),
+                                    _ptr(a1), _ptr(a2), _ptr(logits), _ptr(lse), _ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
+                  'sgnn_head_fwd')
         ctx.save_for_backward(x, W1, W2, W3, a1, a2, logits, lse, labels, out)
-        ctx.p, ctx.dims = float(p), (B, H1, H2, K)
+        ctx.p, ctx.dims, ctx.ml = float(p), (B, H1, H2, K), bool(ml)
         ctx.has_bias = (b1 is not None, b2 is not None, b3 is not None)
         ctx.set_materialize_grads(False)
         if labels is None:
@@ -2433,16 +2481,20 @@ class _FusedHead(torch.autograd.Function):
         B, H1, H2, K = ctx.dims
         dev = x.device
         if g_logits is None and g_loss is None:
-            return (None,) * 10
+            return (None,) * 11
         g_logits = g_logits.contiguous() if g_logits is not None else None
         g_loss = g_loss.reshape(1).contiguous().float() if g_loss is not None else None
         P = int(lib.sgnn_head_partial_floats(H1, H2, K))
         nb = int(lib.sgnn_head_blocks(B))
         dz1 = torch.empty((B, H1), dtype=torch.float32, device=dev)
         partial = torch.empty((nb, P), dtype=torch.float32, device=dev)
-        check(lib.sgnn_head_bwd(_ptr(logits), _ptr(lse), _ptr(labels), _ptr(g_loss), _ptr(g_logits),
-                                ctypes.c_void_p(out.data_ptr() + 8) if out is not None else None, _ptr(a1), _ptr(a2), _ptr(W2),
-                                _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream()), 'sgnn_head_bwd')
+        rows = ctypes.c_void_p(out.data_ptr() + 8) if out is not None else None
+        if ctx.ml:
+            check(lib.sgnn_head_bwd_ml(_ptr(logits), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2), _ptr(W2),
+                                       _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream()), 'sgnn_head_bwd_ml')
+        else:
+            check(lib.sgnn_head_bwd(_ptr(logits), _ptr(lse), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2),
+                                    _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream()), 'sgnn_head_bwd')
         # gW1 = dz1^T x: block partials on the matrix cores; its blocks and the head kernel's partials are added by ONE launch
         flat = torch.empty(P, dtype=torch.float32, device=dev)
         jobs_part, jobs_nb, jobs_n, jobs_out = [partial], [nb], [P], [flat]
@@ -2473,19 +2525,26 @@ class _FusedHead(torch.autograd.Function):
         need = ctx.needs_input_grad
         dx = dz1 @ W1 if need[0] else None
         return (dx, gW1, gb1 if (hb[0] and need[2]) else None, gW2 if need[3] else None, gb2 if (hb[1] and need[4]) else None,
-                gW3 if need[5] else None, gb3 if (hb[2] and need[6]) else None, None, None, None)
+                gW3 if need[5] else None, gb3 if (hb[2] and need[6]) else None, None, None, None, None)
 
 
-def fused_head(x, lin, lin2, lin3, labels=None, p=0.0, rng=None):
-    """The head's three Linear layers with relu + dropout(p) between them, and -- with ``labels`` -- the mean cross entropy and
-    the accuracy of the logits (``lin*``: nn.Linear modules).  -> (logits, loss or None, accuracy (1,) or None).
+def fused_head(x, lin, lin2, lin3, labels=None, p=0.0, rng=None, targets=None):
+    """The head's three Linear layers with relu + dropout(p) between them, and -- with ``labels`` (int64 (B,)) -- the mean cross
+    entropy and the accuracy of the logits, or -- with ``targets`` (int64 (B, K) indicator matrix, multi-label) -- the mean binary
+    cross entropy with logits and the exact-match accuracy (``lin*``: nn.Linear modules).
+    -> (logits, loss or None, accuracy (1,) or None).
     ``rng``: int64 (2,) device tensor {seed, step} when p > 0 (the launch advances step)."""
+    if labels is not None and targets is not None:
+        raise ValueError('fused_head: labels (single-label) and targets (multi-label) exclude each other')
     if p > 0 and rng is None:
         raise ValueError('fused_head: dropout needs the {seed, step} tensor')
     if x.stride(1) != 1 or x.stride(0) != x.shape[1]:
         x = x.contiguous()
+    if targets is not None:
+        return _FusedHead.apply(x, lin.weight, lin.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias, targets.contiguous(),
+                                float(p), rng if p > 0 else None, True)
     return _FusedHead.apply(x, lin.weight, lin.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias,
-                            labels.contiguous() if labels is not None else None, float(p), rng if p > 0 else None)
+                            labels.contiguous() if labels is not None else None, float(p), rng if p > 0 else None, False)
 
 
 class _GatherRows(torch.autograd.Function):

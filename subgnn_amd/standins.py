@@ -18,6 +18,12 @@ constructor reads them like real data.
                          best_model_hyperparameters/em_user/hyperparams.json (k=2 border, B=32,
                          trainable_cc) with all three channels on, fp16-stored table, ff_attn read-out; the dense
                          (N, N) float64 hop matrix would be 26 GB -> hotpath.prepare_sparse
+  hpo_neuro  (no BASELINE    the paper's multi-label dataset: the HPO graph of hpo_metab (BA n=14 587 m=222), 10 classes, a
+             configuration)  label pair ``a-b`` on every third subgraph (neuro_labels), so the loss is BCE with logits and the
+                         accuracy exact-match; best_model_hyperparameters/hpo_neuro/hyperparams.json (structure channel only,
+                         5 layers, B=128, head 64/64, 43 structure patches per layer and similarity epoch).  SURVEY section 8
+                         quotes neither the number nor the size of HPO-NEURO's subgraphs: both are hpo_metab's (2 400
+                         subgraphs of ~14 nodes in 1-2 pieces).  bench.py does not list it: standins.bench_config('hpo_neuro')
 """
 import os
 
@@ -63,12 +69,26 @@ def _ppi_pieces(rng):
     return [int(s) for s in rng.permutation([1, 1, 1, 1, 1, 2, 3])[:int(rng.integers(5, 8))]]
 
 
+def _hpo_pieces(rng):
+    return [10, 4] if rng.random() < 0.6 else [14]
+
+
+def neuro_labels(n_sub, n_classes=10):
+    """The label column of the hpo_neuro stand-in's subgraphs.pth: subgraph i carries class i % n_classes, and every third
+    subgraph a second one, written ``a-b`` as read_subgraphs parses it (su:24-92) -> list of n_sub strings."""
+    out = []
+    for i in range(n_sub):
+        a = i % n_classes
+        out.append('%d-%d' % (a, (a + 1 + (i // n_classes) % (n_classes - 1)) % n_classes) if i % 3 == 0 else str(a))
+    return out
+
+
 PRESETS = {
     'density_n': dict(recipe='density', n=1000, n_sub=250, D=32, sparse=False, hp=H1),
     'ppi_bp': dict(n=17080, m=19, n_sub=1591, n_classes=6, D=128, sparse=False, pieces=_ppi_pieces, hp=H2),
     'hpo_metab': dict(
         n=14587, m=222, n_sub=2400, n_classes=6, D=128, sparse=False,
-        pieces=lambda rng: [10, 4] if rng.random() < 0.6 else [14],
+        pieces=_hpo_pieces,
         hp=dict(_COMMON, **{
             "seed": 0, "sample_walk_len": 50, "n_triangular_walks": 5, "random_walk_len": 10, "rw_beta": 0.65,
             "batch_size": 64, "learning_rate": 0.0003658242069498871, "grad_clip": 0.26758489792349655, "n_layers": 4,
@@ -91,6 +111,18 @@ PRESETS = {
             # (the attention read-out over a batch's 32 x 20 component rows: 640 rows take the library GEMM on half-rounded
             # operands + the fused epilogue; the hand-written v_mfma_f32_32x32x16_f16 kernel serves calls of >= 2048 rows --
             # whole-split evaluation, tests/test_gpu_configs.py::test_em_user_with_ff_attn_half_mfma_scores)
+    'hpo_neuro': dict(
+        n=14587, m=222, n_sub=2400, n_classes=10, D=128, sparse=False, pieces=_hpo_pieces, labels=neuro_labels,
+        hp=dict(_COMMON, **{     # reference best_model_hyperparameters/hpo_neuro/hyperparams.json (+ max_sim_epochs, embedding_type;
+            # compute_similarities stays on: the stand-in ships no precomputed similarity files)
+            "use_neighborhood": False, "use_structure": True, "use_position": False, "seed": 786236,
+            "sample_walk_len": 50, "n_triangular_walks": 5, "random_walk_len": 10, "rw_beta": 0.65,
+            "batch_size": 128, "learning_rate": 0.0009504832387210769, "grad_clip": 0.16373986338411073, "n_layers": 5,
+            "neigh_sample_border_size": 2, "n_anchor_patches_pos_out": 186, "n_anchor_patches_pos_in": 67,
+            "n_anchor_patches_N_in": 23, "n_anchor_patches_N_out": 46, "n_anchor_patches_structure": 43,
+            "gamma_shortest_max_distance_P": 5, "linear_hidden_dim_1": 64, "linear_hidden_dim_2": 64,
+            "lstm_dropout": 0.0866602723218498, "lstm_n_layers": 1, "lin_dropout": 0.2143192412485139,
+            "cc_aggregator": "sum", "trainable_cc": False, "auto_lr_find": False, "structure_similarity_fn": "dtw"})),
 }
 
 
@@ -112,6 +144,7 @@ def write_standin(root, name, seed=7):
     und = np.unique(np.sort(edges, axis=1), axis=0)
     np.savetxt(os.path.join(d, 'edge_list.txt'), und, fmt='%d')
     rng = np.random.default_rng(seed)
+    labels = P['labels'](n_sub, P['n_classes']) if P.get('labels') else [str(i % P['n_classes']) for i in range(n_sub)]
     lines = []
     for i in range(n_sub):
         nodes = []
@@ -119,7 +152,7 @@ def write_standin(root, name, seed=7):
             nodes.extend(synthetic.bfs_subgraphs(rowptr, col, 1, int(size), int(rng.integers(1 << 30)))[0])
         nodes = list(dict.fromkeys(nodes))
         sp = 'train' if i < int(0.8 * n_sub) else ('val' if i < int(0.9 * n_sub) else 'test')
-        lines.append('-'.join(str(v - 1) for v in nodes) + '\t' + str(i % P['n_classes']) + '\t' + sp + '\t\n')
+        lines.append('-'.join(str(v - 1) for v in nodes) + '\t' + labels[i] + '\t' + sp + '\t\n')
     with open(os.path.join(d, 'subgraphs.pth'), 'w') as f:
         f.write(''.join(lines))
     torch.save(torch.randn(n, P['D'], generator=torch.Generator().manual_seed(seed)),
@@ -261,16 +294,18 @@ def time_epochs(model, hp, epochs=4, trainer_kw=None):
                 'checkpoint_write_s': round(tr.checkpoint_write_s, 4)} if tr.checkpoint_k > 0 else {})}
 
 
-def bench_config(name, steps=30, warmup=5, deterministic=True, root=None, count=True, also_atomics=False, epochs=0):
+def bench_config(name, steps=30, warmup=5, deterministic=True, root=None, count=True, also_atomics=False, epochs=0, hp_over=None):
     """One BASELINE configuration's stand-in end to end -> dict: dataset write, graph metrics, prepare_data, then the
     batch-sized training step eager and replayed (ms per step, subgraphs/s, kernels per step).  What bench.py's
-    ``configs`` object and tools/bench_standin.py report."""
+    ``configs`` object and tools/bench_standin.py report.  ``hp_over``: hyper-parameters laid over the preset's (a comparator
+    run, e.g. {'fused_multilabel_loss': False})."""
     import tempfile
     import time
     from . import config, hotpath, precompute_graph_metrics as pgm
     from .SubGNN import SubGNN, dataset_paths
     P = PRESETS[name]
     hp = dict(P['hp'])
+    hp.update(hp_over or {})
     hp['deterministic'] = bool(deterministic)
     own_root = root is None
     root = root or tempfile.mkdtemp(prefix=name + '_')
@@ -346,6 +381,7 @@ def bench_config(name, steps=30, warmup=5, deterministic=True, root=None, count=
     B = hp['batch_size']
     return {
         'metric': 'subgraphs/sec fwd+bwd (all 3 channels on)' if (hp['use_position'] and hp['use_structure']) else
+                  'subgraphs/sec fwd+bwd (structure channel only)' if hp['use_structure'] else
                   'subgraphs/sec fwd+bwd (neighborhood channel only: configs[0] as BASELINE words it)',
         'unit': 'subgraphs/s', 'n_gpus': 1,
         'value': B * 1e3 / ms_graph, 'ms_per_step': ms_graph, 'hip_graph_step': True,
