@@ -672,26 +672,20 @@ def finish_pass(model, st, timer=None):
         # benchmark's 50k) and is pure overhead on the external side (nearly all distinct).  Which it is
         # depends only on the split's components and the graph: decided on the first pass, kept.
         group = model.__dict__.setdefault('_dtw_group_rows', {})
-        xprep = model.__dict__.setdefault('_dtw_x_prep', {})
-        ent = group.get(split)
-        if ent is None or ent[0] != cc_sets.n:
+        rec = group.get(split)
+        if rec is None or rec.n != cc_sets.n:
             # the first pass of a split does not group (a choice of kernels, never of values) and does not WAIT for the answer
             # either: the distinct-row counts travel to pinned memory behind its launches (75 ms of read-back on the driver's
             # box in round 5) and a later pass picks them up
-            ent = group[split] = (cc_sets.n, False, False,
-                                  (ops.distinct_rows_async(cc_sets.ptr, ci, mx), ops.distinct_rows_async(cc_sets.ptr, ce, mx)))
-            xprep[split] = ({}, {})
+            rec = group[split] = _DtwRows(cc_sets.n, *(_DtwSide(ops.distinct_rows_async(cc_sets.ptr, x, mx)) for x in (ci, ce)))
             t.mark('dtw_row_grouping_counts_queued(first pass only)')
-        elif ent[3] is not None and not torch.cuda.is_current_stream_capturing():
-            ent = _settle_dtw_grouping(model, split, wait=False)
+        elif rec.internal.group is None and not torch.cuda.is_current_stream_capturing():
+            _settle_dtw_grouping(model, split, wait=False)
         # the component side of the DTW calls (grouping of repeated degree sequences, processing order) depends on the
-        # split's components only -- the same every pass: kept from the first one (xprep), like the dispatch orders
-        st.attrs[split + '_int_struc_similarities'] = \
-            ops.dtw_similarity(cc_sets.ptr, ci, mx, a_sets.ptr, ai, my, tie, dedupe=ent[1], x_prep=xprep[split][0],
-                               fn=fn).view(S, C, -1)
-        st.attrs[split + '_bor_struc_similarities'] = \
-            ops.dtw_similarity(cc_sets.ptr, ce, mx, a_sets.ptr, ae, my, tie, dedupe=ent[2], x_prep=xprep[split][1],
-                               fn=fn).view(S, C, -1)
+        # split's components only -- the same every pass: kept from the first one (side.prep), like the dispatch orders
+        for name, side, x, y in (('_int', rec.internal, ci, ai), ('_bor', rec.external, ce, ae)):
+            sim = ops.dtw_similarity(cc_sets.ptr, x, mx, a_sets.ptr, y, my, tie, dedupe=bool(side.group), x_prep=side.prep, fn=fn)
+            st.attrs[split + name + '_struc_similarities'] = sim.view(S, C, -1)
         t.mark('dtw')
     elif split + '_int_struc_similarities' not in st.attrs:
         st.attrs[split + '_int_struc_similarities'] = None
@@ -699,19 +693,29 @@ def finish_pass(model, st, timer=None):
     return st
 
 
+class _DtwSide:
+    """One side (internal / external degree sequences) of a split's DTW rows: whether repeated rows are grouped -- None (not
+    yet) while the distinct-row count is ``pending`` (ops.distinct_rows_async) --, and the preparation kept for the rows."""
+
+    def __init__(self, pending):
+        self.group, self.pending, self.prep = None, pending, ops.DtwRowPrep()
+
+
+_DtwRows = collections.namedtuple('_DtwRows', 'n internal external')        # model.__dict__['_dtw_group_rows'][split]
+
+
 def _settle_dtw_grouping(model, split, wait):
     """Pick up the distinct-row counts the split's first pass sent to pinned memory and decide which DTW side groups repeated
-    rows (a choice of kernels, never of values).  ``wait``: block until the copies have landed -- what a recording of the
-    preparation does BEFORE its capture starts (an event wait inside a capture invalidates it)."""
-    group = model.__dict__.setdefault('_dtw_group_rows', {})
-    ent = group.get(split)
-    if ent is None or ent[3] is None:
-        return ent
-    fr = [ops.distinct_rows_ready(p, wait=wait) for p in ent[3]]
+    rows (a choice of kernels, never of values; the kept preparations start over).  ``wait``: block until the copies have
+    landed -- what a recording of the preparation does BEFORE its capture starts (an event wait inside a capture invalidates it)."""
+    rec = model.__dict__.get('_dtw_group_rows', {}).get(split)
+    if rec is None or rec.internal.group is not None:
+        return
+    sides = (rec.internal, rec.external)
+    fr = [ops.distinct_rows_ready(s.pending, wait=wait) for s in sides]
     if all(f is not None for f in fr):
-        ent = group[split] = (ent[0], fr[0] <= 0.5, fr[1] <= 0.5, None)
-        model.__dict__.setdefault('_dtw_x_prep', {})[split] = ({}, {})
-    return ent
+        for s, f in zip(sides, fr):
+            s.group, s.pending, s.prep = f <= 0.5, None, ops.DtwRowPrep()
 
 
 def install_pass(model, st, timer=None):

@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory, streams, autograd bookkeeping); every o
 below runs a hand-written HIP kernel of libsubgnn_hip.so on the current stream.  Inputs
 must already live on the GPU; nothing here falls back to a CPU implementation.
 """
+import collections
 import ctypes
 import functools
 import threading
@@ -874,21 +875,10 @@ def _unique_rows(rows):
     return rows[is_rep], gid[rep]
 
 
-def distinct_row_fraction(x_ptr, x_val, max_x):
-    """Share of the x rows that are distinct (one host round trip): what decides whether grouping
-    repeated rows before the DTW pays.  A property of the split's components and the graph -- callers
-    that run the same rows every pass (hotpath.prepare_sparse) ask once and keep the answer."""
-    n = x_ptr.numel() - 1
-    if n <= 1024 or max_x > 64:
-        return 1.0
-    rows = Ragged(x_ptr, x_val, max_len=max_x).to_padded(width=max_x, fill=-1, dtype=torch.int32)
-    rep = _row_representatives(rows)
-    return float((rep == torch.arange(n, device=rows.device)).sum().item()) / n
-
-
 def distinct_rows_async(x_ptr, x_val, max_x):
-    """distinct_row_fraction without the wait: the count of distinct rows travels to pinned host memory behind the launches
-    queued here -> (pinned int64 (1,), event, n rows) or None where the answer is known (few rows / long rows: no grouping).
+    """How many of the x rows are distinct -- what decides whether grouping them before the DTW pays, a property of the
+    split's components and the graph -- without a wait: the count travels to pinned host memory behind the launches queued
+    here -> (pinned int64 (1,), event, n rows) or None where the answer is known (few rows / long rows: no grouping).
     ``distinct_rows_ready`` reads it once the copy has landed."""
     n = x_ptr.numel() - 1
     if n <= 1024 or max_x > 64:
@@ -915,11 +905,98 @@ def distinct_rows_ready(pending, wait=False):
     return float(int(host[0])) / n
 
 
-DTW_FNS = ('dtw', 'dtw_exact')          # values of hparams['structure_similarity_fn'] the library computes
+_DTW_ENTRIES = {                        # fn -> (workspace query, similarity entry, whether it takes tie_order)
+    'dtw': ('sgnn_dtw_workspace_bytes', 'sgnn_dtw_similarity', True),
+    'dtw_exact': ('sgnn_dtw_exact_workspace_bytes', 'sgnn_dtw_exact_similarity', False),
+}
+DTW_FNS = tuple(_DTW_ENTRIES)           # values of hparams['structure_similarity_fn'] the library computes
+
+# The grouping of repeated x rows: every row keeps its slot, the rows that repeat an earlier one are given length 0 (their
+# pairs exit at once -- sorted by length they fill whole wavefronts) and read the result row of their representative ``rep``
+# afterwards.  ``ptr``: the grouped rows' offsets; ``entry_dst``: where every ENTRY of x_val goes in the grouped values (what
+# is dropped: the spare slot behind them); ``live``: device-side (first, count) of the live rows in processing order, or None.
+DtwGrouping = collections.namedtuple('DtwGrouping', 'ptr rep entry_dst live')
+
+
+class DtwRowPrep:
+    """What a caller keeps for ONE set of x rows between ``dtw_similarity`` calls (the degree sequences of a split's
+    components are the same rows every pass): ``grouping`` (a DtwGrouping), ``order`` (the processing order of the rows as
+    given) and ``grouped_order`` (that of the grouped rows), each None until a call needs it.  Only the structure is kept:
+    the series the kernel reads are always the call's ``x_val``."""
+    __slots__ = ('shape', 'grouping', 'order', 'grouped_order')
+
+    def __init__(self):
+        self.shape = self.grouping = self.order = self.grouped_order = None
+
+    def fit(self, x_ptr, x_val):
+        """Forget what was kept for rows of another count or another ``x_val`` length: it is rebuilt, never reused."""
+        shape = (x_ptr.numel() - 1, x_val.numel())
+        if shape != self.shape:
+            self.shape, self.grouping, self.order, self.grouped_order = shape, None, None, None
+        return self
+
+
+def _group_rows(x_ptr, x_val, max_x, want_live):
+    """-> the DtwGrouping of these rows, without a host round trip (a boolean-mask index would be one, and a caller that
+    records its passes into a hipGraph has ONE eager pass left once the grouping is decided -- hotpath._settle_dtw_grouping)."""
+    n, spare, dev = x_ptr.numel() - 1, x_val.numel(), x_ptr.device
+    rows = Ragged(x_ptr, x_val, max_len=max_x).to_padded(width=max_x, fill=-1, dtype=torch.int32)
+    rep = _row_representatives(rows)
+    kept = rep == torch.arange(n, device=dev)
+    lens = torch.where(kept, x_ptr[1:] - x_ptr[:-1], 0)
+    uptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lens, 0, out=uptr[1:])
+    # entry e belongs to row searchsorted(x_ptr[1:], e, right=True) and moves by as much as its row's start does; entries of
+    # emptied rows and those at or behind x_ptr[-1] (x_val may carry an arena tail: "row" n) go to the spare slot
+    e = torch.arange(spare, device=dev)
+    shift = torch.cat([torch.where(kept, uptr[:-1] - x_ptr[:-1], spare), uptr.new_full((1,), spare)])
+    entry_dst = (shift[torch.searchsorted(x_ptr[1:], e, right=True)] + e).clamp_(max=spare)
+    live = None
+    if want_live:
+        # the length-first processing order puts the emptied rows in front: hand the kernel the live range (a device-side
+        # pair, no round trip) so that it deals its lanes over the live rows only
+        n_live = (lens > 0).sum()
+        live = torch.stack((n - n_live, n_live))
+    return DtwGrouping(uptr, rep, entry_dst, live)
+
+
+def _dtw_row_order(x_ptr, x_val):
+    """The processing order of the x rows: by (length, then the series sampled at its start, thirds and end) -- rows are
+    sorted degree sequences, four quantiles place a series' shape well enough that the lanes of a wavefront sweep similar
+    windows; one int64 key per row (sgnn_dtw_order_keys), no host round trip.
+    Measured on the benchmark's external side (round 1 kernel): unordered 8.9 ms, (length, median, sum) 8.1 ms,
+    (length, four quantiles) 7.5 ms, full lexicographic order 7.9 ms; round 2: the coarse-series key, see the kernel."""
+    nx = x_ptr.numel() - 1
+    key = torch.empty(nx, dtype=torch.int64, device=x_ptr.device)
+    check(_lib.load().sgnn_dtw_order_keys(_ptr(x_ptr), _ptr(x_val), nx, _ptr(key), _stream()), 'sgnn_dtw_order_keys')
+    return torch.argsort(key).to(torch.int32).contiguous()
+
+
+def _dtw_launch(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order, kernel, fn, order, live):
+    """One workspace query and one library call -> (n_x, n_y) float32.  ``live``: only positions [first, first + count) of
+    ``order`` are computed (the ``_live`` entry; it needs an order), the other rows of the result are 0."""
+    lib = _lib.load()
+    for t, dt, nm in ((x_ptr, torch.int64, 'x_ptr'), (y_ptr, torch.int64, 'y_ptr'), (x_val, torch.int32, 'x_val'),
+                      (y_val, torch.int32, 'y_val')):
+        _req(t, dt, nm)
+    nx, ny = x_ptr.numel() - 1, y_ptr.numel() - 1
+    out = (torch.empty if live is None else torch.zeros)((nx, ny), dtype=torch.float32, device=x_ptr.device)
+    ws_entry, entry, takes_tie = _DTW_ENTRIES[fn]
+    wsb = getattr(lib, ws_entry)(nx, max_x, ny, max_y)
+    ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=x_ptr.device)
+    args = [_ptr(x_ptr), _ptr(x_val), nx, max_x, _ptr(y_ptr), _ptr(y_val), ny, max_y]
+    if takes_tie:
+        args.append(tie_order)
+    args += [int(kernel), _ptr(order)]
+    if live is not None and order is not None:
+        entry += '_live'
+        args.append(_ptr(live))
+    check(getattr(lib, entry)(*args, _ptr(out), _ptr(ws), wsb, _stream()), entry)
+    return out
 
 
 def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, order_rows=True, dedupe=True, order=None,
-                   _live=None, x_prep=None, kernel=0, fn='dtw'):
+                   x_prep=None, kernel=0, fn='dtw'):
     """1/(1+fastdtw) for all (x row, y row) pairs -> (n_x, n_y) float32; empty x rows -> PAD.
     ``fn``: hparams['structure_similarity_fn'] -- 'dtw' = fastdtw(radius=1), 'dtw_exact' = the exact DTW distance over the
     whole grid (sgnn_dtw_exact_similarity; ``tie_order`` is ignored: a minimum over warp paths has no predecessor rule).
@@ -928,116 +1005,34 @@ def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, ord
     components of the benchmark have 2.7k distinct internal sequences) are computed once and the
     result rows gathered back.  ``order_rows``: process the x rows sorted by (length, coarse series) so
     that the lanes of a wavefront work on similar series.  Neither changes any value.
-    ``x_prep``: a dict the caller keeps for THESE x rows (the degree sequences of a split's components are the same
-    every pass): the grouping of repeated rows and the processing order are computed on the first call and reused;
-    the series the kernel reads are always this call's ``x_val``.
+    ``x_prep``: a DtwRowPrep the caller keeps for THESE x rows: the grouping of repeated rows and the processing order are
+    computed on the first call and reused (one that was made for another row count or ``x_val`` length starts over); the
+    series the kernel reads are always this call's ``x_val``.  None = a temporary one.  ``order``: the caller's own (tuning).
     ``kernel``: 0 = pick by size, 1 = the general (workspace-resident) kernel; same values.
     ``tie_order``: fastdtw's predecessor rule (0 / 1 / 2); None = config.DTW_TIE_ORDER, the product's default."""
     if fn not in DTW_FNS:
         raise ValueError('structure similarity function %r: one of %s' % (fn, ', '.join(map(repr, DTW_FNS))))
     if tie_order is None:
         from .config import DTW_TIE_ORDER as tie_order
-    tie_order = int(tie_order)
+    prep = (x_prep if x_prep is not None else DtwRowPrep()).fit(x_ptr, x_val)
+    ptr, val, g = x_ptr, x_val, None
     if dedupe and x_ptr.numel() - 1 > 1024 and max_x <= 64:
-        kept = x_prep.get('dedupe') if x_prep is not None else None
-        if kept is not None and kept[1].numel() == x_ptr.numel() - 1:
-            # the grouping (which row stands for which, where the kept entries go) is reused; the VALUES the kernel reads
-            # are this call's: scattered again from x_val
-            uptr, rep, dst, live = kept
-            # where every ENTRY of x_val goes (kept rows: their slot; entries of rows that repeat an earlier row: the spare
-            # slot): the padded form's map restricted to the real entries, made once -- two launches per pass (zeros, scatter)
-            # instead of the eight of padding the rows again
-            dst_e = x_prep.get('dedupe_entry_dst')
-            if dst_e is None or dst_e.numel() != x_val.numel():
-                nrow = x_ptr.numel() - 1
-                j = torch.arange(max_x, device=x_ptr.device).view(1, -1)
-                real = j < (x_ptr[1:] - x_ptr[:-1]).view(-1, 1)
-                dst_e = dst.view(nrow, max_x)[real].contiguous()                 # row-major = the order of x_val
-                if dst_e.numel() < x_val.numel():                               # (x_val may carry an arena tail behind the last row)
-                    dst_e = torch.cat([dst_e, dst_e.new_full((x_val.numel() - dst_e.numel(),), x_val.numel())])
-                x_prep['dedupe_entry_dst'] = dst_e
-            uval = torch.zeros(x_val.numel() + 1, dtype=torch.int32, device=x_ptr.device)
-            uval.scatter_(0, dst_e, x_val)
-            out_u = dtw_similarity(uptr, uval, max_x, y_ptr, y_val, max_y, tie_order, order_rows, dedupe=False, order=order,
-                                   _live=live, x_prep=x_prep.setdefault('grouped', {}), kernel=kernel, fn=fn)
-            return out_u.index_select(0, rep)
-        # no host round trip: every row keeps its slot, the rows that repeat an earlier one are given
-        # length 0 (their pairs exit at once -- sorted by length they fill whole wavefronts) and read
-        # their representative's result row afterwards
-        n = x_ptr.numel() - 1
-        rows = Ragged(x_ptr, x_val, max_len=max_x).to_padded(width=max_x, fill=-1, dtype=torch.int32)
-        rep = _row_representatives(rows)
-        pos = torch.arange(n, device=x_ptr.device)
-        lens = torch.where(rep == pos, x_ptr[1:] - x_ptr[:-1], torch.zeros_like(pos))
-        uptr = torch.zeros(n + 1, dtype=torch.int64, device=x_ptr.device)
-        torch.cumsum(lens, 0, out=uptr[1:])
-        j = torch.arange(max_x, device=x_ptr.device).view(1, -1)
-        dst = torch.where(j < lens.view(-1, 1), uptr[:-1].view(-1, 1) + j, x_val.numel())   # dropped entries -> spare slot
-        uval = torch.zeros(x_val.numel() + 1, dtype=torch.int32, device=x_ptr.device)
-        uval.scatter_(0, dst.reshape(-1), rows.reshape(-1))
-        live = None
-        if order is None and order_rows:
-            # the length-first processing order puts the emptied rows in front: hand the kernel the live
-            # range (a device-side pair, no round trip) so that it deals its lanes over the live rows only
-            n_live = (lens > 0).sum()
-            live = torch.stack((n - n_live, n_live))
-        if x_prep is not None:
-            x_prep['dedupe'] = (uptr, rep, dst.reshape(-1), live)
-            # (the per-entry map of the kept path, made here as well: a mask index is a host round trip, and a caller that records
-            # its passes into a hipGraph has ONE eager pass left once the grouping is decided -- hotpath._settle_dtw_grouping)
-            real = j < (x_ptr[1:] - x_ptr[:-1]).view(-1, 1)
-            dst_e = dst[real].contiguous()
-            if dst_e.numel() < x_val.numel():
-                dst_e = torch.cat([dst_e, dst_e.new_full((x_val.numel() - dst_e.numel(),), x_val.numel())])
-            x_prep['dedupe_entry_dst'] = dst_e
-        out_u = dtw_similarity(uptr, uval, max_x, y_ptr, y_val, max_y, tie_order, order_rows, dedupe=False, order=order,
-                               _live=live, x_prep=x_prep.setdefault('grouped', {}) if x_prep is not None else None, kernel=kernel,
-                               fn=fn)
-        return out_u.index_select(0, rep)
-    lib = _lib.load()
-    for t, nm in ((x_ptr, 'x_ptr'), (y_ptr, 'y_ptr')):
-        _req(t, torch.int64, nm)
-    for t, nm in ((x_val, 'x_val'), (y_val, 'y_val')):
-        _req(t, torch.int32, nm)
-    nx, ny = x_ptr.numel() - 1, y_ptr.numel() - 1
-    out = (torch.empty if _live is None else torch.zeros)((nx, ny), dtype=torch.float32, device=x_ptr.device)
-    if order is not None:                                   # caller's processing order (tuning)
+        # the grouping (which row stands for which, where the kept entries go) may be a kept one; the VALUES the kernel reads
+        # are this call's: two launches (zeros, scatter)
+        g = prep.grouping = prep.grouping or _group_rows(x_ptr, x_val, max_x, order is None and order_rows)
+        ptr, val = g.ptr, torch.zeros(x_val.numel() + 1, dtype=torch.int32, device=x_ptr.device)
+        val.scatter_(0, g.entry_dst, x_val)
+    live = g.live if g is not None and order is None else None      # (it describes the order made here, not a caller's)
+    if order is not None:
         order = order.to(torch.int32).contiguous()
-    elif order_rows and nx > 64:
-        # (length, then the series sampled at its start, thirds and end): rows are sorted degree
-        # sequences, four quantiles place a series' shape well enough that the lanes of a wavefront
-        # sweep similar windows -- one int64 key per row (sgnn_dtw_order_keys), no host round trip.
-        # Measured on the benchmark's external side (round 1 kernel): unordered 8.9 ms, (length, median, sum) 8.1 ms,
-        # (length, four quantiles) 7.5 ms, full lexicographic order 7.9 ms; round 2: the coarse-series key, see the kernel.
-        order = x_prep.get('order') if x_prep is not None else None
-        if order is None or order.numel() != nx:
-            key = torch.empty(nx, dtype=torch.int64, device=x_ptr.device)
-            check(lib.sgnn_dtw_order_keys(_ptr(x_ptr), _ptr(x_val), nx, _ptr(key), _stream()), 'sgnn_dtw_order_keys')
-            order = torch.argsort(key).to(torch.int32).contiguous()
-            if x_prep is not None:
-                x_prep['order'] = order
-    if fn == 'dtw_exact':
-        wsb = lib.sgnn_dtw_exact_workspace_bytes(nx, max_x, ny, max_y)
-        ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=x_ptr.device)
-        if _live is not None and order is not None:
-            check(lib.sgnn_dtw_exact_similarity_live(_ptr(x_ptr), _ptr(x_val), nx, max_x, _ptr(y_ptr), _ptr(y_val), ny, max_y,
-                                                     int(kernel), _ptr(order), _ptr(_live), _ptr(out), _ptr(ws), wsb, _stream()),
-                  'sgnn_dtw_exact_similarity_live')
-            return out
-        check(lib.sgnn_dtw_exact_similarity(_ptr(x_ptr), _ptr(x_val), nx, max_x, _ptr(y_ptr), _ptr(y_val), ny, max_y,
-                                            int(kernel), _ptr(order), _ptr(out), _ptr(ws), wsb, _stream()),
-              'sgnn_dtw_exact_similarity')
-        return out
-    wsb = lib.sgnn_dtw_workspace_bytes(nx, max_x, ny, max_y)
-    ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=x_ptr.device)
-    if _live is not None and order is not None:
-        check(lib.sgnn_dtw_similarity_live(_ptr(x_ptr), _ptr(x_val), nx, max_x, _ptr(y_ptr), _ptr(y_val), ny, max_y,
-                                           tie_order, int(kernel), _ptr(order), _ptr(_live), _ptr(out), _ptr(ws), wsb, _stream()),
-              'sgnn_dtw_similarity_live')
-        return out
-    check(lib.sgnn_dtw_similarity(_ptr(x_ptr), _ptr(x_val), nx, max_x, _ptr(y_ptr), _ptr(y_val), ny, max_y, tie_order,
-                                  int(kernel), _ptr(order), _ptr(out), _ptr(ws), wsb, _stream()), 'sgnn_dtw_similarity')
-    return out
+    elif order_rows and ptr.numel() - 1 > 64:
+        which = 'order' if g is None else 'grouped_order'
+        order = getattr(prep, which)
+        if order is None:
+            order = _dtw_row_order(ptr, val)
+            setattr(prep, which, order)
+    out = _dtw_launch(ptr, val, max_x, y_ptr, y_val, max_y, int(tie_order), kernel, fn, order, live)
+    return out if g is None else out.index_select(0, g.rep)
 
 
 # ---------------------------------------------------------------------------------------

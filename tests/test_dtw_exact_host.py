@@ -104,6 +104,17 @@ def test_unknown_similarity_function_is_rejected_before_the_library_is_touched(m
     assert ops.DTW_FNS == ('dtw', 'dtw_exact')
 
 
+def test_dtw_similarity_takes_no_live_range_and_the_blocking_row_count_is_gone():
+    """The live range is the grouping's own business (ops.DtwRowPrep), not an argument; the distinct-row count has the
+    non-blocking form only."""
+    import inspect
+    from subgnn_amd import ops
+    params = list(inspect.signature(ops.dtw_similarity).parameters)
+    assert '_live' not in params
+    assert params[:9] == ['x_ptr', 'x_val', 'max_x', 'y_ptr', 'y_val', 'max_y', 'tie_order', 'order_rows', 'dedupe']
+    assert [n for n in dir(ops) if n.startswith('distinct_row')] == ['distinct_rows_async', 'distinct_rows_ready']
+
+
 @pytest.mark.parametrize('pattern,max_vgprs', [
     ('dtw_exact_reg_kernel<12, 4, true>', 128),               # 4 wavefronts per SIMD
     ('dtw_exact_reg_kernel<20, 2, true>', 256),               # 2: column, kept costs, x + 1 and reciprocals = 160 registers

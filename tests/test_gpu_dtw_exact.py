@@ -110,14 +110,14 @@ def test_an_empty_y_row_gives_what_the_fastdtw_entry_gives():
 
 def test_grouping_order_kept_preparation_and_live_range_change_nothing():
     """3000 x rows drawn from 40 distinct ones: grouping repeated rows (which hands the kernel the live range of the
-    processing order), ordering the rows, and a kept x_prep over three calls whose values change all give the plain call's
+    processing order), ordering the rows, and a kept preparation over three calls whose values change all give the plain call's
     matrix, and that one is the restatement's."""
     ops = _ops()
     rng = np.random.default_rng(77)
     base = [sorted(rng.integers(0, 6, int(rng.integers(0, 21))).tolist()) for _ in range(40)]
     pick = rng.integers(0, 40, 3000)
     ys = [sorted(rng.integers(0, 50, int(rng.integers(1, 51))).tolist()) for _ in range(23)]
-    keep, keep_plain = {}, {}
+    keep, keep_plain = ops.DtwRowPrep(), ops.DtwRowPrep()
     for shift in (0, 3, 1):                                   # same rows repeat each other; other values every call
         xs = [[v + shift for v in base[int(i)]] for i in pick]
         plain = _call(xs, ys, 20, 50, dedupe=False, order_rows=False)
@@ -129,8 +129,8 @@ def test_grouping_order_kept_preparation_and_live_range_change_nothing():
         assert torch.equal(_call(xs, ys, 20, 50, x_prep=keep), plain)
         assert torch.equal(_call(xs, ys, 20, 50, dedupe=False, x_prep=keep_plain), plain)
         assert torch.equal(_call(xs, ys, 20, 50, kernel=1, x_prep=keep), plain)
-    assert 'dedupe' in keep and keep['dedupe'][3] is not None and 'order' in keep['grouped']      # the live-range form ran
-    assert 'order' in keep_plain
+    assert keep.grouping is not None and keep.grouping.live is not None and keep.grouped_order is not None   # the live-range form ran
+    assert keep_plain.order is not None
     # the live-range entry itself: positions [first, first + count) of the order are computed, the rest stays as it was
     from subgnn_amd import _lib
     lib = _lib.load()

@@ -1047,7 +1047,7 @@ def test_degree_sequence_understated_set_bound_is_loud():
 
 
 def test_dtw_similarity_kept_row_preparation(golden):
-    """x_prep: the grouping of repeated x rows and the processing order are kept by the caller and reused; same values."""
+    """x_prep (ops.DtwRowPrep): the grouping of repeated x rows and the processing order are kept by the caller and reused; same values."""
     ops = _ops()
     rng = np.random.default_rng(5)
     base = [sorted(rng.integers(0, 9, size=rng.integers(1, 12)).tolist()) for _ in range(40)]
@@ -1055,15 +1055,96 @@ def test_dtw_similarity_kept_row_preparation(golden):
     ys = [sorted(rng.integers(0, 30, size=rng.integers(3, 25)).tolist()) for _ in range(9)]
     X, Y = ops.Ragged.from_lists(xs, DEV), ops.Ragged.from_lists(ys, DEV)
     want = ops.dtw_similarity(X.ptr, X.nodes, 12, Y.ptr, Y.nodes, 25)
-    keep = {}
+    keep = ops.DtwRowPrep()
     for _ in range(3):
         got = ops.dtw_similarity(X.ptr, X.nodes, 12, Y.ptr, Y.nodes, 25, x_prep=keep)
         assert torch.equal(got, want)
-    assert 'dedupe' in keep and 'order' in keep['grouped']
-    keep2 = {}
+    assert keep.grouping is not None and keep.grouped_order is not None
+    keep2 = ops.DtwRowPrep()
     for _ in range(2):
         assert torch.equal(ops.dtw_similarity(X.ptr, X.nodes, 12, Y.ptr, Y.nodes, 25, dedupe=False, x_prep=keep2), want)
-    assert 'order' in keep2
+    assert keep2.order is not None
+
+
+_PREP_BASE = [[], [0, 0, 1, 1, 2, 3, 3, 4, 6, 6, 7, 8], [5], [0, 2], [1, 1, 1, 4, 8], [2, 3, 3, 3, 5, 6, 7], [0, 4, 4, 6, 6, 7, 7, 8, 8]]
+_PREP_YS = [[4], [0, 2, 2, 7, 11], [1, 1, 3, 5, 5, 6, 9, 9, 14]]
+_PREP_ORACLE = {}
+
+
+def _prep_oracle(fn, shift):
+    """The CPU oracle's (7, 3) similarities of the distinct rows, every entry + ``shift``: computed once per (fn, shift)."""
+    if (fn, shift) not in _PREP_ORACLE:
+        xs = [[v + shift for v in b] for b in _PREP_BASE]
+        if fn == 'dtw':
+            from subgnn_amd import config
+            _PREP_ORACLE[fn, shift] = cbind.fastdtw_sim(*cbind.ragged(xs), *cbind.ragged(_PREP_YS), config.DTW_TIE_ORDER)
+        else:
+            from dtw_exact_ref import exact_dtw_similarities
+            _PREP_ORACLE[fn, shift] = exact_dtw_similarities(xs, _PREP_YS)
+    return _PREP_ORACLE[fn, shift]
+
+
+@pytest.mark.parametrize('fn', ['dtw', 'dtw_exact'])
+def test_dtw_row_preparation_threshold_tail_live_range_reuse_and_staleness(fn):
+    """ops.DtwRowPrep around the grouping threshold (1024 rows: an order, no grouping; 1025: a grouping with a live range and
+    a grouped order), with an arena tail behind the last row, with one live row and with none, reused over three calls whose
+    values change (the same tensors are kept), handed other rows (rebuilt at the new sizes) and through the general kernel:
+    every matrix is the plain call's bit for bit, and the plain call's is the CPU oracle's on the 7 distinct rows."""
+    ops = _ops()
+    assert len(_PREP_BASE) == 7 and max(map(len, _PREP_BASE)) == 12 and max(map(len, _PREP_YS)) == 9
+    yp, yv = (torch.from_numpy(a).to(DEV) for a in cbind.ragged(_PREP_YS))
+    rng = np.random.default_rng(11)
+    draw = rng.integers(0, 7, 1030)
+    draw[:7] = np.arange(7)                                               # every distinct row is among the first 1024
+
+    def run(pick, prep, shift=0, tail=0, **kw):
+        """-> (x_ptr, x_val) of rows _PREP_BASE[pick] + shift; the call with ``prep`` equals the plain call equals the oracle."""
+        xp, xv = cbind.ragged([[v + shift for v in _PREP_BASE[i]] for i in pick])
+        x_ptr, x_val = torch.from_numpy(xp).to(DEV), torch.from_numpy(np.concatenate([xv, np.full(tail, 77, xv.dtype)])).to(DEV)
+        plain = ops.dtw_similarity(x_ptr, x_val, 12, yp, yv, 9, dedupe=False, order_rows=False, fn=fn)
+        assert np.array_equal(plain.cpu().numpy(), _prep_oracle(fn, shift)[pick])
+        assert torch.equal(ops.dtw_similarity(x_ptr, x_val, 12, yp, yv, 9, x_prep=prep, fn=fn, **kw), plain)
+        return x_ptr, x_val
+
+    def grouped(prep, x_ptr, x_val, n_live):
+        """The preparation holds a grouping of these rows with ``n_live`` live rows, and the grouped order -- nothing else."""
+        n, g = x_ptr.numel() - 1, prep.grouping
+        assert g is not None and g.live is not None and g.live.tolist() == [n - n_live, n_live]
+        assert prep.grouped_order is not None and prep.grouped_order.numel() == n and prep.order is None
+        assert g.ptr.numel() == n + 1 and g.rep.numel() == n and g.entry_dst.numel() == x_val.numel()
+        assert int(g.entry_dst.max()) <= x_val.numel() and int(g.ptr[-1]) <= x_val.numel()
+
+    # threshold: 1024 rows are not grouped, 1025 are
+    prep = ops.DtwRowPrep()
+    run(draw[:1024], prep)
+    assert prep.grouping is None and prep.grouped_order is None and prep.order is not None and prep.order.numel() == 1024
+    prep = ops.DtwRowPrep()
+    grouped(prep, *run(draw[:1025], prep), 6)
+    # arena tail: 5 entries behind the last row
+    prep = ops.DtwRowPrep()
+    x_ptr, x_val = run(draw[:1025], prep, tail=5)
+    grouped(prep, x_ptr, x_val, 6)
+    assert bool((prep.grouping.entry_dst[-5:] == x_val.numel()).all())   # the spare slot
+    # degenerate live ranges: one live row; none (the library takes no null value pointer: the empty rows lie in front of a tail)
+    prep = ops.DtwRowPrep()
+    grouped(prep, *run(np.full(1025, 5), prep), 1)
+    prep = ops.DtwRowPrep()
+    x_ptr, x_val = run(np.zeros(1025, dtype=np.int64), prep, tail=5)
+    grouped(prep, x_ptr, x_val, 0)
+    assert float(ops.dtw_similarity(x_ptr, x_val, 12, yp, yv, 9, x_prep=prep, fn=fn).abs().max()) == 0.0      # PAD
+    # reuse: one object, three calls, other values every call -- the same grouping, the same tensors
+    prep = ops.DtwRowPrep()
+    kept = None
+    for shift in (0, 3, 1):
+        grouped(prep, *run(draw[:1025], prep, shift=shift), 6)
+        now = (prep.grouping, prep.grouping.entry_dst.data_ptr(), prep.grouped_order.data_ptr())
+        assert kept is None or (now[0] is kept[0] and now[1:] == kept[1:])
+        kept = now
+    run(draw[:1025], prep, kernel=1)                                      # the general kernel with the kept preparation
+    assert prep.grouping is kept[0]
+    # stale: the same object, 1030 rows -- rebuilt at the new sizes
+    grouped(prep, *run(draw, prep), 6)
+    assert prep.grouping is not kept[0]
 
 
 # ---- padded rows -> ragged sets, node views, in-border filter (the set plumbing every stage goes through) -----------------

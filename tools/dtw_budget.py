@@ -35,7 +35,7 @@ fn = getattr(lib, 'sgnn_dtw_probe_counts', None)
 if fn is None:
     raise SystemExit('libsubgnn_hip.so was not built with -DDTW_PROBE_COUNT')
 fn.argtypes, fn.restype = [ctypes.c_void_p, ctypes.c_int], ctypes.c_int
-prep = {}
+prep = ops.DtwRowPrep()
 ops.dtw_similarity(sets.ptr, x, NX, a_sets.ptr, y, 50, x_prep=prep)       # (keeps the grouping / order: the counted call is the steady one)
 torch.cuda.synchronize()
 buf = (ctypes.c_ulonglong * 64)()

@@ -66,13 +66,13 @@ def calls(only=None):
     for side, (x, y, dedupe) in sides.items():
         fns[side] = {}
         for name, kw in VARIANTS:
-            prep = {}
+            prep = ops.DtwRowPrep()
             f = (lambda x=x, y=y, dedupe=dedupe, prep=prep, kw=kw:
                  ops.dtw_similarity(sets.ptr, x, NX, a_sets.ptr, y, 50, dedupe=dedupe, x_prep=prep, **kw))
             f()
             outs[side, name] = f()
             fns[side][name] = f
-            live = prep['dedupe'][3] if dedupe else None
+            live = prep.grouping.live if dedupe else None
             rows = int(live[1]) if live is not None else sets.n
             tasks[side] = a_sets.n * ((rows + 63) // 64)
     torch.cuda.synchronize()

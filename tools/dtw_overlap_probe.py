@@ -19,7 +19,7 @@ patches = ops.triangular_walks(g, 0, 210, 50, 0.65, 0, tape.stream_id(tape.STREA
 a_sets = ops.Ragged.from_padded(patches)
 ai, ae = ops.degree_sequence(g, a_sets)
 ci, ce = ops.degree_sequence(g, sets)
-prep = {}
+prep = ops.DtwRowPrep()
 src = torch.from_numpy(np.random.default_rng(0).integers(1, n + 1, 183).astype(np.int32)).to(dev)
 E = torch.randn(n + 1, 64, device=dev)
 gE, mE, vE = torch.randn_like(E), torch.zeros_like(E), torch.zeros_like(E)

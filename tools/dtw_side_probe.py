@@ -20,7 +20,7 @@ a_sets = ops.Ragged.from_padded(patches)
 ai, ae = ops.degree_sequence(g, a_sets)
 ci, ce = ops.degree_sequence(g, sets)
 x, y = (ce, ae) if side == 'external' else (ci, ai)
-prep = {}
+prep = ops.DtwRowPrep()
 f = lambda: ops.dtw_similarity(sets.ptr, x, NX, a_sets.ptr, y, 50, x_prep=prep)
 out = f(); f()
 torch.cuda.synchronize()

@@ -20,7 +20,7 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 out = {}
 for tie in (0, 1, 2):
     for side, x, y in (('ext', ce, ae), ('int', ci, ai)):
-        prep = {}
+        prep = ops.DtwRowPrep()
         ops.dtw_similarity(sets.ptr, x, 20, a_sets.ptr, y, 50, tie, x_prep=prep)
         torch.cuda.synchronize()
         e0.record()
