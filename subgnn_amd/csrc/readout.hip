@@ -18,6 +18,9 @@
 #define RO_ROWS_PER_BLOCK 64
 #define RO_TA 64                       // column lanes of a workgroup (one wavefront reads 256 consecutive bytes of a row)
 #define RO_TR 4                        // row lanes
+#define RO_THREADS 256                 // threads of a workgroup (every kernel of this file is launched with 256)
+#define RO_COMP_STEP 4                 // components per trip of the forward kernels' component loop
+#define RO_GS_CHUNK 1024               // anchors of d s staged in LDS at a time by the d wp finish
 
 // ------------------------------------------------------------------------------------------------------------------
 // a thread owns four (subgraph, anchor) elements a quarter of the grid apart: their loads are independent and in flight
@@ -45,11 +48,11 @@ __global__ __launch_bounds__(256) void readout_sum_fwd_kernel(const float* __res
     }
     // four components at a time: 16 independent loads in flight (a batch of subgraphs with 7-50 components each walked them one
     // round trip after the other: the dense similarity slab is a cache miss per element)
-    for (int32_t c0 = 0; c0 < C; c0 += 4) {
-        float w[4][4];
-        bool live[4][4];
+    for (int32_t c0 = 0; c0 < C; c0 += RO_COMP_STEP) {
+        float w[RO_COMP_STEP][4];
+        bool live[RO_COMP_STEP][4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < RO_COMP_STEP; ++u) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int64_t r = b[j] * C + c0 + u;
@@ -58,7 +61,7 @@ __global__ __launch_bounds__(256) void readout_sum_fwd_kernel(const float* __res
             }
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < RO_COMP_STEP; ++u) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (live[u][j]) acc[j] += fmaxf(fmaf(w[u][j], sa[j], bb), 0.f);
@@ -292,11 +295,11 @@ __global__ __launch_bounds__(256) void readout_sum_fwd_many_kernel(const RoPiece
         col[j] = sim_col ? sim_col[a[j]] : a[j];
         acc[j] = 0.f;
     }
-    for (int32_t c0 = 0; c0 < C; c0 += 4) {
-        float w[4][4];
-        bool live[4][4];
+    for (int32_t c0 = 0; c0 < C; c0 += RO_COMP_STEP) {
+        float w[RO_COMP_STEP][4];
+        bool live[RO_COMP_STEP][4];
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < RO_COMP_STEP; ++u) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int64_t r = b[j] * C + c0 + u;
@@ -305,7 +308,7 @@ __global__ __launch_bounds__(256) void readout_sum_fwd_many_kernel(const RoPiece
             }
         }
 #pragma unroll
-        for (int u = 0; u < 4; ++u) {
+        for (int u = 0; u < RO_COMP_STEP; ++u) {
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (live[u][j]) acc[j] += fmaxf(fmaf(w[u][j], sa[j], bb), 0.f);
@@ -431,18 +434,18 @@ __global__ __launch_bounds__(256) void readout_bwd_finish_many_kernel(const RoPi
     __threadfence();
     if (P.gwp[p] && P.X[p] && P.gs[p]) {
         // d s staged in LDS (its volatile reads were one dependent round trip per anchor: 70 us for 183 anchors), anchors in chunks
-        __shared__ float s_gs[1024];
-        __shared__ float s_part[256];
+        __shared__ float s_gs[RO_GS_CHUNK];
+        __shared__ float s_part[RO_THREADS];
         const volatile float* gs = P.gs[p];
         const float* __restrict__ X = P.X[p];
-        if (D <= 128 && 256 % D == 0) {
+        if (D <= RO_THREADS / 2 && RO_THREADS % D == 0) {
             // the anchors in 256 / D contiguous ranges, one per group of D threads; the ranges' sums added in range order
-            const int nq = 256 / D, q = threadIdx.x / D, d = threadIdx.x - q * D;
+            const int nq = RO_THREADS / D, q = threadIdx.x / D, d = threadIdx.x - q * D;
             double v = 0.0;
-            for (int a0 = 0; a0 < A; a0 += 1024) {
-                const int na = A - a0 < 1024 ? A - a0 : 1024;
+            for (int a0 = 0; a0 < A; a0 += RO_GS_CHUNK) {
+                const int na = A - a0 < RO_GS_CHUNK ? A - a0 : RO_GS_CHUNK;
                 __syncthreads();
-                for (int aa = threadIdx.x; aa < na; aa += 256) s_gs[aa] = gs[a0 + aa];
+                for (int aa = threadIdx.x; aa < na; aa += RO_THREADS) s_gs[aa] = gs[a0 + aa];
                 __syncthreads();
                 const int per = (na + nq - 1) / nq, lo = q * per, hi = lo + per < na ? lo + per : na;
 #pragma unroll 8
@@ -457,14 +460,14 @@ __global__ __launch_bounds__(256) void readout_bwd_finish_many_kernel(const RoPi
             }
         } else {
             float v[4] = {0.f, 0.f, 0.f, 0.f};                       // columns d, d + 256, ... of this thread (D <= 1024 here)
-            for (int a0 = 0; a0 < A; a0 += 1024) {
-                const int na = A - a0 < 1024 ? A - a0 : 1024;
+            for (int a0 = 0; a0 < A; a0 += RO_GS_CHUNK) {
+                const int na = A - a0 < RO_GS_CHUNK ? A - a0 : RO_GS_CHUNK;
                 __syncthreads();
-                for (int aa = threadIdx.x; aa < na; aa += 256) s_gs[aa] = gs[a0 + aa];
+                for (int aa = threadIdx.x; aa < na; aa += RO_THREADS) s_gs[aa] = gs[a0 + aa];
                 __syncthreads();
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const int d = threadIdx.x + 256 * q;
+                    const int d = threadIdx.x + RO_THREADS * q;
                     if (d < D) {
 #pragma unroll 8
                         for (int aa = 0; aa < na; ++aa) v[q] = fmaf(s_gs[aa], X[(int64_t)(a0 + aa) * D + d], v[q]);
@@ -472,7 +475,7 @@ __global__ __launch_bounds__(256) void readout_bwd_finish_many_kernel(const RoPi
                 }
             }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { const int d = threadIdx.x + 256 * q; if (d < D) P.gwp[p][d] = v[q]; }
+            for (int q = 0; q < 4; ++q) { const int d = threadIdx.x + RO_THREADS * q; if (d < D) P.gwp[p][d] = v[q]; }
         }
     }
     if (threadIdx.x == 0) P.ticket[p] = 0u;
