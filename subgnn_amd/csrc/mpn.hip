@@ -29,6 +29,16 @@ __device__ static inline float group_sum(float v, int lanes) {
 }
 
 #define MPN_U 4
+// The launch shapes.  A call with few component rows does not fill the chip with one lane group per row: below
+// MPN_SPLIT_BELOW_GX row workgroups, and from MPN_SPLIT_MIN_A anchors, a row's anchors are split over grid.y towards
+// MPN_SPLIT_WANT workgroups, MPN_CHUNK_MIN_A anchors per chunk at the least (the forward and the atomic GATHER backward).
+#define MPN_SPLIT_BELOW_GX 512
+#define MPN_SPLIT_MIN_A 16
+#define MPN_SPLIT_WANT 1024
+#define MPN_CHUNK_MIN_A 8
+// grid caps of the grid-stride kernels (the forward keeps sgnn_grid_for's default)
+#define MPN_DENSE_BWD_GRID_CAP 2048
+#define MPN_WIDE_GRID_CAP 8192
 // T: element type of the GATHER table (float, or __half for an fp16-stored table; fp32 accumulate)
 // (bx, gx, by, gy: the workgroup's place in its body's own grid -- blockIdx / gridDim for a single launch, a body's share of a
 // many-bodies launch otherwise)
@@ -265,6 +275,12 @@ __global__ __launch_bounds__(256) void mpn_bwd_gather_kernel(sgnn_mpn_args a, co
 // down to 4 rows for a batch of a few hundred component rows, where the item chunks become the
 // second grid dimension instead of a loop.
 #define MPN_SH_TILE 64
+// 64-row tiles from MPN_SH_FULL_TILES of them; fewer rows: shorter tiles towards MPN_SH_WANT workgroups (the deterministic form:
+// MPN_SH_DET_WANT, two per CU); at most MPN_SH_GRID_CAP row-tile workgroups, which then loop
+#define MPN_SH_FULL_TILES 1024
+#define MPN_SH_WANT 1024
+#define MPN_SH_GRID_CAP 4096
+#define MPN_SH_DET_WANT 512
 __global__ __launch_bounds__(256) void mpn_bwd_shared_kernel(sgnn_mpn_args a, const float* __restrict__ grad_agg,
                                                              const float* __restrict__ grad_z,
                                                              float* __restrict__ grad_x, float* __restrict__ grad_wp,
@@ -535,9 +551,9 @@ static int mpn_fwd_chunks(const sgnn_mpn_args* args)
 {
     const int gx = sgnn_grid_for(args->R * (args->D / 4), 256);
     int chunks = 1;
-    if (gx < 512 && args->A >= 16) {                          // too few rows to fill 256 CUs: split the anchors
-        chunks = (1024 + gx - 1) / gx;
-        const int64_t most = (args->A + 7) / 8;               // at least 8 anchors per chunk
+    if (gx < MPN_SPLIT_BELOW_GX && args->A >= MPN_SPLIT_MIN_A) {     // too few rows to fill 256 CUs: split the anchors
+        chunks = (MPN_SPLIT_WANT + gx - 1) / gx;
+        const int64_t most = (args->A + MPN_CHUNK_MIN_A - 1) / MPN_CHUNK_MIN_A;
         if (chunks > most) chunks = (int)most;
     }
     return chunks < 1 ? 1 : chunks;
@@ -583,28 +599,28 @@ extern "C" int sgnn_mpn_bwd(const sgnn_mpn_args* args, const float* grad_agg, co
     if (args->src == SGNN_SRC_SHARED) {
         int64_t tile_rows = MPN_SH_TILE, chunks = 1;
         int64_t n_tiles = (args->R + tile_rows - 1) / tile_rows;
-        if (n_tiles < 1024) {                       // too few rows to fill 256 CUs with 64-row tiles
+        if (n_tiles < MPN_SH_FULL_TILES) {                       // too few rows to fill 256 CUs with 64-row tiles
             chunks = (args->A * D4 + 255) / 256;
-            const int64_t want = (1024 + chunks - 1) / chunks;
+            const int64_t want = (MPN_SH_WANT + chunks - 1) / chunks;
             tile_rows = (args->R + want - 1) / want;
             tile_rows = tile_rows < 4 ? 4 : (tile_rows > MPN_SH_TILE ? MPN_SH_TILE : tile_rows);
             n_tiles = (args->R + tile_rows - 1) / tile_rows;
         }
-        const int grid = (int)(n_tiles < 4096 ? n_tiles : 4096);
+        const int grid = (int)(n_tiles < MPN_SH_GRID_CAP ? n_tiles : MPN_SH_GRID_CAP);
         hipLaunchKernelGGL(mpn_bwd_shared_kernel, dim3(grid, (unsigned)chunks), dim3(256), 0, st, *args, grad_agg, grad_z,
                            grad_x, grad_wp, D4, tile_rows);
     } else {
-        const int grid = sgnn_grid_for(args->R * D4, 256, 2048);
+        const int grid = sgnn_grid_for(args->R * D4, 256, MPN_DENSE_BWD_GRID_CAP);
         if (args->src == SGNN_SRC_DENSE)
             hipLaunchKernelGGL(mpn_bwd_kernel<SGNN_SRC_DENSE>, dim3(grid), dim3(256), 0, st, *args, grad_agg, grad_z,
                                grad_x, grad_wp, D4);
         else
         {
-            const int gx = sgnn_grid_for(args->R * args->D, 256, 8192);
+            const int gx = sgnn_grid_for(args->R * args->D, 256, MPN_WIDE_GRID_CAP);
             int chunks = 1;
-            if (gx < 512 && args->A >= 16) {
-                chunks = (1024 + gx - 1) / gx;
-                const int64_t most = (args->A + 7) / 8;
+            if (gx < MPN_SPLIT_BELOW_GX && args->A >= MPN_SPLIT_MIN_A) {
+                chunks = (MPN_SPLIT_WANT + gx - 1) / gx;
+                const int64_t most = (args->A + MPN_CHUNK_MIN_A - 1) / MPN_CHUNK_MIN_A;
                 if (chunks > most) chunks = (int)most;
             }
             hipLaunchKernelGGL(mpn_bwd_gather_kernel, dim3(gx, chunks), dim3(256), 0, st, *args, grad_agg, grad_z, grad_x,
@@ -622,7 +638,7 @@ extern "C" int sgnn_mpn_bwd_edges(const sgnn_mpn_args* args, const float* grad_z
     if (rc != SGNN_OK) return rc;
     if (args->src != SGNN_SRC_GATHER || !out_keys || !out_c1) return SGNN_ERR_BAD_ARG;
     if (args->R * args->A == 0) return SGNN_OK;
-    hipLaunchKernelGGL(mpn_bwd_edges_kernel, dim3(sgnn_grid_for(args->R * args->A, 256, 8192)), dim3(256), 0,
+    hipLaunchKernelGGL(mpn_bwd_edges_kernel, dim3(sgnn_grid_for(args->R * args->A, 256, MPN_WIDE_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, *args, grad_z, out_keys, out_c1, out_c2);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
@@ -639,7 +655,7 @@ extern "C" int sgnn_mpn_bwd_edges_many(int64_t n, const sgnn_mpn_args* args, con
         if (rc != SGNN_OK) return rc;
         if (args[k].src != SGNN_SRC_GATHER || !out_keys[k] || !out_c1[k] || args[k].R * args[k].A <= 0) return SGNN_ERR_BAD_ARG;
         M.a[k] = args[k]; M.gz[k] = grad_z[k]; M.keys[k] = out_keys[k]; M.c1[k] = out_c1[k]; M.c2[k] = out_c2[k];
-        M.gx[k] = sgnn_grid_for(args[k].R * args[k].A, 256, 8192);
+        M.gx[k] = sgnn_grid_for(args[k].R * args[k].A, 256, MPN_WIDE_GRID_CAP);
         if (M.gx[k] > mx) mx = M.gx[k];
     }
     hipLaunchKernelGGL(mpn_bwd_edges_many_kernel, dim3(mx, (unsigned)n), dim3(256), 0, (hipStream_t)stream, M);
@@ -655,7 +671,7 @@ extern "C" int sgnn_mpn_bwd_wp_partial(const sgnn_mpn_args* args, const float* g
     if (args->src != SGNN_SRC_GATHER || !grad_z || !partial) return SGNN_ERR_BAD_ARG;
     if (partial_ld != args->D && partial_ld != args->D + 1) return SGNN_ERR_BAD_ARG;
     if (args->R == 0) return SGNN_OK;
-    hipLaunchKernelGGL(mpn_bwd_wp_partial_kernel, dim3(sgnn_grid_for(args->R * partial_ld, 256, 8192)), dim3(256), 0,
+    hipLaunchKernelGGL(mpn_bwd_wp_partial_kernel, dim3(sgnn_grid_for(args->R * partial_ld, 256, MPN_WIDE_GRID_CAP)), dim3(256), 0,
                        (hipStream_t)stream, *args, grad_z, partial, partial_ld);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
@@ -664,7 +680,7 @@ extern "C" int sgnn_mpn_bwd_wp_partial(const sgnn_mpn_args* args, const float* g
 static void mpn_shared_det_tiling(int64_t R, int64_t A, int64_t D4, int64_t* tile_rows, int64_t* n_tiles, int64_t* chunks)
 {
     *chunks = (A * D4 + 255) / 256;
-    const int64_t want = (512 + *chunks - 1) / *chunks;                 // ~512 workgroups: two per CU; fewer tiles = a shorter reduction
+    const int64_t want = (MPN_SH_DET_WANT + *chunks - 1) / *chunks;                 // ~512 workgroups: two per CU; fewer tiles = a shorter reduction
     int64_t tr = (R + want - 1) / want;
     tr = tr < 4 ? 4 : (tr > MPN_SH_TILE ? MPN_SH_TILE : tr);
     *tile_rows = tr;

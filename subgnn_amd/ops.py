@@ -1381,6 +1381,9 @@ class _MPN(torch.autograd.Function):
         z = torch.empty((R, A), dtype=torch.float32, device=x.device)
         if A == 0:
             agg = torch.zeros((R, D), dtype=torch.float32, device=x.device)
+        elif R == 0:
+            # no component row: nothing to launch (an empty tensor has no address to hand to the library, which refuses a null one)
+            agg = torch.zeros((1, 0, D) if keep_chunks else (0, D), dtype=torch.float32, device=x.device)
         else:
             a = _mpn_args(src, x, ids, id_div, edge_mask, row_mask, sims, sim_col, sims_per_edge, wp, bp, R, A, D)
             if relu_z:
@@ -1409,6 +1412,8 @@ class _MPN(torch.autograd.Function):
         lib = _lib.load()
         x, wp, bp, sims, ids, edge_mask, row_mask, sim_col = ctx.saved_tensors[:8]
         src, id_div, sims_per_edge, R, A, D = ctx.meta
+        if R == 0:
+            A = 0                                     # no component row: no launch, every gradient below is its zero fill
         need_x, need_wp, need_bp = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
         if g_z is None:
             # nobody read the read-out (the neighbourhood channel's bodies): its weight and bias get NO gradient -- None, as autograd
@@ -1987,7 +1992,7 @@ def mpn(x, wp, bp, sims, *, src, R, A, ids=None, id_div=1, edge_mask=None, row_m
     read-out comes back activated, relu(z) (what generate_pos_struc_embeddings, mpn:122-131, makes of it next).  ``lazy`` (with
     keep_chunks): the forward launch is queued and goes out with the other bodies of its layer (``flush_lazy_mpn``) -- the caller
     must not read agg or z before that."""
-    sims2 = sims.reshape(R, -1)
+    sims2 = sims.reshape(R, -1) if R else sims.reshape(0, sims.shape[-1])
     if not sims2.is_contiguous():
         sims2 = sims2.contiguous()
     if src == SRC_SHARED and A > 0 and R >= SHARED_GEMM_MIN_ROWS:

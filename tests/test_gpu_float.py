@@ -251,7 +251,9 @@ def test_mpn_gather_shared_ids_over_components(det):
 @pytest.mark.parametrize('R,A', [(150, 13), (150, 123), (66000, 13)])
 def test_mpn_shared_random(D, mode, R, A, det):
     """SRC_SHARED: P-border (ids -> column id-1) and structure (index list) anchors; a batch-sized
-    row count (short row tiles x item chunks in the backward) and a shard-sized one (64-row tiles)."""
+    row count (short row tiles x item chunks in the backward) and a shard-sized one, which ops.mpn hands to the
+    library's GEMMs (ops._mpn_shared_gemm, R >= SHARED_GEMM_MIN_ROWS): the 64-row tiles of the hand-written
+    backward are tests/test_gpu_mpn.py's."""
     ops = _ops()
     N, C = 200, 3
     E, _, row_mask, sims, wp, bp, gagg, gz = _rand_case(D + 1, R, A, D, N, C)
