@@ -150,6 +150,28 @@ int sgnn_cc_compact_huge(const int64_t* sub_ptr, const int32_t* sub_nodes, const
                          int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * a7b  Structural properties of induced subgraphs: what the DENSITY, CUT RATIO, CORENESS and COMPONENT labels of the
+ * synthetic benchmarks are made of (reference prepare_dataset/prepare_dataset.py:519-550: nx.density, nx.edge_boundary,
+ * nx.core_number, nx.number_connected_components of G.subgraph(nodes)), for all sets in one call.  Integer only.
+ * A member is an entry v with 1 <= v <= max_id and a non-empty row; other entries (PAD included) are dropped, as
+ * G.subgraph drops ids that are not nodes; a repeated member counts once.
+ * out_counts int64 (n_sets, 6): {members, edges among them (no self loops, an undirected edge once, an id repeated inside
+ * a row once), members with a self loop, boundary edges = distinct (member, non-member neighbour) pairs, connected
+ * components, sum of the members' core numbers (self loops ignored)}.
+ * out_core (nullable) int32, aligned with sub_nodes: the member's core number (repeats carry the same value), -1 for a
+ * dropped entry.
+ * rows_simple != 0: no row of col_sorted holds an id twice (the wave form then takes degree - self loop for a member's
+ * distinct neighbours instead of reading the row).  max_len: longest set, 0 = unknown.  Sets of at most 64 entries take one
+ * wavefront, sets of at most 2048 one workgroup with its tables in LDS; larger ones need max_len > 2048, total_nodes =
+ * sub_ptr[n_sets] and a workspace of sgnn_subgraph_properties_workspace_bytes(total_nodes) bytes (any content), else
+ * SGNN_ERR_BAD_ARG.  A set longer than max_len (or than 2048 with max_len unknown) gets -1 everywhere. */
+int64_t sgnn_subgraph_properties_workspace_bytes(int64_t total_nodes);
+int sgnn_subgraph_properties(const int64_t* rowptr, const int32_t* col_sorted, int64_t nnz, int64_t max_id, int rows_simple,
+                             const int64_t* sub_ptr, const int32_t* sub_nodes, int64_t n_sets, int64_t max_len,
+                             int64_t total_nodes, int64_t* out_counts, int32_t* out_core, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * a8  k-hop border of a component, and the hop level of each border node.
  * Replaces subgraph_utils.get_component_border_neighborhood_set (SubGNN/subgraph_utils.py:
  * 146-176) / SubGNN.initialize_border_sets (SubGNN/SubGNN.py:673-700).

@@ -492,6 +492,27 @@ def cc_labels(g, subs):
     return out
 
 
+def subgraph_properties(g, sets, want_core=True):
+    """The integer quantities behind the density / cut-ratio / coreness / component labels of prepare_dataset.py:519-550 for
+    every set of ``sets`` at once (sgnn_subgraph_properties) -> (counts int64 (n, 6), core int32 aligned with ``sets.nodes`` or
+    None).  counts[:, k] = members (entries that are nodes of the graph, a repeat once), edges among them, members with a self
+    loop, boundary edges, connected components, sum of the members' core numbers; core = the member's core number, -1 for an
+    entry that is no node of the graph.  Sets of more than 2048 entries take the workspace-backed form: as in ``cc_labels``,
+    the one host round trip (the total) is theirs."""
+    lib = _lib.load()
+    counts = torch.empty((sets.n, 6), dtype=torch.int64, device=g.device)
+    core = torch.full((sets.nodes.numel(),), -1, dtype=torch.int32, device=g.device) if want_core else None
+    max_len = int(sets.max_len)
+    ws, wsb, total = None, 0, 0
+    if max_len > CC_LDS_MAX:
+        total = int(sets.total)
+        ws, wsb = _huge_ws(lib, total, g.device, 'sgnn_subgraph_properties_workspace_bytes')
+    check(lib.sgnn_subgraph_properties(_ptr(g.rowptr), _ptr(g.col_sorted), g.nnz, g.max_id, 1 if getattr(g, 'simple_rows', False) else 0,
+                                       _ptr(sets.ptr), _ptr(sets.nodes), sets.n, max(max_len, 1), total, _ptr(counts), _ptr(core),
+                                       _ptr(ws), wsb, _stream()), 'sgnn_subgraph_properties')
+    return counts, core
+
+
 def cc_compact(sub_ptr, sub_nodes, labels, max_sub_len=0, dims_reduce=None, dims=None):
     """cc labels -> the padded (S, C, L) int64 component tensor of initialize_cc_ids, canonical order
     (components by their first node's position, nodes in subgraph order, duplicates dropped).
