@@ -753,6 +753,9 @@ int sgnn_mpn_bwd_edges_many(int64_t n, const struct sgnn_mpn_args* args, const f
  * Backward: dpre = grad_out * (out > 0); [grad_x | grad_aggr] = dpre W (either may be NULL: not computed);
  * grad_W = dpre^T [x | aggr], grad_b = column sums of dpre (either may be NULL) -- contracted over row blocks whose
  * partial sums (workspace) are added in block order: bit-reproducible.
+ * relu(v) = v <= 0 ? 0 : v: a NaN pre-activation stays NaN as under torch.relu; -Inf and -0 give 0.
+ * R == 0: nothing is launched and the pointers of the empty tensors may be NULL (the backward zeroes grad_W / grad_b).
+ * A call refused for its arguments (SGNN_ERR_BAD_ARG, SGNN_ERR_UNSUPPORTED_D) has written nothing.
  * ------------------------------------------------------------------------------------- */
 int sgnn_update_fwd(const float* x, const float* aggr, const float* W, const float* b, int64_t R, int64_t D,
                     float* out, void* stream);

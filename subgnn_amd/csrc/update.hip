@@ -1,6 +1,7 @@
 // a12 update():  out = relu([x | aggr] W^T + b)   (reference SubGNN/subgraph_mpn.py:233-241, nn.Linear(2D, D) of
 // subgraph_mpn.py:33) and its backward, for one row per component: x = the component embeddings (R, D), aggr = the
 // aggregated messages (R, D), W (D, 2D) row-major, b (D).
+// relu(v) = v <= 0 ? 0 : v: a NaN pre-activation stays NaN as under torch.relu (fmaxf would return the 0), -Inf and -0 give 0.
 //
 // As torch ops the layer was cat (R x 2D written and read back) + a library GEMM whose 64-column output runs far from
 // the chip's width + relu, and five more launches per direction in the backward: 47 us forward, 215 us forward +
@@ -93,7 +94,8 @@ __global__ __launch_bounds__(64) void update_fwd_kernel(const float* __restrict_
 #pragma unroll
         for (int v = 0; v < 16; ++v) {
             const int64_t r = row0 + upd_acc_row(v, h);
-            if (r < R) out[r * D + col] = fmaxf(acc[v] + bias, 0.f);
+            const float pre = acc[v] + bias;
+            if (r < R) out[r * D + col] = pre <= 0.f ? 0.f : pre;             // (not fmaxf: a NaN stays a NaN)
         }
     }
 }
@@ -167,7 +169,8 @@ __global__ __launch_bounds__(256) void update_fwd_ksplit_kernel(const float* __r
     for (int v = 0; v < 16; ++v) {
         const float sum = ((acc[v] + s_part[v * 64 + lane]) + s_part[(16 + v) * 64 + lane]) + s_part[(32 + v) * 64 + lane];
         const int64_t r = row0 + upd_acc_row(v, h);
-        if (r < R) out[r * D + col] = fmaxf(sum + bias, 0.f);
+        const float pre = sum + bias;
+        if (r < R) out[r * D + col] = pre <= 0.f ? 0.f : pre;                 // (not fmaxf: a NaN stays a NaN)
     }
 }
 
@@ -346,9 +349,10 @@ extern "C" int sgnn_update_fwd_chunks(const float* x, const float* aggr_chunks, 
 static int update_fwd_run(const float* x, const float* aggr, int n_chunks, const float* W, const float* b, int64_t R, int64_t D,
                           float* out, float* aggr_sum, void* stream)
 {
-    if (!x || !aggr || !W || !out || R < 0) return SGNN_ERR_BAD_ARG;
+    if (R < 0) return SGNN_ERR_BAD_ARG;
     if (D != 32 && D != 64 && D != 128) return SGNN_ERR_UNSUPPORTED_D;
-    if (R == 0) return SGNN_OK;
+    if (R == 0) return SGNN_OK;                                          // (an empty tensor's pointer may be NULL)
+    if (!x || !aggr || !W || !out) return SGNN_ERR_BAD_ARG;
     hipStream_t st = (hipStream_t)stream;
     const unsigned grid = (unsigned)((R + 31) / 32);
     // few rows: the feature tiles side by side (more wavefronts than CUs only from ~8k rows on)
@@ -376,17 +380,19 @@ extern "C" int sgnn_update_bwd(const float* grad_out, const float* out, const fl
                                int64_t R, int64_t D, float* grad_x, float* grad_aggr, float* grad_W, float* grad_b,
                                void* workspace, int64_t workspace_bytes, void* stream)
 {
-    if (!grad_out || !out || !W || R < 0) return SGNN_ERR_BAD_ARG;
-    if ((grad_W || grad_b) && (!x || !aggr)) return SGNN_ERR_BAD_ARG;
+    if (R < 0) return SGNN_ERR_BAD_ARG;
     if (D != 32 && D != 64 && D != 128) return SGNN_ERR_UNSUPPORTED_D;
     hipStream_t st = (hipStream_t)stream;
-    if (R == 0) {
+    if (R == 0) {                                                        // (an empty tensor's pointer may be NULL)
         hipError_t e = hipSuccess;
         if (grad_W) e = hipMemsetAsync(grad_W, 0, (size_t)(D * 2 * D * 4), st);
         if (e == hipSuccess && grad_b) e = hipMemsetAsync(grad_b, 0, (size_t)(D * 4), st);
         if (e != hipSuccess) { sgnn_set_last_error(e); return SGNN_ERR_LAUNCH; }
         return SGNN_OK;
     }
+    if (!grad_out || !out || !W) return SGNN_ERR_BAD_ARG;
+    // every refusal comes before the first launch: a refused call writes nothing
+    if ((grad_W || grad_b) && (!x || !aggr || !workspace || workspace_bytes < sgnn_update_bwd_workspace_bytes(R, D))) return SGNN_ERR_BAD_ARG;
     if (grad_x || grad_aggr) {
         const unsigned grid = (unsigned)((R + 31) / 32);
 #define UPD_LAUNCH_DX(DD) do { if (split) hipLaunchKernelGGL((update_bwd_dx_kernel<DD, true>), dim3(grid, 2 * DD / 32), dim3(64), 0, st, grad_out, out, W, R, grad_x, grad_aggr, UPD_NONE); \
@@ -397,7 +403,6 @@ extern "C" int sgnn_update_bwd(const float* grad_out, const float* out, const fl
         SGNN_CHECK_LAUNCH();
     }
     if (grad_W || grad_b) {
-        if (!workspace || workspace_bytes < sgnn_update_bwd_workspace_bytes(R, D)) return SGNN_ERR_BAD_ARG;
         const int64_t nb = (R + upd_block_rows(R) - 1) / upd_block_rows(R);
         float* pW = (float*)workspace;
         float* pb = pW + nb * D * 2 * D;
