@@ -228,6 +228,17 @@ int sgnn_khop_border_sample(const int64_t* rowptr, const int32_t* col, const int
  * the sets are one shard); sims (n_sets, n_slots) float32 := hop level, 0 on PAD. */
 int sgnn_khop_sample_finish(int64_t* anchor, const uint8_t* hop, const uint8_t* allneg, const int64_t* counts,
                             const int64_t* width, int64_t n_sets, int64_t n_slots, float* sims, void* stream);
+/* The one-hop border of every set WRITTEN in ascending id order by the one-hop kernel's own rank pass (no sort): for a caller
+ * whose sets stay the same from call to call, which then draws with sgnn_sample_border_anchors instead of rebuilding the border
+ * inside sgnn_khop_border_sample.  Two calls: out_ids == NULL writes out_count[s] only; with out_ptr (the caller's exclusive
+ * prefix sum of the counts, n_sets + 1 entries) and out_ids, set s's border goes to out_ids[out_ptr[s] .. out_ptr[s+1])
+ * (out_count, if given, is written again).  col_sorted, bitmap_in_lds and workspace (16 bytes: the set counter) as for
+ * sgnn_khop_border_sample with k = 1 -- but where that call would leave its specialised kernel (no LDS plan for the id range,
+ * or slices needed and col_sorted == NULL) this one returns SGNN_ERR_SET_TOO_LARGE and writes nothing. */
+int sgnn_khop1_border_sorted(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz, int64_t max_id,
+                             const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets,
+                             int64_t* out_count, const int64_t* out_ptr /* nullable */, int32_t* out_ids /* nullable */,
+                             void* workspace, int64_t workspace_bytes, int bitmap_in_lds, void* stream);
 
 /* Padded id rows (n_rows, row_len) int64 -> ragged sets: PAD (0) entries stripped -- or, with mask (uint8, same shape), the
  * entries whose mask is 0 -- order kept (how gamma.py:27, anchor_patch_samplers.py:131 and SubGNN.py:769 strip PAD).
@@ -279,6 +290,13 @@ int sgnn_sample_anchors_padded(const int64_t* ids, int64_t n_rows, int64_t L, in
 int sgnn_sample_anchors_ragged(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets,
                                const uint8_t* row_has_pad, int64_t n_slots,
                                uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t* out, void* stream);
+/* The neighbourhood-border draw on kept sorted borders (sgnn_khop1_border_sorted: ptr, ids, counts), one launch: the law of
+ * sgnn_sample_anchors_ragged with row_has_pad[r] = counts[r] < width[0] (width: DEVICE scalar, the padded border matrix's width)
+ * and out_sims (n_sets, n_slots) float32 = hop where the anchor is a node, 0 on PAD -- bit for bit what sgnn_khop_border_sample
+ * followed by sgnn_khop_sample_finish write for k = hop = 1.  An empty border gives anchor 0, similarity 0. */
+int sgnn_sample_border_anchors(const int64_t* ptr, const int32_t* ids, const int64_t* counts, int64_t n_sets,
+                               const int64_t* width, int64_t n_slots, uint64_t seed, uint64_t stream_id, int64_t item_base,
+                               int hop, int64_t* out_anchor, float* out_sims, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * a5/a6  Uniform draws with replacement from a list (position anchors, structure picks).

@@ -1794,6 +1794,199 @@ extern "C" int sgnn_khop_border_sample(const int64_t* rowptr, const int32_t* col
 }
 
 // ---------------------------------------------------------------------------------------------
+// The one-hop border WRITTEN, in ascending id order: what khop1_sample_kernel rebuilds in LDS for every draw depends on
+// the sets and the graph only, so a caller whose sets stay the same builds it once (count launch, prefix sum, write launch)
+// and draws from the kept ids afterwards (sgnn_sample_border_anchors) -- the draw's rank query becomes one indexed read.
+// Same workgroup shape, set counter, expansion, member un-set, rank pass and wipe as khop1_sample_kernel, in a copy of
+// its own (that kernel's register allocation is tuned statement by statement); it runs once per split, so it carries none
+// of the cross-set prefetching.  Where the sample kernel answers slots from the rank table, thread tid walks its run of
+// words [tid*run, tid*run+run) and stores the id of every set bit behind its exclusive rank: ranks follow word order, word
+// order is id order, so the border comes out sorted.  SLICED: one pass over the slices in either mode -- slices ascend,
+// a slice's ids go behind the total of the slices before it.
+// ---------------------------------------------------------------------------------------------
+template <bool SLICED>
+__global__ __launch_bounds__(K1_THREADS) void khop1_border_write_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t max_id,
+    const int64_t* __restrict__ set_ptr, const int32_t* __restrict__ set_nodes, int64_t n_sets,
+    int64_t* __restrict__ out_count, const int64_t* __restrict__ out_ptr, int32_t* __restrict__ out_ids,
+    int64_t slice_ids, int n_slices, unsigned long long* __restrict__ next_set)
+{
+    extern __shared__ uint32_t s_bm[];                       // bitmap of one slice of the id range
+    __shared__ int32_t s_wtot[K1_THREADS / 64];
+    __shared__ long long s_next;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
+    constexpr int NW = K1_THREADS / 64;
+    const int gl = tid & 15;
+    const int words_alloc = (int)((((slice_ids + 31) / 32 + K1_THREADS - 1) / K1_THREADS) | 1) * K1_THREADS;   // host: k1_alloc_bytes
+    {
+        int4* bm4 = reinterpret_cast<int4*>(s_bm);
+        for (int i = tid; i < words_alloc / 4; i += K1_THREADS) bm4[i] = make_int4(0, 0, 0, 0);
+    }
+    __syncthreads();
+    int64_t si_next = 0, si_end = 0;
+    while (true) {
+        if (si_next >= si_end) {
+            if (tid == 0) s_next = (long long)atomicAdd(next_set, (unsigned long long)K1_TAKE);
+            __syncthreads();
+            si_next = s_next;
+            si_end = si_next + K1_TAKE;
+            __syncthreads();
+        }
+        const int64_t s = si_next++;
+        if (s >= n_sets) break;
+        const int64_t beg = set_ptr[s];
+        const int n = (int)(set_ptr[s + 1] - beg);
+        const int64_t w_beg = out_ids ? out_ptr[s] : 0, w_end = out_ids ? out_ptr[s + 1] : 0;     // this set's slice of out_ids
+        int64_t before = 0;                                      // border ids in the slices before this one
+        for (int sl = 0; sl < (SLICED ? n_slices : 1); ++sl) {
+            const int64_t lo_id = (int64_t)sl * slice_ids;
+            const int64_t hi_id = lo_id + slice_ids < max_id + 1 ? lo_id + slice_ids : max_id + 1;
+            const int64_t words = (hi_id - lo_id + 31) / 32;
+            // ---- expansion: OR the bits of every member's neighbours (of this slice) ----------------
+            for (int t0 = 0; t0 < n; t0 += 64) {
+                uint32_t r0 = 0;
+                int32_t deg = 0;
+                if (t0 + lane < n) {
+                    const int32_t v = set_nodes[beg + t0 + lane];
+                    int64_t a = rowptr[v], b = rowptr[v + 1];
+                    if (SLICED) {                              // rows ascending: the list's part inside [lo_id, hi_id)
+                        int64_t l = a, h = b;
+                        while (l < h) { const int64_t m = (l + h) >> 1; if ((int64_t)col[m] < lo_id) l = m + 1; else h = m; }
+                        const int64_t first = l;
+                        h = b;
+                        while (l < h) { const int64_t m = (l + h) >> 1; if ((int64_t)col[m] < hi_id) l = m + 1; else h = m; }
+                        a = first; b = l;
+                    }
+                    r0 = (uint32_t)a;
+                    deg = (int32_t)(b - a);
+                }
+                // a list of >= K1_LONG entries is shared by all wavefronts in 64-entry chunks, a shorter one belongs whole
+                // to wavefront (member index) % 16
+#define K1W_OR_BIT(C) do { if ((C) >= 0) { const int32_t x_ = (C) - (int32_t)lo_id; \
+        __hip_atomic_fetch_or(&s_bm[x_ >> 5], 1u << (x_ & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } } while (0)
+                uint64_t longs = __ballot(deg >= K1_LONG);
+                while (longs) {
+                    const int m = __ffsll((long long)longs) - 1;
+                    longs &= longs - 1;
+                    const int32_t m_deg = __builtin_amdgcn_readlane(deg, m);
+                    const uint32_t m_r0 = (uint32_t)__builtin_amdgcn_readlane((int)r0, m);
+                    for (int32_t tb = wave_s * 64; tb < m_deg; tb += K1_INFLIGHT * NW * 64) {
+                        int32_t c[K1_INFLIGHT];
+#pragma unroll
+                        for (int u = 0; u < K1_INFLIGHT; ++u) {
+                            const int32_t t = tb + u * NW * 64 + lane;
+                            c[u] = t < m_deg ? col[m_r0 + (uint32_t)t] : -1;
+                        }
+#pragma unroll
+                        for (int u = 0; u < K1_INFLIGHT; ++u) K1W_OR_BIT(c[u]);
+                    }
+                }
+                for (int m = wave_s; m < 64 && t0 + m < n; m += NW) {
+                    const int32_t m_deg = __builtin_amdgcn_readlane(deg, m);
+                    if (m_deg >= K1_LONG) continue;
+                    const uint32_t m_r0 = (uint32_t)__builtin_amdgcn_readlane((int)r0, m);
+                    for (int32_t tb = 0; tb < m_deg; tb += K1_INFLIGHT * 64) {
+                        int32_t c[K1_INFLIGHT];
+#pragma unroll
+                        for (int u = 0; u < K1_INFLIGHT; ++u) {
+                            const int32_t t = tb + u * 64 + lane;
+                            c[u] = t < m_deg ? col[m_r0 + (uint32_t)t] : -1;
+                        }
+#pragma unroll
+                        for (int u = 0; u < K1_INFLIGHT; ++u) K1W_OR_BIT(c[u]);
+                    }
+                }
+#undef K1W_OR_BIT
+            }
+            k1_lds_barrier();
+            // ---- the members themselves are not border ---------------------------------------------
+            for (int i = tid; i < n; i += K1_THREADS) {
+                const int64_t v = (int64_t)set_nodes[beg + i];
+                if (v >= lo_id && v < hi_id) {
+                    const int32_t x = (int32_t)(v - lo_id);
+                    __hip_atomic_fetch_and(&s_bm[x >> 5], ~(1u << (x & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            }
+            k1_lds_barrier();
+            // ---- rank pass: popcount of each thread's run of words, exclusive prefix -----------------
+            // (the allocation is run x K1_THREADS words, zero beyond `words`: no bounds tests)
+            const int run = (int)(((words + K1_THREADS - 1) / K1_THREADS) | 1);
+            const uint32_t* __restrict__ mine_ = s_bm + tid * run;
+            int c = 0;
+            for (int u = 0; u < run; ++u) c += __popc(mine_[u]);
+            const int inc = sgnn_wave_incl_scan(c);
+            if (lane == 63) s_wtot[wave] = inc;
+            k1_lds_barrier();
+            const int wt = s_wtot[gl];                                        // NW = 16 totals, replicated in every row
+            const int wincl = sgnn_row_incl_scan(wt);
+            const int total = __builtin_amdgcn_readlane(wincl, NW - 1);
+            if (out_ids) {
+                // ---- the write: this thread's bits, in word order, behind its exclusive rank ---------
+                int64_t pos = w_beg + before + __builtin_amdgcn_readlane(wincl - wt, wave_s) + (inc - c);
+                const int64_t id0 = lo_id + (int64_t)tid * run * 32;
+                for (int u = 0; u < run && c > 0; ++u) {
+                    uint32_t word = mine_[u];
+                    while (word) {
+                        const int bit = __ffs((int)word) - 1;
+                        word &= word - 1;
+                        if (pos < w_end) out_ids[pos] = (int32_t)(id0 + u * 32 + bit);   // (out_ptr from another graph or other sets: nothing past the slice)
+                        ++pos;
+                        --c;
+                    }
+                }
+            }
+            before += total;
+            // ---- wipe for the next slice / set ------------------------------------------------------
+            k1_lds_barrier();
+            {
+                int4* bm4 = reinterpret_cast<int4*>(s_bm);
+                const int n4 = (int)((words + 3) / 4);
+                for (int i = tid; i < n4; i += K1_THREADS) bm4[i] = make_int4(0, 0, 0, 0);
+            }
+            k1_lds_barrier();
+        }
+        if (tid == 0 && out_count) out_count[s] = before;
+    }
+}
+
+extern "C" int sgnn_khop1_border_sorted(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
+                                        int64_t max_id, const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets,
+                                        int64_t* out_count, const int64_t* out_ptr, int32_t* out_ids,
+                                        void* workspace, int64_t workspace_bytes, int bitmap_in_lds, void* stream)
+{
+    if (!rowptr || !col || !set_ptr || !set_nodes || !workspace || n_sets < 0 || max_id < 0 || workspace_bytes < 16) return SGNN_ERR_BAD_ARG;
+    if (!out_count && !out_ids) return SGNN_ERR_BAD_ARG;
+    if (out_ids && !out_ptr) return SGNN_ERR_BAD_ARG;
+    if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
+    int64_t slice_ids = 0;
+    int n_slices = 0;
+    // no LDS plan for this id range, or slices without ascending rows: refused (the fused draw has a general kernel to fall
+    // back on; a kept border has not)
+    if (!k1_applies(max_id, 1, col_sorted != nullptr, bitmap_in_lds, &slice_ids, &n_slices)) return SGNN_ERR_SET_TOO_LARGE;
+    if (n_sets == 0) return SGNN_OK;
+    hipStream_t st = (hipStream_t)stream;
+    unsigned long long* next_set = (unsigned long long*)((char*)workspace + ((workspace_bytes - 8) & ~(int64_t)7));
+    { const hipError_t me = hipMemsetAsync(next_set, 0, 8, st); if (me != hipSuccess) { sgnn_set_last_error(me); return SGNN_ERR_LAUNCH; } }
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)khop1_border_write_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, K1_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)khop1_border_write_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, K1_LDS_MAX);
+        attr_set = true;
+    }
+    const int64_t nwg = kb_n_wg(n_sets, true);
+    const size_t lds = (size_t)k1_alloc_bytes(slice_ids);
+    if (n_slices == 1)
+        hipLaunchKernelGGL(khop1_border_write_kernel<false>, dim3((int)nwg), dim3(K1_THREADS), lds, st, rowptr, col, max_id,
+                           set_ptr, set_nodes, n_sets, out_count, out_ptr, out_ids, slice_ids, 1, next_set);
+    else
+        hipLaunchKernelGGL(khop1_border_write_kernel<true>, dim3((int)nwg), dim3(K1_THREADS), lds, st, rowptr, col_sorted, max_id,
+                           set_ptr, set_nodes, n_sets, out_count, out_ptr, out_ids, slice_ids, n_slices, next_set);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // a3  in-border nodes of a patch (reference SubGNN/subgraph_utils.py:126-144, with the id-1 /
 // node-order indexing quirk: id x is read as the node at position x-1 of G.nodes()).
 // One workgroup per patch; patch ids in an LDS hash; one thread per member walks "its" list.

@@ -72,6 +72,43 @@ extern "C" int sgnn_sample_anchors_ragged(const int64_t* set_ptr, const int32_t*
     return SGNN_OK;
 }
 
+// Neighbourhood-border anchors drawn from KEPT sorted borders (sgnn_khop1_border_sorted): the law of
+// sample_anchors_ragged_kernel with has_pad = counts[r] < width[0], and the slot's similarity (the hop level, 0 on PAD) in the
+// same launch -- what khop1_sample_kernel + khop_sample_finish_kernel produce together, without rebuilding the border.
+__global__ __launch_bounds__(256) void sample_anchors_border_kernel(
+    const int64_t* __restrict__ ptr, const int32_t* __restrict__ ids, const int64_t* __restrict__ counts, int64_t n_sets,
+    const int64_t* __restrict__ width, int64_t n_slots, uint64_t h0, int64_t item_base, float hop,
+    int64_t* __restrict__ out_anchor, float* __restrict__ out_sims)
+{
+    const int64_t total = n_sets * n_slots;
+    const int64_t wd = width[0];
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = t / n_slots;
+        const int64_t n = counts[r];
+        int64_t v = 0;
+        if (n > 0) {
+            const uint64_t h1 = sgnn_tape_h1(h0, (uint64_t)(t + item_base * n_slots));
+            if (!(n < wd && sgnn_nanchor_allneg(h1, (uint32_t)n))) v = ids[ptr[r] + sgnn_nanchor_index(h1, (uint32_t)n)];
+        }
+        out_anchor[t] = v;
+        out_sims[t] = v == 0 ? 0.f : hop;
+    }
+}
+
+extern "C" int sgnn_sample_border_anchors(const int64_t* ptr, const int32_t* ids, const int64_t* counts, int64_t n_sets,
+                                          const int64_t* width, int64_t n_slots, uint64_t seed, uint64_t stream_id,
+                                          int64_t item_base, int hop, int64_t* out_anchor, float* out_sims, void* stream)
+{
+    if (!ptr || !ids || !counts || !width || !out_anchor || !out_sims || n_sets < 0 || n_slots < 0 || item_base < 0 || hop < 0)
+        return SGNN_ERR_BAD_ARG;
+    if (n_sets == 0 || n_slots == 0) return SGNN_OK;
+    hipLaunchKernelGGL(sample_anchors_border_kernel, dim3(sgnn_grid_for(n_sets * n_slots, 256)), dim3(256), 0,
+                       (hipStream_t)stream, ptr, ids, counts, n_sets, width, n_slots, sgnn_tape_h0(seed, stream_id), item_base,
+                       (float)hop, out_anchor, out_sims);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // a5/a6  np.random.choice(seq, n, replace=True) (reference anchor_patch_samplers.py:206,208,326)
 // ---------------------------------------------------------------------------------------------

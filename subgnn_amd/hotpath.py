@@ -577,6 +577,7 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
         has_pad_c = (cc_sets.lengths < Lc).to(torch.uint8)
         cc_canon = ops.sort_ragged(cc_sets)                     # the draw ranks the ascending members
         ni, nb, plans = {}, {}, {}
+        border = _kept_border(model, split, subs, cc_sets, k)
         for l in range(L):
             ni[l] = ops.sample_anchors_ragged(cc_canon, hp['n_anchor_patches_N_in'], seed,
                                               tape.stream_id(tape.STREAM_N_INT, split, l, ep), has_pad_c,
@@ -588,11 +589,21 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
             # components and the graph, not of the draw: reduced (over the ranks too) on the first pass, kept afterwards
             widths = model.__dict__.setdefault('_border_width', {})
             wkey = (split, k, cc_sets.n, shard.world if shard is not None else 1)
-            a, w, counts = ops.khop_border_sample(g, cc_sets, k, hp['n_anchor_patches_N_out'], seed,
-                                                  tape.stream_id(tape.STREAM_N_BOR, split, l, ep),     # taken dynamically: a dispatch order buys nothing here
-                                                  item_base=base * C,
-                                                  count_reduce=shard.reduce_max if shard is not None else None,
-                                                  width=widths.get(wkey))
+            # the one-hop border itself is such a property too: written once per split, sorted (_kept_border), and every pass,
+            # layer and resample epoch draws from the kept ids -- the draw is all that changes
+            if border is not None:
+                if wkey not in widths:
+                    wmax = border.counts.max().view(1)
+                    widths[wkey] = shard.reduce_max(wmax) if shard is not None else wmax
+                a, w, counts = ops.draw_border_anchors(border, hp['n_anchor_patches_N_out'], seed,
+                                                       tape.stream_id(tape.STREAM_N_BOR, split, l, ep), item_base=base * C,
+                                                       width=widths[wkey])
+            else:
+                a, w, counts = ops.khop_border_sample(g, cc_sets, k, hp['n_anchor_patches_N_out'], seed,
+                                                      tape.stream_id(tape.STREAM_N_BOR, split, l, ep),     # taken dynamically: a dispatch order buys nothing here
+                                                      item_base=base * C,
+                                                      count_reduce=shard.reduce_max if shard is not None else None,
+                                                      width=widths.get(wkey))
             if wkey not in widths:
                 wmax = counts.max().view(1)
                 widths[wkey] = shard.reduce_max(wmax) if shard is not None else wmax
@@ -651,6 +662,33 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
     st.attrs[split + '_neigh_pos_similarities'] = sims if sims else None
     st.attrs[split + '_N_border'] = None
     return st
+
+
+KEPT_BORDER_BYTES = 4 << 30         # ids of a split's kept one-hop borders (hparams['kept_border_bytes']; 0: never keep)
+
+
+def _kept_border(model, split, subs, cc_sets, k):
+    """The split's sorted one-hop borders (ops.KeptBorders), built by its first pass and kept: they depend on the split's
+    components and the graph only.  None where the pass takes the fused border + draw kernel instead: k != 1, a graph the one-hop
+    kernel does not serve, a budget of 0 or a border beyond the budget (decided once: the count is not repeated), and a
+    recording that finds nothing kept -- building reads a size back, which a capture cannot (an eager pass builds first)."""
+    hp, g = model.hparams, model.networkx_graph
+    budget = int(hp.get('kept_border_bytes', KEPT_BORDER_BYTES))
+    if k != 1 or budget <= 0:
+        return None
+    kept = model.__dict__.setdefault('_kept_borders', {})
+    sub_g = getattr(model, split + '_sub_G')
+    tag = (id(sub_g), subs.n, cc_sets.n, id(g), budget)
+    rec = kept.get(split)
+    if rec is None or rec[0] != tag:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        border = ops.khop1_borders_sorted(g, cc_sets, max_bytes=budget) if ops.khop1_applies(g, cc_sets.n) else None
+        rec = kept[split] = (tag, border, sub_g, g)              # (the list and the graph are held: their ids stay theirs)
+    border = rec[1]
+    if border is not None:
+        border.wait(torch.cuda.current_stream())
+    return border
 
 
 def finish_pass(model, st, timer=None):

@@ -656,6 +656,94 @@ def khop_border_sample(g, sets, k, n_slots, seed, stream_id, bitmap_in_lds=None,
     return anchor, sims, counts
 
 
+def _k1_mode(bitmap_in_lds):
+    return 1 if bitmap_in_lds is None else (int(bitmap_in_lds) if not isinstance(bitmap_in_lds, bool) else (1 if bitmap_in_lds else 0))
+
+
+def khop1_applies(g, n_sets, bitmap_in_lds=None):
+    """Whether the specialised one-hop kernels serve this graph (an LDS plan exists for its id range; slices need ascending
+    rows): where khop_border_sample runs khop1_sample_kernel and khop1_borders_sorted can build."""
+    return _lib.load().sgnn_khop_border_sample_workspace_bytes(g.max_id, n_sets, 1, 1 if g.col_sorted is not None else 0,
+                                                               _k1_mode(bitmap_in_lds)) == 16
+
+
+class KeptBorders:
+    """The one-hop borders of a list of sets, each in ascending id order: ``ids[ptr[s]:ptr[s+1]]`` int32, ``counts`` int64 (n),
+    ``ready``: the event behind the write launch (a consumer on another stream waits for it once)."""
+
+    def __init__(self, ptr, ids, counts, ready, timing=None):
+        self.ptr, self.ids, self.counts, self.ready = ptr, ids, counts, ready
+        self.n = counts.numel()
+        self.nbytes = ids.numel() * 4 + ptr.numel() * 8 + counts.numel() * 8
+        self._timing = timing                 # (start, end) events around the two launches; build_ms() reads them
+        self._waited = set()
+
+    def build_ms(self):
+        return self._timing[0].elapsed_time(self._timing[1])
+
+    def rows(self, lo, hi):
+        """Rows lo:hi as a view (the ids are shared; ptr keeps its offsets into them)."""
+        return KeptBorders(self.ptr[lo:hi + 1], self.ids, self.counts[lo:hi], self.ready, self._timing)
+
+    def wait(self, stream):
+        """Order ``stream`` behind the build (once per stream: the ids never change afterwards)."""
+        key = stream.cuda_stream
+        if key in self._waited:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            return                            # (torch synchronises the device before a capture begins: the build has ended, and
+            #                                   a wait for an outside event would invalidate the capture)
+        self._waited.add(key)
+        for t in (self.ptr, self.ids, self.counts):
+            t.record_stream(stream)           # (a kept border that is replaced is freed while this stream may still read it)
+        if not self.ready.query():
+            stream.wait_event(self.ready)
+
+
+def khop1_borders_sorted(g, sets, bitmap_in_lds=None, max_bytes=None):
+    """One-hop border of every set, sorted, written by the one-hop kernel's own rank pass (khop1_border_write_kernel): a count
+    launch, a prefix sum, ONE host read (the total) and a write launch -> KeptBorders.  ``max_bytes``: above it, None is returned
+    after the count launch with nothing allocated for the ids.  Raises where the one-hop kernel does not apply (khop1_applies)."""
+    lib = _lib.load()
+    mode = _k1_mode(bitmap_in_lds)
+    ws = torch.zeros(4, dtype=torch.int32, device=g.device)       # the set counter: the build's own (the fused call's may be in use on another stream)
+    counts = torch.zeros(sets.n, dtype=torch.int64, device=g.device)
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    check(lib.sgnn_khop1_border_sorted(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, g.max_id, _ptr(sets.ptr),
+                                       _ptr(sets.nodes), sets.n, _ptr(counts), None, None, _ptr(ws), 16, mode, _stream()),
+          'sgnn_khop1_border_sorted(count)')
+    ptr = torch.zeros(sets.n + 1, dtype=torch.int64, device=g.device)
+    torch.cumsum(counts, 0, out=ptr[1:])
+    total = int(ptr[-1].item())                                  # the one host round trip
+    if max_bytes is not None and total * 4 > max_bytes:
+        return None
+    ids = torch.empty(max(total, 1), dtype=torch.int32, device=g.device)
+    check(lib.sgnn_khop1_border_sorted(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, g.max_id, _ptr(sets.ptr),
+                                       _ptr(sets.nodes), sets.n, None, _ptr(ptr), _ptr(ids), _ptr(ws), 16, mode, _stream()),
+          'sgnn_khop1_border_sorted(write)')
+    ev1.record()
+    return KeptBorders(ptr, ids, counts, ev1, (ev0, ev1))
+
+
+def draw_border_anchors(kept, n_slots, seed, stream_id, item_base=0, width=None):
+    """Neighbourhood-border anchors drawn from kept sorted one-hop borders -> (anchors (n, n_slots) int64, similarities
+    float32, border sizes): what khop_border_sample(g, sets, 1, ...) returns for the sets ``kept`` was built from, bit for bit,
+    in one launch.  ``item_base``: number of the first row within the whole matrix when ``kept`` holds a shard of its rows
+    (or is a ``rows`` view); ``width``: the padded border matrix's width as a device scalar (default: the largest border of
+    these rows)."""
+    lib = _lib.load()
+    ptr, counts, n = kept.ptr, kept.counts, kept.n
+    if width is None:
+        width = counts.max().view(1) if n > 0 else torch.zeros(1, dtype=torch.int64, device=kept.ids.device)
+    anchor = torch.empty((n, n_slots), dtype=torch.int64, device=kept.ids.device)
+    sims = torch.empty((n, n_slots), dtype=torch.float32, device=kept.ids.device)
+    check(lib.sgnn_sample_border_anchors(_ptr(ptr), _ptr(kept.ids), _ptr(counts), n, _ptr(width.to(torch.int64)), n_slots, seed,
+                                         stream_id, int(item_base), 1, _ptr(anchor), _ptr(sims), _stream()),
+          'sgnn_sample_border_anchors')
+    return anchor, sims, counts
+
+
 SORT_SETS_MAX = 1024
 
 
