@@ -895,9 +895,6 @@ __device__ __forceinline__ uint32_t kb_word(const uint32_t* bm, int64_t w)
 #ifndef KB_TAKE
 #define KB_TAKE 4                // sets a workgroup takes per trip to the device-wide counter (1 / 2 / 4: 2.50 / 2.37 / 2.35 ms)
 #endif
-#ifndef KB_STATIC_DISPATCH
-#define KB_STATIC_DISPATCH 0     // 1: sets dealt round-robin in dispatch order instead of taken from a device-wide counter
-#endif
 
 template <bool LDS_BM, int THREADS>
 __device__ __forceinline__ void kb_select(const KbSample& smp, int64_t s, const uint32_t* bm, int64_t words,
@@ -998,10 +995,6 @@ __global__ __launch_bounds__(THREADS) void khop_border_kernel(
     // members' degrees: a static round-robin leaves CUs idle behind the unlucky ones), in the caller's
     // dispatch order when given (heaviest first).
     __shared__ long long s_next;
-#if KB_STATIC_DISPATCH
-    for (int64_t si = blockIdx.x; si < n_sets; si += gridDim.x) {
-        __syncthreads();
-#else
     int64_t si_next = 0, si_end = 0;                          // KB_TAKE consecutive sets per trip to the counter
     while (true) {
         if (si_next >= si_end) {                              // uniform over the workgroup
@@ -1012,7 +1005,6 @@ __global__ __launch_bounds__(THREADS) void khop_border_kernel(
         }
         const int64_t si = si_next++;
         if (si >= n_sets) break;
-#endif
         const int64_t s = set_order ? set_order[si] : si;
         const int64_t beg = set_ptr[s];
         const int n = (int)(set_ptr[s + 1] - beg);
@@ -1091,7 +1083,6 @@ __global__ __launch_bounds__(THREADS) void khop_border_kernel(
                         }                                                                                      \
                     }                                                                                          \
                 } while (0)
-#ifndef KB_DEBUG_SKIP_EDGES
                 // (a) the long lists, one after the other, every wavefront a share of each
                 uint64_t bigm = ((uint64_t)s_big[1] << 32) | s_big[0];
                 while (bigm) {
@@ -1138,7 +1129,6 @@ __global__ __launch_bounds__(THREADS) void khop_border_kernel(
                     }
                     KB_PROCESS_GROUP();
                 }
-#endif
 #undef KB_PROCESS_GROUP
                 if (!need_queue && wave_new) {                     // wave-uniform
                     if (lane == 0) atomicAdd(&s_qn, wave_new);
@@ -1166,19 +1156,13 @@ __global__ __launch_bounds__(THREADS) void khop_border_kernel(
             const int32_t v = set_nodes[beg + i];
             atomicAnd(&bm[v >> 5], ~(1u << (v & 31)));
         }
-#ifndef KB_DEBUG_SKIP_SELECT
         if (smp.n_slots > 0) {
             __syncthreads();
             kb_select<LDS_BM, THREADS>(smp, s, bm, words, q, cnt, hops, s_lvl, s_pref, s_wtot, s_sel, tid);
             __syncthreads();
         }
-#endif
         // un-set every border bit so the next component handled by the workgroup starts clean
-#ifdef KB_DEBUG_SKIP_WIPE
-        if (false) {
-#else
         if (LDS_BM && (!need_queue || (int64_t)cnt * 8 > words)) {
-#endif
             // cheaper than re-reading the queue: wipe the LDS bitmap with 16-byte stores
             int4* bm4 = reinterpret_cast<int4*>(s_bm);
             for (int64_t i = tid; i < (words + 3) / 4; i += THREADS) bm4[i] = make_int4(0, 0, 0, 0);
@@ -1284,9 +1268,6 @@ extern "C" int sgnn_khop_border_arena(const int64_t* rowptr, const int32_t* col,
 #ifndef K1_INFLIGHT
 #define K1_INFLIGHT 4           // 64-entry chunk loads a wavefront issues before it sets any bit
 #endif
-#ifndef K1_RANK_UNROLL
-#define K1_RANK_UNROLL 8
-#endif
 #ifndef K1_LONG
 #define K1_LONG 512             // lists of at least this many entries are shared by all wavefronts of the workgroup
 #endif
@@ -1331,6 +1312,133 @@ __device__ __forceinline__ int k1_nth_set_bit(uint32_t word, int n)           //
     return pos;
 }
 
+// ---- the parts the two one-hop kernels (khop1_sample_kernel, khop1_border_write_kernel) share ------------------------
+
+// The rank pass gives every thread a run of `run` words (odd: conflict-free strides) and reads them without bounds tests,
+// so the bitmap is allocated as run x K1_THREADS words (the padding is never set and stays zero).
+// (khop1_sample_kernel writes its `run` out and keeps its rank pass's popcount in its body: through k1_run the compiler folds
+// a loop guard there, and in a function of its own the popcount's accumulating v_bcnt chain splits into v_bcnt + v_add3 --
+// 2 instructions fewer and 10 more in a kernel whose register allocation is tuned against the exact instruction sequence)
+__host__ __device__ static inline int64_t k1_run(int64_t words) { return ((words + K1_THREADS - 1) / K1_THREADS) | 1; }
+__host__ __device__ static inline int64_t k1_alloc_bytes(int64_t slice_ids) { return k1_run((slice_ids + 31) / 32) * K1_THREADS * 4; }
+
+// zeroes the first n4 16-byte words of the bitmap (the whole allocation at the kernel's start, a slice's words after it)
+__device__ __forceinline__ void k1_zero_fill(uint32_t* s_bm, int n4, int tid)
+{
+    int4* bm4 = reinterpret_cast<int4*>(s_bm);
+    for (int i = tid; i < n4; i += K1_THREADS) bm4[i] = make_int4(0, 0, 0, 0);
+}
+
+// one trip to the device-wide set counter: the first of the K1_TAKE consecutive sets this workgroup takes (the second
+// barrier: s_next is rewritten by the next trip)
+__device__ __forceinline__ int64_t k1_take_sets(unsigned long long* __restrict__ next_set, long long* s_next, int tid)
+{
+    if (tid == 0) *s_next = (long long)atomicAdd(next_set, (unsigned long long)K1_TAKE);
+    __syncthreads();
+    const int64_t first = *s_next;
+    __syncthreads();
+    return first;
+}
+
+// member v's neighbour list as (start, length); SLICED: rows ascending, the list's part inside [lo_id, hi_id)
+template <bool SLICED>
+__device__ __forceinline__ void k1_row_range(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int32_t v,
+                                             int64_t lo_id, int64_t hi_id, uint32_t& r0, int32_t& deg)
+{
+    int64_t a = rowptr[v], b = rowptr[v + 1];
+    if (SLICED) {
+        int64_t l = a, h = b;
+        while (l < h) { const int64_t m = (l + h) >> 1; if ((int64_t)col[m] < lo_id) l = m + 1; else h = m; }
+        const int64_t first = l;
+        h = b;
+        while (l < h) { const int64_t m = (l + h) >> 1; if ((int64_t)col[m] < hi_id) l = m + 1; else h = m; }
+        a = first; b = l;
+    }
+    r0 = (uint32_t)a;
+    deg = (int32_t)(b - a);
+}
+
+__device__ __forceinline__ void k1_or_bit(uint32_t* s_bm, int32_t c, int64_t lo_id)      // c < 0: a chunk's slot past the list's end
+{
+    if (c >= 0) {
+        const int32_t x = c - (int32_t)lo_id;
+        __hip_atomic_fetch_or(&s_bm[x >> 5], 1u << (x & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
+// The expansion of one tile of 64 members (lane m holds member t0 + m's r0 / deg): OR the bits of their neighbours.
+// Who reads what, without any search: a list of >= K1_LONG entries is shared by all wavefronts
+// (wavefront w takes the 64-entry chunks w, w + 16, ...), a shorter one belongs whole to wavefront
+// (member index) % 16.  Everything that selects a list is a ballot bit or a v_readlane -- rounds 1-2
+// numbered all chunks through and every wavefront walked the whole member list in scalar registers
+// to find its own: ~500 scalar instructions per wavefront and set.
+__device__ __forceinline__ void k1_expand_tile(const int32_t* __restrict__ col, uint32_t* s_bm, uint32_t r0, int32_t deg,
+                                               int t0, int n, int64_t lo_id, int wave_s, int lane)
+{
+    constexpr int NW = K1_THREADS / 64;
+    uint64_t longs = __ballot(deg >= K1_LONG);
+    while (longs) {                                               // scalar loop over the long lists
+        const int m = __ffsll((long long)longs) - 1;
+        longs &= longs - 1;
+        const int32_t m_deg = __builtin_amdgcn_readlane(deg, m);
+        const uint32_t m_r0 = (uint32_t)__builtin_amdgcn_readlane((int)r0, m);
+        for (int32_t tb = wave_s * 64; tb < m_deg; tb += K1_INFLIGHT * NW * 64) {
+            int32_t c[K1_INFLIGHT];
+#pragma unroll
+            for (int u = 0; u < K1_INFLIGHT; ++u) {
+                const int32_t t = tb + u * NW * 64 + lane;
+                c[u] = t < m_deg ? col[m_r0 + (uint32_t)t] : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < K1_INFLIGHT; ++u) k1_or_bit(s_bm, c[u], lo_id);
+        }
+    }
+    // (skipping the slots past a list's end with scalar tests, or unrolling the short lists exactly,
+    // was slower: 1.48 -> 1.52-1.60 ms -- the branches cost more than the predicated-off instructions)
+    for (int m = wave_s; m < 64 && t0 + m < n; m += NW) {          // this wavefront's short lists
+        const int32_t m_deg = __builtin_amdgcn_readlane(deg, m);
+        if (m_deg >= K1_LONG) continue;
+        const uint32_t m_r0 = (uint32_t)__builtin_amdgcn_readlane((int)r0, m);
+        for (int32_t tb = 0; tb < m_deg; tb += K1_INFLIGHT * 64) {
+            int32_t c[K1_INFLIGHT];
+#pragma unroll
+            for (int u = 0; u < K1_INFLIGHT; ++u) {
+                const int32_t t = tb + u * 64 + lane;
+                c[u] = t < m_deg ? col[m_r0 + (uint32_t)t] : -1;
+            }
+#pragma unroll
+            for (int u = 0; u < K1_INFLIGHT; ++u) k1_or_bit(s_bm, c[u], lo_id);
+        }
+    }
+}
+
+__device__ __forceinline__ void k1_unset_bit(uint32_t* s_bm, int64_t v, int64_t lo_id, int64_t hi_id)
+{
+    if (v >= lo_id && v < hi_id) {
+        const int32_t x = (int32_t)(v - lo_id);
+        __hip_atomic_fetch_and(&s_bm[x >> 5], ~(1u << (x & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
+// the members themselves are not border: un-set the bits of members [from, n)
+__device__ __forceinline__ void k1_unset_members(uint32_t* s_bm, const int32_t* set_nodes, int64_t beg, int from, int n,
+                                                 int64_t lo_id, int64_t hi_id, int tid)
+{
+    for (int i = from + tid; i < n; i += K1_THREADS) k1_unset_bit(s_bm, (int64_t)set_nodes[beg + i], lo_id, hi_id);
+}
+
+// The 16 wavefront totals, from each wavefront's inclusive scan `inc` of its threads' counts: published with ONE barrier
+// (which also publishes whatever else the caller wrote to LDS before the call), then every 16-lane group scans them
+// itself (a DPP row scan).  wt / wincl: lane gl holds wavefront gl's total / the inclusive scan up to it; returns the sum.
+__device__ __forceinline__ int k1_wave_totals(int inc, int32_t* s_wtot, int wave, int lane, int gl, int& wt, int& wincl)
+{
+    if (lane == 63) s_wtot[wave] = inc;
+    k1_lds_barrier();
+    wt = s_wtot[gl];                                                  // NW = 16 totals, replicated in every row
+    wincl = sgnn_row_incl_scan(wt);
+    return __builtin_amdgcn_readlane(wincl, K1_THREADS / 64 - 1);
+}
+
 template <bool SLICED>
 __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t max_id,
@@ -1348,11 +1456,8 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
     const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);          // the same number, known to be uniform
     constexpr int NW = K1_THREADS / 64;
     const int grp = tid >> 4, gl = tid & 15, gshift = (lane >> 4) * 16;     // 64 groups of 16 lanes
-    const int words_alloc = (int)((((slice_ids + 31) / 32 + K1_THREADS - 1) / K1_THREADS) | 1) * K1_THREADS;   // host: k1_alloc_bytes
-    {
-        int4* bm4 = reinterpret_cast<int4*>(s_bm);
-        for (int i = tid; i < words_alloc / 4; i += K1_THREADS) bm4[i] = make_int4(0, 0, 0, 0);
-    }
+    const int words_alloc = (int)(k1_alloc_bytes(slice_ids) / 4);
+    k1_zero_fill(s_bm, words_alloc / 4, tid);
     __syncthreads();
     int64_t si_next = 0, si_end = 0;
 #ifdef K1_DEBUG_TIMING
@@ -1364,11 +1469,8 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
     int64_t trip0 = 0, trip_ptr = 0;
     while (true) {
         if (si_next >= si_end) {
-            if (tid == 0) s_next = (long long)atomicAdd(next_set, (unsigned long long)K1_TAKE);
-            __syncthreads();
-            si_next = s_next;
+            si_next = k1_take_sets(next_set, &s_next, tid);
             si_end = si_next + K1_TAKE;
-            __syncthreads();
             // the trip's slice of set_ptr in one load (lane j: set si_next + j), read back lane by lane below
             trip0 = si_next;
             trip_ptr = 0;
@@ -1424,81 +1526,14 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
                     else if (t0 + lane < n) {
                         const int32_t v = set_nodes[beg + t0 + lane];
                         if (t0 == 0) v_tile0 = v;
-                        int64_t a = rowptr[v], b = rowptr[v + 1];
-                        if (SLICED) {                              // rows ascending: the list's part inside [lo_id, hi_id)
-                            int64_t l = a, h = b;
-                            while (l < h) { const int64_t m = (l + h) >> 1; if ((int64_t)col[m] < lo_id) l = m + 1; else h = m; }
-                            const int64_t first = l;
-                            h = b;
-                            while (l < h) { const int64_t m = (l + h) >> 1; if ((int64_t)col[m] < hi_id) l = m + 1; else h = m; }
-                            a = first; b = l;
-                        }
-                        r0 = (uint32_t)a;
-                        deg = (int32_t)(b - a);
+                        k1_row_range<SLICED>(rowptr, col, v, lo_id, hi_id, r0, deg);
                     }
                     K1_T(6);                                       // (debug) tile ready
                     // step 1 of the prefetch, issued only now: a load issued before the prefetched row pointers
                     // above are consumed would have to complete first (the counter of outstanding loads cannot
                     // tell them apart across the loop's back edge)
                     if (t0 == 0 && can_pf && lane < nx_end - nx_beg) nx_v = set_nodes[nx_beg + lane];
-                    // Who reads what, without any search: a list of >= K1_LONG entries is shared by all wavefronts
-                    // (wavefront w takes the 64-entry chunks w, w + 16, ...), a shorter one belongs whole to wavefront
-                    // (member index) % 16.  Everything that selects a list is a ballot bit or a v_readlane -- rounds 1-2
-                    // numbered all chunks through and every wavefront walked the whole member list in scalar registers
-                    // to find its own: ~500 scalar instructions per wavefront and set.
-#define K1_OR_BIT(C) do { if ((C) >= 0) { const int32_t x_ = (C) - (int32_t)lo_id; K1_OR_AT(x_); } } while (0)
-#ifdef K1_DEBUG_NO_OR
-#define K1_OR_AT(X) do { if ((X) == 0x7fffffff) s_bm[0] = 1; } while (0)
-#else
-#define K1_OR_AT(X) __hip_atomic_fetch_or(&s_bm[(X) >> 5], 1u << ((X) & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)
-#endif
-#ifdef K1_DEBUG_NO_LOAD
-#define K1_COL(I) (int32_t)(((uint32_t)(I)) * 2654435761u % (uint32_t)max_id)
-#else
-#define K1_COL(I) col[(I)]
-#endif
-#ifdef K1_DEBUG_SKIP_CHUNKS
-                    if (false)
-#endif
-                    {
-                        uint64_t longs = __ballot(deg >= K1_LONG);
-                        while (longs) {                                               // scalar loop over the long lists
-                            const int m = __ffsll((long long)longs) - 1;
-                            longs &= longs - 1;
-                            const int32_t m_deg = __builtin_amdgcn_readlane(deg, m);
-                            const uint32_t m_r0 = (uint32_t)__builtin_amdgcn_readlane((int)r0, m);
-                            for (int32_t tb = wave_s * 64; tb < m_deg; tb += K1_INFLIGHT * NW * 64) {
-                                int32_t c[K1_INFLIGHT];
-#pragma unroll
-                                for (int u = 0; u < K1_INFLIGHT; ++u) {
-                                    const int32_t t = tb + u * NW * 64 + lane;
-                                    c[u] = t < m_deg ? K1_COL(m_r0 + (uint32_t)t) : -1;
-                                }
-#pragma unroll
-                                for (int u = 0; u < K1_INFLIGHT; ++u) K1_OR_BIT(c[u]);
-                            }
-                        }
-                        // (skipping the slots past a list's end with scalar tests, or unrolling the short lists exactly,
-                        // was slower: 1.48 -> 1.52-1.60 ms -- the branches cost more than the predicated-off instructions)
-                        for (int m = wave_s; m < 64 && t0 + m < n; m += NW) {          // this wavefront's short lists
-                            const int32_t m_deg = __builtin_amdgcn_readlane(deg, m);
-                            if (m_deg >= K1_LONG) continue;
-                            const uint32_t m_r0 = (uint32_t)__builtin_amdgcn_readlane((int)r0, m);
-                            for (int32_t tb = 0; tb < m_deg; tb += K1_INFLIGHT * 64) {
-                                int32_t c[K1_INFLIGHT];
-#pragma unroll
-                                for (int u = 0; u < K1_INFLIGHT; ++u) {
-                                    const int32_t t = tb + u * 64 + lane;
-                                    c[u] = t < m_deg ? K1_COL(m_r0 + (uint32_t)t) : -1;
-                                }
-#pragma unroll
-                                for (int u = 0; u < K1_INFLIGHT; ++u) K1_OR_BIT(c[u]);
-                            }
-                        }
-                    }
-#undef K1_OR_BIT
-#undef K1_OR_AT
-#undef K1_COL
+                    k1_expand_tile(col, s_bm, r0, deg, t0, n, lo_id, wave_s, lane);
                 }
                 K1_T(7);                                               // (debug) own chunks done
                 if (n == 0 && can_pf && lane < nx_end - nx_beg) nx_v = set_nodes[nx_beg + lane];    // (no tile ran step 1)
@@ -1521,26 +1556,12 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
                 // ---- the members themselves are not border ---------------------------------------------
                 // (two separate paths: with the load of the members beyond the first tile in the same loop, the wait for it sat on
                 // the common path -- and, the counter of outstanding loads being in-order, waited for the prefetch above as well)
-                if (tid < 64 && tid < n) {                                           // wavefront 0 still holds the first tile
-                    const int64_t v = (int64_t)v_tile0;
-                    if (v >= lo_id && v < hi_id) {
-                        const int32_t x = (int32_t)(v - lo_id);
-                        __hip_atomic_fetch_and(&s_bm[x >> 5], ~(1u << (x & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    }
-                }
-                if (n > 64) {
-                    for (int i = 64 + tid; i < n; i += K1_THREADS) {
-                        const int64_t v = (int64_t)set_nodes[beg + i];
-                        if (v >= lo_id && v < hi_id) {
-                            const int32_t x = (int32_t)(v - lo_id);
-                            __hip_atomic_fetch_and(&s_bm[x >> 5], ~(1u << (x & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        }
-                    }
-                }
+                if (tid < 64 && tid < n) k1_unset_bit(s_bm, (int64_t)v_tile0, lo_id, hi_id);      // wavefront 0 still holds the first tile
+                if (n > 64) k1_unset_members(s_bm, set_nodes, beg, 64, n, lo_id, hi_id, tid);     // (the test: as before the loop was shared)
                 k1_lds_barrier();
                 K1_T(2);                                           // members un-set
                 // ---- rank table: popcount of each thread's run of words, exclusive prefix ----------------
-                const int run = (int)(((words + K1_THREADS - 1) / K1_THREADS) | 1);     // odd: conflict-free strides
+                const int run = (int)(((words + K1_THREADS - 1) / K1_THREADS) | 1);     // k1_run(words), written out: see there
                 int c = 0;
                 {
                     // 32-bit indices and no bounds tests (the allocation is run x K1_THREADS words, zero beyond `words`):
@@ -1548,9 +1569,6 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
                     // groups have already counted are masked by loop-invariant scalars -- a read + a v_bcnt per word (the
                     // first version selected every index and every count with scalar compares: ~10 instructions per word)
                     const uint32_t* __restrict__ mine_ = s_bm + tid * run;
-#ifdef K1_DEBUG_SKIP_RANK
-                    if (false)
-#endif
                     if (run >= 8) {
                         for (int g = 0; g < (run >> 3); ++g) {
                             uint32_t x[8];
@@ -1578,12 +1596,9 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
                 // separate "totals known" from "global prefixes written"
                 const int inc = sgnn_wave_incl_scan(c);
                 s_pref[tid] = inc - c;
-                if (lane == 63) s_wtot[wave] = inc;
-                k1_lds_barrier();
-                const int wt = s_wtot[gl];                                        // NW = 16 totals, replicated in every row
-                const int wincl = sgnn_row_incl_scan(wt);
+                int wt, wincl;
+                const int total = k1_wave_totals(inc, s_wtot, wave, lane, gl, wt, wincl);
                 const int wexcl = wincl - wt;                                     // lane gl: ranks before wavefront gl's runs
-                const int total = __builtin_amdgcn_readlane(wincl, NW - 1);
                 if (SLICED && pass == 0) {
                     if (tid == 0) { if (sl == 0) s_cum[0] = 0; s_cum[sl + 1] = (sl == 0 ? 0 : s_cum[sl]) + total; }
                     k1_lds_barrier();                                             // (pass 1 reads s_cum)
@@ -1597,9 +1612,6 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
                     // Every lane of a group hashes its slot's tape draws itself (three 64-bit mixes: cheaper than a
                     // trip through LDS and a barrier), the searches' prefix sums run on the DPP path inside the row,
                     // and the lane that holds the answer writes it.
-#ifdef K1_DEBUG_SKIP_DRAW
-                    if (false)
-#endif
                     for (int64_t c0 = 0; c0 < smp.n_slots; c0 += K1_THREADS / 16) {
                         if (c0 + wave_s * 4 >= smp.n_slots) continue;                // none of this wavefront's four slots exists
                         const int64_t slot = c0 + grp;
@@ -1665,13 +1677,7 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
                 // ---- wipe for the next slice / set ------------------------------------------------------
                 k1_lds_barrier();
                 K1_T(4);                                           // draw
-#ifndef K1_DEBUG_SKIP_WIPE
-                {
-                    int4* bm4 = reinterpret_cast<int4*>(s_bm);
-                    const int n4 = (int)((words + 3) / 4);
-                    for (int i = tid; i < n4; i += K1_THREADS) bm4[i] = make_int4(0, 0, 0, 0);
-                }
-#endif
+                k1_zero_fill(s_bm, (int)((words + 3) / 4), tid);
                 k1_lds_barrier();
                 K1_T(5);                                           // wipe
             }
@@ -1679,10 +1685,6 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_sample_kernel(
     }
 }
 
-// The rank pass gives every thread a run of `run` words (odd: conflict-free strides) and reads them without bounds tests,
-// so the bitmap is allocated as run x K1_THREADS words (the padding is never set and stays zero).
-static inline int64_t k1_run(int64_t words) { return ((words + K1_THREADS - 1) / K1_THREADS) | 1; }
-static inline int64_t k1_alloc_bytes(int64_t slice_ids) { return k1_run((slice_ids + 31) / 32) * K1_THREADS * 4; }
 #define K1_LDS_MAX (155 * 1024)          // dynamic LDS the kernel may take (4.2 KB of static tables on top: 160 KB per CU)
 
 static int k1_plan(int64_t max_id, int64_t lds_budget, int64_t* slice_ids, int* n_slices)
@@ -1747,6 +1749,30 @@ extern "C" int sgnn_khop_sample_finish(int64_t* anchor, const uint8_t* hop, cons
     return SGNN_OK;
 }
 
+// The launch recipe of the two one-hop kernels (whole / sliced: the kernel's <false> / <true> instantiation): the set counter
+// in the last 8-byte aligned 8 bytes of the workspace, zeroed on the stream; the opt-in to K1_LDS_MAX of dynamic LDS (once per
+// kernel: attr_set is one flag per instantiation of this template); the general LDS kernel's grid; the padded bitmap.
+// launch(kernel, col, n_slices, grid, lds, next_set) issues the caller's kernel with its own argument list.
+template <typename Kernel, typename Launch>
+static int k1_launch(Kernel whole, Kernel sliced, const int32_t* col, const int32_t* col_sorted, int64_t n_sets,
+                     int64_t slice_ids, int n_slices, void* workspace, int64_t workspace_bytes, hipStream_t st, Launch launch)
+{
+    unsigned long long* next_set = (unsigned long long*)((char*)workspace + ((workspace_bytes - 8) & ~(int64_t)7));
+    { const hipError_t me = hipMemsetAsync(next_set, 0, 8, st); if (me != hipSuccess) { sgnn_set_last_error(me); return SGNN_ERR_LAUNCH; } }
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)whole, hipFuncAttributeMaxDynamicSharedMemorySize, K1_LDS_MAX);
+        (void)hipFuncSetAttribute((const void*)sliced, hipFuncAttributeMaxDynamicSharedMemorySize, K1_LDS_MAX);
+        attr_set = true;
+    }
+    const dim3 grid((int)kb_n_wg(n_sets, true));
+    const size_t lds = (size_t)k1_alloc_bytes(slice_ids);
+    if (n_slices == 1) launch(whole, col, 1, grid, lds, next_set);
+    else launch(sliced, col_sorted, n_slices, grid, lds, next_set);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
 extern "C" int sgnn_khop_border_sample(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
                                        int64_t max_id,
                                        const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, int k,
@@ -1767,25 +1793,12 @@ extern "C" int sgnn_khop_border_sample(const int64_t* rowptr, const int32_t* col
             if (workspace_bytes < 16) return SGNN_ERR_BAD_ARG;
             if (n_sets == 0) return SGNN_OK;
             hipStream_t st = (hipStream_t)stream;
-            // the set counter: the last 8-byte aligned 8 bytes of the workspace
-            unsigned long long* next_set = (unsigned long long*)((char*)workspace + ((workspace_bytes - 8) & ~(int64_t)7));
-            { const hipError_t me = hipMemsetAsync(next_set, 0, 8, st); if (me != hipSuccess) { sgnn_set_last_error(me); return SGNN_ERR_LAUNCH; } }
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute((const void*)khop1_sample_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, K1_LDS_MAX);
-                (void)hipFuncSetAttribute((const void*)khop1_sample_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, K1_LDS_MAX);
-                attr_set = true;
-            }
-            const int64_t nwg = kb_n_wg(n_sets, true);
-            const size_t lds = (size_t)k1_alloc_bytes(slice_ids);
-            if (n_slices == 1)
-                hipLaunchKernelGGL(khop1_sample_kernel<false>, dim3((int)nwg), dim3(K1_THREADS), lds, st, rowptr, col, max_id,
-                                   set_ptr, set_nodes, n_sets, out_count, smp, slice_ids, 1, next_set, set_order);
-            else
-                hipLaunchKernelGGL(khop1_sample_kernel<true>, dim3((int)nwg), dim3(K1_THREADS), lds, st, rowptr, col_sorted, max_id,
-                                   set_ptr, set_nodes, n_sets, out_count, smp, slice_ids, n_slices, next_set, set_order);
-            SGNN_CHECK_LAUNCH();
-            return SGNN_OK;
+            return k1_launch(khop1_sample_kernel<false>, khop1_sample_kernel<true>, col, col_sorted, n_sets, slice_ids,
+                             n_slices, workspace, workspace_bytes, st,
+                             [&](auto kernel, const int32_t* c, int ns, dim3 grid, size_t lds, unsigned long long* next_set) {
+                                 hipLaunchKernelGGL(kernel, grid, dim3(K1_THREADS), lds, st, rowptr, c, max_id, set_ptr, set_nodes,
+                                                    n_sets, out_count, smp, slice_ids, ns, next_set, set_order);
+                             });
         }
     }
     bitmap_in_lds = bitmap_in_lds && kb_fits_lds(max_id) ? 1 : 0;      // general kernel; beyond the LDS bitmap: bitmap in L2
@@ -1797,9 +1810,9 @@ extern "C" int sgnn_khop_border_sample(const int64_t* rowptr, const int32_t* col
 // The one-hop border WRITTEN, in ascending id order: what khop1_sample_kernel rebuilds in LDS for every draw depends on
 // the sets and the graph only, so a caller whose sets stay the same builds it once (count launch, prefix sum, write launch)
 // and draws from the kept ids afterwards (sgnn_sample_border_anchors) -- the draw's rank query becomes one indexed read.
-// Same workgroup shape, set counter, expansion, member un-set, rank pass and wipe as khop1_sample_kernel, in a copy of
-// its own (that kernel's register allocation is tuned statement by statement); it runs once per split, so it carries none
-// of the cross-set prefetching.  Where the sample kernel answers slots from the rank table, thread tid walks its run of
+// Shared with khop1_sample_kernel (the k1_* functions above it): the set counter, the row ranges, the expansion, the member
+// un-set, the wavefront totals and the wipe; it runs once per split, so it carries none of the cross-set prefetching and
+// counts its run of words in a plain loop.  Its own: where the sample kernel answers slots from the rank table, thread tid walks its run of
 // words [tid*run, tid*run+run) and stores the id of every set bit behind its exclusive rank: ranks follow word order, word
 // order is id order, so the border comes out sorted.  SLICED: one pass over the slices in either mode -- slices ascend,
 // a slice's ids go behind the total of the slices before it.
@@ -1816,22 +1829,15 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_border_write_kernel(
     __shared__ long long s_next;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wave_s = __builtin_amdgcn_readfirstlane(tid >> 6);
-    constexpr int NW = K1_THREADS / 64;
     const int gl = tid & 15;
-    const int words_alloc = (int)((((slice_ids + 31) / 32 + K1_THREADS - 1) / K1_THREADS) | 1) * K1_THREADS;   // host: k1_alloc_bytes
-    {
-        int4* bm4 = reinterpret_cast<int4*>(s_bm);
-        for (int i = tid; i < words_alloc / 4; i += K1_THREADS) bm4[i] = make_int4(0, 0, 0, 0);
-    }
+    const int words_alloc = (int)(k1_alloc_bytes(slice_ids) / 4);
+    k1_zero_fill(s_bm, words_alloc / 4, tid);
     __syncthreads();
     int64_t si_next = 0, si_end = 0;
     while (true) {
         if (si_next >= si_end) {
-            if (tid == 0) s_next = (long long)atomicAdd(next_set, (unsigned long long)K1_TAKE);
-            __syncthreads();
-            si_next = s_next;
+            si_next = k1_take_sets(next_set, &s_next, tid);
             si_end = si_next + K1_TAKE;
-            __syncthreads();
         }
         const int64_t s = si_next++;
         if (s >= n_sets) break;
@@ -1847,80 +1853,22 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_border_write_kernel(
             for (int t0 = 0; t0 < n; t0 += 64) {
                 uint32_t r0 = 0;
                 int32_t deg = 0;
-                if (t0 + lane < n) {
-                    const int32_t v = set_nodes[beg + t0 + lane];
-                    int64_t a = rowptr[v], b = rowptr[v + 1];
-                    if (SLICED) {                              // rows ascending: the list's part inside [lo_id, hi_id)
-                        int64_t l = a, h = b;
-                        while (l < h) { const int64_t m = (l + h) >> 1; if ((int64_t)col[m] < lo_id) l = m + 1; else h = m; }
-                        const int64_t first = l;
-                        h = b;
-                        while (l < h) { const int64_t m = (l + h) >> 1; if ((int64_t)col[m] < hi_id) l = m + 1; else h = m; }
-                        a = first; b = l;
-                    }
-                    r0 = (uint32_t)a;
-                    deg = (int32_t)(b - a);
-                }
-                // a list of >= K1_LONG entries is shared by all wavefronts in 64-entry chunks, a shorter one belongs whole
-                // to wavefront (member index) % 16
-#define K1W_OR_BIT(C) do { if ((C) >= 0) { const int32_t x_ = (C) - (int32_t)lo_id; \
-        __hip_atomic_fetch_or(&s_bm[x_ >> 5], 1u << (x_ & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); } } while (0)
-                uint64_t longs = __ballot(deg >= K1_LONG);
-                while (longs) {
-                    const int m = __ffsll((long long)longs) - 1;
-                    longs &= longs - 1;
-                    const int32_t m_deg = __builtin_amdgcn_readlane(deg, m);
-                    const uint32_t m_r0 = (uint32_t)__builtin_amdgcn_readlane((int)r0, m);
-                    for (int32_t tb = wave_s * 64; tb < m_deg; tb += K1_INFLIGHT * NW * 64) {
-                        int32_t c[K1_INFLIGHT];
-#pragma unroll
-                        for (int u = 0; u < K1_INFLIGHT; ++u) {
-                            const int32_t t = tb + u * NW * 64 + lane;
-                            c[u] = t < m_deg ? col[m_r0 + (uint32_t)t] : -1;
-                        }
-#pragma unroll
-                        for (int u = 0; u < K1_INFLIGHT; ++u) K1W_OR_BIT(c[u]);
-                    }
-                }
-                for (int m = wave_s; m < 64 && t0 + m < n; m += NW) {
-                    const int32_t m_deg = __builtin_amdgcn_readlane(deg, m);
-                    if (m_deg >= K1_LONG) continue;
-                    const uint32_t m_r0 = (uint32_t)__builtin_amdgcn_readlane((int)r0, m);
-                    for (int32_t tb = 0; tb < m_deg; tb += K1_INFLIGHT * 64) {
-                        int32_t c[K1_INFLIGHT];
-#pragma unroll
-                        for (int u = 0; u < K1_INFLIGHT; ++u) {
-                            const int32_t t = tb + u * 64 + lane;
-                            c[u] = t < m_deg ? col[m_r0 + (uint32_t)t] : -1;
-                        }
-#pragma unroll
-                        for (int u = 0; u < K1_INFLIGHT; ++u) K1W_OR_BIT(c[u]);
-                    }
-                }
-#undef K1W_OR_BIT
+                if (t0 + lane < n) k1_row_range<SLICED>(rowptr, col, set_nodes[beg + t0 + lane], lo_id, hi_id, r0, deg);
+                k1_expand_tile(col, s_bm, r0, deg, t0, n, lo_id, wave_s, lane);
             }
             k1_lds_barrier();
             // ---- the members themselves are not border ---------------------------------------------
-            for (int i = tid; i < n; i += K1_THREADS) {
-                const int64_t v = (int64_t)set_nodes[beg + i];
-                if (v >= lo_id && v < hi_id) {
-                    const int32_t x = (int32_t)(v - lo_id);
-                    __hip_atomic_fetch_and(&s_bm[x >> 5], ~(1u << (x & 31)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-            }
+            k1_unset_members(s_bm, set_nodes, beg, 0, n, lo_id, hi_id, tid);
             k1_lds_barrier();
             // ---- rank pass: popcount of each thread's run of words, exclusive prefix -----------------
             // (the allocation is run x K1_THREADS words, zero beyond `words`: no bounds tests)
-            const int run = (int)(((words + K1_THREADS - 1) / K1_THREADS) | 1);
+            const int run = (int)k1_run(words);
             const uint32_t* __restrict__ mine_ = s_bm + tid * run;
             int c = 0;
             for (int u = 0; u < run; ++u) c += __popc(mine_[u]);
             const int inc = sgnn_wave_incl_scan(c);
-            if (lane == 63) s_wtot[wave] = inc;
-            k1_lds_barrier();
-            const int wt = s_wtot[gl];                                        // NW = 16 totals, replicated in every row
-            const int wincl = sgnn_row_incl_scan(wt);
-            const int total = __builtin_amdgcn_readlane(wincl, NW - 1);
+            int wt, wincl;
+            const int total = k1_wave_totals(inc, s_wtot, wave, lane, gl, wt, wincl);
             if (out_ids) {
                 // ---- the write: this thread's bits, in word order, behind its exclusive rank ---------
                 int64_t pos = w_beg + before + __builtin_amdgcn_readlane(wincl - wt, wave_s) + (inc - c);
@@ -1939,11 +1887,7 @@ __global__ __launch_bounds__(K1_THREADS) void khop1_border_write_kernel(
             before += total;
             // ---- wipe for the next slice / set ------------------------------------------------------
             k1_lds_barrier();
-            {
-                int4* bm4 = reinterpret_cast<int4*>(s_bm);
-                const int n4 = (int)((words + 3) / 4);
-                for (int i = tid; i < n4; i += K1_THREADS) bm4[i] = make_int4(0, 0, 0, 0);
-            }
+            k1_zero_fill(s_bm, (int)((words + 3) / 4), tid);
             k1_lds_barrier();
         }
         if (tid == 0 && out_count) out_count[s] = before;
@@ -1966,24 +1910,12 @@ extern "C" int sgnn_khop1_border_sorted(const int64_t* rowptr, const int32_t* co
     if (!k1_applies(max_id, 1, col_sorted != nullptr, bitmap_in_lds, &slice_ids, &n_slices)) return SGNN_ERR_SET_TOO_LARGE;
     if (n_sets == 0) return SGNN_OK;
     hipStream_t st = (hipStream_t)stream;
-    unsigned long long* next_set = (unsigned long long*)((char*)workspace + ((workspace_bytes - 8) & ~(int64_t)7));
-    { const hipError_t me = hipMemsetAsync(next_set, 0, 8, st); if (me != hipSuccess) { sgnn_set_last_error(me); return SGNN_ERR_LAUNCH; } }
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)khop1_border_write_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, K1_LDS_MAX);
-        (void)hipFuncSetAttribute((const void*)khop1_border_write_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, K1_LDS_MAX);
-        attr_set = true;
-    }
-    const int64_t nwg = kb_n_wg(n_sets, true);
-    const size_t lds = (size_t)k1_alloc_bytes(slice_ids);
-    if (n_slices == 1)
-        hipLaunchKernelGGL(khop1_border_write_kernel<false>, dim3((int)nwg), dim3(K1_THREADS), lds, st, rowptr, col, max_id,
-                           set_ptr, set_nodes, n_sets, out_count, out_ptr, out_ids, slice_ids, 1, next_set);
-    else
-        hipLaunchKernelGGL(khop1_border_write_kernel<true>, dim3((int)nwg), dim3(K1_THREADS), lds, st, rowptr, col_sorted, max_id,
-                           set_ptr, set_nodes, n_sets, out_count, out_ptr, out_ids, slice_ids, n_slices, next_set);
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
+    return k1_launch(khop1_border_write_kernel<false>, khop1_border_write_kernel<true>, col, col_sorted, n_sets, slice_ids,
+                     n_slices, workspace, workspace_bytes, st,
+                     [&](auto kernel, const int32_t* c, int ns, dim3 grid, size_t lds, unsigned long long* next_set) {
+                         hipLaunchKernelGGL(kernel, grid, dim3(K1_THREADS), lds, st, rowptr, c, max_id, set_ptr, set_nodes, n_sets,
+                                            out_count, out_ptr, out_ids, slice_ids, ns, next_set);
+                     });
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -614,6 +614,10 @@ def khop_border_one_pass(g, sets, bitmap_in_lds=None):
     return arena, off, counts
 
 
+def _k1_mode(bitmap_in_lds):
+    return 1 if bitmap_in_lds is None else (int(bitmap_in_lds) if not isinstance(bitmap_in_lds, bool) else (1 if bitmap_in_lds else 0))
+
+
 def khop_border_sample(g, sets, k, n_slots, seed, stream_id, bitmap_in_lds=None, order=None, item_base=0,
                        count_reduce=None, width=None):
     """k-hop border BFS + neighbourhood-border anchor draw without a padded border matrix.  Returns
@@ -623,7 +627,7 @@ def khop_border_sample(g, sets, k, n_slots, seed, stream_id, bitmap_in_lds=None,
     ``bitmap_in_lds``: None = LDS (id ranges beyond the LDS bitmap are processed in slices when k = 1, else
     the bitmap moves to the workspace); False = workspace; an int > 1 = LDS bytes the bitmap may take."""
     lib = _lib.load()
-    mode = 1 if bitmap_in_lds is None else (int(bitmap_in_lds) if not isinstance(bitmap_in_lds, bool) else (1 if bitmap_in_lds else 0))
+    mode = _k1_mode(bitmap_in_lds)
     ws_bytes = lib.sgnn_khop_border_sample_workspace_bytes(g.max_id, sets.n, k, 1, mode)
     if ws_bytes <= 16:
         ws = _KHOP_WS.get(('k1', str(g.device)))
@@ -654,10 +658,6 @@ def khop_border_sample(g, sets, k, n_slots, seed, stream_id, bitmap_in_lds=None,
     check(lib.sgnn_khop_sample_finish(_ptr(anchor), _ptr(hop), _ptr(allneg), _ptr(counts), _ptr(width.to(torch.int64)), sets.n, n_slots,
                                       _ptr(sims), _stream()), 'sgnn_khop_sample_finish')
     return anchor, sims, counts
-
-
-def _k1_mode(bitmap_in_lds):
-    return 1 if bitmap_in_lds is None else (int(bitmap_in_lds) if not isinstance(bitmap_in_lds, bool) else (1 if bitmap_in_lds else 0))
 
 
 def khop1_applies(g, n_sets, bitmap_in_lds=None):

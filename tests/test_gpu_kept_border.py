@@ -106,6 +106,92 @@ def test_pad_rule_edges_on_stars():
     assert (an[3] == 0).any()                                              # one leaf: PAD wins half the slots
 
 
+_LONG_LEAVES = (511, 512, 513, 4200)
+_long_cache = []
+
+
+def _long_list_case():
+    """Host CSR (rows ascending), the sets and their numpy borders for test_long_lists_set_sizes_and_order; built once."""
+    if _long_cache:
+        return _long_cache[0]
+    n = 8000
+    adj = [[] for _ in range(n + 1)]
+
+    def edge(u, v):
+        adj[u].append(v)
+        adj[v].append(u)
+
+    centres, nxt = [], 1
+    for k in _LONG_LEAVES:                              # stars on consecutive ids: centre, then its leaves
+        centres.append(nxt)
+        for v in range(nxt + 1, nxt + 1 + k):
+            edge(nxt, v)
+        nxt += 1 + k
+    ring0 = nxt                                         # the other ids: a ring with a chord from every seventh node
+    for v in range(ring0, n + 1):
+        edge(v, v + 1 if v < n else ring0)
+    for v in range(ring0, n - 400, 7):
+        edge(v, v + 400)
+    rowptr = np.zeros(n + 2, dtype=np.int64)
+    for v in range(n + 1):
+        rowptr[v + 1] = rowptr[v] + len(adj[v])
+    col = np.asarray([u for v in range(n + 1) for u in sorted(adj[v])], dtype=np.int32)
+    sets = [list(range(ring0, ring0 + 60)) + [c + 1 for c in centres],       # 64 members: one tile exactly; four leaves
+            list(range(ring0 + 100, ring0 + 230, 2)),                        # 65 members: a second tile of one
+            []]
+    sets += [[c] for c in centres]
+    sets += [[centres[2], centres[3]]]                                       # two long lists in one tile
+    sets += [[v] for v in range(ring0 + 300, ring0 + 313)]                   # one-node sets
+    borders = []
+    for m in sets:
+        members = np.asarray(m, dtype=np.int32)
+        nb = np.concatenate([col[rowptr[v]:rowptr[v + 1]] for v in m]) if m else np.zeros(0, np.int32)
+        borders.append(np.setdiff1d(np.unique(nb), members))
+    _long_cache.append((rowptr, col, centres, sets, borders))
+    return _long_cache[0]
+
+
+@pytest.mark.parametrize('lds', [None, 256])          # 256 bytes of bitmap: 2048 ids per slice, so the 4200 leaves are a list of
+def test_long_lists_set_sizes_and_order(lds):         # at least K1_LONG entries inside a slice too
+    """List lengths at the edge of K1_LONG = 512 (511, 512, 513: the first belongs to one wavefront, the others are shared by
+    all) and one of 4200 entries, more than one round of the long-list loop covers (K1_INFLIGHT * 16 * 64 = 4096); sets of 64
+    and 65 members (one tile exactly, a second tile of one), an empty set, two long lists in one set; a set count that is
+    no multiple of the K1_TAKE = 8 sets a workgroup takes per trip; the order= argument.  The borders are checked against
+    numpy on the host CSR, the anchors against the tape's law on those borders."""
+    ops = _ops()
+    rowptr, col, centres, sets, borders = _long_list_case()
+    # the case is what it is meant to be
+    assert [int(rowptr[c + 1] - rowptr[c]) for c in centres] == list(_LONG_LEAVES)
+    assert all(np.all(np.diff(col[rowptr[v]:rowptr[v + 1]]) > 0) for v in range(len(rowptr) - 1))
+    assert [len(m) for m in sets[:3]] == [64, 65, 0] and sets[3:7] == [[c] for c in centres] and len(sets[7]) == 2
+    assert len(sets) % 8 != 0 and all(len(m) == 1 for m in sets[8:])
+    assert [len(b) for b in borders[3:8]] == list(_LONG_LEAVES) + [513 + 4200]
+    assert len(rowptr) - 2 == 8000
+
+    n = len(rowptr) - 2
+    dg = ops.DeviceGraph(rowptr, col, np.arange(1, n + 1, dtype=np.int32), DEV)
+    r = ops.Ragged.from_lists(sets, DEV)
+    kept = ops.khop1_borders_sorted(dg, r, bitmap_in_lds=lds)
+    ptr, ids = kept.ptr.cpu().numpy(), kept.ids.cpu().numpy()
+    assert kept.counts.tolist() == [len(b) for b in borders]
+    for i, b in enumerate(borders):
+        assert ptr[i + 1] - ptr[i] == len(b) and np.array_equal(ids[ptr[i]:ptr[i + 1]], b), i
+
+    A, seed, st = 70, 13, T.stream_id(T.STREAM_N_BOR, 'train', 0)            # more than 64 slots
+    anchors, sims, counts = ops.khop_border_sample(dg, r, 1, A, seed, st, bitmap_in_lds=lds)
+    assert counts.tolist() == [len(b) for b in borders]
+    an, mx = anchors.cpu().numpy(), max(len(b) for b in borders)
+    for i, b in enumerate(borders):
+        for s in range(A):
+            kk = T.nanchor_pick(seed, st, i * A + s, len(b), len(b) < mx)
+            assert an[i, s] == (0 if kk < 0 else b[kk]), (i, s)
+    a, w, c = ops.draw_border_anchors(kept, A, seed, st)
+    assert torch.equal(a, anchors) and torch.equal(w, sims) and torch.equal(c, counts)
+    perm = torch.from_numpy(np.random.default_rng(8).permutation(len(sets)).astype(np.int32)).to(DEV)
+    a, w, c = ops.khop_border_sample(dg, r, 1, A, seed, st, bitmap_in_lds=lds, order=perm)
+    assert torch.equal(a, anchors) and torch.equal(w, sims) and torch.equal(c, counts)
+
+
 # ---- pass level ---------------------------------------------------------------------------
 
 def _same(x, y, where=''):

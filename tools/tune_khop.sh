@@ -1,6 +1,6 @@
 #!/bin/bash
 # Rebuild graph_sets.hip with different border-BFS settings and time the border stage (tools/khop_probe.py).
-#   bash tools/tune_khop.sh "-DK1_DEBUG_SKIP_DRAW" ...     (K1_DEBUG_* switches compile parts out: timing only, wrong results)
+#   bash tools/tune_khop.sh "-DK1_TAKE=4" "-DK1_LONG=256" ...     (the tunables: K1_INFLIGHT, K1_LONG, K1_TAKE, KB_TAKE)
 for flags in "" "$@"; do
   touch subgnn_amd/csrc/graph_sets.hip
   SGNN_HIPCC_FLAGS="$flags" python -m subgnn_amd.build > /dev/null 2>&1
