@@ -403,6 +403,24 @@ int sgnn_bfs_min_hops_to_sets(const int64_t* rowptr, const int32_t* col, int64_t
                               const int32_t* sources, int64_t n_sources, int max_hops, int pull_alpha, int push_levels,
                               const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets,
                               float* out, int32_t* out_status, void* workspace, int64_t workspace_bytes, void* stream);
+/* labels[v] = the smallest node id of v's connected component, for every id 0..max_id (int32; ids without edges, the pad
+ * id 0 among them, label themselves).  The CSR is taken as undirected.  Synchronises the stream (one word is read back per
+ * round): meant to run once per graph, outside any capture. */
+int64_t sgnn_graph_component_labels_workspace_bytes(int64_t max_id);
+int sgnn_graph_component_labels(const int64_t* rowptr, const int32_t* col, int64_t nnz, int64_t max_id,
+                                int32_t* labels, void* workspace, int64_t workspace_bytes, void* stream);
+/* sgnn_bfs_min_hops_to_sets that stops once every set has its hops.  On a symmetric CSR a source reaches a member iff both
+ * carry the same component label (labels: sgnn_graph_component_labels), so the pairs that will ever hold a level are known
+ * up front; when all of them are recorded the search is closed and every later launch returns at once.
+ * Values: those of sgnn_bfs_min_hops_to_sets bit for bit whenever out_status[1] == 0.  out_status: [0] = the closing level,
+ * else the last level that found anything; [1] = 1 only if the enqueued levels ran out before the search closed and before
+ * the frontier died; [2], [3] as above. */
+int64_t sgnn_bfs_min_hops_closing_workspace_bytes(int64_t max_id, int64_t n_sources, int max_hops, int64_t n_sets);
+int sgnn_bfs_min_hops_to_sets_closing(const int64_t* rowptr, const int32_t* col, int64_t nnz, int64_t max_id,
+                                      const int32_t* sources, int64_t n_sources, int max_hops, int pull_alpha, int push_levels,
+                                      const int32_t* labels, const int64_t* set_ptr, const int32_t* set_nodes,
+                                      int64_t n_sets, float* out, int32_t* out_status, void* workspace, int64_t workspace_bytes,
+                                      void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * a11  Structure similarity: 1 / (1 + fastdtw(x, y, radius=1, dist=calc_dist)).

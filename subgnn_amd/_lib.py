@@ -79,6 +79,11 @@ SIGNATURES = {
     'sgnn_bfs_min_hops_workspace_bytes': (c_i64, [c_i64, c_i64, c_int, c_i64]),
     'sgnn_bfs_min_hops_to_sets': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr,
                                           c_ptr, c_i64, c_ptr]),
+    'sgnn_graph_component_labels_workspace_bytes': (c_i64, [c_i64]),
+    'sgnn_graph_component_labels': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr]),
+    'sgnn_bfs_min_hops_closing_workspace_bytes': (c_i64, [c_i64, c_i64, c_int, c_i64]),
+    'sgnn_bfs_min_hops_to_sets_closing': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr,
+                                                  c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_bfs_hops': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_int, c_int, c_int, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_min_hops_to_sets': (c_int, [c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     'sgnn_dtw_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i64]),

@@ -81,6 +81,9 @@ extern "C" int sgnn_sp_similarity_dense(const double* apsp, int64_t n_cols,
 //     (32 MB): level 1 of the benchmark's search went from 55 us to the time of its 183 lists.
 //   * host side: a commit launch is enqueued only for the first ``push_levels`` levels (the caller's hint, from the status of
 //     an earlier search: [2] = the level that switched to pull); beyond them the device pulls whatever the frontier's size.
+// The CLOSING form of the set search (sgnn_bfs_min_hops_to_sets_closing; "the closing form" below, in front of msbfs_run) runs
+// the same levels over the same buffers but stops once every set has its hops: the reduction is a launch behind its level
+// and nothing is finalised from the seen rows.
 // ---------------------------------------------------------------------------------------------
 // Row stride (in 64-bit words) of the per-node arrays seen / frontier / next: three words (129-192 sources, the benchmark's
 // 183) are padded to four -- a pull level gathers one row per neighbour, and a 24-byte row straddles two 32-byte sectors
@@ -684,11 +687,136 @@ __global__ void msbfs_status_kernel(const int32_t* __restrict__ flags, int max_h
     if (threadIdx.x == 0 && blockIdx.x == 0) msbfs_write_status(flags, fvol, pull_above, push_levels, max_hops, status);
 }
 
+// ---- the closing form of the set search ------------------------------------------------------------------------------------
+// What is read from a set search is, per (set, source), the level at which the first member was reached -- final long before
+// the last node of the graph has been.  On a symmetric CSR "source s never reaches member v" is a property of the graph (they
+// lie in different connected components: sgnn_graph_component_labels), so the pairs that will ever hold a level are known
+// before the first level runs: per (set, word) the WANTED sources are those whose label is the common label of the set's
+// members (members of more than one component, or none: nothing is wanted, the row stays 0).  The search is CLOSED once every
+// wanted pair is recorded, and nothing after that can change the result.  Protocol (msbfs_run with ``labels``):
+//   * the set reduction is a launch of its own BEHIND its level (not the next launch's prologue: closure would be noticed a
+//     level late): it records only wanted bits and says whether any item is still open.  Its last workgroup (a ticket) closes the search when
+//     no item was open: closed[0] = level + 1 and flags[level] = 0 -- every later launch of the search, commits and push levels
+//     included, then returns at the test of flags[level - 1] that ends a search whose frontier died (one exception: a search
+//     closed by the SEEDS' reduction -- nothing wanted, or every wanted source a member -- still runs level 1's expand launch,
+//     which does not test flags[0]; its commit returns and nothing reads what it pushed).
+//   * a level is the level launch (without its prologue), its commit launch if it lies at or below push_levels, and the
+//     reduction.
+//   * no finalisation over the seen rows (stale after a closure): unwanted pairs were never written.
+struct MsbfsClosing {
+    const int32_t* labels;       // component label per node id
+    const int32_t* sources;
+    uint64_t* wanted;            // per (set, word)
+    uint32_t* open;              // per level: some item still misses a wanted bit after the level's reduction
+    uint32_t* ticket;            // per level: workgroups of the reduction that are through
+    uint32_t* closed;            // [0] = closing level + 1 (0: open)
+};
+
+#define MSBFS_CLOSING_LDS_SOURCES 1024
+
+__global__ __launch_bounds__(256) void msbfs_closing_reduce_kernel(
+    MsbfsBufs B, int64_t n_words, int64_t n_sources, int64_t rs, MsbfsSets sets, MsbfsClosing c, int32_t* __restrict__ flags,
+    const unsigned long long* __restrict__ fvol, unsigned long long pull_above, int push_levels, int level)
+{
+    if (level > 0 && flags[level - 1] == 0) return;          // the level did not run (frontier dead, or closed)
+    __shared__ int32_t s_lab[MSBFS_CLOSING_LDS_SOURCES];
+    const bool lds = n_sources <= MSBFS_CLOSING_LDS_SOURCES;
+    const uint64_t* cur = B.b[2];                            // seeds / a push level: the commit left the new bits here
+    const uint64_t* old = nullptr;
+    if (level > 0) {
+        bool pull, prev_pull;
+        int k;
+        msbfs_mode(fvol, pull_above, push_levels, level, pull, prev_pull, k);
+        if (pull) { cur = B.b[(k + 1) % 3]; old = B.b[k % 3]; }      // pull number k wrote B[(k + 1) % 3] from B[k % 3]
+    } else if (lds) {
+        for (int64_t i = threadIdx.x; i < n_sources; i += blockDim.x) s_lab[i] = c.labels[c.sources[i]];
+        __syncthreads();
+    }
+    bool open = false;
+    const int64_t total = sets.n_sets * n_words;
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = t / n_words, w = t % n_words;
+        const int64_t beg = sets.set_ptr[r], end = sets.set_ptr[r + 1];
+        uint64_t want = 0;
+        if (level == 0) {
+            bool one = end > beg;
+            int32_t common = -1;
+            for (int64_t i = beg; i < end; ++i) {
+                const int32_t lab = c.labels[sets.set_nodes[i]];
+                if (i == beg) common = lab; else if (lab != common) one = false;
+            }
+            if (one)
+                for (int b = 0; b < 64 && w * 64 + b < n_sources; ++b) {
+                    const int64_t s = w * 64 + b;
+                    if ((lds ? s_lab[s] : c.labels[c.sources[s]]) == common) want |= 1ull << b;
+                }
+            c.wanted[t] = want;
+        } else
+            want = c.wanted[t];
+        const uint64_t have = sets.set_seen[t];
+        if ((want & ~have) == 0) continue;                   // nothing (left) to record
+        uint64_t acc = 0;
+        for (int64_t i = beg; i < end; ++i) {
+            const int64_t o = (int64_t)sets.set_nodes[i] * rs + w;
+            acc |= old ? (cur[o] & ~old[o]) : cur[o];
+        }
+        const uint64_t fresh = acc & want & ~have;
+        if (fresh) {
+            sets.set_seen[t] = have | fresh;
+            uint64_t bits = fresh;
+            while (bits) {
+                const int b = __ffsll((unsigned long long)bits) - 1;
+                bits &= bits - 1;
+                sets.out[r * n_sources + w * 64 + b] = (float)level;      // (wanted bits are below n_sources)
+            }
+        }
+        if (want & ~(have | fresh)) open = true;
+    }
+    if (__syncthreads_or(open ? 1 : 0) && threadIdx.x == 0) atomicOr(&c.open[level], 1u);
+    if (threadIdx.x == 0) {
+        __threadfence();
+        if (atomicAdd(&c.ticket[level], 1u) == gridDim.x - 1) {      // the last workgroup: every other one's verdict is in
+            __threadfence();
+            if (__hip_atomic_load(&c.open[level], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) == 0) {
+                c.closed[0] = (uint32_t)level + 1;
+                flags[level] = 0;
+            }
+        }
+    }
+}
+
+// the closing search's status: [0] the closing level, else the last level that found anything; [1] the enqueued levels ran
+// out before the search closed and before the frontier died; [2] the first level that pulled among the levels that ran
+__global__ void msbfs_closing_status_kernel(const int32_t* __restrict__ flags, const unsigned long long* __restrict__ fvol,
+                                            unsigned long long pull_above, int push_levels, int max_hops,
+                                            const uint32_t* __restrict__ closed, int32_t* __restrict__ status)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const int c = (int)closed[0];
+    int last = c ? c - 1 : 0;
+    if (!c) for (int l = 1; l <= max_hops; ++l) if (flags[l]) last = l;
+    status[0] = last;
+    status[1] = !c && flags[max_hops] != 0;
+    int first_pull = 0;
+    for (int l = 2; l <= (c ? last : last + 1) && l <= max_hops && first_pull == 0; ++l) {
+        bool pull, prev_pull;
+        int k;
+        msbfs_mode(fvol, pull_above, push_levels, l, pull, prev_pull, k);
+        if (pull) first_pull = l;
+    }
+    status[2] = first_pull;
+    status[3] = 0;
+}
+
+static inline int64_t msbfs_closing_state_words(int max_hops) { return (2 * ((int64_t)max_hops + 2) + 2 + 1) / 2; }   // 64-bit words
+
 static int msbfs_run(const int64_t* rowptr, const int32_t* col, int64_t nnz, int64_t max_id,
                      const int32_t* sources, int64_t n_sources, int max_hops, int node_major, uint8_t* dist,
                      const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, float* set_out,
-                     void* workspace, hipStream_t st, int pull_alpha, int32_t* status = nullptr, int push_levels = -1)
+                     void* workspace, hipStream_t st, int pull_alpha, int32_t* status = nullptr, int push_levels = -1,
+                     const int32_t* labels = nullptr)
 {
+    // labels: the closing form (above; sets only)
     // push_levels: levels that may still push (a commit launch is enqueued for each); beyond them the search pulls.  < 0, or
     // alpha = 0 (never pull: the caller's choice): every level
     if (push_levels < 0 || pull_alpha == 0 || push_levels > max_hops) push_levels = max_hops;
@@ -710,8 +838,19 @@ static int msbfs_run(const int64_t* rowptr, const int32_t* col, int64_t nnz, int
     const unsigned long long pull_above =
         g_bfs_alpha > 0 ? (unsigned long long)((nnz * n_words) / g_bfs_alpha) : ~0ull;
     const int big = sgnn_grid_for(n_ids * ((dist && n_sources > rs) ? n_sources : rs), 256);
+    // the closing form's state lies behind set_seen and is zeroed with it: open | ticket | closed; then wanted
+    MsbfsClosing cl = {};
+    int64_t n_zero = set_out ? n_sets * n_words : 0;
+    if (labels) {
+        cl.labels = labels; cl.sources = sources;
+        cl.open = (uint32_t*)(set_seen + n_sets * n_words);
+        cl.ticket = cl.open + max_hops + 2;
+        cl.closed = cl.ticket + max_hops + 2;
+        cl.wanted = set_seen + n_sets * n_words + msbfs_closing_state_words(max_hops);
+        n_zero += msbfs_closing_state_words(max_hops);
+    }
     hipLaunchKernelGGL(msbfs_init_kernel, dim3(big), dim3(256), 0, st, sources, n_sources, n_words, n_ids, seen,
-                       frontier, next, dist, flags, fvol, fbits, max_hops, rs, set_seen, set_out ? n_sets * n_words : 0,
+                       frontier, next, dist, flags, fvol, fbits, max_hops, rs, set_seen, n_zero,
                        set_out, set_out ? n_sets * n_sources : 0);
     SGNN_CHECK_LAUNCH();
     hipLaunchKernelGGL(msbfs_seed_kernel, dim3((int)((n_sources + 255) / 256)), dim3(256), 0, st, sources, n_sources,
@@ -724,6 +863,31 @@ static int msbfs_run(const int64_t* rowptr, const int32_t* col, int64_t nnz, int
     const int g_commit = sgnn_grid_for(n_ids, 256, 256 * 4);
     MsbfsBufs bufs;
     bufs.b[0] = seen; bufs.b[1] = next; bufs.b[2] = frontier;
+    if (labels) {
+        MsbfsSets none = sets;
+        none.n_sets = 0;                                     // (no prologue reduction: every level's own launch follows it)
+        for (int level = 0; level <= max_hops; ++level) {
+            if (level >= 1) {
+                hipLaunchKernelGGL(msbfs_level_kernel, dim3(g_expand), dim3(256), 0, st, rowptr, col, n_ids, n_words, n_sources,
+                                   bufs, flags, fvol, pull_above, push_levels, level, fbits, fbits + fwords, fdone, rs, none, dist, ss, sv);
+                SGNN_CHECK_LAUNCH();
+            }
+            if (level >= 1 && level <= push_levels) {            // (a level beyond them pulls: it commits itself)
+                hipLaunchKernelGGL(msbfs_commit_kernel, dim3(g_commit), dim3(256), 0, st, rowptr, n_ids, n_words, n_sources, seen,
+                                   frontier, next, dist, flags, fvol, level, ss, sv, fbits, fdone, rs, pull_above, push_levels);
+                SGNN_CHECK_LAUNCH();
+            }
+            hipLaunchKernelGGL(msbfs_closing_reduce_kernel, dim3(g_sets), dim3(256), 0, st, bufs, n_words, n_sources, rs, sets, cl,
+                               flags, fvol, pull_above, push_levels, level);
+            SGNN_CHECK_LAUNCH();
+        }
+        if (status) {
+            hipLaunchKernelGGL(msbfs_closing_status_kernel, dim3(1), dim3(64), 0, st, flags, fvol, pull_above, push_levels, max_hops,
+                               cl.closed, status);
+            SGNN_CHECK_LAUNCH();
+        }
+        return SGNN_OK;
+    }
     for (int level = 1; level <= max_hops; ++level) {
         hipLaunchKernelGGL(msbfs_level_kernel, dim3(g_expand), dim3(256), 0, st, rowptr, col, n_ids, n_words, n_sources,
                            bufs, flags, fvol, pull_above, push_levels, level, fbits, fbits + fwords, fdone, rs, sets, dist, ss, sv);
@@ -779,6 +943,101 @@ extern "C" int sgnn_bfs_min_hops_to_sets(const int64_t* rowptr, const int32_t* c
     if (n_sources == 0 || n_sets == 0) return SGNN_OK;
     return msbfs_run(rowptr, col, nnz, max_id, sources, n_sources, max_hops, 0, nullptr, set_ptr, set_nodes, n_sets, out,
                      workspace, (hipStream_t)stream, pull_alpha, out_status, push_levels);
+}
+
+extern "C" int64_t sgnn_bfs_min_hops_closing_workspace_bytes(int64_t max_id, int64_t n_sources, int max_hops, int64_t n_sets) {
+    const int64_t n_words = (n_sources + 63) / 64;
+    return sgnn_bfs_min_hops_workspace_bytes(max_id, n_sources, max_hops, n_sets) +
+           8 * (msbfs_closing_state_words(max_hops) + n_sets * n_words);
+}
+
+extern "C" int sgnn_bfs_min_hops_to_sets_closing(const int64_t* rowptr, const int32_t* col, int64_t nnz, int64_t max_id,
+                                                 const int32_t* sources, int64_t n_sources, int max_hops, int pull_alpha,
+                                                 int push_levels, const int32_t* labels, const int64_t* set_ptr,
+                                                 const int32_t* set_nodes, int64_t n_sets, float* out, int32_t* out_status,
+                                                 void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (!rowptr || !col || !sources || !labels || !set_ptr || !set_nodes || !out || !workspace || n_sources < 0 || n_sets < 0 ||
+        max_hops < 1 || max_hops > 254)
+        return SGNN_ERR_BAD_ARG;
+    if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
+    if (workspace_bytes < sgnn_bfs_min_hops_closing_workspace_bytes(max_id, n_sources, max_hops, n_sets)) return SGNN_ERR_BAD_ARG;
+    if (n_sources == 0 || n_sets == 0) return SGNN_OK;
+    return msbfs_run(rowptr, col, nnz, max_id, sources, n_sources, max_hops, 0, nullptr, set_ptr, set_nodes, n_sets, out,
+                     workspace, (hipStream_t)stream, pull_alpha, out_status, push_levels, labels);
+}
+
+// ---- connected components of the whole graph: labels[v] = the smallest id of v's component (ids without edges label
+// themselves).  Hook the larger root under the smaller one (atomicMin: a parent is never above its child, so a tree's root
+// is its smallest id), flatten, and repeat until no edge joins two trees -- once per graph, the host reads one word a round.
+__device__ __forceinline__ int32_t cc_graph_root(const int32_t* lab, int32_t x)
+{
+    for (int32_t p = __hip_atomic_load(&lab[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); p != x;
+         p = __hip_atomic_load(&lab[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
+        x = p;
+    return x;
+}
+
+__global__ void cc_graph_init_kernel(int32_t* __restrict__ lab, int64_t n_ids)
+{
+    for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < n_ids; v += (int64_t)gridDim.x * blockDim.x) lab[v] = (int32_t)v;
+}
+
+__global__ __launch_bounds__(256) void cc_graph_hook_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                            int64_t n_ids, int32_t* lab, int32_t* __restrict__ changed)
+{
+    const int sub = threadIdx.x & 15;
+    const int64_t group = blockIdx.x * (int64_t)(blockDim.x >> 4) + (threadIdx.x >> 4);
+    const int64_t n_groups = (int64_t)gridDim.x * (blockDim.x >> 4);
+    bool any = false;
+    for (int64_t v = group; v < n_ids; v += n_groups) {
+        const int64_t r0 = rowptr[v], r1 = rowptr[v + 1];
+        for (int64_t e = r0 + sub; e < r1; e += 16) {
+            const int32_t u = col[e];
+            if (u < 0 || u >= n_ids || u == v) continue;
+            const int32_t a = cc_graph_root(lab, (int32_t)v), b = cc_graph_root(lab, u);
+            if (a != b) {
+                atomicMin(&lab[a > b ? a : b], a > b ? b : a);
+                any = true;
+            }
+        }
+    }
+    if (any) *changed = 1;
+}
+
+__global__ void cc_graph_flatten_kernel(int32_t* lab, int64_t n_ids)
+{
+    for (int64_t v = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; v < n_ids; v += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t r = cc_graph_root(lab, (int32_t)v);
+        if (r != (int32_t)v) __hip_atomic_store(&lab[v], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+extern "C" int64_t sgnn_graph_component_labels_workspace_bytes(int64_t max_id) { (void)max_id; return 16; }
+
+extern "C" int sgnn_graph_component_labels(const int64_t* rowptr, const int32_t* col, int64_t nnz, int64_t max_id,
+                                           int32_t* labels, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (!rowptr || (!col && nnz > 0) || !labels || !workspace || max_id < 0 || nnz < 0 ||
+        workspace_bytes < sgnn_graph_component_labels_workspace_bytes(max_id))
+        return SGNN_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n_ids = max_id + 1;
+    int32_t* changed = (int32_t*)workspace;
+    hipLaunchKernelGGL(cc_graph_init_kernel, dim3(sgnn_grid_for(n_ids, 256)), dim3(256), 0, st, labels, n_ids);
+    SGNN_CHECK_LAUNCH();
+    for (int64_t round = 0; round <= n_ids; ++round) {       // (a round that joins nothing ends it; n_ids rounds always suffice)
+        int32_t host = 0;
+        if (hipMemsetAsync(changed, 0, 4, st) != hipSuccess) return SGNN_ERR_LAUNCH;
+        hipLaunchKernelGGL(cc_graph_hook_kernel, dim3(sgnn_grid_for(n_ids * 16, 256)), dim3(256), 0, st, rowptr, col, n_ids, labels, changed);
+        SGNN_CHECK_LAUNCH();
+        hipLaunchKernelGGL(cc_graph_flatten_kernel, dim3(sgnn_grid_for(n_ids, 256)), dim3(256), 0, st, labels, n_ids);
+        SGNN_CHECK_LAUNCH();
+        if (hipMemcpyAsync(&host, changed, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return SGNN_ERR_LAUNCH;
+        if (!host) break;
+    }
+    return SGNN_OK;
 }
 
 __global__ void min_hops_to_sets_kernel(const uint8_t* __restrict__ dist, int64_t n_sources, int64_t n_ids,

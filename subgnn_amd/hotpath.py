@@ -98,6 +98,19 @@ def _bfs_levels(model, key, max_hops):
 BFS_PUSH_MARGIN = 1
 
 
+def _position_until(hp):
+    """hparams['position_search_until']: 'sets' (default) -- the position channel's searches stop once every component has its
+    hops from every anchor (ops.bfs_min_hops_to_sets, until='sets': the same similarities, the levels that only complete the
+    rest of the graph are not run; status[0], the level hint, is then the closing level); 'nodes' -- they run until the
+    frontier dies.  The dealt searches of the strong-scaling form (_dealt_position_sims, _emulated_position_sims) always run
+    until the frontier dies: they enqueue the full cap without hints, where the closing form's reduction launch per level
+    would add a third more launches to a pass that is bound by the host's launches."""
+    until = hp.get('position_search_until', 'sets')
+    if until not in ('sets', 'nodes'):
+        raise ValueError("hparams['position_search_until'] must be 'sets' or 'nodes', not %r" % (until,))
+    return until
+
+
 def _bfs_push_levels(model, key):
     """How many levels of the search ``key`` may still push (each is a second launch, the commit): the level at which the
     first search of the kind switched to pulling, plus a margin; -1 (all of them) until that is known or when it never
@@ -450,6 +463,7 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
                 pint = {l: ops.choice_ragged(subs, hp['n_anchor_patches_pos_in'], seed,
                                              tape.stream_id(tape.STREAM_P_INT, split, l, ep), item_base=base) for l in range(L)}
                 st.per_split['anchors_pos_int'] = pint
+                until = _position_until(hp)
                 for l in range(L):
                     if shard is not None and shard.deal_shared:
                         cap = hp.get('max_bfs_hops', 32)
@@ -467,13 +481,13 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
                         nlev = _bfs_levels(model, ('P_out', split, l), cap)
                         src = anchors_pos_ext[l].to(torch.int32).contiguous()
                         w, status = ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=nlev, want_status=True,
-                                                             push_levels=_bfs_push_levels(model, ('P_out', split, l)))
+                                                             push_levels=_bfs_push_levels(model, ('P_out', split, l)), until=until)
 
-                        def redo(levels, src=src, l=l, sims=sims):
+                        def redo(levels, src=src, l=l, sims=sims, until=until):
                             # the hinted search ran out of levels: the same search with the full cap, similarities replaced.
                             # It runs on the INSTALLING stream: what it reads was allocated on the preparation stream
                             _hand_over(torch.cuda.current_stream(), src, cc_sets)
-                            w2, st2 = ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=levels, want_status=True)
+                            w2, st2 = ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=levels, want_status=True, until=until)
                             sims[('P', 'out', l)] = w2.view(S, C, -1).contiguous()
                             return st2.tolist()
                         _bfs_note(model, st, ('P_out', split, l), status, cap, nlev, redo)

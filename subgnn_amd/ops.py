@@ -307,6 +307,24 @@ class DeviceGraph:
         self.__dict__['_node_records'] = out
         return out
 
+    def component_labels(self):
+        """int32 (max_id + 1,): the smallest node id of every id's connected component (ids without edges label themselves),
+        built on first use and kept -- what the closing set search (bfs_min_hops_to_sets, until='sets') knows "never reached"
+        from.  The build reads a word back per round: it must happen outside a capture (the first, eager pass does it)."""
+        cached = self.__dict__.get('_component_labels')
+        if cached is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError('DeviceGraph.component_labels() reads a word back per round and cannot be built while a stream '
+                                   'is capturing: call it (or run one eager search with until=\'sets\') before recording')
+            lib = _lib.load()
+            cached = torch.empty(self.max_id + 1, dtype=torch.int32, device=self.device)
+            wsb = lib.sgnn_graph_component_labels_workspace_bytes(self.max_id)
+            ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=self.device)
+            check(lib.sgnn_graph_component_labels(_ptr(self.rowptr), _ptr(self.col), self.nnz, self.max_id, _ptr(cached), _ptr(ws),
+                                                  wsb, _stream()), 'sgnn_graph_component_labels')
+            self.__dict__['_component_labels'] = cached
+        return cached
+
 
 _WARM = set()
 
@@ -909,18 +927,32 @@ def bfs_hops(g, sources, max_hops=64, node_major=False, pull_alpha=-1):
     return dist
 
 
-def bfs_min_hops_to_sets(g, sources, sets, max_hops=64, want_status=False, pull_alpha=-1, push_levels=-1):
+def bfs_min_hops_to_sets(g, sources, sets, max_hops=64, want_status=False, pull_alpha=-1, push_levels=-1, until='nodes'):
     """min over the members of every set of the hop distance from every source -> (n_sets, n_sources)
     float32, 0 for unreachable pairs; one multi-source BFS, no (sources x nodes) hop table.
     ``want_status``: also an int32[4] device tensor -- [0] the last level that found anything, [1] whether level
     ``max_hops`` itself still did (too few levels enqueued: the result may be incomplete), [2] the first level that pulled.
     ``push_levels``: levels that may still push (each costs a second launch); beyond them every level pulls.  -1 = all;
-    results do not depend on it."""
+    results do not depend on it.
+    ``until``: 'nodes' runs until no node gains a source; 'sets' is the closing form (sgnn_bfs_min_hops_to_sets_closing): it
+    stops once every set has its hops -- the same values whenever status[1] == 0, status[0] is then the closing level.  It
+    takes the graph as symmetric and uses g.component_labels()."""
     lib = _lib.load()
     _req(sources, torch.int32, 'sources')
     ns = sources.numel()
     out = torch.empty((sets.n, ns), dtype=torch.float32, device=g.device)
     status = torch.zeros(4, dtype=torch.int32, device=g.device) if want_status else None
+    if until == 'sets':
+        labels = g.component_labels()
+        wsb = lib.sgnn_bfs_min_hops_closing_workspace_bytes(g.max_id, ns, max_hops, sets.n)
+        ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=g.device)
+        check(lib.sgnn_bfs_min_hops_to_sets_closing(_ptr(g.rowptr), _ptr(g.col), g.nnz, g.max_id, _ptr(sources), ns, max_hops,
+                                                    int(pull_alpha), int(push_levels), _ptr(labels), _ptr(sets.ptr),
+                                                    _ptr(sets.nodes), sets.n, _ptr(out), _ptr(status), _ptr(ws), wsb, _stream()),
+              'sgnn_bfs_min_hops_to_sets_closing')
+        return (out, status) if want_status else out
+    if until != 'nodes':
+        raise ValueError("until must be 'nodes' or 'sets', not %r" % (until,))
     wsb = lib.sgnn_bfs_min_hops_workspace_bytes(g.max_id, ns, max_hops, sets.n)
     ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=g.device)
     check(lib.sgnn_bfs_min_hops_to_sets(_ptr(g.rowptr), _ptr(g.col), g.nnz, g.max_id, _ptr(sources), ns, max_hops,
