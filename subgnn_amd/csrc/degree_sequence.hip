@@ -17,8 +17,9 @@
 //     popcount over each member's bit range -- no atomics, no divergence on list length;
 //   * per-set ascending order by an in-register rank sort (n <= 64 compare rounds of readlane).
 //   * sets of 65..2048 entries take a 256-thread workgroup variant (LDS scan, LDS integer
-//     atomics, LDS bitonic sort).
-#include "common.h"
+//     atomics, LDS bitonic sort), longer ones a workspace-backed one; both keep the set in the
+//     id table of id_table.h.
+#include "id_table.h"
 
 #define DS_HASH_BITS 10
 #define DS_HASH (1 << DS_HASH_BITS)
@@ -409,10 +410,7 @@ __global__ __launch_bounds__(64 * DS_WAVES) __attribute__((amdgpu_waves_per_eu(S
     }
 }
 
-// ---- workgroup variant for 64 < |S| <= DSB_MAX ------------------------------------------------
-#define DSB_MAX 2048
-#define DSB_HASH_BITS 12
-#define DSB_HASH (1 << DSB_HASH_BITS)
+// ---- workgroup variant for SGNN_SET_WAVE_MAX < |S| <= SGNN_SET_LDS_MAX -------------------------
 #define DSB_THREADS 256
 
 __device__ static inline void dsb_bitonic_sort(int32_t* a, int n_pow2, int tid) {
@@ -438,20 +436,21 @@ __global__ __launch_bounds__(DSB_THREADS) void degseq_block_kernel(
     const int64_t* __restrict__ set_ptr, const int32_t* __restrict__ set_nodes, int64_t n_sets,
     int32_t* __restrict__ out_int, int32_t* __restrict__ out_ext)
 {
-    __shared__ int32_t hash[DSB_HASH];
-    __shared__ int32_t s_v[DSB_MAX];
-    __shared__ uint32_t s_r0[DSB_MAX];
-    __shared__ int32_t s_incl[DSB_MAX];
-    __shared__ int32_t s_cnt[DSB_MAX];
-    __shared__ int32_t s_self[DSB_MAX];
+    __shared__ int32_t s_hash[SGNN_SET_LDS_HASH];
+    __shared__ int32_t s_v[SGNN_SET_LDS_MAX];
+    __shared__ uint32_t s_r0[SGNN_SET_LDS_MAX];
+    __shared__ int32_t s_incl[SGNN_SET_LDS_MAX];
+    __shared__ int32_t s_cnt[SGNN_SET_LDS_MAX];
+    __shared__ int32_t s_self[SGNN_SET_LDS_MAX];
     __shared__ int32_t s_part[DSB_THREADS];
     const int tid = threadIdx.x;
+    const IdTable table = idt_in_lds(s_hash);
     for (int64_t s = blockIdx.x; s < n_sets; s += gridDim.x) {
         const int64_t beg = set_ptr[s];
         const int n = (int)(set_ptr[s + 1] - beg);
-        if (n <= 64 || n > DSB_MAX) continue;               // block-uniform
-        for (int i = tid; i < DSB_HASH; i += DSB_THREADS) hash[i] = 0;
-        __syncthreads();
+        if (n <= SGNN_SET_WAVE_MAX || n > SGNN_SET_LDS_MAX) continue;    // block-uniform
+        idt_clear<false>(table, tid, DSB_THREADS);
+        idt_sync<true>();
         for (int i = tid; i < n; i += DSB_THREADS) {
             const int32_t v = set_nodes[beg + i];
             const int64_t a = rowptr[v], b = rowptr[v + 1];
@@ -460,14 +459,9 @@ __global__ __launch_bounds__(DSB_THREADS) void degseq_block_kernel(
             s_incl[i] = (int32_t)(b - a);
             s_cnt[i] = 0;
             s_self[i] = 0;
-            uint32_t h = sgnn_hash32((uint32_t)v) >> (32 - DSB_HASH_BITS);
-            while (true) {
-                const int32_t old = atomicCAS(&hash[h], 0, v);
-                if (old == 0 || old == v) break;
-                h = (h + 1) & (DSB_HASH - 1);
-            }
+            idt_insert<false>(table, v);
         }
-        __syncthreads();
+        idt_sync<true>();
         // inclusive scan of s_incl[0..n): per-thread chunks of 8, then a scan of the 256 partials
         const int per = (n + DSB_THREADS - 1) / DSB_THREADS;
         const int c0 = tid * per, c1 = (c0 + per < n) ? c0 + per : n;
@@ -495,16 +489,8 @@ __global__ __launch_bounds__(DSB_THREADS) void degseq_block_kernel(
             const int m = lo;
             const int32_t m_excl = (m == 0) ? 0 : s_incl[m - 1];
             const int32_t u = col[s_r0[m] + (uint32_t)(t - m_excl)];
-            uint32_t h = sgnn_hash32((uint32_t)u) >> (32 - DSB_HASH_BITS);
-            bool hit = false;
-            while (true) {
-                const int32_t k = hash[h];
-                if (k == u) { hit = true; break; }
-                if (k == 0) break;
-                h = (h + 1) & (DSB_HASH - 1);
-            }
             if (u == s_v[m]) { atomicAdd(&s_cnt[m], 2); atomicAdd(&s_self[m], 1); }
-            else if (hit) atomicAdd(&s_cnt[m], 1);
+            else if (idt_contains<true>(table, u)) atomicAdd(&s_cnt[m], 1);
         }
         __syncthreads();
         // s_cnt = internal; reuse s_self for external
@@ -542,7 +528,7 @@ static int ds_run(const int64_t* rowptr, const int32_t* col, const int32_t* col_
     if (!rowptr || !col || !set_ptr || !set_nodes || !out_internal || n_sets < 0 || max_set_size <= 0)
         return SGNN_ERR_BAD_ARG;
     if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
-    if (n_sets == 0) return SGNN_OK;                            // (sets of more than DSB_MAX entries: sgnn_degree_sequence_huge)
+    if (n_sets == 0) return SGNN_OK;                            // (sets of more than SGNN_SET_LDS_MAX entries: sgnn_degree_sequence_huge)
     hipStream_t st = (hipStream_t)stream;
     // 256-thread workgroups = 4 independent wavefronts, one set per wavefront: the hardware
     // dispatcher hands out workgroups as CUs free up, which balances the very uneven per-set
@@ -616,7 +602,7 @@ extern "C" int sgnn_degree_sequence_hub_bitmaps(const int64_t* rowptr, const int
 
 extern "C" int64_t sgnn_degree_sequence_search_threshold(void) { return DS_SEARCH; }
 
-// Sets of more than DSB_MAX entries (components of subgraphs with thousands of nodes; rounds 1-2 refused them): the calls
+// Sets of more than SGNN_SET_LDS_MAX entries (components of subgraphs with thousands of nodes; rounds 1-2 refused them): the calls
 // above leave them alone and this one fills in their degrees UNSORTED -- the membership table lives in the caller's
 // workspace (4 int32 slots per entry at the set's own offset), a member's list is streamed by one wavefront, hits counted by
 // ballot.  Same counting rules as above (a self loop counts twice; a repeated member gets its own count).  Sorting such a
@@ -635,23 +621,9 @@ __global__ __launch_bounds__(256) void degseq_huge_kernel(
     for (int64_t s = blockIdx.x; s < n_sets; s += gridDim.x) {
         const int64_t beg = set_ptr[s];
         const int n = (int)(set_ptr[s + 1] - beg);
-        if (n <= DSB_MAX) continue;
-        int32_t* hash = ws + 4 * beg;
-        uint32_t H = 1;
-        while (H < 2u * (uint32_t)n) H <<= 1;
-        for (uint32_t i = tid; i < H; i += 256) hash[i] = 0;
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            const int32_t v = set_nodes[beg + i];
-            uint32_t h = sgnn_hash32((uint32_t)v) & (H - 1);
-            while (true) {
-                const int32_t old = atomicCAS(&hash[h], 0, v);
-                if (old == 0 || old == v) break;
-                h = (h + 1) & (H - 1);
-            }
-        }
-        __threadfence_block();
-        __syncthreads();
+        if (n <= SGNN_SET_LDS_MAX) continue;
+        const IdTable table = idt_in_workspace(ws, beg, n);
+        idt_build<false, false>(table, set_nodes + beg, n, tid, 256);
         for (int i = wave; i < n; i += 4) {
             const int32_t v = set_nodes[beg + i];
             const int64_t a = rowptr[v], b = rowptr[v + 1];
@@ -661,15 +633,7 @@ __global__ __launch_bounds__(256) void degseq_huge_kernel(
                 if (e < b) {
                     const int32_t u = col[e];
                     loop = (u == v);
-                    if (!loop) {
-                        uint32_t h = sgnn_hash32((uint32_t)u) & (H - 1);
-                        while (true) {
-                            const int32_t k = hash[h];
-                            if (k == u) { hit = true; break; }
-                            if (k == 0) break;
-                            h = (h + 1) & (H - 1);
-                        }
-                    }
+                    hit = !loop && idt_contains<false>(table, u);
                 }
                 hits += __popcll(__ballot(hit));
                 self += __popcll(__ballot(loop));

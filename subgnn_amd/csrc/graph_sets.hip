@@ -1,25 +1,17 @@
 // Integer graph kernels on ragged node sets: connected components of induced subgraphs (a7),
 // k-hop border of a component (a8), in-border nodes of an anchor patch (a3).
-#include "common.h"
+#include "id_table.h"
 
 // ---------------------------------------------------------------------------------------------
 // a7  connected components (reference SubGNN/SubGNN.py:589-592)
 // One wavefront per subgraph.  Positions 0..n-1 of the subgraph are the union-find elements
 // (parents in LDS); every ordered pair (i<j) is tested for adjacency by binary search in the
-// shorter of the two sorted neighbour lists, and adjacent / identical nodes are united by a
-// lock-free hook of the larger root under the smaller one, so a component's root is its
-// smallest position.  Integer-only; HBM traffic is the two rowptr pairs + O(log deg) probes.
+// shorter of the two sorted neighbour lists, and adjacent / identical nodes are united by the
+// lock-free union-find of id_table.h, so a component's root is its smallest position.  Integer-only; HBM traffic is the two rowptr pairs + O(log deg) probes.
 // ---------------------------------------------------------------------------------------------
-#define CC_MAX 2048
-
-__device__ static inline int cc_find(volatile int32_t* parent, int x) {
-    int p = parent[x];
-    while (p != x) { x = p; p = parent[x]; }
-    return x;
-}
 
 // NMAX = 64: subgraphs of at most 64 nodes (the common case) keep 512 B of LDS per wavefront, so
-// the CU holds its full complement of wavefronts; NMAX = CC_MAX handles the rest (and only those).
+// the CU holds its full complement of wavefronts; NMAX = SGNN_SET_LDS_MAX handles the rest (and only those).
 template <int NMAX>
 __global__ __launch_bounds__(64) void cc_labels_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col_sorted,
@@ -35,8 +27,8 @@ __global__ __launch_bounds__(64) void cc_labels_kernel(
         const int64_t beg = sub_ptr[s];
         const int n = (int)(sub_ptr[s + 1] - beg);
         if (n <= 0) continue;
-        if (NMAX == 64 ? n > 64 : n <= 64) continue;        // the other instantiation owns it
-        if (n > CC_MAX) {                                   // flagged by the host wrapper too
+        if (NMAX == SGNN_SET_WAVE_MAX ? n > SGNN_SET_WAVE_MAX : n <= SGNN_SET_WAVE_MAX) continue;        // the other instantiation owns it
+        if (n > SGNN_SET_LDS_MAX) {                                   // flagged by the host wrapper too
             for (int i = lane; i < n; i += 64) out_label[beg + i] = -1;
             continue;
         }
@@ -65,22 +57,12 @@ __global__ __launch_bounds__(64) void cc_labels_kernel(
                     if (s_deg[i] <= s_deg[j]) linked = sgnn_sorted_contains(col_sorted + s_r0[i], s_deg[i], b);
                     else linked = sgnn_sorted_contains(col_sorted + s_r0[j], s_deg[j], a);
                 }
-                if (linked) {
-                    int x = i, y = j;
-                    while (true) {
-                        x = cc_find(s_parent, x);
-                        y = cc_find(s_parent, y);
-                        if (x == y) break;
-                        if (x < y) { const int t = x; x = y; y = t; }       // hook x (larger) under y
-                        const int32_t old = atomicCAS(&s_parent[x], x, y);
-                        if (old == x) { merged = true; break; }
-                    }
-                }
+                if (linked) merged = uf_union<true>(s_parent, i, j);
             }
             unions += __popcll(__ballot(merged));           // every successful hook removes one component
         }
         __syncthreads();
-        for (int i = lane; i < n; i += 64) out_label[beg + i] = cc_find(s_parent, i);
+        for (int i = lane; i < n; i += 64) out_label[beg + i] = uf_find<true>(s_parent, i);
         __syncthreads();
     }
 }
@@ -95,8 +77,8 @@ extern "C" int sgnn_cc_labels(const int64_t* rowptr, const int32_t* col_sorted, 
     const int grid = (int)(n_subgraphs < 256 * 32 ? n_subgraphs : 256 * 32);
     hipLaunchKernelGGL(cc_labels_kernel<64>, dim3(grid), dim3(64), 0, (hipStream_t)stream, rowptr, col_sorted,
                        sub_ptr, sub_nodes, n_subgraphs, out_label);
-    if (max_sub_len <= 0 || max_sub_len > 64)
-        hipLaunchKernelGGL(cc_labels_kernel<CC_MAX>, dim3(grid < 2048 ? grid : 2048), dim3(64), 0, (hipStream_t)stream,
+    if (max_sub_len <= 0 || max_sub_len > SGNN_SET_WAVE_MAX)
+        hipLaunchKernelGGL(cc_labels_kernel<SGNN_SET_LDS_MAX>, dim3(grid < 2048 ? grid : 2048), dim3(64), 0, (hipStream_t)stream,
                            rowptr, col_sorted, sub_ptr, sub_nodes, n_subgraphs, out_label);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
@@ -111,9 +93,8 @@ extern "C" int sgnn_cc_labels(const int64_t* rowptr, const int32_t* col_sorted, 
 // Rank of a component = roots at smaller positions (ballot + popcount prefix); position inside a
 // component = kept nodes of the same label before me (64 broadcast steps per 64-node chunk plus a
 // running per-label counter in LDS).  Subgraphs of up to 64 nodes need no hash; longer ones find
-// duplicates through an LDS hash keyed by node id that keeps the smallest position.
+// duplicates through the LDS id table (id_table.h), which keeps the smallest position.
 // ---------------------------------------------------------------------------------------------
-#define CCK_HASH 4096
 
 template <bool BIG, bool WRITE>
 __global__ __launch_bounds__(64) void cc_compact_kernel(
@@ -121,33 +102,22 @@ __global__ __launch_bounds__(64) void cc_compact_kernel(
     int64_t n_sub, int64_t C, int64_t L, int32_t* __restrict__ out_ncc, int32_t* __restrict__ out_maxlen,
     int64_t* __restrict__ out)
 {
-    constexpr int NMAX = BIG ? CC_MAX : 64;
+    constexpr int NMAX = BIG ? SGNN_SET_LDS_MAX : SGNN_SET_WAVE_MAX;
     __shared__ int32_t s_rank[NMAX], s_cnt[NMAX];
-    __shared__ int32_t s_hk[BIG ? CCK_HASH : 1], s_hv[BIG ? CCK_HASH : 1];
+    __shared__ int32_t s_hk[BIG ? SGNN_SET_LDS_HASH : 1], s_hv[BIG ? SGNN_SET_LDS_HASH : 1];
+    const IdTable table = idt_in_lds(s_hk, s_hv);
     const int lane = threadIdx.x;
     const uint64_t lt = (1ull << lane) - 1ull;
     for (int64_t s = blockIdx.x; s < n_sub; s += gridDim.x) {
         const int64_t beg = sub_ptr[s];
         const int n = (int)(sub_ptr[s + 1] - beg);
-        if (n <= 0 || n > NMAX || (BIG && n <= 64)) {
+        if (n <= 0 || n > NMAX || (BIG && n <= SGNN_SET_WAVE_MAX)) {
             if (!WRITE && n <= 0) { if (lane == 0) { out_ncc[s] = 0; out_maxlen[s] = 0; } }
             continue;                                           // the other instantiation owns it
         }
         for (int i = lane; i < n; i += 64) s_cnt[i] = 0;
-        if (BIG) {
-            for (int i = lane; i < CCK_HASH; i += 64) { s_hk[i] = 0; s_hv[i] = 0x7fffffff; }
-            __syncthreads();
-            for (int i = lane; i < n; i += 64) {
-                const int32_t v = sub_nodes[beg + i];
-                uint32_t h = sgnn_hash32((uint32_t)v) >> 20;
-                while (true) {
-                    const int32_t old = atomicCAS(&s_hk[h], 0, v);
-                    if (old == 0 || old == v) { atomicMin(&s_hv[h], i); break; }
-                    h = (h + 1) & (CCK_HASH - 1);
-                }
-            }
-        }
-        __syncthreads();
+        if (BIG) idt_build<true, true>(table, sub_nodes + beg, n, lane, 64);
+        else __syncthreads();
         int running = 0, maxlen = 0;
         // roots and their ranks
         for (int c0 = 0; c0 < n; c0 += 64) {
@@ -166,11 +136,7 @@ __global__ __launch_bounds__(64) void cc_compact_kernel(
             if (i < n) { v = sub_nodes[beg + i]; lab = labels[beg + i]; }
             bool keep = i < n;
             if (BIG) {
-                if (keep) {
-                    uint32_t h = sgnn_hash32((uint32_t)v) >> 20;
-                    while (s_hk[h] != v) h = (h + 1) & (CCK_HASH - 1);
-                    keep = (s_hv[h] == i);
-                }
+                if (keep) keep = idt_first<true>(table, v) == i;
             } else {
                 for (int l = 0; l < n; ++l) { const int32_t vl = __shfl(v, l); if (l < lane && vl == v) keep = false; }
             }
@@ -205,19 +171,19 @@ static int cc_compact_launch(bool write, const int64_t* sub_ptr, const int32_t* 
                              int32_t* out_maxlen, int64_t* out, void* stream)
 {
     if (!sub_ptr || !sub_nodes || !labels || n_sub < 0) return SGNN_ERR_BAD_ARG;
-    if (n_sub == 0) return SGNN_OK;                             // (subgraphs of more than CC_MAX nodes: sgnn_cc_compact_huge)
+    if (n_sub == 0) return SGNN_OK;                             // (subgraphs of more than SGNN_SET_LDS_MAX nodes: sgnn_cc_compact_huge)
     hipStream_t st = (hipStream_t)stream;
     const int grid = (int)(n_sub < 256 * 64 ? n_sub : 256 * 64);
     if (write) {
         hipLaunchKernelGGL((cc_compact_kernel<false, true>), dim3(grid), dim3(64), 0, st, sub_ptr, sub_nodes, labels, n_sub,
                            C, L, out_ncc, out_maxlen, out);
-        if (max_sub_len > 64 || max_sub_len <= 0)
+        if (max_sub_len > SGNN_SET_WAVE_MAX || max_sub_len <= 0)
             hipLaunchKernelGGL((cc_compact_kernel<true, true>), dim3(grid < 2048 ? grid : 2048), dim3(64), 0, st, sub_ptr,
                                sub_nodes, labels, n_sub, C, L, out_ncc, out_maxlen, out);
     } else {
         hipLaunchKernelGGL((cc_compact_kernel<false, false>), dim3(grid), dim3(64), 0, st, sub_ptr, sub_nodes, labels,
                            n_sub, C, L, out_ncc, out_maxlen, out);
-        if (max_sub_len > 64 || max_sub_len <= 0)
+        if (max_sub_len > SGNN_SET_WAVE_MAX || max_sub_len <= 0)
             hipLaunchKernelGGL((cc_compact_kernel<true, false>), dim3(grid < 2048 ? grid : 2048), dim3(64), 0, st, sub_ptr,
                                sub_nodes, labels, n_sub, C, L, out_ncc, out_maxlen, out);
     }
@@ -243,11 +209,12 @@ extern "C" int sgnn_cc_compact(const int64_t* sub_ptr, const int32_t* sub_nodes,
 }
 
 // ---------------------------------------------------------------------------------------------
-// a7 for subgraphs of MORE than CC_MAX nodes (round 3: rounds 1-2 refused them; the reference pads to any size,
+// a7 for subgraphs of MORE than SGNN_SET_LDS_MAX nodes (round 3: rounds 1-2 refused them; the reference pads to any size,
 // SubGNN/SubGNN.py:575-607).  The LDS tables of the kernels above do not hold such a set and their all-pairs test is
 // quadratic, so these take another route, one 256-thread workgroup per subgraph with its state in a caller workspace:
-// node id -> smallest position in an open-addressing table (2-4 slots per node), union-find parents in global memory,
-// and the induced edges found by streaming the members' neighbour lists against the table (work ~ sum of degrees).
+// node id -> smallest position in an open-addressing table (2-4 slots per node), union-find parents in global memory
+// (both from id_table.h, read by its rule for the workspace), and the induced edges found by streaming the members'
+// neighbour lists against the table (work ~ sum of degrees).
 // Compaction: component rank = roots at smaller positions (a running workgroup scan), position inside a component =
 // members of the same component before me, counted chunk by chunk of 256 positions in subgraph order.
 // Layout of the workspace for a call over `total` nodes (sub_ptr[n_sub]): hkey[4 total] | hpos[4 total] | parent[total] |
@@ -260,58 +227,11 @@ extern "C" int64_t sgnn_cc_huge_workspace_bytes(int64_t total_nodes)
     return (total_nodes < 0 ? 0 : total_nodes) * 11 * 4 + 64;
 }
 
-struct CchRegion { int32_t* hk; int32_t* hv; int32_t* par; int32_t* rank; int32_t* cnt; uint32_t H; };
+struct CchRegion { IdTable t; int32_t* par; int32_t* rank; int32_t* cnt; };
 
 __device__ static inline CchRegion cch_region(int32_t* ws, int64_t total, int64_t beg, int n)
 {
-    CchRegion r;
-    r.hk = ws + 4 * beg;
-    r.hv = ws + 4 * total + 4 * beg;
-    r.par = ws + 8 * total + beg;
-    r.rank = ws + 9 * total + beg;
-    r.cnt = ws + 10 * total + beg;
-    uint32_t H = 1;
-    while (H < 2u * (uint32_t)n) H <<= 1;                      // <= 4 n
-    r.H = H;
-    return r;
-}
-
-__device__ static inline void cch_build_table(const CchRegion& r, const int32_t* __restrict__ nodes, int n)
-{
-    for (uint32_t i = threadIdx.x; i < r.H; i += CCH_THREADS) { r.hk[i] = 0; r.hv[i] = 0x7fffffff; }
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += CCH_THREADS) {
-        const int32_t v = nodes[i];
-        uint32_t h = sgnn_hash32((uint32_t)v) & (r.H - 1);
-        while (true) {
-            const int32_t old = atomicCAS(&r.hk[h], 0, v);
-            if (old == 0 || old == v) { atomicMin(&r.hv[h], i); break; }
-            h = (h + 1) & (r.H - 1);
-        }
-    }
-    __syncthreads();
-}
-
-__device__ static inline int cch_lookup(const CchRegion& r, int32_t v)     // smallest position of id v in the set, -1 = absent
-{
-    uint32_t h = sgnn_hash32((uint32_t)v) & (r.H - 1);
-    while (true) {
-        const int32_t k = r.hk[h];
-        if (k == v) return r.hv[h];
-        if (k == 0) return -1;
-        h = (h + 1) & (r.H - 1);
-    }
-}
-
-__device__ static inline void cch_union(int32_t* par, int x, int y)
-{
-    while (true) {
-        x = cc_find(par, x);
-        y = cc_find(par, y);
-        if (x == y) return;
-        if (x < y) { const int t = x; x = y; y = t; }           // hook the larger root under the smaller: root = smallest position
-        if (atomicCAS(&par[x], x, y) == x) return;
-    }
+    return CchRegion{idt_in_workspace(ws, beg, n, ws + 4 * total), ws + 8 * total + beg, ws + 9 * total + beg, ws + 10 * total + beg};
 }
 
 __global__ __launch_bounds__(CCH_THREADS) void cc_huge_labels_kernel(
@@ -323,26 +243,25 @@ __global__ __launch_bounds__(CCH_THREADS) void cc_huge_labels_kernel(
     for (int64_t s = blockIdx.x; s < n_sub; s += gridDim.x) {
         const int64_t beg = sub_ptr[s];
         const int n = (int)(sub_ptr[s + 1] - beg);
-        if (n <= CC_MAX) continue;                              // sgnn_cc_labels owns those
+        if (n <= SGNN_SET_LDS_MAX) continue;                              // sgnn_cc_labels owns those
         const CchRegion r = cch_region(ws, total, beg, n);
         const int32_t* nodes = sub_nodes + beg;
         for (int i = threadIdx.x; i < n; i += CCH_THREADS) r.par[i] = i;
-        cch_build_table(r, nodes, n);
+        idt_build<false, true>(r.t, nodes, n, threadIdx.x, CCH_THREADS);
         // a member's list by one wavefront: every neighbour that is in the set joins the member's component;
         // a repeated id joins its first occurrence
         for (int i = wave; i < n; i += CCH_THREADS / 64) {
             const int32_t v = nodes[i];
-            const int first = cch_lookup(r, v);
-            if (first != i) { if (lane == 0) cch_union(r.par, i, first); continue; }
+            const int first = idt_first<false>(r.t, v);
+            if (first != i) { if (lane == 0) uf_union<false>(r.par, i, first); continue; }
             const int64_t a = rowptr[v], b = rowptr[v + 1];
             for (int64_t e = a + lane; e < b; e += 64) {
-                const int j = cch_lookup(r, col[e]);
-                if (j >= 0 && j != i) cch_union(r.par, i, j);
+                const int j = idt_first<false>(r.t, col[e]);
+                if (j >= 0 && j != i) uf_union<false>(r.par, i, j);
             }
         }
-        __threadfence_block();
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += CCH_THREADS) out_label[beg + i] = cc_find(r.par, i);
+        idt_sync<false>();
+        for (int i = threadIdx.x; i < n; i += CCH_THREADS) out_label[beg + i] = uf_find<false>(r.par, i);
         __syncthreads();
     }
 }
@@ -361,12 +280,12 @@ __global__ __launch_bounds__(CCH_THREADS) void cc_huge_compact_kernel(
     for (int64_t s = blockIdx.x; s < n_sub; s += gridDim.x) {
         const int64_t beg = sub_ptr[s];
         const int n = (int)(sub_ptr[s + 1] - beg);
-        if (n <= CC_MAX) continue;
+        if (n <= SGNN_SET_LDS_MAX) continue;
         const CchRegion r = cch_region(ws, total, beg, n);
         const int32_t* nodes = sub_nodes + beg;
         const int32_t* lab = labels + beg;
         for (int i = tid; i < n; i += CCH_THREADS) r.cnt[i] = 0;
-        cch_build_table(r, nodes, n);
+        idt_build<false, true>(r.t, nodes, n, threadIdx.x, CCH_THREADS);
         // ranks of the roots: a running scan over the positions, 256 at a time
         int running = 0;
         for (int c0 = 0; c0 < n; c0 += CCH_THREADS) {
@@ -384,15 +303,14 @@ __global__ __launch_bounds__(CCH_THREADS) void cc_huge_compact_kernel(
             running += s_scan[CCH_THREADS - 1];
             __syncthreads();
         }
-        __threadfence_block();
-        __syncthreads();
+        idt_sync<false>();
         // positions inside the components, in subgraph order
         int maxlen = 0;
         for (int c0 = 0; c0 < n; c0 += CCH_THREADS) {
             const int i = c0 + tid;
             int32_t v = 0, lb = -1;
             bool keep = i < n;
-            if (keep) { v = nodes[i]; lb = lab[i]; keep = cch_lookup(r, v) == i; }       // repeated ids: first occurrence only
+            if (keep) { v = nodes[i]; lb = lab[i]; keep = idt_first<false>(r.t, v) == i; }       // repeated ids: first occurrence only
             s_my[tid] = keep ? lb : -1 - tid;                   // distinct sentinels for dropped positions
             __syncthreads();
             int before = 0;
@@ -406,15 +324,14 @@ __global__ __launch_bounds__(CCH_THREADS) void cc_huge_compact_kernel(
                 }
             }
             int within = 0;
-            if (keep) within = r.cnt[lb] + before;
+            if (keep) within = idt_ld<false>(r.cnt + lb) + before;
             __syncthreads();
             if (keep && !later) r.cnt[lb] = within + 1;          // the component's last member of this chunk
             if (keep) {
                 maxlen = within + 1 > maxlen ? within + 1 : maxlen;
-                if (WRITE) out[((int64_t)s * C + r.rank[lb]) * L + within] = (int64_t)v;
+                if (WRITE) out[((int64_t)s * C + idt_ld<false>(r.rank + lb)) * L + within] = (int64_t)v;
             }
-            __threadfence_block();
-            __syncthreads();
+            idt_sync<false>();
         }
         if (!WRITE) {
             s_red[tid] = maxlen;
@@ -1921,59 +1838,40 @@ extern "C" int sgnn_khop1_border_sorted(const int64_t* rowptr, const int32_t* co
 // ---------------------------------------------------------------------------------------------
 // a3  in-border nodes of a patch (reference SubGNN/subgraph_utils.py:126-144, with the id-1 /
 // node-order indexing quirk: id x is read as the node at position x-1 of G.nodes()).
-// One workgroup per patch; patch ids in an LDS hash; one thread per member walks "its" list.
+// One workgroup per patch; patch ids in the id table of id_table.h; one thread per member walks "its" list.
+// LDS: patches of up to SGNN_SET_LDS_MAX nodes, the table in LDS; the flags of longer patches are poisoned with 255.
+// !LDS: those longer patches (ego-graph patches around hubs), the table in the caller's workspace (4 int32 slots per patch
+// node at the patch's own offset: sgnn_patch_in_border_huge_workspace_bytes); it overwrites the poison.
 // ---------------------------------------------------------------------------------------------
-#define PB_HASH_BITS 12
-#define PB_HASH (1 << PB_HASH_BITS)
-#define PB_MAX 2048
-
+template <bool LDS>
 __global__ __launch_bounds__(256) void patch_in_border_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
     const int32_t* __restrict__ node_order, const int32_t* __restrict__ node_pos,
     const int64_t* __restrict__ patch_ptr, const int32_t* __restrict__ patch_nodes, int64_t n_patches,
-    uint8_t* __restrict__ out_flag)
+    uint8_t* __restrict__ out_flag, int32_t* __restrict__ ws)
 {
-    __shared__ int32_t hash[PB_HASH];
+    __shared__ int32_t s_hash[LDS ? SGNN_SET_LDS_HASH : 1];
     const int tid = threadIdx.x;
     for (int64_t p = blockIdx.x; p < n_patches; p += gridDim.x) {
         const int64_t beg = patch_ptr[p];
         const int n = (int)(patch_ptr[p + 1] - beg);
-        if (n <= 0) continue;
-        for (int i = tid; i < PB_HASH; i += 256) hash[i] = 0;
-        __syncthreads();
-        if (n <= PB_MAX) {
-            for (int i = tid; i < n; i += 256) {
-                const int32_t v = patch_nodes[beg + i];
-                uint32_t h = sgnn_hash32((uint32_t)v) >> (32 - PB_HASH_BITS);
-                while (true) {
-                    const int32_t old = atomicCAS(&hash[h], 0, v);
-                    if (old == 0 || old == v) break;
-                    h = (h + 1) & (PB_HASH - 1);
-                }
-            }
+        if (LDS ? n <= 0 : n <= SGNN_SET_LDS_MAX) continue;     // (block-uniform) nothing to do / the LDS form owns it
+        if (LDS && n > SGNN_SET_LDS_MAX) {                      // the workspace form owns it: poisoned until then
+            for (int i = tid; i < n; i += 256) out_flag[beg + i] = 255;
+            continue;
         }
-        __syncthreads();
+        const IdTable table = LDS ? idt_in_lds(s_hash) : idt_in_workspace(ws, beg, n);
+        idt_build<LDS, false>(table, patch_nodes + beg, n, tid, 256);
         for (int i = tid; i < n; i += 256) {
-            if (n > PB_MAX) { out_flag[beg + i] = 255; continue; }     // unsupported size: poisoned
             const int32_t x = patch_nodes[beg + i];
-            const int32_t px = node_order[x - 1];
+            const int32_t px = node_order[x - 1];               // the reference's id - 1 / node-order quirk (su:139)
             const int64_t r0 = rowptr[px], r1 = rowptr[px + 1];
             uint8_t flag = 0;
-            for (int64_t e = r0; e < r1 && !flag; ++e) {
-                const int32_t y = node_pos[col[e]] + 1;
-                uint32_t h = sgnn_hash32((uint32_t)y) >> (32 - PB_HASH_BITS);
-                bool member = false;
-                while (true) {
-                    const int32_t kk = hash[h];
-                    if (kk == y) { member = true; break; }
-                    if (kk == 0) break;
-                    h = (h + 1) & (PB_HASH - 1);
-                }
-                if (!member) flag = 1;
-            }
+            for (int64_t e = r0; e < r1 && !flag; ++e)
+                if (!idt_contains<LDS>(table, node_pos[col[e]] + 1)) flag = 1;
             out_flag[beg + i] = flag;
         }
-        __syncthreads();
+        __syncthreads();                                        // the next patch re-initialises the table
     }
 }
 
@@ -1988,68 +1886,15 @@ extern "C" int sgnn_patch_in_border(const int64_t* rowptr, const int32_t* col, i
     (void)n_nodes;
     if (n_patches == 0) return SGNN_OK;
     const int grid = (int)(n_patches < 256 * 8 ? n_patches : 256 * 8);
-    hipLaunchKernelGGL(patch_in_border_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, rowptr, col,
-                       node_order, node_pos, patch_ptr, patch_nodes, n_patches, out_flag);
+    hipLaunchKernelGGL(patch_in_border_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, rowptr, col,
+                       node_order, node_pos, patch_ptr, patch_nodes, n_patches, out_flag, (int32_t*)nullptr);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
 
-// Patches of more than PB_MAX nodes (ego-graph patches around hubs): the membership table lives in the caller's workspace
-// (4 int32 slots per patch node at the patch's own offset) instead of LDS; the kernel above poisons those patches' flags
-// with 255 and this one overwrites them.  workspace: sgnn_patch_in_border_huge_workspace_bytes(total patch nodes).
 extern "C" int64_t sgnn_patch_in_border_huge_workspace_bytes(int64_t total_nodes)
 {
     return (total_nodes < 0 ? 0 : total_nodes) * 4 * 4 + 64;
-}
-
-__global__ __launch_bounds__(256) void patch_in_border_huge_kernel(
-    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
-    const int32_t* __restrict__ node_order, const int32_t* __restrict__ node_pos,
-    const int64_t* __restrict__ patch_ptr, const int32_t* __restrict__ patch_nodes, int64_t n_patches,
-    uint8_t* __restrict__ out_flag, int32_t* __restrict__ ws)
-{
-    const int tid = threadIdx.x;
-    for (int64_t p = blockIdx.x; p < n_patches; p += gridDim.x) {
-        const int64_t beg = patch_ptr[p];
-        const int n = (int)(patch_ptr[p + 1] - beg);
-        if (n <= PB_MAX) continue;                              // sgnn_patch_in_border owns those
-        int32_t* hash = ws + 4 * beg;
-        uint32_t H = 1;
-        while (H < 2u * (uint32_t)n) H <<= 1;
-        for (uint32_t i = tid; i < H; i += 256) hash[i] = 0;
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            const int32_t v = patch_nodes[beg + i];
-            uint32_t h = sgnn_hash32((uint32_t)v) & (H - 1);
-            while (true) {
-                const int32_t old = atomicCAS(&hash[h], 0, v);
-                if (old == 0 || old == v) break;
-                h = (h + 1) & (H - 1);
-            }
-        }
-        __threadfence_block();
-        __syncthreads();
-        for (int i = tid; i < n; i += 256) {
-            const int32_t x = patch_nodes[beg + i];
-            const int32_t px = node_order[x - 1];               // the reference's id - 1 / node-order quirk (su:139)
-            const int64_t r0 = rowptr[px], r1 = rowptr[px + 1];
-            uint8_t flag = 0;
-            for (int64_t e = r0; e < r1 && !flag; ++e) {
-                const int32_t y = node_pos[col[e]] + 1;
-                uint32_t h = sgnn_hash32((uint32_t)y) & (H - 1);
-                bool member = false;
-                while (true) {
-                    const int32_t kk = hash[h];
-                    if (kk == y) { member = true; break; }
-                    if (kk == 0) break;
-                    h = (h + 1) & (H - 1);
-                }
-                if (!member) flag = 1;
-            }
-            out_flag[beg + i] = flag;
-        }
-        __syncthreads();
-    }
 }
 
 extern "C" int sgnn_patch_in_border_huge(const int64_t* rowptr, const int32_t* col, int64_t nnz,
@@ -2066,7 +1911,7 @@ extern "C" int sgnn_patch_in_border_huge(const int64_t* rowptr, const int32_t* c
     if (workspace_bytes < sgnn_patch_in_border_huge_workspace_bytes(total_nodes)) return SGNN_ERR_BAD_ARG;
     (void)n_nodes;
     if (n_patches == 0) return SGNN_OK;
-    hipLaunchKernelGGL(patch_in_border_huge_kernel, dim3((int)(n_patches < 1024 ? n_patches : 1024)), dim3(256), 0,
+    hipLaunchKernelGGL(patch_in_border_kernel<false>, dim3((int)(n_patches < 1024 ? n_patches : 1024)), dim3(256), 0,
                        (hipStream_t)stream, rowptr, col, node_order, node_pos, patch_ptr, patch_nodes, n_patches, out_flag,
                        (int32_t*)workspace);
     SGNN_CHECK_LAUNCH();

@@ -8,30 +8,27 @@
 // members with a self loop, boundary edges = distinct (member, non-member neighbour) pairs, connected components, sum of the
 // members' core numbers (self loops ignored)}.  Per position (optional), int32: the member's core number, -1 for a dropped entry.
 //
-// Tiers, by the number of ENTRIES of the set (the library's 64 / CC_MAX / "huge" classes):
-//   <= SP_WAVE_MAX = 64   one wavefront per set, lane i owns entry i.  The n (n - 1) / 2 pairs are tested 64 per round by a
+// Tiers, by the number of ENTRIES of the set (id_table.h):
+//   <= SGNN_SET_WAVE_MAX  one wavefront per set, lane i owns entry i.  The n (n - 1) / 2 pairs are tested 64 per round by a
 //                         binary search of the shorter of the two sorted rows (a hub's list is never streamed for a 20-node
 //                         set); the hits become the 64-bit rows of the induced adjacency matrix, one row per lane, in a register.
 //                         From there nothing leaves the registers: edges = sum of popcounts / 2, components = Warshall closure
 //                         of the bit rows (row k is broadcast at step k), cores = peeling under a wave-uniform alive mask
 //                         (__ballot): lanes with popcount(row & alive) <= k leave with core k; k rises when none is left.
-//   <= SP_LDS_MAX = 2048  one 256-thread workgroup per set, its tables in LDS (56 KiB: two workgroups per CU).  Bit rows of 2048
+//   <= SGNN_SET_LDS_MAX   one 256-thread workgroup per set, its tables in LDS (56 KiB: two workgroups per CU).  Bit rows of 2048
 //                         members would be 512 KiB, so this form keeps counters instead: an id -> first position hash table,
 //                         union-find parents, the current induced degree per member and a removal queue.  One wavefront streams
 //                         a member's row against the table (degree, boundary, self loop, unions); the peel is level-synchronous:
 //                         members of degree <= k are queued and marked with their core, their rows are streamed again to
 //                         decrement the neighbours, and k jumps to the smallest remaining degree when the queue stays empty.
-//   >  SP_LDS_MAX         the same workgroup code with the tables in the caller's workspace (11 int32 per entry, each set at its
+//   >  SGNN_SET_LDS_MAX   the same workgroup code with the tables in the caller's workspace (11 int32 per entry, each set at its
 //                         own offset; sgnn_subgraph_properties_workspace_bytes).  No set size is refused.
 // Every table is initialised by the set that uses it: neither LDS nor the workspace carries anything from one set or call to
 // the next.
-#include "common.h"
+#include "id_table.h"
 
 SGNN_DEFINE_WARM(subgraph_props)
 
-#define SP_WAVE_MAX 64
-#define SP_LDS_MAX 2048                 // == CC_MAX (graph_sets.hip), DSB_MAX (degree_sequence.hip), ops.CC_LDS_MAX
-#define SP_HASH 4096                    // LDS tier: slots of the id table (load <= 1/2)
 #define SP_THREADS 256
 #define SP_WAVES 4                      // wave tier: wavefronts (= sets) per workgroup
 #define SP_DROPPED INT32_MIN            // deg[] marks of the workgroup form: entry is no member ...
@@ -59,7 +56,7 @@ __global__ __launch_bounds__(64 * SP_WAVES) void subgraph_props_wave_kernel(
     for (int64_t s = (int64_t)blockIdx.x * SP_WAVES + (threadIdx.x >> 6); s < n_sets; s += (int64_t)gridDim.x * SP_WAVES) {
         const int64_t beg = sub_ptr[s];
         const int64_t len = sub_ptr[s + 1] - beg;
-        if (len > SP_WAVE_MAX) {                            // (wave-uniform) the workgroup form owns it ...
+        if (len > SGNN_SET_WAVE_MAX) {                            // (wave-uniform) the workgroup form owns it ...
             if (poison_larger) {                            // ... unless the caller promised there was no such set: marked, never stale
                 if (lane < 6) out_counts[s * 6 + lane] = -1;
                 if (out_core) for (int64_t i = lane; i < len; i += 64) out_core[beg + i] = -1;
@@ -173,42 +170,8 @@ __global__ __launch_bounds__(64 * SP_WAVES) void subgraph_props_wave_kernel(
 }
 
 // ---- sets of more than 64 entries: one workgroup per set, tables in LDS or in the workspace ---------------------------------
-struct SpTables { int32_t* hk; int32_t* hv; int32_t* par; int32_t* deg; int32_t* queue; uint32_t H; };
-
-// The tables are written by atomics and by plain stores of other wavefronts of the workgroup; with the tables in the workspace
-// the fence is device-wide and every read of them is an atomic load, so that none is served from a stale line of the vector L1.
-template <bool LDS> __device__ __forceinline__ void sp_sync() {
-    if (LDS) __threadfence_block(); else __threadfence();
-    __syncthreads();
-}
-
-__device__ __forceinline__ int32_t sp_ld(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ static inline int sp_find(const int32_t* parent, int x) {
-    int p = sp_ld(parent + x);
-    while (p != x) { x = p; p = sp_ld(parent + x); }
-    return x;
-}
-
-__device__ static inline void sp_union(int32_t* par, int x, int y) {
-    while (true) {
-        x = sp_find(par, x);
-        y = sp_find(par, y);
-        if (x == y) return;
-        if (x < y) { const int t = x; x = y; y = t; }       // hook the larger root under the smaller
-        if (atomicCAS(&par[x], x, y) == x) return;
-    }
-}
-
-__device__ static inline int sp_lookup(const SpTables& t, int32_t v) {    // first position of member id v, -1 = not in the set
-    uint32_t h = sgnn_hash32((uint32_t)v) & (t.H - 1);
-    while (true) {
-        const int32_t k = sp_ld(t.hk + h);
-        if (k == v) return sp_ld(t.hv + h);
-        if (k == 0) return -1;
-        h = (h + 1) & (t.H - 1);
-    }
-}
+// (the id table gives the first position of a member's id; how the tables are read and fenced per home: id_table.h)
+struct SpTables { IdTable t; int32_t* par; int32_t* deg; int32_t* queue; };
 
 template <bool LDS>
 __global__ __launch_bounds__(SP_THREADS) void subgraph_props_block_kernel(
@@ -216,8 +179,8 @@ __global__ __launch_bounds__(SP_THREADS) void subgraph_props_block_kernel(
     const int64_t* __restrict__ sub_ptr, const int32_t* __restrict__ sub_nodes, int64_t n_sets, int poison_larger,
     int64_t* __restrict__ out_counts, int32_t* __restrict__ out_core, int32_t* __restrict__ ws)
 {
-    __shared__ int32_t s_hk[LDS ? SP_HASH : 1], s_hv[LDS ? SP_HASH : 1];
-    __shared__ int32_t s_par[LDS ? SP_LDS_MAX : 1], s_deg[LDS ? SP_LDS_MAX : 1], s_queue[LDS ? SP_LDS_MAX : 1];
+    __shared__ int32_t s_hk[LDS ? SGNN_SET_LDS_HASH : 1], s_hv[LDS ? SGNN_SET_LDS_HASH : 1];
+    __shared__ int32_t s_par[LDS ? SGNN_SET_LDS_MAX : 1], s_deg[LDS ? SGNN_SET_LDS_MAX : 1], s_queue[LDS ? SGNN_SET_LDS_MAX : 1];
     __shared__ int32_t s_members, s_self, s_boundary, s_comp, s_qn[2], s_min[2];
     __shared__ unsigned long long s_deg_sum, s_core_sum;
     const int tid = threadIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -225,58 +188,48 @@ __global__ __launch_bounds__(SP_THREADS) void subgraph_props_block_kernel(
     for (int64_t s = blockIdx.x; s < n_sets; s += gridDim.x) {
         const int64_t beg = sub_ptr[s];
         const int64_t len = sub_ptr[s + 1] - beg;
-        if (len <= SP_WAVE_MAX) continue;                   // (block-uniform) the wave form owns it
-        if (LDS && len > SP_LDS_MAX) {
+        if (len <= SGNN_SET_WAVE_MAX) continue;                   // (block-uniform) the wave form owns it
+        if (LDS && len > SGNN_SET_LDS_MAX) {
             if (poison_larger) {                            // no workspace was given: marked, never left as it was
                 if (tid < 6) out_counts[s * 6 + tid] = -1;
                 if (out_core) for (int64_t i = tid; i < len; i += SP_THREADS) out_core[beg + i] = -1;
             }
             continue;
         }
-        if (!LDS && len <= SP_LDS_MAX) continue;
+        if (!LDS && len <= SGNN_SET_LDS_MAX) continue;
         const int n = (int)len;
         const int32_t* nodes = sub_nodes + beg;
         SpTables t;
         if (LDS) {
-            t.hk = s_hk; t.hv = s_hv; t.par = s_par; t.deg = s_deg; t.queue = s_queue; t.H = SP_HASH;
-        } else {                                            // hk[4 total] | hv[4 total] | par[total] | deg[total] | queue[total]
-            t.hk = ws + 4 * beg; t.hv = ws + 4 * total + 4 * beg;
+            t.t = idt_in_lds(s_hk, s_hv); t.par = s_par; t.deg = s_deg; t.queue = s_queue;
+        } else {                                            // keys[4 total] | positions[4 total] | par[total] | deg[total] | queue[total]
+            t.t = idt_in_workspace(ws, beg, n, ws + 4 * total);
             t.par = ws + 8 * total + beg; t.deg = ws + 9 * total + beg; t.queue = ws + 10 * total + beg;
-            uint32_t H = 1;
-            while (H < 2u * (uint32_t)n) H <<= 1;           // < 4 n
-            t.H = H;
         }
-        for (uint32_t i = tid; i < t.H; i += SP_THREADS) { t.hk[i] = 0; t.hv[i] = 0x7fffffff; }
+        idt_clear<true>(t.t, tid, SP_THREADS);
         if (tid == 0) { s_members = 0; s_self = 0; s_boundary = 0; s_comp = 0; s_deg_sum = 0ull; s_core_sum = 0ull; s_qn[0] = 0; s_min[0] = 0x7fffffff; }
-        sp_sync<LDS>();
+        idt_sync<LDS>();
         for (int i = tid; i < n; i += SP_THREADS) {
             const int32_t v = nodes[i];
             const bool member = v >= 1 && (int64_t)v <= max_id && rowptr[v + 1] > rowptr[v];
             t.par[i] = i;
             t.deg[i] = member ? SP_REPEAT : SP_DROPPED;     // (the first position of an id is set to its degree below)
-            if (member) {
-                uint32_t h = sgnn_hash32((uint32_t)v) & (t.H - 1);
-                while (true) {
-                    const int32_t old = atomicCAS(&t.hk[h], 0, v);
-                    if (old == 0 || old == v) { atomicMin(&t.hv[h], i); break; }
-                    h = (h + 1) & (t.H - 1);
-                }
-            }
+            if (member) idt_insert<true>(t.t, v, i);
         }
-        sp_sync<LDS>();
+        idt_sync<LDS>();
         // ---- a member's row by one wavefront: induced degree, boundary, self loop, unions
         for (int i = wave; i < n; i += SP_THREADS / 64) {
-            if (sp_ld(t.deg + i) == SP_DROPPED) continue;   // (wave-uniform)
+            if (idt_ld<LDS>(t.deg + i) == SP_DROPPED) continue;   // (wave-uniform)
             const int32_t v = nodes[i];
-            if (sp_lookup(t, v) != i) continue;             // a repeat: its first position stands for it
+            if (idt_first<LDS>(t.t, v) != i) continue;             // a repeat: its first position stands for it
             const int64_t a = rowptr[v], b = rowptr[v + 1];
             int32_t cnt = 0, bnd = 0, self = 0;
             for (int64_t e = a + lane; e < b; e += 64) {
                 const int32_t u = col[e];
                 if (e > a && col[e - 1] == u) continue;     // an id repeated inside the row counts once
                 if (u == v) { self = 1; continue; }
-                const int j = sp_lookup(t, u);
-                if (j >= 0) { ++cnt; sp_union(t.par, i, j); }
+                const int j = idt_first<LDS>(t.t, u);
+                if (j >= 0) { ++cnt; uf_union<LDS>(t.par, i, j); }
                 else ++bnd;
             }
             cnt = sp_wave_sum(cnt);
@@ -290,10 +243,10 @@ __global__ __launch_bounds__(SP_THREADS) void subgraph_props_block_kernel(
                 atomicAdd(&s_deg_sum, (unsigned long long)cnt);
             }
         }
-        sp_sync<LDS>();
+        idt_sync<LDS>();
         {
             int roots = 0;
-            for (int i = tid; i < n; i += SP_THREADS) roots += (sp_ld(t.deg + i) >= 0 && sp_find(t.par, i) == i) ? 1 : 0;
+            for (int i = tid; i < n; i += SP_THREADS) roots += (idt_ld<LDS>(t.deg + i) >= 0 && uf_find<LDS>(t.par, i) == i) ? 1 : 0;
             if (roots) atomicAdd(&s_comp, roots);
         }
         // ---- level-synchronous peel.  Two barriers per round; the queue length and the smallest remaining degree alternate
@@ -305,7 +258,7 @@ __global__ __launch_bounds__(SP_THREADS) void subgraph_props_block_kernel(
             const int cur = round & 1;
             ++round;
             for (int i = tid; i < n; i += SP_THREADS) {
-                const int32_t d = sp_ld(t.deg + i);
+                const int32_t d = idt_ld<LDS>(t.deg + i);
                 if (d < 0) continue;
                 if (d <= k) {
                     t.deg[i] = -1 - k;
@@ -313,7 +266,7 @@ __global__ __launch_bounds__(SP_THREADS) void subgraph_props_block_kernel(
                     core_sum += (unsigned long long)k;
                 } else atomicMin(&s_min[cur], d);
             }
-            sp_sync<LDS>();
+            idt_sync<LDS>();
             const int qn = s_qn[cur], next_k = s_min[cur];
             if (tid == 0) { s_qn[cur ^ 1] = 0; s_min[cur ^ 1] = 0x7fffffff; }
             alive -= qn;
@@ -321,21 +274,21 @@ __global__ __launch_bounds__(SP_THREADS) void subgraph_props_block_kernel(
             if (qn == 0) k = next_k;                        // nothing left at this level: on to the smallest degree there is
             if (qn == 0 && next_k == 0x7fffffff) break;     // (cannot happen on a symmetric CSR; an asymmetric one must not spin)
             for (int q = wave; q < qn; q += SP_THREADS / 64) {
-                const int i = sp_ld(t.queue + q);
+                const int i = idt_ld<LDS>(t.queue + q);
                 const int32_t v = nodes[i];
                 const int64_t a = rowptr[v], b = rowptr[v + 1];
                 for (int64_t e = a + lane; e < b; e += 64) {
                     const int32_t u = col[e];
                     if (u == v || (e > a && col[e - 1] == u)) continue;
-                    const int j = sp_lookup(t, u);
+                    const int j = idt_first<LDS>(t.t, u);
                     // (members that have left hold a negative mark, and none leaves during this phase)
-                    if (j >= 0 && sp_ld(t.deg + j) >= 0) atomicSub(&t.deg[j], 1);
+                    if (j >= 0 && idt_ld<LDS>(t.deg + j) >= 0) atomicSub(&t.deg[j], 1);
                 }
             }
-            sp_sync<LDS>();
+            idt_sync<LDS>();
         }
         if (core_sum) atomicAdd(&s_core_sum, core_sum);
-        sp_sync<LDS>();
+        idt_sync<LDS>();
         if (tid == 0) {
             int64_t* o = out_counts + s * 6;
             o[0] = s_members;
@@ -347,12 +300,12 @@ __global__ __launch_bounds__(SP_THREADS) void subgraph_props_block_kernel(
         }
         if (out_core) {
             for (int i = tid; i < n; i += SP_THREADS) {
-                int32_t d = sp_ld(t.deg + i);
-                if (d == SP_REPEAT) d = sp_ld(t.deg + sp_lookup(t, nodes[i]));
+                int32_t d = idt_ld<LDS>(t.deg + i);
+                if (d == SP_REPEAT) d = idt_ld<LDS>(t.deg + idt_first<LDS>(t.t, nodes[i]));
                 out_core[beg + i] = d == SP_DROPPED ? -1 : -1 - d;
             }
         }
-        sp_sync<LDS>();                                          // the next set re-initialises the tables
+        idt_sync<LDS>();                                          // the next set re-initialises the tables
     }
 }
 
@@ -370,7 +323,7 @@ extern "C" int sgnn_subgraph_properties(const int64_t* rowptr, const int32_t* co
         return SGNN_ERR_BAD_ARG;
     if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
     if (max_id >= (1ll << 31) - 1) return SGNN_ERR_BAD_ARG;
-    const bool huge = max_len > SP_LDS_MAX;                 // the caller says so: such sets need the workspace
+    const bool huge = max_len > SGNN_SET_LDS_MAX;                 // the caller says so: such sets need the workspace
     if (huge) {
         if (!workspace || workspace_bytes < sgnn_subgraph_properties_workspace_bytes(total_nodes)) return SGNN_ERR_BAD_ARG;
         if (total_nodes >= (1ll << 28)) return SGNN_ERR_SET_TOO_LARGE;       // 4 x total must index with 32 bits
@@ -379,8 +332,8 @@ extern "C" int sgnn_subgraph_properties(const int64_t* rowptr, const int32_t* co
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(subgraph_props_wave_kernel, dim3(sgnn_grid_for(n_sets, SP_WAVES, 1 << 20)), dim3(64 * SP_WAVES), 0, st,
                        rowptr, col_sorted, max_id, rows_simple, sub_ptr, sub_nodes, n_sets,
-                       (max_len > 0 && max_len <= SP_WAVE_MAX) ? 1 : 0, out_counts, out_core);
-    if (max_len <= 0 || max_len > SP_WAVE_MAX)
+                       (max_len > 0 && max_len <= SGNN_SET_WAVE_MAX) ? 1 : 0, out_counts, out_core);
+    if (max_len <= 0 || max_len > SGNN_SET_WAVE_MAX)
         hipLaunchKernelGGL(subgraph_props_block_kernel<true>, dim3((int)(n_sets < 2048 ? n_sets : 2048)), dim3(SP_THREADS), 0, st,
                            rowptr, col_sorted, max_id, sub_ptr, sub_nodes, n_sets, huge ? 0 : 1, out_counts, out_core, (int32_t*)nullptr);
     if (huge)

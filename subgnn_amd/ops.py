@@ -455,11 +455,10 @@ def degree_sequence(g, sets, sort=True, use_degree_dict=True, want_external=True
         check(lib.sgnn_degree_sequence(_ptr(g.rowptr), _ptr(g.col), g.nnz, _ptr(fd), _ptr(sl), _ptr(sets.ptr),
                                        _ptr(sets.nodes), sets.n, max(sets.max_len, 1), 1 if sort else 0, _ptr(out_i),
                                        _ptr(out_e), _ptr(order), _stream()), 'sgnn_degree_sequence')
-    if sets.max_len > CC_LDS_MAX:
+    ws, wsb, total = _huge_ws(lib, sets.max_len, lambda: sets.total, g.device, 'sgnn_degree_sequence_huge_workspace_bytes')
+    if ws is not None:
         # sets beyond the kernels' LDS tables: degrees from the workspace-backed kernel, each such slice ordered by a
         # device sort (they are few: one sort per set)
-        total = int(sets.total)
-        ws, wsb = _huge_ws(lib, total, g.device, 'sgnn_degree_sequence_huge_workspace_bytes')
         check(lib.sgnn_degree_sequence_huge(_ptr(g.rowptr), _ptr(g.col), g.nnz, _ptr(fd), _ptr(sets.ptr), _ptr(sets.nodes),
                                             sets.n, total, _ptr(out_i), _ptr(out_e), _ptr(ws), wsb, _stream()),
               'sgnn_degree_sequence_huge')
@@ -487,12 +486,18 @@ def pack_fused_limits():
     return lim
 
 
-CC_LDS_MAX = 2048          # csrc/graph_sets.hip CC_MAX / PB_MAX: sets up to here keep their tables in LDS
+CC_LDS_MAX = 2048          # csrc/id_table.h SGNN_SET_LDS_MAX: sets up to here keep their tables in LDS
 
 
-def _huge_ws(lib, total, device, query='sgnn_cc_huge_workspace_bytes'):
-    wsb = getattr(lib, query)(int(total))
-    return torch.empty(wsb // 4 + 1, dtype=torch.int32, device=device), wsb
+def _huge_ws(lib, max_len, total, device, query='sgnn_cc_huge_workspace_bytes'):
+    """The workspace tier of a call over ragged sets -> (workspace, its bytes, total entries), or (None, 0, 0) when no set is
+    longer than CC_LDS_MAX.  ``total`` is a callable, called only in the first case: reading the total is that tier's one host
+    round trip."""
+    if max_len <= CC_LDS_MAX:
+        return None, 0, 0
+    n = int(total())
+    wsb = getattr(lib, query)(n)
+    return torch.empty(wsb // 4 + 1, dtype=torch.int32, device=device), wsb, n
 
 
 def cc_labels(g, subs):
@@ -502,9 +507,8 @@ def cc_labels(g, subs):
     out = torch.empty(subs.nodes.numel(), dtype=torch.int32, device=g.device)
     check(lib.sgnn_cc_labels(_ptr(g.rowptr), _ptr(g.col_sorted), g.nnz, _ptr(subs.ptr), _ptr(subs.nodes), subs.n,
                              int(subs.max_len), _ptr(out), _stream()), 'sgnn_cc_labels')
-    if subs.max_len > CC_LDS_MAX:
-        total = int(subs.total)
-        ws, wsb = _huge_ws(lib, total, g.device)
+    ws, wsb, total = _huge_ws(lib, subs.max_len, lambda: subs.total, g.device)
+    if ws is not None:
         check(lib.sgnn_cc_labels_huge(_ptr(g.rowptr), _ptr(g.col_sorted), g.nnz, _ptr(subs.ptr), _ptr(subs.nodes), subs.n, total,
                                       _ptr(out), _ptr(ws), wsb, _stream()), 'sgnn_cc_labels_huge')
     return out
@@ -521,10 +525,7 @@ def subgraph_properties(g, sets, want_core=True):
     counts = torch.empty((sets.n, 6), dtype=torch.int64, device=g.device)
     core = torch.full((sets.nodes.numel(),), -1, dtype=torch.int32, device=g.device) if want_core else None
     max_len = int(sets.max_len)
-    ws, wsb, total = None, 0, 0
-    if max_len > CC_LDS_MAX:
-        total = int(sets.total)
-        ws, wsb = _huge_ws(lib, total, g.device, 'sgnn_subgraph_properties_workspace_bytes')
+    ws, wsb, total = _huge_ws(lib, max_len, lambda: sets.total, g.device, 'sgnn_subgraph_properties_workspace_bytes')
     check(lib.sgnn_subgraph_properties(_ptr(g.rowptr), _ptr(g.col_sorted), g.nnz, g.max_id, 1 if getattr(g, 'simple_rows', False) else 0,
                                        _ptr(sets.ptr), _ptr(sets.nodes), sets.n, max(max_len, 1), total, _ptr(counts), _ptr(core),
                                        _ptr(ws), wsb, _stream()), 'sgnn_subgraph_properties')
@@ -542,12 +543,11 @@ def cc_compact(sub_ptr, sub_nodes, labels, max_sub_len=0, dims_reduce=None, dims
     _req(labels, torch.int32, 'labels')
     S = sub_ptr.numel() - 1
     dev = sub_ptr.device
-    huge = max_sub_len <= 0 or max_sub_len > CC_LDS_MAX      # subgraphs beyond the LDS tables: the workspace-backed kernels too
-    if huge and max_sub_len <= 0:
-        huge = S > 0 and int((sub_ptr[1:] - sub_ptr[:-1]).max().item()) > CC_LDS_MAX
-    if huge:
-        total = int(sub_ptr[-1].item())
-        ws, wsb = _huge_ws(lib, total, dev)
+    longest = max_sub_len
+    if longest <= 0:                                          # not given: read
+        longest = int((sub_ptr[1:] - sub_ptr[:-1]).max().item()) if S > 0 else 0
+    ws, wsb, total = _huge_ws(lib, longest, lambda: sub_ptr[-1].item(), dev)
+    huge = ws is not None                                     # subgraphs beyond the LDS tables: the workspace-backed kernels too
     if dims is not None:
         C, L = int(dims[0]), int(dims[1])
     else:
@@ -883,9 +883,8 @@ def patch_in_border(g, patches):
     check(lib.sgnn_patch_in_border(_ptr(g.rowptr), _ptr(g.col), g.nnz, _ptr(g.node_order), _ptr(g.node_pos),
                                    g.n_nodes, _ptr(patches.ptr), _ptr(patches.nodes), patches.n, _ptr(out), _stream()),
           'sgnn_patch_in_border')
-    if patches.max_len > CC_LDS_MAX:                          # patches beyond the LDS table: membership table in HBM
-        total = int(patches.total)
-        ws, wsb = _huge_ws(lib, total, g.device, 'sgnn_patch_in_border_huge_workspace_bytes')
+    ws, wsb, total = _huge_ws(lib, patches.max_len, lambda: patches.total, g.device, 'sgnn_patch_in_border_huge_workspace_bytes')
+    if ws is not None:                                        # patches beyond the LDS table: membership table in HBM
         check(lib.sgnn_patch_in_border_huge(_ptr(g.rowptr), _ptr(g.col), g.nnz, _ptr(g.node_order), _ptr(g.node_pos),
                                             g.n_nodes, _ptr(patches.ptr), _ptr(patches.nodes), patches.n, total, _ptr(out),
                                             _ptr(ws), wsb, _stream()), 'sgnn_patch_in_border_huge')

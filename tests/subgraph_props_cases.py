@@ -12,9 +12,9 @@ from collections import namedtuple
 import networkx as nx
 import numpy as np
 
-# ---- the constants the dispatch depends on (the host test reads the #defines out of subgraph_props.hip and compares) ----------
-WAVE_MAX = 64                           # #define SP_WAVE_MAX 64: entries one wavefront takes
-LDS_MAX = 2048                          # #define SP_LDS_MAX 2048: entries the workgroup form keeps in LDS (== ops.CC_LDS_MAX)
+# ---- the constants the dispatch depends on (the host test reads the #defines out of csrc/id_table.h and compares) ------------
+WAVE_MAX = 64                           # #define SGNN_SET_WAVE_MAX 64: entries one wavefront takes
+LDS_MAX = 2048                          # #define SGNN_SET_LDS_MAX 2048: entries the workgroup form keeps in LDS (== ops.CC_LDS_MAX)
 SEARCH_THRESHOLD = 512                  # sgnn_degree_sequence_search_threshold(): a list this long is a "hub" list
 
 TIERS = ('wave', 'lds', 'workspace')

@@ -27,11 +27,14 @@ def _same(a, b):
 
 
 def test_constants_are_the_kernels():
-    src = open(os.path.join(REPO, 'subgnn_amd', 'csrc', 'subgraph_props.hip')).read()
-    assert int(re.search(r'#define SP_WAVE_MAX (\d+)', src).group(1)) == SC.WAVE_MAX
-    assert int(re.search(r'#define SP_LDS_MAX (\d+)', src).group(1)) == SC.LDS_MAX
-    gs = open(os.path.join(REPO, 'subgnn_amd', 'csrc', 'graph_sets.hip')).read()
-    assert int(re.search(r'#define CC_MAX (\d+)', gs).group(1)) == SC.LDS_MAX       # the library's tiering
+    # the library's tiering has one definition (id_table.h), and the kernel files use it instead of bounds of their own
+    src = open(os.path.join(REPO, 'subgnn_amd', 'csrc', 'id_table.h')).read()
+    assert int(re.search(r'#define SGNN_SET_WAVE_MAX (\d+)', src).group(1)) == SC.WAVE_MAX
+    assert int(re.search(r'#define SGNN_SET_LDS_MAX (\d+)', src).group(1)) == SC.LDS_MAX
+    for name in ('subgraph_props.hip', 'graph_sets.hip', 'degree_sequence.hip'):
+        user = open(os.path.join(REPO, 'subgnn_amd', 'csrc', name)).read()
+        assert '#include "id_table.h"' in user and 'SGNN_SET_LDS_MAX' in user
+        assert not re.search(r'#define (SP_WAVE_MAX|SP_LDS_MAX|CC_MAX|DSB_MAX|PB_MAX)\b', user), name
     ds = open(os.path.join(REPO, 'subgnn_amd', 'csrc', 'degree_sequence.hip')).read()
     assert int(re.search(r'#define DS_SEARCH (\d+)', ds).group(1)) == SC.SEARCH_THRESHOLD
     from subgnn_amd import ops
