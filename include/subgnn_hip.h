@@ -307,6 +307,39 @@ int sgnn_choice_ragged(const int64_t* ptr, const int32_t* seq, int64_t n_items, 
                        uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * a4-a6 keyed  The same draws for sets that are no rows of a split (prediction on subgraphs outside the dataset).
+ * The reference ties every draw to the row's place in its split: the serial RNG is consumed row by row
+ * (anchor_patch_samplers.py:177,189,206,208) and the PAD rule compares a row with the widest row of the same matrix
+ * (anchor_patch_samplers.py:178,190).  Here the tape item comes from a caller-supplied 64-bit key per set and the PAD rule from
+ * a caller-supplied flag per set, so a set's draw is a function of (seed, stream, key, flag, content) and of nothing else in the
+ * list.
+ *
+ * sgnn_set_keys: out_keys[s] (uint64) = a key of the CONTENT of ragged set s, independent of the order of its entries:
+ *     key = sgnn_mix64( (sum over the n entries v of sgnn_mix64(v)) + (n + 1) * 0x8CB92BA72F3D8DD7 )
+ * in uint64 wrap-around arithmetic (v: the int32 id zero-extended; sgnn_mix64: the tape's splitmix64 finaliser).  The sum
+ * commutes; a repeated entry changes both the sum and n; the empty set has key sgnn_mix64(0x8CB92BA72F3D8DD7).  One wavefront
+ * per set.  Host twin: subgnn_amd.tape.set_key_np.
+ *
+ * sgnn_sample_anchors_ragged_keyed: the law of sgnn_sample_anchors_ragged; set r, slot i draws as tape item
+ * keys[r]*n_slots + i (uint64 wrap-around); row_has_pad (uint8, required) as there.
+ * sgnn_choice_ragged_keyed: the law of sgnn_choice_ragged; list r draws as tape item keys[r].
+ * sgnn_sample_border_anchors_keyed: the law of sgnn_sample_border_anchors on ascending borders of ANY depth
+ * (neigh_sample_border_size: SubGNN.py:673-700) with hops[e] (uint8, aligned with ids) the hop level of entry e: item
+ * keys[r]*n_slots + i, row_has_pad[r] in place of counts[r] < width[0], out_sims = the drawn entry's hop, 0 on PAD.
+ * With keys[r] = item_base + r (and, for the border form, row_has_pad = counts < width, hops = hop) each writes the bits of its
+ * unkeyed twin.  An empty set gives anchor 0 (similarity 0).
+ * ------------------------------------------------------------------------------------- */
+int sgnn_set_keys(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, uint64_t* out_keys, void* stream);
+int sgnn_sample_anchors_ragged_keyed(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets,
+                                     const uint8_t* row_has_pad, const uint64_t* keys, int64_t n_slots,
+                                     uint64_t seed, uint64_t stream_id, int64_t* out, void* stream);
+int sgnn_choice_ragged_keyed(const int64_t* ptr, const int32_t* seq, int64_t n_items, const uint64_t* keys, int64_t n_draws,
+                             uint64_t seed, uint64_t stream_id, int64_t* out, void* stream);
+int sgnn_sample_border_anchors_keyed(const int64_t* ptr, const int32_t* ids, const uint8_t* hops, int64_t n_sets,
+                                     const uint8_t* row_has_pad, const uint64_t* keys, int64_t n_slots, uint64_t seed,
+                                     uint64_t stream_id, int64_t* out_anchor, float* out_sims, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * a1-a3  Triangular random walks.
  * Replaces anchor_patch_samplers.triangular_random_walk / perform_random_walks /
  * sample_structure_anchor_patches (anchor_patch_samplers.py:20-158, 210-243).

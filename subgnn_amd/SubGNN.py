@@ -876,6 +876,9 @@ class SubGNN(nn.Module):
         labels = self.__dict__.pop('_head_labels', None)
         targets = self.__dict__.pop('_head_targets', None)
         x = subgraph_embedding
+        keep = self.__dict__.get('_head_inputs')        # (predict.Predictor: the subgraph embeddings of a request, per chunk)
+        if keep is not None:
+            keep.append(x.detach())
         if (hp.get('fused_forward', True) and hp.get('fused_head', True) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
                 and x.shape[0] > 0 and ops.head_supported(self.lin.out_features, self.lin2.out_features, self.lin3.out_features)
                 and all(l.bias is not None for l in (self.lin, self.lin2, self.lin3))):

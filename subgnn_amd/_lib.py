@@ -69,6 +69,11 @@ SIGNATURES = {
     'sgnn_sample_anchors_padded': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
     'sgnn_sample_anchors_ragged': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_u64, c_u64, c_i64, c_ptr, c_ptr]),
     'sgnn_choice_ragged': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_u64, c_u64, c_i64, c_ptr, c_ptr]),
+    'sgnn_set_keys': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    'sgnn_sample_anchors_ragged_keyed': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
+    'sgnn_choice_ragged_keyed': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
+    'sgnn_sample_border_anchors_keyed': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr,
+                                                 c_ptr]),
     'sgnn_triangular_walks_both': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_dbl, c_u64,
                                            c_u64, c_u64, c_i64, c_i64, c_ptr, c_ptr]),
     'sgnn_triangular_walks': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int,

@@ -52,6 +52,10 @@ __host__ __device__ static inline double sgnn_uniform01(uint64_t h1, uint64_t j)
     uint32_t u = (uint32_t)(sgnn_tape_draw(h1, j) >> 32);
     return (double)u * (1.0 / 4294967296.0);
 }
+// content key of a set from the wrap-around sum of sgnn_mix64 over its n entries (sgnn_set_keys; twin: tape.set_key_np)
+__host__ __device__ static inline uint64_t sgnn_set_key_finish(uint64_t sum, uint64_t n) {
+    return sgnn_mix64(sum + (n + 1) * SGNN_K_DRAW);
+}
 // ---- neighbourhood-anchor law (a4) ------------------------------------------------------------
 // The reference draws, per (row, slot), one N(0,1) variate per column of the padded id row, zeroes
 // the PAD columns and takes the argmax (anchor_patch_samplers.py:177-179,189-191).  In law that is:

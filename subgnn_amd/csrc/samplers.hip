@@ -28,22 +28,37 @@ __global__ __launch_bounds__(256) void sample_anchors_padded_kernel(
     }
 }
 
+// Where a set's tape item comes from: its row number within the whole (possibly sharded) matrix, or a key the caller supplies
+// per set (sgnn_set_keys: a function of the set's content, so the draw does not depend on where the set stands in the list).
+struct ItemOfRow {
+    int64_t base;
+    __device__ uint64_t operator()(int64_t r) const { return (uint64_t)(base + r); }
+};
+struct ItemOfKey {
+    const uint64_t* __restrict__ keys;
+    __device__ uint64_t operator()(int64_t r) const { return keys[r]; }
+};
+
+// the law on one (set, slot): the index of the pick among the set's n ascending entries, -1 = PAD (n == 0 included)
+__device__ static inline int64_t nanchor_pick(uint64_t h0, uint64_t item, int64_t n, bool has_pad) {
+    if (n <= 0) return -1;
+    const uint64_t h1 = sgnn_tape_h1(h0, item);
+    if (has_pad && sgnn_nanchor_allneg(h1, (uint32_t)n)) return -1;
+    return (int64_t)sgnn_nanchor_index(h1, (uint32_t)n);
+}
+
+template <class Item>
 __global__ __launch_bounds__(256) void sample_anchors_ragged_kernel(
     const int64_t* __restrict__ set_ptr, const int32_t* __restrict__ set_nodes, int64_t n_sets,
-    const uint8_t* __restrict__ row_has_pad, int64_t n_slots, uint64_t h0, int64_t item_base, int64_t* __restrict__ out)
+    const uint8_t* __restrict__ row_has_pad, int64_t n_slots, uint64_t h0, Item item, int64_t* __restrict__ out)
 {
     const int64_t total = n_sets * n_slots;
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = t / n_slots;
         const int64_t beg = set_ptr[r];
-        const int64_t n = set_ptr[r + 1] - beg;
         const bool has_pad = row_has_pad ? (row_has_pad[r] != 0) : true;
-        int64_t v = 0;
-        if (n > 0) {
-            const uint64_t h1 = sgnn_tape_h1(h0, (uint64_t)(t + item_base * n_slots));
-            if (!(has_pad && sgnn_nanchor_allneg(h1, (uint32_t)n))) v = set_nodes[beg + sgnn_nanchor_index(h1, (uint32_t)n)];
-        }
-        out[t] = v;
+        const int64_t k = nanchor_pick(h0, item(r) * (uint64_t)n_slots + (uint64_t)(t - r * n_slots), set_ptr[r + 1] - beg, has_pad);
+        out[t] = k < 0 ? 0 : set_nodes[beg + k];
     }
 }
 
@@ -59,39 +74,70 @@ extern "C" int sgnn_sample_anchors_padded(const int64_t* ids, int64_t n_rows, in
     return SGNN_OK;
 }
 
+template <class Item>
+static int launch_sample_anchors_ragged(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, const uint8_t* row_has_pad,
+                                        int64_t n_slots, uint64_t seed, uint64_t stream_id, Item item, int64_t* out, void* stream)
+{
+    if (n_sets == 0 || n_slots == 0) return SGNN_OK;
+    hipLaunchKernelGGL(sample_anchors_ragged_kernel<Item>, dim3(sgnn_grid_for(n_sets * n_slots, 256)), dim3(256), 0,
+                       (hipStream_t)stream, set_ptr, set_nodes, n_sets, row_has_pad, n_slots,
+                       sgnn_tape_h0(seed, stream_id), item, out);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
 extern "C" int sgnn_sample_anchors_ragged(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets,
                                           const uint8_t* row_has_pad, int64_t n_slots,
                                           uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t* out, void* stream)
 {
     if (!set_ptr || !set_nodes || !out || n_sets < 0 || n_slots < 0 || item_base < 0) return SGNN_ERR_BAD_ARG;
-    if (n_sets == 0 || n_slots == 0) return SGNN_OK;
-    hipLaunchKernelGGL(sample_anchors_ragged_kernel, dim3(sgnn_grid_for(n_sets * n_slots, 256)), dim3(256), 0,
-                       (hipStream_t)stream, set_ptr, set_nodes, n_sets, row_has_pad, n_slots,
-                       sgnn_tape_h0(seed, stream_id), item_base, out);
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
+    return launch_sample_anchors_ragged(set_ptr, set_nodes, n_sets, row_has_pad, n_slots, seed, stream_id, ItemOfRow{item_base}, out,
+                                        stream);
+}
+
+extern "C" int sgnn_sample_anchors_ragged_keyed(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets,
+                                                const uint8_t* row_has_pad, const uint64_t* keys, int64_t n_slots,
+                                                uint64_t seed, uint64_t stream_id, int64_t* out, void* stream)
+{
+    if (!set_ptr || !set_nodes || !row_has_pad || !keys || !out || n_sets < 0 || n_slots < 0) return SGNN_ERR_BAD_ARG;
+    return launch_sample_anchors_ragged(set_ptr, set_nodes, n_sets, row_has_pad, n_slots, seed, stream_id, ItemOfKey{keys}, out,
+                                        stream);
 }
 
 // Neighbourhood-border anchors drawn from KEPT sorted borders (sgnn_khop1_border_sorted): the law of
 // sample_anchors_ragged_kernel with has_pad = counts[r] < width[0], and the slot's similarity (the hop level, 0 on PAD) in the
 // same launch -- what khop1_sample_kernel + khop_sample_finish_kernel produce together, without rebuilding the border.
+// Two border forms share the kernel: KEPT one-hop borders (counts beside ptr, the PAD rule from the matrix's width, one hop for
+// all) and KEYED borders of any depth (the caller's row_has_pad, a hop per entry).
+struct BorderOfWidth {
+    const int64_t* __restrict__ counts;
+    const int64_t* __restrict__ width;
+    float hop;
+    __device__ int64_t n(const int64_t*, int64_t r) const { return counts[r]; }
+    __device__ bool has_pad(int64_t r, int64_t n) const { return n < width[0]; }
+    __device__ float sim(int64_t) const { return hop; }
+};
+struct BorderOfFlags {
+    const uint8_t* __restrict__ row_has_pad;
+    const uint8_t* __restrict__ hops;
+    __device__ int64_t n(const int64_t* ptr, int64_t r) const { return ptr[r + 1] - ptr[r]; }
+    __device__ bool has_pad(int64_t r, int64_t) const { return row_has_pad[r] != 0; }
+    __device__ float sim(int64_t e) const { return (float)hops[e]; }
+};
+
+template <class Item, class Border>
 __global__ __launch_bounds__(256) void sample_anchors_border_kernel(
-    const int64_t* __restrict__ ptr, const int32_t* __restrict__ ids, const int64_t* __restrict__ counts, int64_t n_sets,
-    const int64_t* __restrict__ width, int64_t n_slots, uint64_t h0, int64_t item_base, float hop,
-    int64_t* __restrict__ out_anchor, float* __restrict__ out_sims)
+    const int64_t* __restrict__ ptr, const int32_t* __restrict__ ids, int64_t n_sets, Border border, int64_t n_slots, uint64_t h0,
+    Item item, int64_t* __restrict__ out_anchor, float* __restrict__ out_sims)
 {
     const int64_t total = n_sets * n_slots;
-    const int64_t wd = width[0];
     for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = t / n_slots;
-        const int64_t n = counts[r];
-        int64_t v = 0;
-        if (n > 0) {
-            const uint64_t h1 = sgnn_tape_h1(h0, (uint64_t)(t + item_base * n_slots));
-            if (!(n < wd && sgnn_nanchor_allneg(h1, (uint32_t)n))) v = ids[ptr[r] + sgnn_nanchor_index(h1, (uint32_t)n)];
-        }
+        const int64_t n = border.n(ptr, r);
+        const int64_t k = nanchor_pick(h0, item(r) * (uint64_t)n_slots + (uint64_t)(t - r * n_slots), n, border.has_pad(r, n));
+        const int64_t v = k < 0 ? 0 : ids[ptr[r] + k];
         out_anchor[t] = v;
-        out_sims[t] = v == 0 ? 0.f : hop;
+        out_sims[t] = v == 0 ? 0.f : border.sim(ptr[r] + k);
     }
 }
 
@@ -102,9 +148,23 @@ extern "C" int sgnn_sample_border_anchors(const int64_t* ptr, const int32_t* ids
     if (!ptr || !ids || !counts || !width || !out_anchor || !out_sims || n_sets < 0 || n_slots < 0 || item_base < 0 || hop < 0)
         return SGNN_ERR_BAD_ARG;
     if (n_sets == 0 || n_slots == 0) return SGNN_OK;
-    hipLaunchKernelGGL(sample_anchors_border_kernel, dim3(sgnn_grid_for(n_sets * n_slots, 256)), dim3(256), 0,
-                       (hipStream_t)stream, ptr, ids, counts, n_sets, width, n_slots, sgnn_tape_h0(seed, stream_id), item_base,
-                       (float)hop, out_anchor, out_sims);
+    hipLaunchKernelGGL((sample_anchors_border_kernel<ItemOfRow, BorderOfWidth>), dim3(sgnn_grid_for(n_sets * n_slots, 256)), dim3(256),
+                       0, (hipStream_t)stream, ptr, ids, n_sets, BorderOfWidth{counts, width, (float)hop}, n_slots,
+                       sgnn_tape_h0(seed, stream_id), ItemOfRow{item_base}, out_anchor, out_sims);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
+extern "C" int sgnn_sample_border_anchors_keyed(const int64_t* ptr, const int32_t* ids, const uint8_t* hops, int64_t n_sets,
+                                                const uint8_t* row_has_pad, const uint64_t* keys, int64_t n_slots, uint64_t seed,
+                                                uint64_t stream_id, int64_t* out_anchor, float* out_sims, void* stream)
+{
+    if (!ptr || !ids || !hops || !row_has_pad || !keys || !out_anchor || !out_sims || n_sets < 0 || n_slots < 0)
+        return SGNN_ERR_BAD_ARG;
+    if (n_sets == 0 || n_slots == 0) return SGNN_OK;
+    hipLaunchKernelGGL((sample_anchors_border_kernel<ItemOfKey, BorderOfFlags>), dim3(sgnn_grid_for(n_sets * n_slots, 256)), dim3(256),
+                       0, (hipStream_t)stream, ptr, ids, n_sets, BorderOfFlags{row_has_pad, hops}, n_slots,
+                       sgnn_tape_h0(seed, stream_id), ItemOfKey{keys}, out_anchor, out_sims);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
@@ -112,8 +172,9 @@ extern "C" int sgnn_sample_border_anchors(const int64_t* ptr, const int32_t* ids
 // ---------------------------------------------------------------------------------------------
 // a5/a6  np.random.choice(seq, n, replace=True) (reference anchor_patch_samplers.py:206,208,326)
 // ---------------------------------------------------------------------------------------------
+template <class Item>
 __global__ void choice_ragged_kernel(const int64_t* __restrict__ ptr, const int32_t* __restrict__ seq,
-                                     int64_t n_items, int64_t n_draws, uint64_t h0, int64_t item_base,
+                                     int64_t n_items, int64_t n_draws, uint64_t h0, Item item,
                                      int64_t* __restrict__ out)
 {
     const int64_t total = n_items * n_draws;
@@ -122,18 +183,64 @@ __global__ void choice_ragged_kernel(const int64_t* __restrict__ ptr, const int3
         const int64_t beg = ptr[r];
         const int64_t n = ptr[r + 1] - beg;
         int64_t v = 0;
-        if (n > 0) v = seq[beg + sgnn_choice_index(sgnn_tape_h1(h0, (uint64_t)(r + item_base)), (uint64_t)j, (uint32_t)n)];
+        if (n > 0) v = seq[beg + sgnn_choice_index(sgnn_tape_h1(h0, item(r)), (uint64_t)j, (uint32_t)n)];
         out[t] = v;
     }
+}
+
+template <class Item>
+static int launch_choice_ragged(const int64_t* ptr, const int32_t* seq, int64_t n_items, int64_t n_draws, uint64_t seed,
+                                uint64_t stream_id, Item item, int64_t* out, void* stream)
+{
+    if (n_items * n_draws == 0) return SGNN_OK;
+    hipLaunchKernelGGL(choice_ragged_kernel<Item>, dim3(sgnn_grid_for(n_items * n_draws, 256)), dim3(256), 0,
+                       (hipStream_t)stream, ptr, seq, n_items, n_draws, sgnn_tape_h0(seed, stream_id), item, out);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
 }
 
 extern "C" int sgnn_choice_ragged(const int64_t* ptr, const int32_t* seq, int64_t n_items, int64_t n_draws,
                                   uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t* out, void* stream)
 {
     if (!ptr || !seq || !out || n_items < 0 || n_draws < 0 || item_base < 0) return SGNN_ERR_BAD_ARG;
-    if (n_items * n_draws == 0) return SGNN_OK;
-    hipLaunchKernelGGL(choice_ragged_kernel, dim3(sgnn_grid_for(n_items * n_draws, 256)), dim3(256), 0,
-                       (hipStream_t)stream, ptr, seq, n_items, n_draws, sgnn_tape_h0(seed, stream_id), item_base, out);
+    return launch_choice_ragged(ptr, seq, n_items, n_draws, seed, stream_id, ItemOfRow{item_base}, out, stream);
+}
+
+extern "C" int sgnn_choice_ragged_keyed(const int64_t* ptr, const int32_t* seq, int64_t n_items, const uint64_t* keys,
+                                        int64_t n_draws, uint64_t seed, uint64_t stream_id, int64_t* out, void* stream)
+{
+    if (!ptr || !seq || !keys || !out || n_items < 0 || n_draws < 0) return SGNN_ERR_BAD_ARG;
+    return launch_choice_ragged(ptr, seq, n_items, n_draws, seed, stream_id, ItemOfKey{keys}, out, stream);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Content key of a ragged set (subgnn_hip.h, sgnn_set_keys): one wavefront per set, lane l sums sgnn_mix64 of entries l, l + 64,
+// ... (uint64 wrap-around: the sum commutes, so the order of the entries does not matter), a butterfly adds the 64 partial sums.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void set_keys_kernel(const int64_t* __restrict__ set_ptr, const int32_t* __restrict__ set_nodes,
+                                                       int64_t n_sets, uint64_t* __restrict__ out_keys)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
+    for (int64_t s = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); s < n_sets; s += waves) {
+        const int64_t beg = set_ptr[s], n = set_ptr[s + 1] - beg;
+        uint64_t acc = 0;
+        for (int64_t i = lane; i < n; i += 64) acc += sgnn_mix64((uint64_t)(uint32_t)set_nodes[beg + i]);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)acc, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(acc >> 32), d);
+            acc += ((uint64_t)hi << 32) | lo;
+        }
+        if (lane == 0) out_keys[s] = sgnn_set_key_finish(acc, (uint64_t)(n > 0 ? n : 0));
+    }
+}
+
+extern "C" int sgnn_set_keys(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, uint64_t* out_keys, void* stream)
+{
+    if (!set_ptr || !set_nodes || !out_keys || n_sets < 0) return SGNN_ERR_BAD_ARG;
+    if (n_sets == 0) return SGNN_OK;
+    hipLaunchKernelGGL(set_keys_kernel, dim3(sgnn_grid_for(n_sets, 4)), dim3(256), 0, (hipStream_t)stream, set_ptr, set_nodes, n_sets,
+                       out_keys);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }

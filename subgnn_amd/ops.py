@@ -839,6 +839,65 @@ def choice_ragged(sets, n_draws, seed, stream_id, item_base=0):
     return out
 
 
+def set_keys(sets):
+    """Content key of every set -> uint64 (n) (sgnn_set_keys; host twin tape.set_key_np): the same whatever the order of a set's
+    entries.  torch holds them as int64 (the bit pattern is the key)."""
+    lib = _lib.load()
+    _req(sets.ptr, torch.int64, 'ptr')
+    _req(sets.nodes, torch.int32, 'nodes')
+    out = torch.empty(sets.n, dtype=torch.int64, device=sets.ptr.device)
+    check(lib.sgnn_set_keys(_ptr(sets.ptr), _ptr(sets.nodes), sets.n, _ptr(out), _stream()), 'sgnn_set_keys')
+    return out
+
+
+def _req_keys(keys, n, row_has_pad=None):
+    _req(keys, torch.int64, 'keys')
+    if keys.numel() != n:
+        raise ValueError('keys: %d entries for %d sets' % (keys.numel(), n))
+    if row_has_pad is not None:
+        _req(row_has_pad, torch.uint8, 'row_has_pad')
+        if row_has_pad.numel() != n:
+            raise ValueError('row_has_pad: %d entries for %d sets' % (row_has_pad.numel(), n))
+
+
+def sample_anchors_ragged_keyed(sets, keys, row_has_pad, n_slots, seed, stream_id):
+    """sample_anchors_ragged on ascending sets with the tape item of set r taken from ``keys[r]`` (int64 holding the uint64 bit
+    pattern) instead of its row number, and the PAD rule from the caller's ``row_has_pad`` (uint8, one per set)."""
+    lib = _lib.load()
+    _req_keys(keys, sets.n, row_has_pad)
+    out = torch.empty((sets.n, n_slots), dtype=torch.int64, device=sets.ptr.device)
+    check(lib.sgnn_sample_anchors_ragged_keyed(_ptr(sets.ptr), _ptr(sets.nodes), sets.n, _ptr(row_has_pad), _ptr(keys), n_slots,
+                                               seed, stream_id, _ptr(out), _stream()), 'sgnn_sample_anchors_ragged_keyed')
+    return out
+
+
+def choice_ragged_keyed(sets, keys, n_draws, seed, stream_id):
+    """choice_ragged with list r drawing as tape item ``keys[r]``."""
+    lib = _lib.load()
+    _req_keys(keys, sets.n)
+    out = torch.empty((sets.n, n_draws), dtype=torch.int64, device=sets.ptr.device)
+    check(lib.sgnn_choice_ragged_keyed(_ptr(sets.ptr), _ptr(sets.nodes), sets.n, _ptr(keys), n_draws, seed, stream_id, _ptr(out),
+                                       _stream()), 'sgnn_choice_ragged_keyed')
+    return out
+
+
+def draw_border_anchors_keyed(borders, hops, keys, row_has_pad, n_slots, seed, stream_id):
+    """Neighbourhood-border anchors from ascending borders of any depth (``khop_border(want_hops=True)`` through
+    ``sort_ragged(r, extra=hops)``): ``hops`` uint8 aligned with the ids -> (anchors (n, n_slots) int64, similarities float32 =
+    the drawn entry's hop, 0 on PAD)."""
+    lib = _lib.load()
+    _req_keys(keys, borders.n, row_has_pad)
+    _req(hops, torch.uint8, 'hops')
+    if hops.numel() < int(borders.ptr[-1].item()):
+        raise ValueError('hops: fewer entries than border ids')
+    anchor = torch.empty((borders.n, n_slots), dtype=torch.int64, device=borders.ptr.device)
+    sims = torch.empty((borders.n, n_slots), dtype=torch.float32, device=borders.ptr.device)
+    check(lib.sgnn_sample_border_anchors_keyed(_ptr(borders.ptr), _ptr(borders.nodes), _ptr(hops), borders.n, _ptr(row_has_pad),
+                                               _ptr(keys), n_slots, seed, stream_id, _ptr(anchor), _ptr(sims), _stream()),
+          'sgnn_sample_border_anchors_keyed')
+    return anchor, sims
+
+
 def triangular_walks(g, mode, n_items, walk_len, beta, seed, stream_id, patches=None, in_border=None,
                      walks_per_patch=1, kernel=0, item_base=0):
     """mode 0 'graph' / 1 'inside' / 2 'border' -> (n_items, walk_len) int64, PAD filled.

@@ -38,6 +38,20 @@ def read_subgraphs(sub_f):
             split_nodes['test'], split_labels['test'])
 
 
+def label_names(sub_f):
+    """The label strings of ``subgraphs.pth`` by class index: numbered in order of first appearance, as ``read_subgraphs``
+    numbers them (su:24-92) -- ``names[k]`` is what class k is called in the file."""
+    names = {}
+    with open(sub_f) as fin:
+        for line in fin:
+            cols = line.split('\t')
+            if not [n for n in cols[0].split('-') if n != '']:
+                continue
+            for lab in cols[1].split('-'):
+                names.setdefault(lab, len(names))
+    return list(names)
+
+
 def get_border_nodes(graph, patch_nodes):
     """su.get_border_nodes for one patch (list of unique node ids in view order): the patch
     nodes that have an edge leaving the patch (with the reference's id-1 / node-order

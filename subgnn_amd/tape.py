@@ -24,7 +24,8 @@ STREAM_NE_SPLIT = 10
 STREAM_NE_NEG = 11
 STREAM_NE_DROP = 12
 
-SPLIT_CODE = {'train': 0, 'val': 1, 'test': 2}
+# 'predict': requests outside the dataset (predict.py); their draws are keyed by content (set_key_np), not by row number
+SPLIT_CODE = {'train': 0, 'val': 1, 'test': 2, 'predict': 3}
 
 
 def stream_id(kind, split=0, layer=0, epoch=0):
@@ -50,3 +51,26 @@ def draw64_np(seed, stream, item, j):
         h0 = mix(np.uint64((seed & MASK64) ^ ((stream * K_STREAM) & MASK64)))
         h = mix(h0 + np.asarray(item).astype(np.uint64) * np.uint64(K_ITEM))
         return mix(h + np.asarray(j).astype(np.uint64) * np.uint64(K_DRAW))
+
+
+def mix64_np(z):
+    """sgnn_mix64 (csrc/common.h) over a numpy uint64 array."""
+    import numpy as np
+    z = np.asarray(z, dtype=np.uint64)
+    with np.errstate(over='ignore'):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def set_key_np(ids):
+    """Content key of a set of node ids (twin of sgnn_set_keys, include/subgnn_hip.h): independent of the order of the entries,
+
+        key = mix64( sum_v mix64(v)  +  (n + 1) * 0x8CB92BA72F3D8DD7 )      (uint64 wrap-around; n = number of entries)
+
+    so a repeated entry changes the key (sum and n both move) and the empty set has the key mix64(0x8CB92BA72F3D8DD7)."""
+    import numpy as np
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    with np.errstate(over='ignore'):
+        total = mix64_np(ids.astype(np.uint64) & np.uint64(0xFFFFFFFF)).sum(dtype=np.uint64) if ids.size else np.uint64(0)
+        return int(mix64_np(np.uint64(total) + np.uint64(ids.size + 1) * np.uint64(0x8CB92BA72F3D8DD7)))
