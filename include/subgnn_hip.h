@@ -509,6 +509,36 @@ int sgnn_dtw_exact_similarity_live(const int64_t* x_ptr, const int32_t* x_val, i
                                    void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * n1   Nearest rows of a bank of embeddings: the best k of every query's scores, without the Q x N score matrix.
+ * Replaces no reference function (the reference stops at the subgraph embeddings; subgnn_amd/neighbors.py compares them).
+ *   q (Q, D) and bank (N, D) float32, row-major with row strides q_stride / b_stride >= D (in elements); D >= 1, Q >= 1,
+ *   0 <= N < 2^31 (N == 0: bank may be NULL).
+ *   dot(i, j) = the float32 chain acc = fmaf(q[i][d], bank[j][d], acc), d = 0 .. D-1 ascending, from acc = 0
+ *               (v_mfma_f32_32x32x2_f32; tails are padded with zeros, and fmaf(0, 0, acc) == acc)
+ *   SGNN_TOPK_DOT     score = dot                                   higher is better
+ *   SGNN_TOPK_COSINE  score = (dot * q_aux[i]) * b_aux[j]           higher is better; aux = the caller's inverse norms
+ *   SGNN_TOPK_L2      score = (q_aux[i] + b_aux[j]) - 2 * dot       lower is better;  aux = the caller's squared norms
+ *   each operation rounded once, as written.  q_aux (Q) / b_aux (N) float32: required for cosine and l2, ignored for dot.
+ * Order: strict and total -- the better score first, equal scores (-0 == +0) by the smaller bank row, a NaN score behind
+ * every number (by row again).  exclude (Q) int64, nullable: a bank row that query skips, or -1.  Row i of out_score (Q, k)
+ * float32 / out_index (Q, k) int64 lists the first k of that order, best first; slots beyond the candidates hold index -1 and
+ * score -inf (+inf for l2).  A zero score is returned as +0 and a NaN as the quiet NaN 0x7FC00000.  The result does not depend
+ * on `splits`, the number of bank slices that are searched apart and merged: 0 = the library chooses, 1 .. 1024 = as given.
+ * 1 <= k <= sgnn_topk_max_k() (64).  Anything else -- a bad metric, a missing aux vector, a NULL q or output, Q or D < 1, a
+ * workspace smaller than sgnn_topk_rows_workspace_bytes(Q, N, k, splits) (which may be 0: workspace NULL is fine then; < 0
+ * for arguments the call would refuse) -- returns SGNN_ERR_BAD_ARG and writes nothing.  No float atomics; deterministic.
+ * ------------------------------------------------------------------------------------- */
+#define SGNN_TOPK_DOT    0
+#define SGNN_TOPK_COSINE 1
+#define SGNN_TOPK_L2     2
+int64_t sgnn_topk_max_k(void);
+int64_t sgnn_topk_rows_workspace_bytes(int64_t Q, int64_t N, int64_t k, int64_t splits);
+int sgnn_topk_rows(const float* q, int64_t q_stride, int64_t Q, const float* bank, int64_t b_stride, int64_t N,
+                   int64_t D, int64_t k, int metric, const float* q_aux, const float* b_aux, const int64_t* exclude,
+                   int64_t splits, float* out_score, int64_t* out_index, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * a12  CC embedding initialisation: sum or max of member node embeddings.
  * Replaces SubGNN.initialize_cc_embeddings (SubGNN/SubGNN.py:609-622).  E: (n_emb_rows, D) f32.
  * aggregator 0 = sum, 1 = max.  For max, a row shorter than padded_len also competes with the

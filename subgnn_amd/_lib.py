@@ -97,6 +97,10 @@ SIGNATURES = {
     'sgnn_dtw_order_keys': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     'sgnn_dtw_similarity_live': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr,
                                          c_ptr, c_i64, c_ptr]),
+    'sgnn_topk_max_k': (c_i64, []),
+    'sgnn_topk_rows_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    'sgnn_topk_rows': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
+                               c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_dtw_exact_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     'sgnn_dtw_exact_similarity': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr,
                                           c_i64, c_ptr]),

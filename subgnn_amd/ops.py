@@ -3304,3 +3304,87 @@ def link_loss(Z, pos_u, pos_v, neg_u, neg_v, pos_sorted=None):
     sort_edges_by_key(torch.cat([pos_u, pos_v]), Z.shape[0] - 1), kept by a caller whose positives do not change."""
     return _LinkLoss.apply(Z, pos_u, pos_v, neg_u, neg_v, pos_sorted)
 
+
+
+# ---------------------------------------------------------------------------------------
+# nearest rows (csrc/neighbors.hip)
+# ---------------------------------------------------------------------------------------
+TOPK_METRICS = {'dot': 0, 'cosine': 1, 'l2': 2}       # include/subgnn_hip.h SGNN_TOPK_*
+_TOPK_TINY = 1e-30                                     # floor of a squared norm under rsqrt: a zero row scores 0, not NaN
+
+
+def __getattr__(name):
+    if name == 'TOPK_MAX_K':                           # the largest k of topk_rows, asked of the library (sgnn_topk_max_k)
+        value = globals()['TOPK_MAX_K'] = int(_lib.load().sgnn_topk_max_k())
+        return value
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))
+
+
+def topk_aux(x, metric):
+    """The per-row float32 vector topk_rows passes beside ``x``: inverse norms rsqrt(max(sum x^2, tiny)) for 'cosine', squared
+    norms for 'l2', None for 'dot'."""
+    if metric == 'dot':
+        return None
+    sq = (x * x).sum(dim=1, dtype=torch.float32)
+    return torch.rsqrt(sq.clamp_min(_TOPK_TINY)) if metric == 'cosine' else sq
+
+
+def topk_rows(queries, bank, k, metric='cosine', exclude=None, splits=0, q_aux=None, b_aux=None):
+    """The ``k`` rows of ``bank`` (N, D) nearest to every row of ``queries`` (Q, D) -> (scores (Q, k) float32, indices (Q, k)
+    int64), best first, under the strict total order of sgnn_topk_rows (ties by the smaller row, NaN last, fillers -1 / -inf,
+    +inf for 'l2'); no (Q, N) matrix exists at any time.  ``exclude`` (Q,) int64: a bank row each query skips, or -1.
+    ``splits``: bank slices searched apart (0: the library chooses; the result does not depend on it).  ``q_aux`` / ``b_aux``
+    replace the vectors of topk_aux (a bank searched many times computes its own once)."""
+    max_k = globals().get('TOPK_MAX_K') or __getattr__('TOPK_MAX_K')
+    if metric not in TOPK_METRICS:
+        raise ValueError('metric must be one of %s, got %r' % (sorted(TOPK_METRICS), metric))
+    if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > max_k:
+        raise ValueError('k must be an integer in 1 .. %d (TOPK_MAX_K), got %r' % (max_k, k))
+    for name, t in (('queries', queries), ('bank', bank)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError('%s must be a 2-d float32 CUDA/HIP tensor' % name)
+        if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError('%s must have unit column stride' % name)
+    Q, D = queries.shape
+    N = bank.shape[0]
+    if bank.shape[1] != D:
+        raise ValueError('queries are %d wide, the bank %d' % (D, bank.shape[1]))
+    if Q < 1 or D < 1:
+        raise ValueError('queries must have at least one row and one column')
+    if queries.device != bank.device:
+        raise ValueError('queries and bank must be on one device')
+    if not 0 <= int(splits) <= 1024:
+        raise ValueError('splits must be in 0 .. 1024')
+
+    def row_stride(t):
+        s = t.stride(0) if t.shape[0] > 1 else max(t.shape[1], t.stride(0))
+        return s
+    qs, bs = row_stride(queries), row_stride(bank)
+    if qs < D or (N > 0 and bs < D):
+        raise ValueError('rows must not overlap (row stride >= width)')
+    if metric != 'dot':
+        q_aux = topk_aux(queries, metric) if q_aux is None else q_aux
+        b_aux = topk_aux(bank, metric) if b_aux is None else b_aux
+        for name, a, n in (('q_aux', q_aux, Q), ('b_aux', b_aux, N)):
+            _req(a, torch.float32, name)
+            if a.shape != (n,):
+                raise ValueError('%s must have shape (%d,)' % (name, n))
+    else:
+        q_aux = b_aux = None
+    if exclude is not None:
+        _req(exclude, torch.int64, 'exclude')
+        if exclude.shape != (Q,):
+            raise ValueError('exclude must have shape (%d,)' % Q)
+    lib = _lib.load()
+    dev = queries.device
+    scores = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    indices = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    nbytes = int(lib.sgnn_topk_rows_workspace_bytes(Q, N, k, int(splits)))
+    if nbytes < 0:
+        raise ValueError('sgnn_topk_rows_workspace_bytes refused (Q=%d, N=%d, k=%d, splits=%d)' % (Q, N, k, splits))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
+    with torch.cuda.device(dev):
+        check(lib.sgnn_topk_rows(_ptr(queries), qs, Q, _ptr(bank) if N else None, bs, N, D, k, TOPK_METRICS[metric], _ptr(q_aux),
+                                 _ptr(b_aux) if N else None, _ptr(exclude), int(splits), _ptr(scores), _ptr(indices), _ptr(ws),
+                                 nbytes, _stream()), 'sgnn_topk_rows')
+    return scores, indices

@@ -259,6 +259,10 @@ class Predictor:
             out['embeddings'] = emb
         return out
 
+    def nearest(self, index, subgraphs, k=10):
+        """The ``k`` rows of ``index`` (a neighbors.SubgraphIndex) nearest to each requested subgraph: ``index.query``."""
+        return index.query(self, subgraphs, k)
+
     def names_of(self, labels_row):
         """The label strings of one row of ``labels``."""
         name = (lambda k: self.label_names[k]) if self.label_names is not None else str
