@@ -340,6 +340,44 @@ int sgnn_sample_border_anchors_keyed(const int64_t* ptr, const int32_t* ids, con
                                      uint64_t stream_id, int64_t* out_anchor, float* out_sims, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Occlusion sets (no reference counterpart): every leave-one-unit-out variant of every ragged set, for attribution by
+ * occlusion on subgraphs outside the dataset.  The entries of every set are ascending and without repeats (sgnn_sort_sets).
+ *   mode SGNN_OCC_NODE       every entry is a unit; the rank of a unit is its position
+ *   mode SGNN_OCC_COMPONENT  every component is a unit: labels (int32, aligned with set_nodes, required) are those of
+ *                            sgnn_cc_labels -- the smallest position in the set of an entry of the same component; units are
+ *                            ranked by their smallest position (the order of sgnn_cc_compact).  An entry whose label is no
+ *                            position before it that labels itself is a unit of its own (nothing is read out of bounds).
+ * A unit whose removal leaves nothing produces no variant: a set of fewer than two units has none.  Every other unit u
+ * produces the set without u's entries, order kept (so ascending: no sort follows).
+ *
+ * sgnn_occlusion_count: out_units[s], out_variants[s] (int64) and out_len (int64, one slot per ENTRY of the input, zeroed
+ * by the caller): slot set_ptr[s] + u = the length of the variant of unit u of set s, 0 where there is none.  The caller's
+ * exclusive prefix sums are var_ptr (of out_variants, n_sets + 1) and len_scan (of out_len, one per slot): their last
+ * values -- the number of variants and of their entries -- size the outputs of
+ * sgnn_occlusion_write: the variant of unit u of set s is variant v = var_ptr[s] + u: out_ptr[v] = len_scan[set_ptr[s] + u]
+ * (and out_ptr[n_variants] behind the last), its entries in out_nodes from there, out_parent[v] = s, out_unit[v] = u and
+ *     out_keys[v] = sgnn_mix64( sum_parent - (sum over the removed entries r of sgnn_mix64(r)) + (n_variant + 1) * 0x8CB92BA72F3D8DD7 )
+ * in uint64 wrap-around arithmetic: the bits sgnn_set_keys gives for the variant, from one sum over the parent (the variant
+ * is not read again).
+ * A set is read once; all its variants are written from a copy in LDS (up to sgnn_occlusion_lds_max() entries; up to 64 a
+ * wavefront per set), one wavefront writing a variant front to back.  Longer sets are streamed from global memory, in
+ * component mode with their unit tables in the caller's workspace (sgnn_occlusion_workspace_bytes(total_entries) bytes, 16 per
+ * entry of the input; may be NULL when max_set_len says no set is that long).  max_set_len: the longest set, 0 = unknown.
+ * n_sets < 2^31.
+ * ------------------------------------------------------------------------------------- */
+#define SGNN_OCC_NODE 0
+#define SGNN_OCC_COMPONENT 1
+int64_t sgnn_occlusion_lds_max(void);
+int64_t sgnn_occlusion_workspace_bytes(int64_t total_entries);
+int sgnn_occlusion_count(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, int64_t max_set_len, int mode,
+                         const int32_t* labels, int64_t* out_units, int64_t* out_variants, int64_t* out_len,
+                         int64_t total_entries, void* workspace, int64_t workspace_bytes, void* stream);
+int sgnn_occlusion_write(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, int64_t max_set_len, int mode,
+                         const int32_t* labels, const int64_t* var_ptr, const int64_t* len_scan, int64_t n_variants,
+                         int64_t* out_ptr, int32_t* out_nodes, int32_t* out_parent, int32_t* out_unit, uint64_t* out_keys,
+                         int64_t total_entries, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * a1-a3  Triangular random walks.
  * Replaces anchor_patch_samplers.triangular_random_walk / perform_random_walks /
  * sample_structure_anchor_patches (anchor_patch_samplers.py:20-158, 210-243).

@@ -70,6 +70,11 @@ SIGNATURES = {
     'sgnn_sample_anchors_ragged': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_u64, c_u64, c_i64, c_ptr, c_ptr]),
     'sgnn_choice_ragged': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_u64, c_u64, c_i64, c_ptr, c_ptr]),
     'sgnn_set_keys': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    'sgnn_occlusion_lds_max': (c_i64, []),
+    'sgnn_occlusion_workspace_bytes': (c_i64, [c_i64]),
+    'sgnn_occlusion_count': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr]),
+    'sgnn_occlusion_write': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                     c_i64, c_ptr, c_i64, c_ptr]),
     'sgnn_sample_anchors_ragged_keyed': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
     'sgnn_choice_ragged_keyed': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
     'sgnn_sample_border_anchors_keyed': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr,

@@ -850,6 +850,62 @@ def set_keys(sets):
     return out
 
 
+OCCLUSION_MODES = {'node': 0, 'component': 1}          # include/subgnn_hip.h SGNN_OCC_*
+Occlusion = collections.namedtuple('Occlusion', 'sets parent unit keys units variants')
+
+
+def occlusion_lds_max():
+    """Sets up to this many entries are expanded from a copy in LDS; longer ones are streamed (sgnn_occlusion_lds_max)."""
+    return int(_lib.load().sgnn_occlusion_lds_max())
+
+
+def occlusion_sets(sets, unit='node', labels=None):
+    """Every leave-one-unit-out variant of every set of ``sets`` (ascending, without repeats: ``sort_ragged``), a unit being an
+    entry (``unit='node'``) or a component (``unit='component'``: ``labels`` = ``cc_labels`` of the sets) -> Occlusion:
+    ``sets`` the variants as a Ragged (ascending: nothing to sort), ``parent`` / ``unit`` int32 per variant (the set it comes
+    from, the removed unit's rank in it), ``keys`` (int64 holding the uint64 bits of ``set_keys(variants)``), ``units`` /
+    ``variants`` int64 per input set.  A set of fewer than two units has no variants (sgnn_occlusion_count / _write).  One host
+    round trip: the number of variants and of their entries, read together."""
+    lib = _lib.load()
+    if unit not in OCCLUSION_MODES:
+        raise ValueError("unit must be 'node' or 'component', got %r" % (unit,))
+    mode = OCCLUSION_MODES[unit]
+    _req(sets.ptr, torch.int64, 'ptr')
+    _req(sets.nodes, torch.int32, 'nodes')
+    if mode == 1:
+        if labels is None:
+            raise ValueError("unit='component' needs the sets' cc_labels")
+        _req(labels, torch.int32, 'labels')
+        if labels.numel() < sets.nodes.numel():
+            raise ValueError('labels: fewer entries than set nodes')
+    dev = sets.ptr.device
+    n, slots, max_len = sets.n, sets.nodes.numel(), max(int(sets.max_len), 1)             # (0 would say: not known)
+    ws, wsb, total = (None, 0, 0)
+    if mode == 1 and max_len > occlusion_lds_max():
+        total = slots
+        wsb = int(lib.sgnn_occlusion_workspace_bytes(total))
+        ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=dev)
+    units = torch.zeros(n, dtype=torch.int64, device=dev)
+    variants = torch.zeros(n, dtype=torch.int64, device=dev)
+    lens = torch.zeros(max(slots, 1), dtype=torch.int64, device=dev)
+    head = (_ptr(sets.ptr), _ptr(sets.nodes), n, max_len, mode, _ptr(labels) if mode == 1 else None)
+    check(lib.sgnn_occlusion_count(*head, _ptr(units), _ptr(variants), _ptr(lens), total, _ptr(ws), wsb, _stream()),
+          'sgnn_occlusion_count')
+    var_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(variants, 0, out=var_ptr[1:])
+    len_scan = torch.zeros(lens.numel() + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(lens, 0, out=len_scan[1:])
+    V, T = torch.stack((var_ptr[-1], len_scan[-1])).tolist()                  # the one host round trip
+    out_ptr = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+    out_nodes = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
+    parent = torch.empty(V, dtype=torch.int32, device=dev)
+    rank = torch.empty(V, dtype=torch.int32, device=dev)
+    keys = torch.empty(V, dtype=torch.int64, device=dev)
+    check(lib.sgnn_occlusion_write(*head, _ptr(var_ptr), _ptr(len_scan), V, _ptr(out_ptr), _ptr(out_nodes), _ptr(parent),
+                                   _ptr(rank), _ptr(keys), total, _ptr(ws), wsb, _stream()), 'sgnn_occlusion_write')
+    return Occlusion(Ragged(out_ptr, out_nodes, max_len=max(max_len - 1, 0)), parent, rank, keys, units, variants)
+
+
 def _req_keys(keys, n, row_has_pad=None):
     _req(keys, torch.int64, 'keys')
     if keys.numel() != n:

@@ -123,24 +123,42 @@ class Predictor:
         np.cumsum(counts, out=ptr[1:])
         return ptr, flat.astype(np.int32)
 
-    def prepare(self, subgraphs):
-        """Components, anchors and similarities of the request, installed on the model as split 'predict' ->
-        hotpath.PassState (``attrs`` / ``per_split`` hold them by the names forward reads; ``subgraphs``: the mapped node sets, ascending)."""
-        f = self.freeze()
-        m = self.model
-        hp, g, dev = m.hparams, m.networkx_graph, m.device
-        seed, ep, L = f['seed'], f['epoch'], hp['n_layers']
+    def request_sets(self, subgraphs):
+        """``map_subgraphs`` on the device: the request as an ops.Ragged of ascending sets (what ``prepare_sets`` takes)."""
         if len(subgraphs) == 0:
             raise ValueError('no subgraphs')
         ptr, flat = self.map_subgraphs(subgraphs)
+        dev = self.model.device
+        return ops.Ragged(torch.from_numpy(ptr).to(dev), torch.from_numpy(flat).to(dev), max_len=int((ptr[1:] - ptr[:-1]).max()))
+
+    def prepare(self, subgraphs):
+        """Components, anchors and similarities of the request, installed on the model as split 'predict' ->
+        hotpath.PassState (``attrs`` / ``per_split`` hold them by the names forward reads; ``subgraphs``: the mapped node sets, ascending)."""
+        return self.prepare_sets(self.request_sets(subgraphs))
+
+    def prepare_sets(self, sets, epoch_offset=0, want_lists=True, sub_keys=None):
+        """``prepare`` behind the mapping: ``sets`` is a device ops.Ragged of non-empty ascending sets of model ids without repeats
+        (``request_sets``; ``ops.occlusion_sets`` of one).  ``want_lists=False`` leaves ``st.subgraphs`` None: the sets stay on
+        the device.  ``sub_keys``: the sets' ``ops.set_keys``, where the caller holds them.
+
+        ``epoch_offset=d`` is draw d of the request: the neighbourhood anchors (internal and border) and the position-internal
+        anchors are drawn from the streams of resample epoch ``epoch + d``, so draw 0 is ``prepare``'s answer and every draw is
+        keyed by content as that one is.  The model's own shared anchors are NOT redrawn: the position-external anchors, the
+        structure patches and the layers' picks of them stay as restored, whatever the draw (they belong to the trained model,
+        not to the request)."""
+        f = self.freeze()
+        m = self.model
+        hp, g, dev = m.hparams, m.networkx_graph, m.device
+        seed, ep, L = f['seed'], f['epoch'] + int(epoch_offset), hp['n_layers']
+        if sets.n == 0:
+            raise ValueError('no subgraphs')
 
         def stream(kind, l):
             return tape.stream_id(kind, SPLIT, l, ep)
 
         st = hotpath.PassState(SPLIT)
-        st.subgraphs = [a.tolist() for a in np.split(flat, ptr[1:-1])]
-        subs = ops.sort_ragged(ops.Ragged(torch.from_numpy(ptr).to(dev), torch.from_numpy(flat).to(dev),
-                                          max_len=int((ptr[1:] - ptr[:-1]).max())))
+        st.subgraphs = sets.to_lists() if want_lists else None
+        subs = sets
         labels = ops.cc_labels(g, subs)
         cc_ids = subgraph_utils.components_from_labels(subs.ptr, subs.nodes, labels, subs.max_len)
         S, C, Lc = cc_ids.shape
@@ -149,7 +167,9 @@ class Predictor:
         cc_ids._sgnn_mask, cc_ids._sgnn_mask_u8 = real, real.reshape(-1).to(torch.uint8)
         st.attrs[SPLIT + '_cc_ids'] = cc_ids
         cc_sets = ops.sort_ragged(ops.Ragged.from_padded(cc_ids.reshape(S * C, Lc)))
-        cc_keys, sub_keys = ops.set_keys(cc_sets), ops.set_keys(subs)
+        cc_keys = ops.set_keys(cc_sets)
+        if sub_keys is None:
+            sub_keys = ops.set_keys(subs)
         st.keys = {'components': cc_keys.view(S, C), 'subgraphs': sub_keys}
         sims = {}
         if hp['use_neighborhood']:
@@ -238,14 +258,25 @@ class Predictor:
             m.train(was_training)
         return torch.cat(logits, 0), torch.cat(kept, 0)
 
-    def predict(self, subgraphs, batch_size=None, return_embeddings=False):
+    def _probabilities(self, logits):
+        return torch.sigmoid(logits) if self.model.multilabel else torch.softmax(logits, dim=-1)
+
+    def predict(self, subgraphs, batch_size=None, return_embeddings=False, draws=1):
         """-> dict: ``logits`` (R, K) float32, ``probabilities`` (softmax; sigmoid for a multi-label model), ``labels`` (argmax
         (R,) int64; for a multi-label model the (R, K) bool of the float32 expression sigmoid(x) > 0.5, as the fused head
         evaluates it), ``subgraphs`` (the mapped node sets: model ids, ascending) and, on request, ``embeddings`` (R, H).  ``batch_size`` only chunks
-        the forward pass."""
+        the forward pass.  ``draws=E > 1`` adds ``logits_mean``, ``logits_std`` (the sample standard deviation) and
+        ``probabilities_mean`` over draws 0 .. E - 1 of the request's own anchors (``prepare_sets``: ``epoch_offset``); everything
+        else stays draw 0's."""
+        return self._predict_sets(self.request_sets(subgraphs), batch_size, return_embeddings, draws)[0]
+
+    def _predict_sets(self, sets, batch_size, return_embeddings, draws):
+        """``predict`` on device sets -> (its dict, the float32 logits of every draw (E, R, K))."""
         if batch_size is not None and int(batch_size) <= 0:
             raise ValueError('batch_size must be positive')
-        st = self.prepare(subgraphs)
+        if int(draws) != draws or int(draws) <= 0:
+            raise ValueError('draws must be a positive integer')
+        st = self.prepare_sets(sets)
         logits, emb = self.forward_prepared(st, batch_size)
         logits = logits.float()
         if self.model.multilabel:
@@ -257,7 +288,22 @@ class Predictor:
         out = {'logits': logits, 'probabilities': prob, 'labels': labels, 'subgraphs': st.subgraphs}
         if return_embeddings:
             out['embeddings'] = emb
-        return out
+        per_draw = torch.stack([logits] + [self.draw_logits(sets, d, batch_size) for d in range(1, int(draws))])
+        if draws > 1:
+            out['logits_mean'], out['logits_std'] = per_draw.mean(dim=0), per_draw.std(dim=0, unbiased=True)
+            out['probabilities_mean'] = self._probabilities(per_draw).mean(dim=0)
+        return out, per_draw
+
+    def draw_logits(self, sets, draw, batch_size=None, sub_keys=None):
+        """The float32 logits of device sets at draw ``draw`` (``prepare_sets`` + ``forward_prepared``; no Python lists)."""
+        st = self.prepare_sets(sets, epoch_offset=draw, want_lists=False, sub_keys=sub_keys)
+        return self.forward_prepared(st, batch_size)[0].float()
+
+    def explain(self, subgraphs, unit='node', target=None, draws=1, batch_size=None, max_variants=65536):
+        """Leave-one-out attribution of every request over its nodes or components: ``explain.explain``."""
+        from . import explain as _explain
+        return _explain.explain(self, subgraphs, unit=unit, target=target, draws=draws, batch_size=batch_size,
+                                max_variants=max_variants)
 
     def nearest(self, index, subgraphs, k=10):
         """The ``k`` rows of ``index`` (a neighbors.SubgraphIndex) nearest to each requested subgraph: ``index.query``."""
