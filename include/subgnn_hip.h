@@ -524,6 +524,31 @@ int sgnn_dtw_similarity_live(const int64_t* x_ptr, const int32_t* x_val, int64_t
                              const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
                              int tie_order, int kernel, const int32_t* x_order, const int64_t* x_live_range, float* out,
                              void* workspace, int64_t workspace_bytes, void* stream);
+/* The x side prepared ONCE, for a caller whose x rows hold the same values from call to call (the degree sequences of a
+ * split's components): sgnn_dtw_prepare_rows writes the value and reciprocal pyramids and the lengths of the x rows --
+ * what sgnn_dtw_similarity builds into its workspace on every call -- into ``rows``, a device buffer of
+ * sgnn_dtw_rows_bytes(n_x, max_x_len) bytes that the caller owns and keeps alive, and describes it in ``header``, HOST
+ * memory of sgnn_dtw_rows_header_words() int64 that the caller keeps with it (magic, layout, n_x, max_x_len, the buffer's
+ * address and size).  The layout is the one the kernel picked by (max_x_len, kernel, x_order) reads: the register kernel's
+ * (positions follow x_order) or the general kernel's (positions are the row numbers).
+ * sgnn_dtw_similarity_rows / _rows_live are sgnn_dtw_similarity / _live without the x pyramid launch: they take the header
+ * instead of x_ptr / x_val, with the SAME n_x, max_x_len, kernel and x_order (the same permutation) as the preparation; a
+ * header that was not filled by sgnn_dtw_prepare_rows, or for another row count, length bound or layout, is
+ * SGNN_ERR_BAD_ARG -- nothing is launched.  Their workspace (sgnn_dtw_rows_workspace_bytes) does not hold the x pyramids.
+ * Same values as sgnn_dtw_similarity, bit for bit (the same kernels read the same pyramids). */
+int64_t sgnn_dtw_rows_bytes(int64_t n_x, int64_t max_x_len);
+int64_t sgnn_dtw_rows_header_words(void);
+int64_t sgnn_dtw_rows_workspace_bytes(int64_t n_x, int64_t max_x_len, int64_t n_y, int64_t max_y_len);
+int sgnn_dtw_prepare_rows(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len, int kernel,
+                          const int32_t* x_order, void* rows, int64_t rows_bytes, int64_t* header, void* stream);
+int sgnn_dtw_similarity_rows(const int64_t* rows_header, int64_t n_x, int64_t max_x_len,
+                             const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                             int tie_order, int kernel, const int32_t* x_order, float* out, void* workspace,
+                             int64_t workspace_bytes, void* stream);
+int sgnn_dtw_similarity_rows_live(const int64_t* rows_header, int64_t n_x, int64_t max_x_len,
+                                  const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                                  int tie_order, int kernel, const int32_t* x_order, const int64_t* x_live_range, float* out,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * a11x Structure similarity with the EXACT distance: 1 / (1 + DTW(x, y, dist=calc_dist)), the minimum over all warp
@@ -545,6 +570,20 @@ int sgnn_dtw_exact_similarity_live(const int64_t* x_ptr, const int32_t* x_val, i
                                    const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
                                    int kernel, const int32_t* x_order, const int64_t* x_live_range, float* out,
                                    void* workspace, int64_t workspace_bytes, void* stream);
+/* The x side (value + 1, reciprocals, lengths) prepared once: as sgnn_dtw_prepare_rows / sgnn_dtw_similarity_rows above, with
+ * the same header form (sgnn_dtw_rows_header_words() words) and a magic of its own -- a buffer of one is refused by the other. */
+int64_t sgnn_dtwx_rows_bytes(int64_t n_x, int64_t max_x_len);
+int64_t sgnn_dtwx_rows_workspace_bytes(int64_t n_x, int64_t max_x_len, int64_t n_y, int64_t max_y_len);
+int sgnn_dtwx_prepare_rows(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len, int kernel,
+                                const int32_t* x_order, void* rows, int64_t rows_bytes, int64_t* header, void* stream);
+int sgnn_dtwx_similarity_rows(const int64_t* rows_header, int64_t n_x, int64_t max_x_len,
+                                   const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                                   int kernel, const int32_t* x_order, float* out, void* workspace,
+                                   int64_t workspace_bytes, void* stream);
+int sgnn_dtwx_similarity_rows_live(const int64_t* rows_header, int64_t n_x, int64_t max_x_len,
+                                        const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                                        int kernel, const int32_t* x_order, const int64_t* x_live_range, float* out,
+                                        void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
  * n1   Nearest rows of a bank of embeddings: the best k of every query's scores, without the Q x N score matrix.

@@ -218,11 +218,19 @@ class SubGNN(nn.Module):
                                                         self.test_sub_G_label.view(-1))))) + 1
         for sp in ('train', 'val', 'test'):                                   # ids become 1-based
             setattr(self, sp + '_sub_G', [[n + 1 for n in sg] for sg in getattr(self, sp + '_sub_G')])
+        self._forget_split_caches()
         pre = torch.load(root / self.embedding_path, map_location='cpu')
         self.hparams['node_embed_size'] = pre.shape[1]
         table = torch.cat((torch.zeros(1, pre.shape[1]), pre.float()), 0)
         self.node_embeddings = nn.Embedding.from_pretrained(table, freeze=self.hparams['freeze_node_embeds'],
                                                             padding_idx=config.PAD_VALUE)
+
+    def _forget_split_caches(self):
+        """The splits' subgraph lists were (re)read: what hotpath keeps per split of them (SplitFacts) is dropped."""
+        from . import hotpath
+        hotpath.forget_split_facts(self)
+        for sp in ('train', 'val', 'test'):
+            self.__dict__.pop('_subs_' + sp, None)
 
     def _read_memory(self, mem):
         """In-memory twin of read_data for synthetic inputs: ``mem`` = dict(graph=DeviceGraph,
@@ -232,6 +240,7 @@ class SubGNN(nn.Module):
         for sp in ('train', 'val', 'test'):
             setattr(self, sp + '_sub_G', mem['sub_G'].get(sp, []))
             setattr(self, sp + '_sub_G_label', mem['labels'].get(sp, torch.zeros(0, dtype=torch.int64)))
+        self._forget_split_caches()
         self.multilabel, self.multilabel_binarizer = False, None
         self.num_classes = mem.get('num_classes') or int(max(int(l.max()) for l in mem['labels'].values() if l.numel() > 0)) + 1
         pre = mem['embeddings']

@@ -102,6 +102,21 @@ SIGNATURES = {
     'sgnn_dtw_order_keys': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     'sgnn_dtw_similarity_live': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr,
                                          c_ptr, c_i64, c_ptr]),
+    'sgnn_dtw_rows_bytes': (c_i64, [c_i64, c_i64]),
+    'sgnn_dtw_rows_header_words': (c_i64, []),
+    'sgnn_dtw_rows_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    'sgnn_dtw_prepare_rows': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    'sgnn_dtw_similarity_rows': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr,
+                                         c_i64, c_ptr]),
+    'sgnn_dtw_similarity_rows_live': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr, c_ptr,
+                                              c_ptr, c_i64, c_ptr]),
+    'sgnn_dtwx_rows_bytes': (c_i64, [c_i64, c_i64]),
+    'sgnn_dtwx_rows_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i64]),
+    'sgnn_dtwx_prepare_rows': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    'sgnn_dtwx_similarity_rows': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr,
+                                               c_i64, c_ptr]),
+    'sgnn_dtwx_similarity_rows_live': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr,
+                                                    c_ptr, c_i64, c_ptr]),
     'sgnn_topk_max_k': (c_i64, []),
     'sgnn_topk_rows_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     'sgnn_topk_rows': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,

@@ -978,34 +978,81 @@ extern "C" int sgnn_dtw_order_keys(const int64_t* x_ptr, const int32_t* x_val, i
     return SGNN_OK;
 }
 
-static int dtw_run(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len,
-                   const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
-                   int tie_order, int kernel, const int32_t* x_order, const int64_t* x_live, float* out, void* workspace,
-                   int64_t workspace_bytes, void* stream)
-{
-    if (!x_ptr || !x_val || !y_ptr || !y_val || !out || !workspace || n_x < 0 || n_y < 0) return SGNN_ERR_BAD_ARG;
-    if (tie_order < 0 || tie_order > 2 || kernel < 0 || kernel > 1) return SGNN_ERR_BAD_ARG;
+// ---- the x side prepared once ------------------------------------------------------------------
+// The value and reciprocal pyramids and the lengths of the x rows depend on the rows (and, for the register kernel, on the
+// processing order) only: a caller whose rows stay the same from call to call prepares them once into a buffer of its own
+// (sgnn_dtw_prepare_rows) and calls the ``_rows`` entries, which launch the y pyramid and the DP kernel only.  The plain
+// entries prepare into their per-call workspace and take the same path.
+// The buffer: a header of DTW_ROWS_HEAD int64 words, written by the HOST into the caller's host-side ``header`` (it is what a
+// later call checks: no device read-back), and on the device values (n_x * XL doubles), reciprocals (the same), lengths.
+#define DTW_ROWS_MAGIC 0x53474e4e44545752ll       // "SGNNDTWR"
+#define DTW_ROWS_HEAD 8
+enum { DTW_ROWS_ORDERED = 1, DTW_ROWS_NATURAL = 2 };   // the register kernel's layout (positions follow x_order) / the general kernel's
+
+static inline int64_t dtw_rows_bytes(int64_t n_x, const DtwLayout& L) { return 2 * n_x * L.XL * 8 + dtw_align8(n_x * 4); }
+static inline int dtw_rows_layout(int64_t max_x_len, int kernel, const int32_t* x_order) {
+    return (max_x_len <= DTW_R && kernel == 0 && x_order) ? DTW_ROWS_ORDERED : DTW_ROWS_NATURAL;
+}
+
+extern "C" int64_t sgnn_dtw_rows_bytes(int64_t n_x, int64_t max_x_len) {
     if (max_x_len < 1) max_x_len = 1;
-    if (max_y_len < 1) max_y_len = 1;
-    if (max_x_len > 32767 || max_y_len > 32767) return SGNN_ERR_SET_TOO_LARGE;
-    if (workspace_bytes < sgnn_dtw_workspace_bytes(n_x, max_x_len, n_y, max_y_len)) return SGNN_ERR_BAD_ARG;
-    if (n_x * n_y == 0) return SGNN_OK;
+    if (n_x < 0) n_x = 0;
+    return dtw_rows_bytes(n_x, dtw_layout(max_x_len, 1));
+}
+
+extern "C" int64_t sgnn_dtw_rows_header_words(void) { return DTW_ROWS_HEAD; }
+
+extern "C" int64_t sgnn_dtw_rows_workspace_bytes(int64_t n_x, int64_t max_x_len, int64_t n_y, int64_t max_y_len) {
+    return sgnn_dtw_workspace_bytes(n_x, max_x_len, n_y, max_y_len) - sgnn_dtw_rows_bytes(n_x, max_x_len);
+}
+
+static void dtw_prepare_rows(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len, const DtwLayout& L,
+                             int layout, const int32_t* x_order, char* rows, hipStream_t st)
+{
+    double* xpyr = (double*)rows;
+    int32_t* xlen = (int32_t*)(rows + 2 * n_x * L.XL * 8);
+    dtw_launch_pyramid(x_ptr, x_val, n_x, max_x_len, L.XL, 1, xpyr, xpyr + n_x * L.XL, xlen,
+                       layout == DTW_ROWS_ORDERED ? x_order : (const int32_t*)nullptr, st);
+}
+
+extern "C" int sgnn_dtw_prepare_rows(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len, int kernel,
+                                     const int32_t* x_order, void* rows, int64_t rows_bytes, int64_t* header, void* stream)
+{
+    if (!x_ptr || !x_val || !rows || !header || n_x < 0 || kernel < 0 || kernel > 1) return SGNN_ERR_BAD_ARG;
+    if (max_x_len < 1) max_x_len = 1;
+    if (max_x_len > 32767) return SGNN_ERR_SET_TOO_LARGE;
+    const DtwLayout L = dtw_layout(max_x_len, 1);
+    if (rows_bytes < dtw_rows_bytes(n_x, L)) return SGNN_ERR_BAD_ARG;
+    const int layout = dtw_rows_layout(max_x_len, kernel, x_order);
+    header[0] = 0;                                       // (not valid until the launch has been queued)
+    if (n_x > 0) {
+        dtw_prepare_rows(x_ptr, x_val, n_x, max_x_len, L, layout, x_order, (char*)rows, (hipStream_t)stream);
+        SGNN_CHECK_LAUNCH();
+    }
+    header[1] = layout; header[2] = n_x; header[3] = max_x_len; header[4] = (int64_t)(intptr_t)rows; header[5] = rows_bytes;
+    header[6] = header[7] = 0;
+    header[0] = DTW_ROWS_MAGIC;
+    return SGNN_OK;
+}
+
+// y pyramid + the DP launch over prepared x rows.  ``workspace``: scratch, y pyramids, y lengths (sgnn_dtw_rows_workspace_bytes)
+static int dtw_run_rows(const char* rows, int64_t n_x, int64_t max_x_len,
+                        const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                        int tie_order, int kernel, const int32_t* x_order, const int64_t* x_live, float* out, void* workspace,
+                        hipStream_t st)
+{
     const DtwLayout L = dtw_layout(max_x_len, max_y_len);
-    hipStream_t st = (hipStream_t)stream;
     char* w = (char*)workspace;
     const int64_t scratch = dtw_scratch_bytes(L);
     double* wd = (double*)w;
     int32_t* wi = (int32_t*)(w + DTW_NT * L.n_dbl * 8);
     uint32_t* wb = (uint32_t*)(w + DTW_NT * (L.n_dbl * 8 + dtw_align8(L.n_i32 * 4)));
     uint32_t* wq = (uint32_t*)w;           w += scratch;
-    double* xpyr = (double*)w;             w += 2 * n_x * L.XL * 8;          // values, then reciprocals of value + 1
-    double* ypyr = (double*)w;             w += 2 * n_y * L.YL * 8;
-    int32_t* xlen = (int32_t*)w;           w += dtw_align8(n_x * 4);
+    double* ypyr = (double*)w;             w += 2 * n_y * L.YL * 8;          // values, then reciprocals of value + 1
     int32_t* ylen = (int32_t*)w;
+    const double* xpyr = (const double*)rows;
+    const int32_t* xlen = (const int32_t*)(rows + 2 * n_x * L.XL * 8);
     const bool use_reg = max_x_len <= DTW_R && kernel == 0;
-    dtw_launch_pyramid(x_ptr, x_val, n_x, max_x_len, L.XL, 1, xpyr, xpyr + n_x * L.XL, xlen,
-                       use_reg ? x_order : (const int32_t*)nullptr, st);
-    SGNN_CHECK_LAUNCH();
     dtw_launch_pyramid(y_ptr, y_val, n_y, max_y_len, L.YL, 0, ypyr, ypyr + n_y * L.YL, ylen, (const int32_t*)nullptr, st);
     SGNN_CHECK_LAUNCH();
     if (use_reg) {
@@ -1040,6 +1087,47 @@ static int dtw_run(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int6
     return SGNN_OK;
 }
 
+static int dtw_run(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len,
+                   const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                   int tie_order, int kernel, const int32_t* x_order, const int64_t* x_live, float* out, void* workspace,
+                   int64_t workspace_bytes, void* stream)
+{
+    if (!x_ptr || !x_val || !y_ptr || !y_val || !out || !workspace || n_x < 0 || n_y < 0) return SGNN_ERR_BAD_ARG;
+    if (tie_order < 0 || tie_order > 2 || kernel < 0 || kernel > 1) return SGNN_ERR_BAD_ARG;
+    if (max_x_len < 1) max_x_len = 1;
+    if (max_y_len < 1) max_y_len = 1;
+    if (max_x_len > 32767 || max_y_len > 32767) return SGNN_ERR_SET_TOO_LARGE;
+    if (workspace_bytes < sgnn_dtw_workspace_bytes(n_x, max_x_len, n_y, max_y_len)) return SGNN_ERR_BAD_ARG;
+    if (n_x * n_y == 0) return SGNN_OK;
+    // the x rows prepared into the tail of the per-call workspace, then the one launch path
+    const DtwLayout L = dtw_layout(max_x_len, max_y_len);
+    char* rows = (char*)workspace + sgnn_dtw_rows_workspace_bytes(n_x, max_x_len, n_y, max_y_len);
+    dtw_prepare_rows(x_ptr, x_val, n_x, max_x_len, L, dtw_rows_layout(max_x_len, kernel, x_order), x_order, rows, (hipStream_t)stream);
+    SGNN_CHECK_LAUNCH();
+    return dtw_run_rows(rows, n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, tie_order, kernel, x_order, x_live, out, workspace,
+                        (hipStream_t)stream);
+}
+
+static int dtw_run_prepared(const int64_t* header, int64_t n_x, int64_t max_x_len,
+                            const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                            int tie_order, int kernel, const int32_t* x_order, const int64_t* x_live, float* out, void* workspace,
+                            int64_t workspace_bytes, void* stream)
+{
+    if (!header || !y_ptr || !y_val || !out || !workspace || n_x < 0 || n_y < 0) return SGNN_ERR_BAD_ARG;
+    if (tie_order < 0 || tie_order > 2 || kernel < 0 || kernel > 1) return SGNN_ERR_BAD_ARG;
+    if (max_x_len < 1) max_x_len = 1;
+    if (max_y_len < 1) max_y_len = 1;
+    if (max_x_len > 32767 || max_y_len > 32767) return SGNN_ERR_SET_TOO_LARGE;
+    // the buffer must be one that sgnn_dtw_prepare_rows filled for these rows AND for the layout the kernel picked here reads
+    if (header[0] != DTW_ROWS_MAGIC || header[2] != n_x || header[3] != max_x_len || !header[4]) return SGNN_ERR_BAD_ARG;
+    if (header[1] != dtw_rows_layout(max_x_len, kernel, x_order)) return SGNN_ERR_BAD_ARG;
+    if (header[5] < dtw_rows_bytes(n_x, dtw_layout(max_x_len, 1))) return SGNN_ERR_BAD_ARG;
+    if (workspace_bytes < sgnn_dtw_rows_workspace_bytes(n_x, max_x_len, n_y, max_y_len)) return SGNN_ERR_BAD_ARG;
+    if (n_x * n_y == 0) return SGNN_OK;
+    return dtw_run_rows((const char*)(intptr_t)header[4], n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, tie_order, kernel, x_order,
+                        x_live, out, workspace, (hipStream_t)stream);
+}
+
 extern "C" int sgnn_dtw_similarity(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len,
                                    const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
                                    int tie_order, int kernel, const int32_t* x_order, float* out, void* workspace,
@@ -1057,6 +1145,25 @@ extern "C" int sgnn_dtw_similarity_live(const int64_t* x_ptr, const int32_t* x_v
     if (x_live_range && !x_order) return SGNN_ERR_BAD_ARG;
     return dtw_run(x_ptr, x_val, n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, tie_order, kernel, x_order, x_live_range, out,
                    workspace, workspace_bytes, stream);
+}
+
+extern "C" int sgnn_dtw_similarity_rows(const int64_t* rows_header, int64_t n_x, int64_t max_x_len,
+                                        const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                                        int tie_order, int kernel, const int32_t* x_order, float* out, void* workspace,
+                                        int64_t workspace_bytes, void* stream)
+{
+    return dtw_run_prepared(rows_header, n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, tie_order, kernel, x_order, nullptr, out,
+                            workspace, workspace_bytes, stream);
+}
+
+extern "C" int sgnn_dtw_similarity_rows_live(const int64_t* rows_header, int64_t n_x, int64_t max_x_len,
+                                             const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                                             int tie_order, int kernel, const int32_t* x_order, const int64_t* x_live_range,
+                                             float* out, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (x_live_range && !x_order) return SGNN_ERR_BAD_ARG;
+    return dtw_run_prepared(rows_header, n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, tie_order, kernel, x_order, x_live_range,
+                            out, workspace, workspace_bytes, stream);
 }
 
 SGNN_DEFINE_WARM(dtw)

@@ -178,32 +178,69 @@ __global__ __launch_bounds__(DTWX_THREADS, MINB) void dtw_exact_reg_kernel(
 #define DTWX_MINB20 2
 #define DTWX_MINB32 2
 
-static int dtw_exact_run(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len,
-                         const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
-                         int kernel, const int32_t* x_order, const int64_t* x_live, float* out, void* workspace,
-                         int64_t workspace_bytes, void* stream)
-{
-    if (!x_ptr || !x_val || !y_ptr || !y_val || !out || !workspace || n_x < 0 || n_y < 0) return SGNN_ERR_BAD_ARG;
-    if (kernel < 0 || kernel > 1) return SGNN_ERR_BAD_ARG;
+// ---- the x side prepared once (as dtw.hip's sgnn_dtw_prepare_rows: same header form, its own magic) -------------------------
+// device buffer: value + 1 (n_x * MX doubles), reciprocals (the same), lengths
+#define DTWX_ROWS_MAGIC 0x53474e4e44545758ll      // "SGNNDTWX"
+#define DTWX_ROWS_HEAD 8
+enum { DTWX_ROWS_ORDERED = 1, DTWX_ROWS_NATURAL = 2 };  // the register kernels' layout (positions follow x_order) / the general kernel's
+
+static inline int dtwx_rows_layout(int64_t MX, int kernel, const int32_t* x_order) {
+    return (MX <= DTWX_R && kernel == 0 && x_order) ? DTWX_ROWS_ORDERED : DTWX_ROWS_NATURAL;
+}
+
+extern "C" int64_t sgnn_dtwx_rows_bytes(int64_t n_x, int64_t max_x_len) {
     if (max_x_len < 1) max_x_len = 1;
-    if (max_y_len < 1) max_y_len = 1;
-    if (max_x_len > 32767 || max_y_len > 32767) return SGNN_ERR_SET_TOO_LARGE;
-    if (workspace_bytes < sgnn_dtw_exact_workspace_bytes(n_x, max_x_len, n_y, max_y_len)) return SGNN_ERR_BAD_ARG;
-    if (n_x * n_y == 0) return SGNN_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t MX = max_x_len, MY = max_y_len;
+    if (n_x < 0) n_x = 0;
+    return 2 * n_x * max_x_len * 8 + dtwx_align8(n_x * 4);
+}
+
+extern "C" int64_t sgnn_dtwx_rows_workspace_bytes(int64_t n_x, int64_t max_x_len, int64_t n_y, int64_t max_y_len) {
+    return sgnn_dtw_exact_workspace_bytes(n_x, max_x_len, n_y, max_y_len) - sgnn_dtwx_rows_bytes(n_x, max_x_len);
+}
+
+static void dtw_exact_prepare_rows(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t MX, int layout,
+                                   const int32_t* x_order, char* rows, hipStream_t st)
+{
+    double* xa = (double*)rows;
+    double* xr = xa + n_x * MX;
+    int32_t* xlen = (int32_t*)(rows + 2 * n_x * MX * 8);
+    hipLaunchKernelGGL(dtw_exact_prepare_kernel, dim3(sgnn_grid_for(n_x * MX, 256)), dim3(256), 0, st, x_ptr, x_val, n_x, MX, 1,
+                       xa, xr, xlen, layout == DTWX_ROWS_ORDERED ? x_order : (const int32_t*)nullptr);
+}
+
+extern "C" int sgnn_dtwx_prepare_rows(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len, int kernel,
+                                           const int32_t* x_order, void* rows, int64_t rows_bytes, int64_t* header, void* stream)
+{
+    if (!x_ptr || !x_val || !rows || !header || n_x < 0 || kernel < 0 || kernel > 1) return SGNN_ERR_BAD_ARG;
+    if (max_x_len < 1) max_x_len = 1;
+    if (max_x_len > 32767) return SGNN_ERR_SET_TOO_LARGE;
+    if (rows_bytes < sgnn_dtwx_rows_bytes(n_x, max_x_len)) return SGNN_ERR_BAD_ARG;
+    const int layout = dtwx_rows_layout(max_x_len, kernel, x_order);
+    header[0] = 0;                                       // (not valid until the launch has been queued)
+    if (n_x > 0) {
+        dtw_exact_prepare_rows(x_ptr, x_val, n_x, max_x_len, layout, x_order, (char*)rows, (hipStream_t)stream);
+        SGNN_CHECK_LAUNCH();
+    }
+    header[1] = layout; header[2] = n_x; header[3] = max_x_len; header[4] = (int64_t)(intptr_t)rows; header[5] = rows_bytes;
+    header[6] = header[7] = 0;
+    header[0] = DTWX_ROWS_MAGIC;
+    return SGNN_OK;
+}
+
+// the y side + the DP launch over prepared x rows.  ``workspace``: the general kernel's columns, y values, y reciprocals, y lengths
+static int dtw_exact_run_rows(const char* rows, int64_t n_x, int64_t MX, const int64_t* y_ptr, const int32_t* y_val, int64_t n_y,
+                              int64_t MY, int kernel, const int32_t* x_order, const int64_t* x_live, float* out, void* workspace,
+                              hipStream_t st)
+{
     char* w = (char*)workspace;
     double* wd = (double*)w;               w += DTWX_NT * MX * 8;
-    double* xa = (double*)w;               w += n_x * MX * 8;
-    double* xr = (double*)w;               w += n_x * MX * 8;
     double* ya = (double*)w;               w += n_y * MY * 8;
     double* yr = (double*)w;               w += n_y * MY * 8;
-    int32_t* xlen = (int32_t*)w;           w += dtwx_align8(n_x * 4);
     int32_t* ylen = (int32_t*)w;
+    const double* xa = (const double*)rows;
+    const double* xr = xa + n_x * MX;
+    const int32_t* xlen = (const int32_t*)(rows + 2 * n_x * MX * 8);
     const bool use_reg = MX <= DTWX_R && kernel == 0;
-    hipLaunchKernelGGL(dtw_exact_prepare_kernel, dim3(sgnn_grid_for(n_x * MX, 256)), dim3(256), 0, st, x_ptr, x_val, n_x, MX, 1,
-                       xa, xr, xlen, use_reg ? x_order : (const int32_t*)nullptr);
-    SGNN_CHECK_LAUNCH();
     hipLaunchKernelGGL(dtw_exact_prepare_kernel, dim3(sgnn_grid_for(n_y * MY, 256)), dim3(256), 0, st, y_ptr, y_val, n_y, MY, 0,
                        ya, yr, ylen, (const int32_t*)nullptr);
     SGNN_CHECK_LAUNCH();
@@ -223,6 +260,46 @@ static int dtw_exact_run(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x
     return SGNN_OK;
 }
 
+static int dtw_exact_run(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len,
+                         const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                         int kernel, const int32_t* x_order, const int64_t* x_live, float* out, void* workspace,
+                         int64_t workspace_bytes, void* stream)
+{
+    if (!x_ptr || !x_val || !y_ptr || !y_val || !out || !workspace || n_x < 0 || n_y < 0) return SGNN_ERR_BAD_ARG;
+    if (kernel < 0 || kernel > 1) return SGNN_ERR_BAD_ARG;
+    if (max_x_len < 1) max_x_len = 1;
+    if (max_y_len < 1) max_y_len = 1;
+    if (max_x_len > 32767 || max_y_len > 32767) return SGNN_ERR_SET_TOO_LARGE;
+    if (workspace_bytes < sgnn_dtw_exact_workspace_bytes(n_x, max_x_len, n_y, max_y_len)) return SGNN_ERR_BAD_ARG;
+    if (n_x * n_y == 0) return SGNN_OK;
+    // the x rows prepared into the tail of the per-call workspace, then the one launch path
+    char* rows = (char*)workspace + sgnn_dtwx_rows_workspace_bytes(n_x, max_x_len, n_y, max_y_len);
+    dtw_exact_prepare_rows(x_ptr, x_val, n_x, max_x_len, dtwx_rows_layout(max_x_len, kernel, x_order), x_order, rows,
+                           (hipStream_t)stream);
+    SGNN_CHECK_LAUNCH();
+    return dtw_exact_run_rows(rows, n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, kernel, x_order, x_live, out, workspace,
+                              (hipStream_t)stream);
+}
+
+static int dtw_exact_run_prepared(const int64_t* header, int64_t n_x, int64_t max_x_len,
+                                  const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                                  int kernel, const int32_t* x_order, const int64_t* x_live, float* out, void* workspace,
+                                  int64_t workspace_bytes, void* stream)
+{
+    if (!header || !y_ptr || !y_val || !out || !workspace || n_x < 0 || n_y < 0) return SGNN_ERR_BAD_ARG;
+    if (kernel < 0 || kernel > 1) return SGNN_ERR_BAD_ARG;
+    if (max_x_len < 1) max_x_len = 1;
+    if (max_y_len < 1) max_y_len = 1;
+    if (max_x_len > 32767 || max_y_len > 32767) return SGNN_ERR_SET_TOO_LARGE;
+    if (header[0] != DTWX_ROWS_MAGIC || header[2] != n_x || header[3] != max_x_len || !header[4]) return SGNN_ERR_BAD_ARG;
+    if (header[1] != dtwx_rows_layout(max_x_len, kernel, x_order)) return SGNN_ERR_BAD_ARG;
+    if (header[5] < sgnn_dtwx_rows_bytes(n_x, max_x_len)) return SGNN_ERR_BAD_ARG;
+    if (workspace_bytes < sgnn_dtwx_rows_workspace_bytes(n_x, max_x_len, n_y, max_y_len)) return SGNN_ERR_BAD_ARG;
+    if (n_x * n_y == 0) return SGNN_OK;
+    return dtw_exact_run_rows((const char*)(intptr_t)header[4], n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, kernel, x_order, x_live,
+                              out, workspace, (hipStream_t)stream);
+}
+
 extern "C" int sgnn_dtw_exact_similarity(const int64_t* x_ptr, const int32_t* x_val, int64_t n_x, int64_t max_x_len,
                                          const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
                                          int kernel, const int32_t* x_order, float* out, void* workspace,
@@ -240,6 +317,25 @@ extern "C" int sgnn_dtw_exact_similarity_live(const int64_t* x_ptr, const int32_
     if (x_live_range && !x_order) return SGNN_ERR_BAD_ARG;
     return dtw_exact_run(x_ptr, x_val, n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, kernel, x_order, x_live_range, out,
                          workspace, workspace_bytes, stream);
+}
+
+extern "C" int sgnn_dtwx_similarity_rows(const int64_t* rows_header, int64_t n_x, int64_t max_x_len,
+                                              const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                                              int kernel, const int32_t* x_order, float* out, void* workspace,
+                                              int64_t workspace_bytes, void* stream)
+{
+    return dtw_exact_run_prepared(rows_header, n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, kernel, x_order, nullptr, out,
+                                  workspace, workspace_bytes, stream);
+}
+
+extern "C" int sgnn_dtwx_similarity_rows_live(const int64_t* rows_header, int64_t n_x, int64_t max_x_len,
+                                                   const int64_t* y_ptr, const int32_t* y_val, int64_t n_y, int64_t max_y_len,
+                                                   int kernel, const int32_t* x_order, const int64_t* x_live_range, float* out,
+                                                   void* workspace, int64_t workspace_bytes, void* stream)
+{
+    if (x_live_range && !x_order) return SGNN_ERR_BAD_ARG;
+    return dtw_exact_run_prepared(rows_header, n_x, max_x_len, y_ptr, y_val, n_y, max_y_len, kernel, x_order, x_live_range, out,
+                                  workspace, workspace_bytes, stream);
 }
 
 SGNN_DEFINE_WARM(dtw_exact)

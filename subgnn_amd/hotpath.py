@@ -324,6 +324,7 @@ class PassState:
         self.per_split = {}        # attribute name (a dict keyed by split on the model) -> this split's value
         self.sim_cols = None       # (anchors_structure, {layer: device index tensor}) when new patches were drawn
         self.dtw_inputs = None     # between prepare_pass(defer_dtw=True) and finish_pass: what the DTW launches read
+        self.x_fixed = False       # the component degree sequences among them are the split's kept ones (SplitFacts)
         self.bfs_checks = []       # hinted position-channel searches to verify before the pass is consumed (_verify_bfs)
         self.pool_reused = False   # the pass re-picked from an earlier pass's structure-patch pool (prepare_pass(pool=...))
 
@@ -385,37 +386,62 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
         side = main
     t.mark('start')
     # ---- components (main) ---------------------------------------------------------------
-    subs = ops.Ragged.from_lists(getattr(model, split + '_sub_G'), dev) if not hasattr(model, '_subs_' + split) \
-        else getattr(model, '_subs_' + split)
-    setattr(model, '_subs_' + split, subs)
-    labels = ops.cc_labels(g, subs)
-    # the padded (components per subgraph, component length) is a property of the split's subgraph lists (and, sharded,
-    # of all ranks'): read back on the first pass, kept afterwards -- one statistics launch and one host round trip less
-    kept = model.__dict__.setdefault('_cc_dims', {})
-    tag = (id(getattr(model, split + '_sub_G')), subs.n)
-    hit = kept.get(split)
-    cc_ids = subgraph_utils.components_from_labels(subs.ptr, subs.nodes, labels, subs.max_len,
-                                                   dims_reduce=shard.reduce_max if shard is not None else None,
-                                                   dims=hit[1] if hit is not None and hit[0] == tag else None)
-    kept[split] = (tag, tuple(cc_ids.shape[1:]))
+    sub_g = getattr(model, split + '_sub_G')
+    srcs = model.__dict__.setdefault('_subs_src', {})
+    if not hasattr(model, '_subs_' + split) or srcs.get(split, sub_g) is not sub_g or getattr(model, '_subs_' + split).n != len(sub_g):
+        setattr(model, '_subs_' + split, ops.Ragged.from_lists(sub_g, dev))
+    srcs[split] = sub_g                                         # (the list the device copy was made from: another, or one
+    #                                                             that changed its length, is uploaded again)
+    subs = getattr(model, '_subs_' + split)
+    # What depends on the split's subgraph lists and the graph only -- the components with what hangs on them, the component
+    # sets, their sorted form and their degree sequences -- is computed by the split's first pass and kept (SplitFacts):
+    # a steady pass launches nothing for it.  hparams['keep_split_facts'] = False: every pass computes it, as before.
+    keep_facts = bool(hp.get('keep_split_facts', True))
+    facts = _split_facts(model, split, sub_g, subs.n, g, shard) if keep_facts else None
+    # (a recording that finds nothing kept computes per pass: what it allocates belongs to the recording)
+    facts_new = keep_facts and facts is None and not torch.cuda.is_current_stream_capturing()
+    once = '(first pass only)' if facts_new else ''
+    det = bool(getattr(model, '_deterministic', ops.DETERMINISTIC))
+    if facts is not None:
+        facts.wait(main)
+        cc_ids, cc_sets, real = facts.cc_ids, facts.cc_sets, facts.real
+        S, C, Lc = cc_ids.shape
+    else:
+        labels = ops.cc_labels(g, subs)
+        # the padded (components per subgraph, component length) is a property of the split's subgraph lists (and, sharded,
+        # of all ranks'): read back on the first pass, kept afterwards -- one statistics launch and one host round trip less
+        kept = model.__dict__.setdefault('_cc_dims', {})
+        tag = (id(sub_g), subs.n)
+        hit = kept.get(split)
+        cc_ids = subgraph_utils.components_from_labels(subs.ptr, subs.nodes, labels, subs.max_len,
+                                                       dims_reduce=shard.reduce_max if shard is not None else None,
+                                                       dims=hit[1] if hit is not None and hit[0] == tag else None)
+        kept[split] = (tag, tuple(cc_ids.shape[1:]))
+        S, C, Lc = cc_ids.shape
     st.attrs[split + '_cc_ids'] = cc_ids
-    S, C, Lc = cc_ids.shape
-    if getattr(model, '_deterministic', ops.DETERMINISTIC):
+    if det:
         # the component-embedding backward scatters per member id in sorted order: the members of a split's
         # components are the same every pass, so their order is computed on the first pass and kept
         mo = model.__dict__.setdefault('_cc_member_order', {})
+        if facts_new:
+            mo.pop(split, None)                                 # (new facts: maybe another list of the same size)
         if mo.get(split) is None or mo[split][0].numel() != cc_ids.numel():
             mo[split] = ops.sort_edges_by_key(cc_ids.reshape(-1).to(torch.int32), g.max_id)
         cc_ids._sgnn_member_order = mo[split]
-    cc_ids._sgnn_ids32 = cc_ids.reshape(-1).to(torch.int32)        # what the component-embedding kernel reads
+    elif getattr(cc_ids, '_sgnn_member_order', None) is not None:
+        del cc_ids._sgnn_member_order                           # (kept components of a model that was deterministic before)
     base = shard.start if shard is not None else 0             # global number of this rank's first subgraph
-    cc_sets = ops.Ragged.from_padded(cc_ids.reshape(S * C, Lc))
-    real = (cc_ids[:, :, 0] != 0)
-    # which component rows are real, as forward reads it (SubGNN._forward: bool (S, C) and its uint8 twin): made here, beside the
-    # sampling stages, and carried on the tensor -- two small launches less per training half
-    cc_ids._sgnn_mask = real
-    cc_ids._sgnn_mask_u8 = real.reshape(-1).to(torch.uint8)
-    t.mark('components')
+    if facts is None:
+        cc_ids._sgnn_ids32 = cc_ids.reshape(-1).to(torch.int32)        # what the component-embedding kernel reads
+        cc_sets = ops.Ragged.from_padded(cc_ids.reshape(S * C, Lc))
+        real = (cc_ids[:, :, 0] != 0)
+        # which component rows are real, as forward reads it (SubGNN._forward: bool (S, C) and its uint8 twin): made here, beside
+        # the sampling stages, and carried on the tensor -- two small launches less per training half
+        cc_ids._sgnn_mask = real
+        cc_ids._sgnn_mask_u8 = real.reshape(-1).to(torch.uint8)
+        if facts_new:
+            facts = _keep_split_facts(model, split, SplitFacts(sub_g, subs.n, g, shard, cc_ids, cc_sets, real))
+        t.mark('components' + once)
     # dispatch order of the component sets, heaviest (largest total degree) first: a property of the
     # split's subgraphs and the graph, computed once per split and kept.  The set kernels whose cost is
     # the members' degree sum (degree sequences, border BFS) take their sets in this order.
@@ -426,9 +452,10 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
     set_order = orders[split]
     sims = {}
     a_sets = ai = ae = None
-    det = bool(getattr(model, '_deterministic', ops.DETERMINISTIC))
     # ---- side stream: position channel + structure patches / walks -------------------------
     side.wait_stream(main)
+    if facts is not None and side is not main:
+        facts.wait(side)
     with torch.cuda.stream(side):
         # The structure patches keep the walks' full width (no trim to the longest walk: that was a host round trip, and
         # with a second prepared pass queued on this stream the host waited for that pass's DTW launch there).
@@ -588,8 +615,14 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
     # ---- main stream: neighbourhood channel + component degree sequences --------------------
     if hp['use_neighborhood']:
         k = hp['neigh_sample_border_size']
-        has_pad_c = (cc_sets.lengths < Lc).to(torch.uint8)
-        cc_canon = ops.sort_ragged(cc_sets)                     # the draw ranks the ascending members
+        if facts is not None and facts.cc_canon is not None:
+            has_pad_c, cc_canon = facts.has_pad_c, facts.cc_canon
+        else:
+            has_pad_c = (cc_sets.lengths < Lc).to(torch.uint8)
+            cc_canon = ops.sort_ragged(cc_sets)                 # the draw ranks the ascending members
+            if facts is not None and not torch.cuda.is_current_stream_capturing():
+                facts.has_pad_c, facts.cc_canon = has_pad_c, cc_canon
+                facts.built()
         ni, nb, plans = {}, {}, {}
         border = _kept_border(model, split, subs, cc_sets, k)
         for l in range(L):
@@ -634,10 +667,17 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
         st.per_split['_mpn_edge_plans'] = plans
         t.mark('border_bfs+N_anchors')
     ci = ce = None
+    x_fixed = False                                             # the DTW launches' x side comes from kept facts (finish_pass)
     if hp['use_structure'] and pool is None:
-        ci, ce = ops.degree_sequence(g, cc_sets, sort=True, use_degree_dict=g.full_degree is not None,
-                                     order=set_order)
-        t.mark('degree_sequences')
+        if facts is not None and facts.ci is not None:
+            ci, ce, x_fixed = facts.ci, facts.ce, True
+        else:
+            ci, ce = ops.degree_sequence(g, cc_sets, sort=True, use_degree_dict=g.full_degree is not None,
+                                         order=set_order)
+            if facts is not None and not torch.cuda.is_current_stream_capturing():
+                facts.ci, facts.ce, x_fixed = ci, ce, True
+                facts.built()
+            t.mark('degree_sequences' + once)
     if hp['use_structure'] and side is not main:
         main.wait_event(patch_ev)
         _hand_over(main, structure_anchors)
@@ -654,6 +694,7 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
     # overlaps with them instead of delaying them (6 250 subgraphs: the main chain reaches this point after ~1.3 ms, the search
     # ends at ~1.6).  At the benchmark's 50k subgraphs the search has long finished when the main chain gets here.
     st.dtw_inputs = (cc_sets, ci, ce, a_sets, ai, ae, (S, C)) if (hp['use_structure'] and pool is None) else None
+    st.x_fixed = x_fixed
     if pool is not None and hp['use_structure']:
         st.attrs[split + '_int_struc_similarities'], st.attrs[split + '_bor_struc_similarities'] = pool['int_sims'], pool['bor_sims']
     if late_bfs:
@@ -678,7 +719,109 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
     return st
 
 
-KEPT_BORDER_BYTES = 4 << 30         # ids of a split's kept one-hop borders (hparams['kept_border_bytes']; 0: never keep)
+class SplitFacts:
+    """What a pass computes from a split's subgraph lists and the graph ALONE -- no draw, no resample epoch, no embedding table
+    enters it -- built by the split's first pass and taken by every later one (model.__dict__['_split_facts'][split]):
+
+        cc_ids (S, C, Lc)   with what hangs on it: _sgnn_ids32, _sgnn_mask, _sgnn_mask_u8 (and _sgnn_member_order)
+        cc_sets, real       the component rows as ragged sets; which rows are real
+        has_pad_c, cc_canon the neighbourhood draws' pad flags and ascending members   (None until a pass needs them)
+        ci, ce              the components' internal / external degree sequences        (None until a pass needs them)
+
+    The key: the subgraph LIST OBJECT (held here and compared by identity -- an ``id()`` alone is recycled once a list is
+    freed), the subgraph count, the graph object and, sharded, (start, world).  Anything else builds new facts.
+    ``ready``: the event behind the launches that wrote the tensors; a pass on another stream waits for it once and tells the
+    allocator (``wait``), like ops.KeptBorders."""
+
+    def __init__(self, sub_g, n, graph, shard, cc_ids, cc_sets, real):
+        self.sub_g, self.n, self.graph = sub_g, n, graph
+        self.shard_key = self.shard_key_of(shard)
+        self.cc_ids, self.cc_sets, self.real = cc_ids, cc_sets, real
+        self.has_pad_c = self.cc_canon = self.ci = self.ce = None
+        self.ready, self._waited = None, set()
+        self.built()
+
+    @staticmethod
+    def shard_key_of(shard):
+        return None if shard is None else (int(shard.start), int(shard.world))
+
+    def matches(self, sub_g, n, graph, shard):
+        return self.sub_g is sub_g and self.n == n and len(sub_g) == n and self.graph is graph \
+            and self.shard_key == self.shard_key_of(shard)
+
+    def tensors(self):
+        cc = self.cc_ids
+        out = [cc, self.real, self.has_pad_c, self.ci, self.ce, self.cc_sets.ptr, self.cc_sets.nodes]
+        out += [getattr(cc, nm, None) for nm in ('_sgnn_ids32', '_sgnn_mask_u8')]
+        if self.cc_canon is not None:
+            out += [self.cc_canon.ptr, self.cc_canon.nodes]
+        return [t for t in out if t is not None]
+
+    @property
+    def nbytes(self):
+        seen = {}
+        for t in self.tensors():
+            seen[t.data_ptr()] = t.numel() * t.element_size()
+        return sum(seen.values())
+
+    def built(self):
+        """Tensors were added by launches just queued on the current stream."""
+        if not self.cc_ids.is_cuda:
+            return                            # (host tensors -- the keying tests: nothing to order)
+        self.ready = torch.cuda.Event()
+        self.ready.record()
+        self._waited = {torch.cuda.current_stream().cuda_stream}
+
+    def wait(self, stream):
+        """Order ``stream`` behind the build (once per stream: the tensors never change afterwards)."""
+        key = stream.cuda_stream
+        if key in self._waited or torch.cuda.is_current_stream_capturing():
+            return                            # (torch synchronises the device before a capture begins: the build has ended, and
+            #                                   a wait for an outside event would invalidate the capture)
+        self._waited.add(key)
+        for t in self.tensors():
+            t.record_stream(stream)           # (facts that are replaced are freed while this stream may still read them)
+        if not self.ready.query():
+            stream.wait_event(self.ready)
+
+
+def _split_facts(model, split, sub_g, n, graph, shard):
+    """The split's kept facts if they are those of THIS list, count, graph and shard, else None (the caller builds)."""
+    facts = model.__dict__.get('_split_facts', {}).get(split)
+    return facts if facts is not None and facts.matches(sub_g, n, graph, shard) else None
+
+
+def _keep_split_facts(model, split, facts):
+    kept = model.__dict__.setdefault('_split_facts', {})
+    if kept.get(split) is not None:
+        # other lists than the kept ones: whatever else was derived from the old components goes with them
+        for name in ('_dtw_group_rows', '_degseq_order'):
+            model.__dict__.get(name, {}).pop(split, None)
+        widths = model.__dict__.get('_border_width', {})
+        for k in [k for k in widths if k[0] == split]:
+            widths.pop(k)
+    kept[split] = facts
+    return facts
+
+
+def forget_split_facts(model, split=None):
+    """Drop the kept facts of ``split`` (None: of every split): the next pass computes them again.  For code that changes a
+    split's subgraphs in a way the key cannot see (editing the list in place)."""
+    kept = model.__dict__.get('_split_facts')
+    if kept:
+        for sp in ([split] if split is not None else list(kept)):
+            kept.pop(sp, None)
+
+
+def split_facts_bytes(model, split='train'):
+    """Device bytes kept for a split: (the facts' tensors, the DTW row sides' grouped values and prepared rows)."""
+    facts = model.__dict__.get('_split_facts', {}).get(split)
+    rec = model.__dict__.get('_dtw_group_rows', {}).get(split)
+    return (facts.nbytes if facts is not None else 0,
+            sum(s.prep.nbytes for s in (rec.internal, rec.external)) if rec is not None else 0)
+
+
+KEPT_BORDER_BYTES = 4 << 30        # ids of a split's kept one-hop borders (hparams['kept_border_bytes']; 0: never keep)
 
 
 def _kept_border(model, split, subs, cc_sets, k):
@@ -736,7 +879,9 @@ def finish_pass(model, st, timer=None):
         # the component side of the DTW calls (grouping of repeated degree sequences, processing order) depends on the
         # split's components only -- the same every pass: kept from the first one (side.prep), like the dispatch orders
         for name, side, x, y in (('_int', rec.internal, ci, ai), ('_bor', rec.external, ce, ae)):
-            sim = ops.dtw_similarity(cc_sets.ptr, x, mx, a_sets.ptr, y, my, tie, dedupe=bool(side.group), x_prep=side.prep, fn=fn)
+            # (kept degree sequences: the same VALUES every pass too -- the x side of the launch is prepared once, ops.DtwRows)
+            sim = ops.dtw_similarity(cc_sets.ptr, x, mx, a_sets.ptr, y, my, tie, dedupe=bool(side.group), x_prep=side.prep, fn=fn,
+                                     x_fixed=st.x_fixed)
             st.attrs[split + name + '_struc_similarities'] = sim.view(S, C, -1)
         t.mark('dtw')
     elif split + '_int_struc_similarities' not in st.attrs:

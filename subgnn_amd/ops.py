@@ -1164,7 +1164,41 @@ _DTW_ENTRIES = {                        # fn -> (workspace query, similarity ent
     'dtw': ('sgnn_dtw_workspace_bytes', 'sgnn_dtw_similarity', True),
     'dtw_exact': ('sgnn_dtw_exact_workspace_bytes', 'sgnn_dtw_exact_similarity', False),
 }
+_DTW_ROWS_ENTRIES = {                   # fn -> (size query, preparation, workspace query, similarity entry) of the x side kept
+    'dtw': ('sgnn_dtw_rows_bytes', 'sgnn_dtw_prepare_rows', 'sgnn_dtw_rows_workspace_bytes', 'sgnn_dtw_similarity_rows'),
+    'dtw_exact': ('sgnn_dtwx_rows_bytes', 'sgnn_dtwx_prepare_rows', 'sgnn_dtwx_rows_workspace_bytes', 'sgnn_dtwx_similarity_rows'),
+}
 DTW_FNS = tuple(_DTW_ENTRIES)           # values of hparams['structure_similarity_fn'] the library computes
+
+
+class DtwRows:
+    """The x side of a DTW call prepared once (sgnn_dtw_prepare_rows): the device buffer ``buf`` with the pyramids and lengths
+    of the rows, the library's host-side ``header`` describing it, and ``key`` = (fn, kernel, max_x, grouped): the call form
+    it was prepared for.  The library refuses a header of another row count, length bound or layout."""
+    __slots__ = ('buf', 'header', 'key', 'nbytes')
+
+    def __init__(self, buf, header, key, nbytes):
+        self.buf, self.header, self.key, self.nbytes = buf, header, key, nbytes
+
+    @property
+    def header_ptr(self):
+        return ctypes.addressof(self.header)
+
+
+def dtw_prepare_rows(x_ptr, x_val, max_x, kernel=0, fn='dtw', order=None, key=None):
+    """-> DtwRows of these x rows for ``_dtw_launch(..., rows=...)``: one launch.  ``order``: the processing order the later
+    calls pass (the register kernels read the rows laid out in it)."""
+    lib = _lib.load()
+    _req(x_ptr, torch.int64, 'x_ptr')
+    _req(x_val, torch.int32, 'x_val')
+    size_q, entry = _DTW_ROWS_ENTRIES[fn][:2]
+    nx = x_ptr.numel() - 1
+    nbytes = getattr(lib, size_q)(nx, max_x)
+    buf = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=x_ptr.device)
+    header = (ctypes.c_int64 * int(lib.sgnn_dtw_rows_header_words()))()
+    check(getattr(lib, entry)(_ptr(x_ptr), _ptr(x_val), nx, max_x, int(kernel), _ptr(order), _ptr(buf), nbytes,
+                              ctypes.addressof(header), _stream()), entry)
+    return DtwRows(buf, header, key, nbytes)
 
 # The grouping of repeated x rows: every row keeps its slot, the rows that repeat an earlier one are given length 0 (their
 # pairs exit at once -- sorted by length they fill whole wavefronts) and read the result row of their representative ``rep``
@@ -1177,18 +1211,53 @@ class DtwRowPrep:
     """What a caller keeps for ONE set of x rows between ``dtw_similarity`` calls (the degree sequences of a split's
     components are the same rows every pass): ``grouping`` (a DtwGrouping), ``order`` (the processing order of the rows as
     given) and ``grouped_order`` (that of the grouped rows), each None until a call needs it.  Only the structure is kept:
-    the series the kernel reads are always the call's ``x_val``."""
-    __slots__ = ('shape', 'grouping', 'order', 'grouped_order')
+    the series the kernel reads are always the call's ``x_val`` -- unless the caller declares them fixed
+    (``dtw_similarity(x_fixed=True)``): then ``grouped_val`` (the grouped rows' values) and ``rows`` (a DtwRows: the
+    pyramids the kernel reads) are kept too, with ``ready``, the event behind their build (a call on another stream waits
+    for it once, like KeptBorders.wait)."""
+    __slots__ = ('shape', 'grouping', 'order', 'grouped_order', 'grouped_val', 'rows', 'fixed_src', 'ready', '_waited')
 
     def __init__(self):
-        self.shape = self.grouping = self.order = self.grouped_order = None
+        self.shape = None
+        self.forget()
 
-    def fit(self, x_ptr, x_val):
-        """Forget what was kept for rows of another count or another ``x_val`` length: it is rebuilt, never reused."""
+    def forget(self):
+        self.grouping = self.order = self.grouped_order = self.grouped_val = self.rows = self.fixed_src = self.ready = None
+        self._waited = set()
+
+    def fit(self, x_ptr, x_val, fixed=False):
+        """Forget what was kept for rows of another count or another ``x_val`` length: it is rebuilt, never reused.
+        ``fixed``: the call declares its values fixed -- then also for another ``x_val`` TENSOR than the one the kept values
+        were made from (held here, compared by identity: the promise is about that tensor)."""
         shape = (x_ptr.numel() - 1, x_val.numel())
-        if shape != self.shape:
-            self.shape, self.grouping, self.order, self.grouped_order = shape, None, None, None
+        if shape != self.shape or (fixed and self.fixed_src is not None and self.fixed_src is not x_val):
+            self.shape = shape
+            self.forget()
+        if fixed:
+            self.fixed_src = x_val
         return self
+
+    @property
+    def nbytes(self):
+        """Device bytes of the kept VALUES (grouped values, prepared rows)."""
+        return (self.rows.nbytes if self.rows is not None else 0) + (self.grouped_val.numel() * 4 if self.grouped_val is not None else 0)
+
+    def built(self):
+        """Something was kept by launches just queued on the current stream: other streams wait for them (``hand_over``)."""
+        self.ready = torch.cuda.Event()
+        self.ready.record()
+        self._waited = {torch.cuda.current_stream().cuda_stream}
+
+    def hand_over(self, stream):
+        """Order ``stream`` behind the build of the kept values (once per stream: they never change afterwards)."""
+        if self.ready is None or stream.cuda_stream in self._waited or torch.cuda.is_current_stream_capturing():
+            return                            # (capturing: torch synchronised the device before the capture began)
+        self._waited.add(stream.cuda_stream)
+        for t in (self.grouped_val, self.rows.buf if self.rows is not None else None, self.order, self.grouped_order):
+            if t is not None:
+                t.record_stream(stream)       # (a preparation that is replaced is freed while this stream may still read it)
+        if not self.ready.query():
+            stream.wait_event(self.ready)
 
 
 def _group_rows(x_ptr, x_val, max_x, want_live):
@@ -1227,9 +1296,10 @@ def _dtw_row_order(x_ptr, x_val):
     return torch.argsort(key).to(torch.int32).contiguous()
 
 
-def _dtw_launch(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order, kernel, fn, order, live):
+def _dtw_launch(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order, kernel, fn, order, live, rows=None):
     """One workspace query and one library call -> (n_x, n_y) float32.  ``live``: only positions [first, first + count) of
-    ``order`` are computed (the ``_live`` entry; it needs an order), the other rows of the result are 0."""
+    ``order`` are computed (the ``_live`` entry; it needs an order), the other rows of the result are 0.  ``rows``: a DtwRows
+    prepared from these x rows with this ``kernel`` and ``order``: the ``_rows`` entry, which does not build the x side."""
     lib = _lib.load()
     for t, dt, nm in ((x_ptr, torch.int64, 'x_ptr'), (y_ptr, torch.int64, 'y_ptr'), (x_val, torch.int32, 'x_val'),
                       (y_val, torch.int32, 'y_val')):
@@ -1237,9 +1307,11 @@ def _dtw_launch(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order, kernel, fn,
     nx, ny = x_ptr.numel() - 1, y_ptr.numel() - 1
     out = (torch.empty if live is None else torch.zeros)((nx, ny), dtype=torch.float32, device=x_ptr.device)
     ws_entry, entry, takes_tie = _DTW_ENTRIES[fn]
+    if rows is not None:
+        ws_entry, entry = _DTW_ROWS_ENTRIES[fn][2:]
     wsb = getattr(lib, ws_entry)(nx, max_x, ny, max_y)
     ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=x_ptr.device)
-    args = [_ptr(x_ptr), _ptr(x_val), nx, max_x, _ptr(y_ptr), _ptr(y_val), ny, max_y]
+    args = ([_ptr(x_ptr), _ptr(x_val)] if rows is None else [rows.header_ptr]) + [nx, max_x, _ptr(y_ptr), _ptr(y_val), ny, max_y]
     if takes_tie:
         args.append(tie_order)
     args += [int(kernel), _ptr(order)]
@@ -1251,7 +1323,7 @@ def _dtw_launch(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order, kernel, fn,
 
 
 def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, order_rows=True, dedupe=True, order=None,
-                   x_prep=None, kernel=0, fn='dtw'):
+                   x_prep=None, kernel=0, fn='dtw', x_fixed=False):
     """1/(1+fastdtw) for all (x row, y row) pairs -> (n_x, n_y) float32; empty x rows -> PAD.
     ``fn``: hparams['structure_similarity_fn'] -- 'dtw' = fastdtw(radius=1), 'dtw_exact' = the exact DTW distance over the
     whole grid (sgnn_dtw_exact_similarity; ``tie_order`` is ignored: a minimum over warp paths has no predecessor rule).
@@ -1263,20 +1335,36 @@ def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, ord
     ``x_prep``: a DtwRowPrep the caller keeps for THESE x rows: the grouping of repeated rows and the processing order are
     computed on the first call and reused (one that was made for another row count or ``x_val`` length starts over); the
     series the kernel reads are always this call's ``x_val``.  None = a temporary one.  ``order``: the caller's own (tuning).
+    ``x_fixed`` (with an ``x_prep``): the caller promises that ``x_val`` holds the SAME values on every call with this
+    ``x_prep`` (the degree sequences of a split's components: hotpath's kept split facts).  The first such call then also
+    keeps the values' side -- the grouped values (``zeros`` + ``scatter_``) and the prepared rows (``DtwRows``: the x pyramid
+    launch) -- and later calls launch the y pyramid and the DP kernel only (the ``_rows`` entries).  Same values, bit for bit.
+    Nothing is kept by a call that is being recorded into a hipGraph (its allocations belong to the recording) or that brings
+    its own ``order``.
     ``kernel``: 0 = pick by size, 1 = the general (workspace-resident) kernel; same values.
     ``tie_order``: fastdtw's predecessor rule (0 / 1 / 2); None = config.DTW_TIE_ORDER, the product's default."""
     if fn not in DTW_FNS:
         raise ValueError('structure similarity function %r: one of %s' % (fn, ', '.join(map(repr, DTW_FNS))))
     if tie_order is None:
         from .config import DTW_TIE_ORDER as tie_order
-    prep = (x_prep if x_prep is not None else DtwRowPrep()).fit(x_ptr, x_val)
+    fixed = bool(x_fixed) and x_prep is not None and order is None
+    prep = (x_prep if x_prep is not None else DtwRowPrep()).fit(x_ptr, x_val, fixed)
+    # what of the VALUES may be kept and read back: see ``x_fixed``
+    keep = fixed and not torch.cuda.is_current_stream_capturing()
+    if fixed:
+        prep.hand_over(torch.cuda.current_stream())
+    built = False
     ptr, val, g = x_ptr, x_val, None
     if dedupe and x_ptr.numel() - 1 > 1024 and max_x <= 64:
         # the grouping (which row stands for which, where the kept entries go) may be a kept one; the VALUES the kernel reads
-        # are this call's: two launches (zeros, scatter)
+        # are this call's: two launches (zeros, scatter) -- unless they are fixed and kept
         g = prep.grouping = prep.grouping or _group_rows(x_ptr, x_val, max_x, order is None and order_rows)
-        ptr, val = g.ptr, torch.zeros(x_val.numel() + 1, dtype=torch.int32, device=x_ptr.device)
-        val.scatter_(0, g.entry_dst, x_val)
+        ptr, val = g.ptr, prep.grouped_val if fixed else None
+        if val is None:
+            val = torch.zeros(x_val.numel() + 1, dtype=torch.int32, device=x_ptr.device)
+            val.scatter_(0, g.entry_dst, x_val)
+            if keep:
+                prep.grouped_val, built = val, True
     live = g.live if g is not None and order is None else None      # (it describes the order made here, not a caller's)
     if order is not None:
         order = order.to(torch.int32).contiguous()
@@ -1286,7 +1374,16 @@ def dtw_similarity(x_ptr, x_val, max_x, y_ptr, y_val, max_y, tie_order=None, ord
         if order is None:
             order = _dtw_row_order(ptr, val)
             setattr(prep, which, order)
-    out = _dtw_launch(ptr, val, max_x, y_ptr, y_val, max_y, int(tie_order), kernel, fn, order, live)
+    rows = None
+    if fixed:
+        key = (fn, int(kernel), int(max_x), g is not None)
+        rows = prep.rows if prep.rows is not None and prep.rows.key == key else None
+        if rows is None and keep:
+            rows = prep.rows = dtw_prepare_rows(ptr, val, max_x, kernel, fn, order, key)
+            built = True
+    if built:
+        prep.built()
+    out = _dtw_launch(ptr, val, max_x, y_ptr, y_val, max_y, int(tie_order), kernel, fn, order, live, rows)
     return out if g is None else out.index_select(0, g.rep)
 
 

@@ -10,15 +10,19 @@ rows = list(csv.DictReader(open(sys.argv[1])))
 min_us = float(sys.argv[2]) if len(sys.argv) > 2 else 40.0
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 idx = [i for i, r in enumerate(rows) if 'cc_labels_kernel' in r['Kernel_Name']]
-p = rows[idx[-2]:idx[-1]]
+adam = [i for i, r in enumerate(rows) if 'optim_adam_kernel' in r['Kernel_Name']]
+# a pass that labels its components starts there; with the split's facts kept (hotpath.SplitFacts) only the first pass does, and
+# a steady pass starts behind the previous pass's last kernel, the table's Adam
+labelled = len(idx) >= 2 and len(idx) >= len(adam) - 1
+p = rows[idx[-2]:idx[-1]] if labelled else rows[adam[-3] + 1:adam[-2] + 1]
 ours = ('cc_labels', 'cc_compact', 'cc_embed', 'choice_ragged', 'msbfs', 'triangular', 'degseq', 'khop', 'dtw_', 'mpn_',
         'masked_sum', 'sample_anchors', 'patch_in_border', 'attn_scores', 'sp_sim', 'min_hops', 'sort_sets', 'scatter_runs',
         'scatter_chains', 'lstm_', 'update_', 'head_')
 marks = [('triangular_walks', 'patches'), ('msbfs_init', 'position'), ('triangular_walks', 'walks'), ('sort_sets', 'border'),
-         ('khop_border', 'border'), ('degseq_wave_kernel<true, false', 'degseq+dtw_prep'), ('dtw_pyramid', 'dtw'),
+         ('khop_border', 'border'), ('sample_anchors_border', 'border'), ('degseq_wave_kernel<true, false', 'degseq+dtw_prep'), ('dtw_pyramid', 'dtw'),
          ('cc_embed_fwd_kernel', 'fwd+bwd+opt')]
 order = ['components', 'patches', 'position', 'walks', 'border', 'degseq+dtw_prep', 'dtw', 'fwd+bwd+opt']
-stage = 'components'
+stage = 'components' if labelled else 'patches'
 tot = collections.defaultdict(lambda: [0.0, 0.0, 0, 0])
 names = collections.defaultdict(collections.Counter)
 t0 = int(p[0]['Start_Timestamp'])
@@ -29,7 +33,8 @@ for r in p:
         if m in n and order.index(s) == order.index(stage) + 1:          # stages follow each other in this order
             stage = s
             break
-        if m in n and s in ('border',) and order.index(s) > order.index(stage):
+        # (a steady pass from kept facts has no component degree sequences: its DTW stage follows the border stage)
+        if m in n and s in ('border', 'dtw') and order.index(s) > order.index(stage):
             stage = s
             break
     d = (int(r['End_Timestamp']) - int(r['Start_Timestamp'])) / 1e3
