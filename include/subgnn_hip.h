@@ -378,6 +378,38 @@ int sgnn_occlusion_write(const int64_t* set_ptr, const int32_t* set_nodes, int64
                          int64_t total_entries, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Insertion sets (no reference counterpart): every add-one-candidate variant of every ragged set, for scoring the nodes a
+ * subgraph outside the dataset could gain.  A set is ascending and without repeats (sgnn_sort_sets); it may be empty.  A
+ * candidate row is the same.  The candidates are cand_ptr (int64) / cand_ids (int32):
+ *   shared 0   one candidate row per set (n_sets + 1 pointers)
+ *   shared 1   ONE row (two pointers) that every set takes (a pool is not replicated per set)
+ * The variants of set s of n entries are, in the order of its candidate row, one per candidate v that is no member of s: the
+ * ascending set s U {v} of n + 1 entries (so no sort follows).  A candidate that is a member is skipped, not an error; the
+ * variants of an empty set are the singletons.
+ *
+ * sgnn_insertion_count: out_variants[s] (int64) = the number of candidates of set s that are no members.  The caller's
+ * exclusive prefix sums are var_ptr (of out_variants) and entry_ptr (of out_variants[s] * (n_s + 1)), n_sets + 1 each: their
+ * last values -- the number of variants and of their entries -- size the outputs of
+ * sgnn_insertion_write: the k-th variant of set s is variant v = var_ptr[s] + k: out_ptr[v] = entry_ptr[s] + k (n_s + 1) (and
+ * out_ptr[n_variants] behind the last), its entries in out_nodes from there, out_parent[v] = s, out_cand[v] = the inserted id
+ * (int32 both) and
+ *     out_keys[v] = sgnn_mix64( sum_parent + sgnn_mix64(v) + (n_s + 2) * 0x8CB92BA72F3D8DD7 )
+ * in uint64 wrap-around arithmetic: the bits sgnn_set_keys gives for the variant, from one sum over the parent (the variant
+ * is not read again).
+ * One workgroup per set: the set is read once (into LDS up to 1024 entries; up to 64 a wavefront per set; longer ones are
+ * read from global memory), the candidate row in chunks of one candidate per thread, each placed by a binary search in the
+ * set.  max_set_len: the longest set, 0 = unknown.  n_sets and n_variants < 2^31.  SGNN_ERR_BAD_ARG, with nothing written,
+ * for negative sizes, sizes beyond that, shared outside {0, 1}, a NULL input with sets to read or a NULL output with variants
+ * to write.
+ * ------------------------------------------------------------------------------------- */
+int sgnn_insertion_count(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, int64_t max_set_len,
+                         const int64_t* cand_ptr, const int32_t* cand_ids, int shared, int64_t* out_variants, void* stream);
+int sgnn_insertion_write(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, int64_t max_set_len,
+                         const int64_t* cand_ptr, const int32_t* cand_ids, int shared, const int64_t* var_ptr,
+                         const int64_t* entry_ptr, int64_t n_variants, int64_t* out_ptr, int32_t* out_nodes,
+                         int32_t* out_parent, int32_t* out_cand, uint64_t* out_keys, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * a1-a3  Triangular random walks.
  * Replaces anchor_patch_samplers.triangular_random_walk / perform_random_walks /
  * sample_structure_anchor_patches (anchor_patch_samplers.py:20-158, 210-243).

@@ -906,6 +906,49 @@ def occlusion_sets(sets, unit='node', labels=None):
     return Occlusion(Ragged(out_ptr, out_nodes, max_len=max(max_len - 1, 0)), parent, rank, keys, units, variants)
 
 
+Insertion = collections.namedtuple('Insertion', 'sets parent cand keys variants')
+
+
+def insertion_sets(sets, candidates, shared=False):
+    """Every add-one-candidate variant of every set of ``sets`` (ascending, without repeats; a set may be empty): set s gains,
+    in turn, every id of row s of ``candidates`` (a Ragged of ``sets.n`` ascending rows; ``shared=True``: of ONE row that every
+    set takes) that is no member of it -> Insertion: ``sets`` the variants as a Ragged (ascending: nothing to sort), ``parent``
+    / ``cand`` int32 per variant (the set it comes from, the inserted id), ``keys`` (int64 holding the uint64 bits of
+    ``set_keys(variants)``), ``variants`` int64 per input set (sgnn_insertion_count / _write).  One host round trip: the
+    number of variants and of their entries, read together."""
+    _req(sets.ptr, torch.int64, 'ptr')
+    _req(sets.nodes, torch.int32, 'nodes')
+    _req(candidates.ptr, torch.int64, 'candidates.ptr')
+    _req(candidates.nodes, torch.int32, 'candidates.nodes')
+    rows = 1 if shared else sets.n
+    if candidates.n != rows:
+        raise ValueError('candidates: %d rows for %d sets%s' % (candidates.n, sets.n, ' (shared: one row)' if shared else ''))
+    lib = _lib.load()
+    dev = sets.ptr.device
+    n, max_len = sets.n, int(sets.max_len)                                              # (0 says: not known -- every tier is launched)
+    spare = torch.zeros(1, dtype=torch.int32, device=dev)                               # (a tensor of no elements has no address)
+    nodes = sets.nodes if sets.nodes.numel() else spare
+    cand = candidates.nodes if candidates.nodes.numel() else spare
+    head = (_ptr(sets.ptr), _ptr(nodes), n, max_len, _ptr(candidates.ptr), _ptr(cand), 1 if shared else 0)
+    variants = torch.zeros(n, dtype=torch.int64, device=dev)
+    check(lib.sgnn_insertion_count(*head, _ptr(variants), _stream()), 'sgnn_insertion_count')
+    var_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(variants, 0, out=var_ptr[1:])
+    entry_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(variants * (sets.lengths + 1), 0, out=entry_ptr[1:])
+    V, T = torch.stack((var_ptr[-1], entry_ptr[-1])).tolist()                 # the one host round trip
+    if V > 0x7fffffff:
+        raise ValueError('%d variants: more than 2^31 - 1 (send fewer sets or candidates at a time)' % V)
+    out_ptr = torch.zeros(V + 1, dtype=torch.int64, device=dev)
+    out_nodes = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
+    parent = torch.empty(V, dtype=torch.int32, device=dev)
+    inserted = torch.empty(V, dtype=torch.int32, device=dev)
+    keys = torch.empty(V, dtype=torch.int64, device=dev)
+    check(lib.sgnn_insertion_write(*head, _ptr(var_ptr), _ptr(entry_ptr), V, _ptr(out_ptr), _ptr(out_nodes), _ptr(parent),
+                                   _ptr(inserted), _ptr(keys), _stream()), 'sgnn_insertion_write')
+    return Insertion(Ragged(out_ptr, out_nodes, max_len=max_len + 1), parent, inserted, keys, variants)
+
+
 def _req_keys(keys, n, row_has_pad=None):
     _req(keys, torch.int64, 'keys')
     if keys.numel() != n:

@@ -305,6 +305,18 @@ class Predictor:
         return _explain.explain(self, subgraphs, unit=unit, target=target, draws=draws, batch_size=batch_size,
                                 max_variants=max_variants)
 
+    def suggest(self, subgraphs, candidates='border', hops=1, target=None, draws=1, batch_size=None, max_variants=65536):
+        """The gain of every node each request could be given (its border, or a shared pool of ids): ``suggest.suggest``."""
+        from . import suggest as _suggest
+        return _suggest.suggest(self, subgraphs, candidates=candidates, hops=hops, target=target, draws=draws,
+                                batch_size=batch_size, max_variants=max_variants)
+
+    def grow(self, subgraphs, steps, target=None, min_gain=0.0, candidates='border', hops=1, draws=1, batch_size=None):
+        """Greedy growth: every request takes its best candidate, round by round, while it gains: ``suggest.grow``."""
+        from . import suggest as _suggest
+        return _suggest.grow(self, subgraphs, steps, target=target, min_gain=min_gain, candidates=candidates, hops=hops,
+                             draws=draws, batch_size=batch_size)
+
     def nearest(self, index, subgraphs, k=10):
         """The ``k`` rows of ``index`` (a neighbors.SubgraphIndex) nearest to each requested subgraph: ``index.query``."""
         return index.query(self, subgraphs, k)
