@@ -38,7 +38,7 @@ extern "C" {
 #define SGNN_ERR_LAUNCH         -4   /* hipGetLastError() after a launch */
 #define SGNN_ERR_UNSUPPORTED_D  -5   /* embedding width not supported by the vector path */
 
-#define SGNN_ABI_VERSION 12
+#define SGNN_ABI_VERSION 13
 int sgnn_abi_version(void);
 /* Load the code objects of every translation unit of the library on the current device (one empty launch each on ``stream``):
  * what the first call of each kernel family would otherwise pay, 5-25 ms at a time, inside the reference's one-time
@@ -796,27 +796,14 @@ int sgnn_lstm_tail_bwd(const float* dX, const float* s, int64_t n_patches, int64
                        int last_only, const float* W_lin, int64_t D, float* dy, float* dW_lin, float* db_lin, void* stream);
 
 /* ---------------------------------------------------------------------------------------
- * a16  Masked sum over the components of a subgraph (subgraph_utils.masked_sum,
- * SubGNN/subgraph_utils.py:213-237, as used at SubGNN/SubGNN.py:303).  x (B,C,H), mask (B,C)
- * -> out (B,H); backward scatters grad_out to the real components.
- * ------------------------------------------------------------------------------------- */
-int sgnn_masked_sum_fwd(const float* x, const uint8_t* mask, int64_t B, int64_t C, int64_t H,
-                        float* out, void* stream);
-int sgnn_masked_sum_bwd(const float* grad_out, const uint8_t* mask, int64_t B, int64_t C, int64_t H,
-                        float* grad_x, void* stream);
-
-/* ---------------------------------------------------------------------------------------
- * a16b  The tail of the forward pass without the (B, C, H) concatenation (SubGNN/SubGNN.py:286-312: cat of the
+ * a16  The tail of the forward pass without the (B, C, H) concatenation (SubGNN/SubGNN.py:286-312: cat of the
  * channel outputs, then masked_sum): every piece is summed over a subgraph's real components straight into its
  * column slot of the (B, H) subgraph embedding (row stride out_ld / grad_ld, in floats).
- *   sgnn_masked_sum_slot_fwd/_bwd: a piece that exists as a tensor x (B, C, W) (component embeddings).
- *   sgnn_readout_sum_fwd/_bwd: the read-out of a layer over SHARED anchors (subgraph_mpn.py:122-131: position read-out
- *     of the messages + relu) when only the read-out is consumed.  With s[a] = X[a,:] . wp (A values, the caller's)
- *       out[b, a] = sum over real components c of  relu(W[b,c,a] * s[a] + bp[0]),
- *       W[b,c,a] = sims[(b C + c) sims_ld + (sim_col ? sim_col[a] : a)]    (sims NULL: W = 0)
- *     row_mask (B C, nullable): 0 = padded component (contributes nothing).  Backward: grad_s[a] = sum_r g [z>0] W,
- *     grad_bp = sum g [z>0], by per-row-block partials added in block order (no atomics: bit-reproducible);
- *     either output may be NULL.  workspace: sgnn_readout_sum_bwd_workspace_bytes.
+ *   sgnn_masked_sum_slot_fwd/_bwd: a piece that exists as a tensor x (B, C, W) (component embeddings), mask (B, C):
+ *     the masked sum over the components of a subgraph (subgraph_utils.masked_sum, SubGNN/subgraph_utils.py:213-237,
+ *     as used at SubGNN/SubGNN.py:303) into columns [0, W) of out; backward scatters those columns of grad_out to
+ *     the real components.  out_ld == W (grad_ld == W) is the plain masked sum x (B, C, W) -> out (B, W).
+ *   sgnn_readout_many_fwd/_bwd (below): the read-outs of layers over SHARED anchors, of which only the sum is consumed.
  * ------------------------------------------------------------------------------------- */
 int sgnn_masked_sum_slot_fwd(const float* x, const uint8_t* mask, int64_t B, int64_t C, int64_t W, float* out,
                              int64_t out_ld, void* stream);
@@ -869,22 +856,19 @@ int64_t sgnn_column_sum_workspace_bytes(int64_t R, int64_t A);
 int sgnn_column_sum(const float* x, int64_t ld, int64_t R, int64_t A, float* out, void* workspace, int64_t workspace_bytes,
                     void* stream);
 
-int sgnn_readout_sum_fwd(const float* sims, int64_t sims_ld, const int64_t* sim_col, const float* s, const float* bp,
-                         const uint8_t* row_mask, int64_t B, int64_t C, int64_t A, float* out, int64_t out_ld,
-                         void* stream);
-int64_t sgnn_readout_sum_bwd_workspace_bytes(int64_t B, int64_t C, int64_t A);
-int sgnn_readout_sum_bwd(const float* grad_out, int64_t grad_ld, const float* sims, int64_t sims_ld,
-                         const int64_t* sim_col, const float* s, const float* bp, const uint8_t* row_mask, int64_t B,
-                         int64_t C, int64_t A, float* grad_s, float* grad_bp, void* workspace, int64_t workspace_bytes,
-                         void* stream);
-
-/* Every read-out piece of a step in ONE launch each way (n <= sgnn_readout_many_max() pieces; all arrays HOST arrays with one
- * entry per piece, of DEVICE pointers where they hold pointers).  Piece k: similarity rows sims[k] (ld sims_ld[k]; NULL = all
- * zero), columns sim_col[k] (nullable), anchor embeddings X[k] (A[k], D) with read-out weight wp[k] (D) -- the scores
- * s[a] = X[a, :] . wp, 0 where ids[k][a] == 0 (ids nullable) or X[k] is NULL, are computed by the call into s[k] (A[k] floats) --
- * bias bp[k], row mask row_mask[k] (nullable), column slot off[k] .. off[k] + A[k] of the (B, out_ld) embedding.
- * Backward: grad_X[k] (A[k], D), grad_wp[k] (D), grad_bp[k] (1), each nullable; tickets: RO_MAX_PIECES uint32, zero before the
- * first call and left zero.  Same sums in the same order as the single-piece calls. */
+/* The read-out of a layer over SHARED anchors (subgraph_mpn.py:122-131: position read-out of the messages + relu) when only
+ * its sum over a subgraph's components is consumed: with the scores s[a] = X[a, :] . wp
+ *     out[b, off + a] = sum over real components c of  relu(W[b,c,a] * s[a] + bp[0]),
+ *     W[b,c,a] = sims[(b C + c) sims_ld + (sim_col ? sim_col[a] : a)]    (sims NULL: W = 0)
+ * for every read-out piece of a step in ONE launch each way (n <= sgnn_readout_many_max() pieces; all arrays HOST arrays with
+ * one entry per piece, of DEVICE pointers where they hold pointers).  Piece k: similarity rows sims[k] (ld sims_ld[k]; NULL = all
+ * zero), columns sim_col[k] (nullable), anchor embeddings X[k] (A[k], D) with read-out weight wp[k] (D) -- the scores, 0 where
+ * ids[k][a] == 0 (ids nullable) or X[k] is NULL, are computed by the call into s[k] (A[k] floats) --
+ * bias bp[k], row mask row_mask[k] (B C, nullable: 0 = padded component, contributes nothing), column slot off[k] .. off[k] + A[k]
+ * of the (B, out_ld) embedding.  Backward: d s[a] = sum_r g [z>0] W and grad_bp = sum g [z>0] by per-row-block partials added in
+ * block order (no atomics on a value: bit-reproducible), grad_X[k] (A[k], D) = d s wp^T, grad_wp[k] (D) = X^T d s, grad_bp[k] (1),
+ * each nullable; tickets: RO_MAX_PIECES uint32, zero before the first call and left zero.  Scores that exist already go in as
+ * X (A, 1) with wp = {1}: s is X exactly and grad_X is d s. */
 int64_t sgnn_readout_many_max(void);
 int sgnn_readout_many_fwd(int64_t n, const float* const* sims, const int64_t* sims_ld, const int64_t* const* sim_col,
                           const float* const* X, const float* const* wp, const float* const* bp,

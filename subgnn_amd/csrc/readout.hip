@@ -4,15 +4,29 @@
 // components).
 //
 // For a layer whose anchors are shared by all component rows (position-border anchors, structure patches) the message
-// of edge (row r, anchor a) is W[r,a] * X[a,:] and its read-out is W[r,a] * (X[a,:] . wp) + bp: with s = X wp (A values,
-// a tiny product left to the caller) the whole (R, A) read-out is an element-wise function of the similarity rows.  What
-// the model consumes of it, when the layer is the channel's last one, is only
+// of edge (row r, anchor a) is W[r,a] * X[a,:] and its read-out is W[r,a] * (X[a,:] . wp) + bp: with the scores s = X wp
+// (A values, 0 for a PAD anchor) the whole (R, A) read-out is an element-wise function of the similarity rows.  What the
+// model consumes of it, when the layer is the channel's last one, is only
 //     out[b, a] = sum over the real components c of subgraph b of relu(W[b,c,a] * s[a] + bp)
 // which lands in a column slot of the (B, H) subgraph embedding.  The library form materialised W (column select, two
 // mask multiplies), the read-out (addcmul), its relu, the concatenation of all channel outputs into (B, C, H) and the
 // masked sum: 7 passes over 50k x 183 floats and 2 over 50k x 516 on the benchmark; here one pass reads the similarity
-// rows and writes the slot.  Backward: d s[a] = sum_r g[b(r), a] [z > 0] W[r, a], d bp = sum_{r,a} g [z > 0]: per
-// row-block partials, then one workgroup adds them in block order -- no atomics, bit-reproducible.
+// rows and writes the slot.
+//
+// A pass has one such read-out piece per channel side whose last layer runs over SHARED anchors or all-zero similarities
+// (benchmark: P internal, P border, S internal, S border), and all pieces of a call travel together as kernel arguments
+// (RoPieces, blockIdx.y = piece): two launches forward, two backward, whatever the number of pieces.
+//   forward   readout_scores_kernel: s = X wp of every piece (the matrix-vector product and its PAD mask were four
+//             launches per piece); readout_sum_fwd_many_kernel: every slot.
+//   backward  readout_sum_bwd_partial_many_kernel: d s[a] = sum_r g[b(r), a] [z > 0] W[r, a] and d bp = sum_{r,a} g [z > 0]
+//             as partials per block of RO_ROWS_PER_BLOCK component rows; readout_bwd_finish_many_kernel: one wavefront per
+//             column adds the block partials in block order and turns d s[a] into row a of d X = d s wp^T, and the piece's
+//             last workgroup (a ticket) makes d wp = X^T d s.
+// No atomics on a value and every sum in a fixed order: bit-reproducible.  A caller that has the scores already passes
+// them as X (A, 1) with wp = {1}: the kernel's score is then s[a] exactly and d X is d s.
+//
+// Further down: column sums of a tall matrix (sgnn_column_sum) and the masked sum of the tensor pieces into their slots
+// (sgnn_masked_sum_slot_* one vectorised launch per piece, sgnn_masked_sum_slots_* all pieces in one scalar launch).
 #include "common.h"
 
 #define RO_ROWS_PER_BLOCK 64
@@ -22,221 +36,9 @@
 #define RO_COMP_STEP 4                 // components per trip of the forward kernels' component loop
 #define RO_GS_CHUNK 1024               // anchors of d s staged in LDS at a time by the d wp finish
 
-// ------------------------------------------------------------------------------------------------------------------
-// a thread owns four (subgraph, anchor) elements a quarter of the grid apart: their loads are independent and in flight
-// together (one element per thread was latency-bound: 45 us for 50k x 183, a wavefront's life being one load round trip)
-__global__ __launch_bounds__(256) void readout_sum_fwd_kernel(const float* __restrict__ sims, int64_t ld,
-                                                              const int64_t* __restrict__ sim_col, const float* __restrict__ s,
-                                                              const float* __restrict__ bp, const uint8_t* __restrict__ row_mask,
-                                                              int64_t B, int32_t C, int32_t A, float* __restrict__ out, int64_t out_ld)
-{
-    const int64_t total = B * A, T = (int64_t)gridDim.x * 256;
-    const int64_t t0 = blockIdx.x * 256ll + threadIdx.x;
-    const float bb = bp[0];
-    int64_t b[4], col[4];
-    int32_t a[4];
-    float sa[4], acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t t = t0 + j * T;
-        const bool on = t < total;
-        b[j] = on ? t / A : -1;
-        a[j] = on ? (int32_t)(t - b[j] * A) : 0;
-        sa[j] = s[a[j]];
-        col[j] = sim_col ? sim_col[a[j]] : a[j];
-        acc[j] = 0.f;
-    }
-    // four components at a time: 16 independent loads in flight (a batch of subgraphs with 7-50 components each walked them one
-    // round trip after the other: the dense similarity slab is a cache miss per element)
-    for (int32_t c0 = 0; c0 < C; c0 += RO_COMP_STEP) {
-        float w[RO_COMP_STEP][4];
-        bool live[RO_COMP_STEP][4];
-#pragma unroll
-        for (int u = 0; u < RO_COMP_STEP; ++u) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int64_t r = b[j] * C + c0 + u;
-                live[u][j] = b[j] >= 0 && c0 + u < C && (!row_mask || row_mask[r]);
-                w[u][j] = (live[u][j] && sims) ? sims[r * ld + col[j]] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < RO_COMP_STEP; ++u) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                if (live[u][j]) acc[j] += fmaxf(fmaf(w[u][j], sa[j], bb), 0.f);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (b[j] >= 0) out[b[j] * out_ld + a[j]] = acc[j];
-}
-
-// one workgroup per block of RO_ROWS_PER_BLOCK component rows, thread = (row lane tr, column lane ta), columns walked in
-// chunks of RO_TA; a thread's rows are loaded four at a time (independent loads in flight: the loop is latency-bound
-// otherwise -- 168 us for 50k x 183 with one dependent row per iteration).  d s: the row lanes' sums are added in lane
-// order through LDS -> partial_s [A][nblk]; d bp: all of the workgroup's terms added in a fixed order -> partial_b [nblk].
-__global__ __launch_bounds__(256) void readout_sum_bwd_partial_kernel(const float* __restrict__ g, int64_t g_ld,
-                                                                      const float* __restrict__ sims, int64_t ld,
-                                                                      const int64_t* __restrict__ sim_col, const float* __restrict__ s,
-                                                                      const float* __restrict__ bp, const uint8_t* __restrict__ row_mask,
-                                                                      int64_t R, int32_t C, int32_t A, int64_t nblk,
-                                                                      float* __restrict__ partial_s, float* __restrict__ partial_b)
-{
-    __shared__ float sh_s[RO_TR][RO_TA];
-    __shared__ float sh_b[256];
-    const int ta = threadIdx.x % RO_TA, tr = threadIdx.x / RO_TA;
-    const int64_t blk = blockIdx.x;
-    const int64_t r0 = blk * RO_ROWS_PER_BLOCK;
-    const int nrows = (int)((r0 + RO_ROWS_PER_BLOCK < R ? r0 + RO_ROWS_PER_BLOCK : R) - r0);
-    const float bb = bp[0];
-    constexpr int PER = RO_ROWS_PER_BLOCK / RO_TR;                     // rows per thread: tr, tr + TR, ...
-    // the rows' mask bits and subgraph numbers do not depend on the column chunk
-    uint32_t live = 0;
-    int32_t sub[PER];
-#pragma unroll
-    for (int k = 0; k < PER; ++k) {
-        const int i = tr + k * RO_TR;
-        if (i < nrows && (!row_mask || row_mask[r0 + i])) live |= 1u << k;
-        sub[k] = (int32_t)((uint32_t)(r0 + i) / (uint32_t)C);
-    }
-    float acc_b = 0.f;
-    for (int32_t a0 = 0; a0 < A; a0 += RO_TA) {
-        const int32_t a = a0 + ta;
-        float acc_s = 0.f;
-        if (a < A) {
-            const float sa = s[a];
-            const int64_t col = sim_col ? sim_col[a] : a;
-#pragma unroll
-            for (int k0 = 0; k0 < PER; k0 += 4) {
-                float w[4], gz[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int64_t r = r0 + tr + (k0 + j) * RO_TR;
-                    const bool on = (live >> (k0 + j)) & 1;
-                    w[j] = (on && sims) ? sims[r * ld + col] : 0.f;
-                    gz[j] = on ? g[(int64_t)sub[k0 + j] * g_ld + a] : 0.f;
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (((live >> (k0 + j)) & 1) && fmaf(w[j], sa, bb) > 0.f) {
-                        acc_s = fmaf(gz[j], w[j], acc_s);
-                        acc_b += gz[j];
-                    }
-            }
-        }
-        sh_s[tr][ta] = acc_s;
-        __syncthreads();
-        if (tr == 0 && a < A) {
-            float vs = sh_s[0][ta];
-#pragma unroll
-            for (int k = 1; k < RO_TR; ++k) vs += sh_s[k][ta];
-            partial_s[(int64_t)a * nblk + blk] = vs;
-        }
-        __syncthreads();
-    }
-    sh_b[threadIdx.x] = acc_b;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        float v = (sh_b[threadIdx.x] + sh_b[threadIdx.x + 64]) + (sh_b[threadIdx.x + 128] + sh_b[threadIdx.x + 192]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);          // fixed tree: the same order every run
-        if (threadIdx.x == 0) partial_b[blk] = v;
-    }
-}
-
-__device__ __forceinline__ float ro_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// one wavefront per column (4 per workgroup): a lane adds every 64th block partial, the lanes are added by a fixed
-// butterfly.  The workgroup after the last column group does the same for d bp.
-__global__ __launch_bounds__(256) void readout_sum_bwd_finish_kernel(const float* __restrict__ partial_s,
-                                                                     const float* __restrict__ partial_b, int32_t A, int64_t nblk,
-                                                                     float* __restrict__ grad_s, float* __restrict__ grad_bp)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int32_t groups = (A + 3) / 4;
-    const float* p;
-    float* dst;
-    if ((int32_t)blockIdx.x < groups) {
-        const int32_t a = blockIdx.x * 4 + wave;
-        if (a >= A || !grad_s) return;
-        p = partial_s + (int64_t)a * nblk;
-        dst = grad_s + a;
-    } else {
-        if (wave != 0 || !grad_bp) return;
-        p = partial_b;
-        dst = grad_bp;
-    }
-    float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;                      // four loads in flight; combined in a fixed order
-    int64_t k = lane;
-    for (; k + 192 < nblk; k += 256) { v0 += p[k]; v1 += p[k + 64]; v2 += p[k + 128]; v3 += p[k + 192]; }
-    for (; k < nblk; k += 64) v0 += p[k];
-    const float v = ro_wave_sum((v0 + v1) + (v2 + v3));
-    if (lane == 0) *dst = v;
-}
-
-extern "C" int sgnn_readout_sum_fwd(const float* sims, int64_t sims_ld, const int64_t* sim_col, const float* s, const float* bp,
-                                    const uint8_t* row_mask, int64_t B, int64_t C, int64_t A, float* out, int64_t out_ld,
-                                    void* stream)
-{
-    if (!s || !bp || !out || B < 0 || C < 0 || A < 0 || out_ld < A || (sims && sims_ld < 1)) return SGNN_ERR_BAD_ARG;
-    if (A > 0x7fffffff || C > 0x7fffffff || (B * A + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-    if (B * A == 0) return SGNN_OK;
-    hipLaunchKernelGGL(readout_sum_fwd_kernel, dim3((unsigned)((B * A + 1023) / 1024)), dim3(256), 0, (hipStream_t)stream, sims,
-                       sims_ld, sim_col, s, bp, row_mask, B, (int32_t)C, (int32_t)A, out, out_ld);
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
-}
-
 static inline int64_t ro_blocks(int64_t R) { return (R + RO_ROWS_PER_BLOCK - 1) / RO_ROWS_PER_BLOCK; }
 
-extern "C" int64_t sgnn_readout_sum_bwd_workspace_bytes(int64_t B, int64_t C, int64_t A)
-{
-    if (B < 0 || C < 0 || A < 0) return -1;
-    return (A + 1) * ro_blocks(B * C) * (int64_t)sizeof(float) + 16;
-}
-
-extern "C" int sgnn_readout_sum_bwd(const float* grad_out, int64_t grad_ld, const float* sims, int64_t sims_ld,
-                                    const int64_t* sim_col, const float* s, const float* bp, const uint8_t* row_mask, int64_t B,
-                                    int64_t C, int64_t A, float* grad_s, float* grad_bp, void* workspace, int64_t workspace_bytes,
-                                    void* stream)
-{
-    if (!grad_out || !s || !bp || B < 0 || C < 0 || A < 0 || grad_ld < A || (sims && sims_ld < 1)) return SGNN_ERR_BAD_ARG;
-    if (A > 0x7fffffff || C > 0x7fffffff || B * C > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-    if (!grad_s && !grad_bp) return SGNN_OK;
-    hipStream_t st = (hipStream_t)stream;
-    const int64_t R = B * C;
-    if (R * A == 0) {
-        if (grad_s && A) { if (hipMemsetAsync(grad_s, 0, A * sizeof(float), st) != hipSuccess) return SGNN_ERR_LAUNCH; }
-        if (grad_bp) { if (hipMemsetAsync(grad_bp, 0, sizeof(float), st) != hipSuccess) return SGNN_ERR_LAUNCH; }
-        return SGNN_OK;
-    }
-    if (!workspace || workspace_bytes < sgnn_readout_sum_bwd_workspace_bytes(B, C, A)) return SGNN_ERR_BAD_ARG;
-    const int64_t nblk = ro_blocks(R);
-    if (nblk > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-    float* partial_s = (float*)workspace;
-    float* partial_b = partial_s + A * nblk;
-    hipLaunchKernelGGL(readout_sum_bwd_partial_kernel, dim3((unsigned)nblk), dim3(256), 0, st, grad_out, grad_ld, sims, sims_ld,
-                       sim_col, s, bp, row_mask, R, (int32_t)C, (int32_t)A, nblk, partial_s, partial_b);
-    SGNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(readout_sum_bwd_finish_kernel, dim3((unsigned)((A + 3) / 4 + 1)), dim3(256), 0, st, partial_s, partial_b,
-                       (int32_t)A, nblk, grad_s, grad_bp);
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
-}
-
-// ---- every read-out piece of a step in one launch each way ------------------------------------------------------------------
-// A pass has one read-out piece per channel side whose last layer runs over SHARED anchors or all-zero similarities (benchmark:
-// P internal, P border, S internal, S border).  Each was: s = X wp (a matrix-vector launch), its PAD mask (three element-wise
-// launches), the slot launch above; backward: partials + finish per piece, then the backward of s = X wp (two more products and
-// two multiplies) -- 11 launches forward and 15 backward per pass.  Here: the scores of all pieces in one launch
-// (readout_scores_kernel), all slots in one (blockIdx.y = piece), the backward partials in one, and one finish launch that
-// also turns d s into d X = d s wp^T (the wavefront that owns column a writes row a) and, in the piece's last workgroup (a
-// ticket), d wp = X^T d s and d bp.  Every sum keeps the fixed order of the single-piece kernels.
+// ---- the read-out pieces of a call ------------------------------------------------------------------------------------------
 #define RO_MAX_PIECES 8
 struct RoPieces {
     const float* sims[RO_MAX_PIECES]; long long ld[RO_MAX_PIECES]; const int64_t* sim_col[RO_MAX_PIECES];
@@ -268,6 +70,10 @@ __global__ __launch_bounds__(256) void readout_scores_kernel(const RoPieces P)
     }
 }
 
+// a thread owns four (subgraph, anchor) elements a quarter of the piece's grid apart: their loads are independent and in
+// flight together (one element per thread was latency-bound: 45 us for 50k x 183, a wavefront's life being one load round
+// trip), and it walks four components at a time: 16 independent loads (a batch of subgraphs with 7-50 components each
+// walked them one round trip after the other: the dense similarity slab is a cache miss per element)
 __global__ __launch_bounds__(256) void readout_sum_fwd_many_kernel(const RoPieces P, int64_t B, int32_t C, float* __restrict__ out,
                                                                    int64_t out_ld)
 {
@@ -319,6 +125,10 @@ __global__ __launch_bounds__(256) void readout_sum_fwd_many_kernel(const RoPiece
         if (b[j] >= 0) out[b[j] * out_ld + P.off[p] + a[j]] = acc[j];
 }
 
+// one workgroup per block of RO_ROWS_PER_BLOCK component rows, thread = (row lane tr, column lane ta), columns walked in
+// chunks of RO_TA; a thread's rows are loaded four at a time (independent loads in flight: the loop is latency-bound
+// otherwise -- 168 us for 50k x 183 with one dependent row per iteration).  d s: the row lanes' sums are added in lane
+// order through LDS -> partial_s [A][nblk]; d bp: all of the workgroup's terms added in a fixed tree -> partial_b [nblk].
 __global__ __launch_bounds__(256) void readout_sum_bwd_partial_many_kernel(const RoPieces P, const float* __restrict__ g, int64_t g_ld,
                                                                            int64_t R, int32_t C, int64_t nblk)
 {
@@ -392,8 +202,9 @@ __global__ __launch_bounds__(256) void readout_sum_bwd_partial_many_kernel(const
     }
 }
 
-// workgroups [0, groups) of a piece: one wavefront per column a -> d s[a] (block partials added as in readout_sum_bwd_finish_kernel)
-// and row a of d X; workgroup `groups`: d bp; the LAST workgroup of the piece to finish: d wp[d] = sum_a d s[a] X[a, d], a in order.
+// workgroups [0, groups) of a piece: one wavefront per column a -> d s[a] (a lane adds every 64th block partial, the lanes are
+// added by a fixed butterfly) and row a of d X; workgroup `groups`: d bp; the LAST workgroup of the piece to finish:
+// d wp[d] = sum_a d s[a] X[a, d], a in order.
 __global__ __launch_bounds__(256) void readout_bwd_finish_many_kernel(const RoPieces P, int64_t nblk, int max_groups)
 {
     __shared__ int s_last;
@@ -572,7 +383,7 @@ extern "C" int sgnn_readout_many_bwd(int64_t n, const float* grad_out, int64_t g
 // ------------------------------------------------------------------------------------------------------------------
 // Column sums of a tall matrix x (R, A) -- the bias gradient of a Linear over R rows (autograd of SubGNN/SubGNN.py:304-312 and
 // of the read-out weights): per-256-row-block partials with four loads in flight per thread, then the block partials of a
-// column added in block order by one wavefront (readout_sum_bwd_finish_kernel).  torch's reduction over the leading
+// column added in block order by one wavefront (column_sum_finish_kernel).  torch's reduction over the leading
 // dimension of a tall, narrow matrix took three launches (a row-block view, two sums) + an add for the tail.
 // rows per block: 256 for a very tall matrix, fewer when that would leave the chip short of workgroups (>= ~1000 blocks)
 static inline int64_t cs_rows_per_block(int64_t R) {
@@ -612,6 +423,29 @@ __global__ __launch_bounds__(256) void column_sum_partial_kernel(const float* __
     }
 }
 
+__device__ __forceinline__ float ro_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// one wavefront per column (4 per workgroup): a lane adds every 64th block partial, the lanes are added by a fixed
+// butterfly
+__global__ __launch_bounds__(256) void column_sum_finish_kernel(const float* __restrict__ partial, int32_t A, int64_t nblk,
+                                                                float* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int32_t a = blockIdx.x * 4 + wave;
+    if (a >= A) return;
+    const float* p = partial + (int64_t)a * nblk;
+    float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f;                      // four loads in flight; combined in a fixed order
+    int64_t k = lane;
+    for (; k + 192 < nblk; k += 256) { v0 += p[k]; v1 += p[k + 64]; v2 += p[k + 128]; v3 += p[k + 192]; }
+    for (; k < nblk; k += 64) v0 += p[k];
+    const float v = ro_wave_sum((v0 + v1) + (v2 + v3));
+    if (lane == 0) out[a] = v;
+}
+
 extern "C" int64_t sgnn_column_sum_workspace_bytes(int64_t R, int64_t A)
 {
     if (R < 0 || A < 0) return -1;
@@ -632,15 +466,16 @@ extern "C" int sgnn_column_sum(const float* x, int64_t ld, int64_t R, int64_t A,
     float* partial = (float*)workspace;
     hipLaunchKernelGGL(column_sum_partial_kernel, dim3((unsigned)nblk), dim3(256), 0, st, x, ld, R, (int32_t)A, nblk, rpb, partial);
     SGNN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(readout_sum_bwd_finish_kernel, dim3((unsigned)((A + 3) / 4)), dim3(256), 0, st, partial, (const float*)nullptr,
-                       (int32_t)A, nblk, out, (float*)nullptr);
+    hipLaunchKernelGGL(column_sum_finish_kernel, dim3((unsigned)((A + 3) / 4)), dim3(256), 0, st, partial, (int32_t)A, nblk, out);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
 // masked sum of one channel output (B, C, W) into a column slot of the (B, H) subgraph embedding, and its backward out of
-// a slot of the embedding's gradient (SubGNN/subgraph_utils.py:213-237 applied per concatenated piece: no (B, C, H) tensor)
+// a slot of the embedding's gradient (SubGNN/subgraph_utils.py:213-237 applied per concatenated piece: no (B, C, H) tensor);
+// out_ld == W is the plain masked sum of a (B, C, W) tensor.  V = float4: four consecutive columns per thread (16-byte loads
+// and stores, one index division per four elements) where ro_vec4_ok allows -- 50k x 448 went from 2.5 to ~5 TB/s
 template <typename V>
 __global__ __launch_bounds__(256) void masked_sum_slot_fwd_kernel(const V* __restrict__ x, const uint8_t* __restrict__ mask, int64_t B,
                                                                   int64_t C, int64_t Wv, V* __restrict__ out, int64_t out_ldv)

@@ -2405,7 +2405,7 @@ class _MaskedSum(torch.autograd.Function):
         _req(mask, torch.uint8, 'mask')
         B, C, H = x.shape
         out = torch.empty((B, H), dtype=torch.float32, device=x.device)
-        check(lib.sgnn_masked_sum_fwd(_ptr(x), _ptr(mask), B, C, H, _ptr(out), _stream()), 'sgnn_masked_sum_fwd')
+        check(lib.sgnn_masked_sum_slot_fwd(_ptr(x), _ptr(mask), B, C, H, _ptr(out), H, _stream()), 'sgnn_masked_sum_slot_fwd')
         ctx.save_for_backward(mask)
         ctx.shape = (B, C, H)
         return out
@@ -2417,7 +2417,7 @@ class _MaskedSum(torch.autograd.Function):
         B, C, H = ctx.shape
         g = g.contiguous()
         gx = torch.empty((B, C, H), dtype=torch.float32, device=g.device)
-        check(lib.sgnn_masked_sum_bwd(_ptr(g), _ptr(mask), B, C, H, _ptr(gx), _stream()), 'sgnn_masked_sum_bwd')
+        check(lib.sgnn_masked_sum_slot_bwd(_ptr(g), H, _ptr(mask), B, C, H, _ptr(gx), _stream()), 'sgnn_masked_sum_slot_bwd')
         return gx, None
 
 
@@ -2429,19 +2429,20 @@ def masked_sum(x, mask):
 class ReadoutPiece:
     """The read-out of a layer over SHARED anchors (or with all-zero edge weights) that nobody has materialised yet:
     relu(W * s + bp) with W (R, A) = similarity columns x row mask, s (A) = X wp.  ``subgraph_embedding`` sums it over a
-    subgraph's components straight into the embedding's column slot (sgnn_readout_sum_fwd); ``dense()`` is the (B, C, A)
+    subgraph's components straight into the embedding's column slot (sgnn_readout_many_fwd); ``dense()`` is the (B, C, A)
     tensor for a consumer that wants it (attention read-out, gathered heads)."""
 
     def __init__(self, sims2, sim_col, s, bp, A, row_mask, R, X=None, wp=None, ids=None):
-        """``s`` given: the scores as a tensor (the caller made them).  ``s`` None: the scores are X wp (0 where ids == 0; all zero
-        without X) and ``subgraph_embedding`` computes them inside its own launches, for all such pieces of a step together
-        (sgnn_readout_many_fwd / _bwd: the gradients of X, wp and bp come out of the same two launches)."""
-        self.sims2, self.sim_col, self.s, self.bp, self.A, self.row_mask, self.R = sims2, sim_col, s, bp, int(A), row_mask, int(R)
+        """The scores are X wp (0 where ids == 0; all zero without X) and ``subgraph_embedding`` computes them inside its own
+        launches, for all pieces of a step together (sgnn_readout_many_fwd / _bwd: the gradients of X, wp and bp come out of
+        the same two launches).  ``s`` given (the caller made the scores): they are the one-column anchors of a weight 1 --
+        the launches' score is s[a] exactly, and d X is d s, which autograd carries to ``s``."""
+        if s is not None:
+            X, wp, ids = s.reshape(-1, 1), torch.ones(1, dtype=s.dtype, device=s.device), None
+        self.sims2, self.sim_col, self.bp, self.A, self.row_mask, self.R = sims2, sim_col, bp, int(A), row_mask, int(R)
         self.X, self.wp, self.ids = X, (wp.reshape(-1) if wp is not None else None), ids
 
     def scores(self):
-        if self.s is not None:
-            return self.s
         if self.X is None:
             return torch.zeros(self.A, dtype=self.bp.dtype, device=self.bp.device)
         s = self.X @ self.wp
@@ -2462,7 +2463,8 @@ SLOTS_TOGETHER_BELOW = 1 << 22          # (B C H) elements: below, the tensor pi
 class _SubgraphEmbedding(torch.autograd.Function):
     """(B, H) subgraph embedding = [masked sum over components of every piece], written slot by slot: no (B, C, H)
     concatenation (S.py:286-312).  pieces: tensors (B, C, w) and ReadoutPiece objects; tensors: the differentiable
-    inputs in piece order (x | s, bp)."""
+    inputs in piece order (x | X, wp, bp).  The tensor pieces go through sgnn_masked_sum_slot(s)_fwd / _bwd, the read-out
+    pieces through sgnn_readout_many_fwd / _bwd."""
 
     @staticmethod
     def forward(ctx, mask, B, C, pieces, *tensors):
@@ -2471,7 +2473,7 @@ class _SubgraphEmbedding(torch.autograd.Function):
         widths = [p.A if isinstance(p, ReadoutPiece) else p.shape[-1] for p in pieces]
         H = sum(widths)
         out = torch.empty((B, H), dtype=torch.float32, device=mask.device)
-        off, k, plan = 0, 0, []
+        off, k, plan = 0, 0, []                      # plan: (column offset, width, index in tensors) of every tensor piece
         # batch-sized calls: all tensor pieces in one launch each way (scalar lanes; the shard-sized call keeps a vectorised
         # launch per piece, where the bytes matter and the launches do not)
         n_x = sum(1 for p in pieces if not isinstance(p, ReadoutPiece))
@@ -2479,8 +2481,7 @@ class _SubgraphEmbedding(torch.autograd.Function):
         slots = []
         many = []                                    # (piece, its column offset, index of its first tensor, its scores buffer)
         for p, w in zip(pieces, widths):
-            dst = ctypes.c_void_p(out.data_ptr() + 4 * off)
-            if isinstance(p, ReadoutPiece) and p.s is None:
+            if isinstance(p, ReadoutPiece):
                 X, wp, bp = tensors[k], tensors[k + 1], tensors[k + 2]
                 _req(X, torch.float32, 'X'), _req(wp, torch.float32, 'wp'), _req(bp, torch.float32, 'bp')
                 _req(p.sims2, torch.float32, 'sims'), _req(p.sim_col, torch.int64, 'sim_col'), _req(p.row_mask, torch.uint8, 'row_mask')
@@ -2488,19 +2489,7 @@ class _SubgraphEmbedding(torch.autograd.Function):
                 if p.R != B * C or (X is not None and (X.shape[0] != w or wp is None or wp.numel() != X.shape[1])):
                     raise ValueError('read-out piece: %d rows for B C = %d, anchors %s for width %d' % (p.R, B * C, None if X is None else tuple(X.shape), w))
                 many.append((p, off, k, torch.empty(w, dtype=torch.float32, device=mask.device)))
-                plan.append(('m', off, w, k, p))
                 k += 3
-            elif isinstance(p, ReadoutPiece):
-                s, bp = tensors[k], tensors[k + 1]
-                _req(s, torch.float32, 's'), _req(bp, torch.float32, 'bp'), _req(p.sims2, torch.float32, 'sims')
-                _req(p.sim_col, torch.int64, 'sim_col'), _req(p.row_mask, torch.uint8, 'row_mask')
-                if p.R != B * C or s.numel() != w:
-                    raise ValueError('read-out piece: %d rows for B C = %d, %d scores for %d anchors' % (p.R, B * C, s.numel(), w))
-                ld = p.sims2.shape[1] if p.sims2 is not None else 0
-                check(lib.sgnn_readout_sum_fwd(_ptr(p.sims2), ld, _ptr(p.sim_col), _ptr(s), _ptr(bp), _ptr(p.row_mask), B, C, w,
-                                               dst, H, _stream()), 'sgnn_readout_sum_fwd')
-                plan.append(('r', off, w, k, p))
-                k += 2
             else:
                 x = tensors[k]
                 _req(x, torch.float32, 'piece')
@@ -2509,12 +2498,13 @@ class _SubgraphEmbedding(torch.autograd.Function):
                 if together:
                     slots.append((x.data_ptr(), w, off))
                 else:
+                    dst = ctypes.c_void_p(out.data_ptr() + 4 * off)
                     check(lib.sgnn_masked_sum_slot_fwd(_ptr(x), _ptr(mask), B, C, w, dst, H, _stream()), 'sgnn_masked_sum_slot_fwd')
-                plan.append(('x', off, w, k, None))
+                plan.append((off, w, k))
                 k += 1
             off += w
         if slots:
-            ptrs, ws, offs = (np.array(v, dtype=t) for v, t in zip(zip(*slots), (np.uint64, np.int64, np.int64)))
+            ptrs, ws, offs = _slot_tables(slots)
             check(lib.sgnn_masked_sum_slots_fwd(ptrs.ctypes.data, ws.ctypes.data, offs.ctypes.data, len(slots), _ptr(mask), B, C,
                                                 _ptr(out), H, _stream()), 'sgnn_masked_sum_slots_fwd')
         ctx.many = []
@@ -2538,12 +2528,12 @@ class _SubgraphEmbedding(torch.autograd.Function):
         grads = [None] * len(tensors)
         if ctx.together:
             slots = []
-            for kind, off, w, k, p in ctx.plan:
-                if kind == 'x' and ctx.needs_input_grad[4 + k]:
+            for off, w, k in ctx.plan:
+                if ctx.needs_input_grad[4 + k]:
                     grads[k] = torch.empty((B, C, w), dtype=torch.float32, device=g.device)
                     slots.append((grads[k].data_ptr(), w, off))
             if slots:
-                ptrs, ws, offs = (np.array(v, dtype=t) for v, t in zip(zip(*slots), (np.uint64, np.int64, np.int64)))
+                ptrs, ws, offs = _slot_tables(slots)
                 check(lib.sgnn_masked_sum_slots_bwd(_ptr(g), H, _ptr(mask), B, C, ptrs.ctypes.data, ws.ctypes.data, offs.ctypes.data,
                                                     len(slots), _stream()), 'sgnn_masked_sum_slots_bwd')
         for group in ctx.many:
@@ -2566,30 +2556,18 @@ class _SubgraphEmbedding(torch.autograd.Function):
                 grads[k] = a
                 grads[k + 1] = b_.view_as(tensors[k + 1]) if b_ is not None else None
                 grads[k + 2] = c.view_as(tensors[k + 2]) if c is not None else None
-        for kind, off, w, k, p in ctx.plan:
-            src = ctypes.c_void_p(g.data_ptr() + 4 * off)
-            if kind == 'm':
-                continue
-            if kind == 'x':
-                if ctx.needs_input_grad[4 + k] and not ctx.together:
-                    gx = torch.empty((B, C, w), dtype=torch.float32, device=g.device)
-                    check(lib.sgnn_masked_sum_slot_bwd(src, H, _ptr(mask), B, C, w, _ptr(gx), _stream()), 'sgnn_masked_sum_slot_bwd')
-                    grads[k] = gx
-                continue
-            s, bp = tensors[k], tensors[k + 1]
-            need_s, need_b = ctx.needs_input_grad[4 + k], ctx.needs_input_grad[5 + k]
-            if not (need_s or need_b):
-                continue
-            gs = torch.empty(w, dtype=torch.float32, device=g.device) if need_s else None
-            gb = torch.empty(1, dtype=torch.float32, device=g.device) if need_b else None
-            wsb = lib.sgnn_readout_sum_bwd_workspace_bytes(B, C, w)
-            ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=g.device)
-            ld = p.sims2.shape[1] if p.sims2 is not None else 0
-            check(lib.sgnn_readout_sum_bwd(src, H, _ptr(p.sims2), ld, _ptr(p.sim_col), _ptr(s), _ptr(bp), _ptr(p.row_mask), B, C, w,
-                                           _ptr(gs), _ptr(gb), _ptr(ws), wsb, _stream()), 'sgnn_readout_sum_bwd')
-            grads[k] = gs.view_as(s) if gs is not None else None
-            grads[k + 1] = gb.view_as(bp) if gb is not None else None
+        if not ctx.together:
+            for off, w, k in ctx.plan:
+                if ctx.needs_input_grad[4 + k]:
+                    src = ctypes.c_void_p(g.data_ptr() + 4 * off)
+                    grads[k] = torch.empty((B, C, w), dtype=torch.float32, device=g.device)
+                    check(lib.sgnn_masked_sum_slot_bwd(src, H, _ptr(mask), B, C, w, _ptr(grads[k]), _stream()), 'sgnn_masked_sum_slot_bwd')
         return (None, None, None, None) + tuple(grads)
+
+
+def _slot_tables(slots):
+    """(device pointer, width, column offset) per tensor piece -> the three host arrays of sgnn_masked_sum_slots_fwd / _bwd."""
+    return tuple(np.array(v, dtype=t) for v, t in zip(zip(*slots), (np.uint64, np.int64, np.int64)))
 
 
 _RO_TICKETS = {}
@@ -2641,11 +2619,9 @@ def subgraph_embedding(pieces, mask, B, C):
     """cat(pieces, -1) summed over each subgraph's real components -> (B, H); mask (B C) uint8."""
     tensors = []
     for p in pieces:
-        if isinstance(p, ReadoutPiece) and p.s is None:
+        if isinstance(p, ReadoutPiece):
             tensors += [p.X.contiguous() if p.X is not None else None, p.wp.contiguous() if p.wp is not None else None,
                         p.bp.contiguous().view(-1)]
-        elif isinstance(p, ReadoutPiece):
-            tensors += [p.s.contiguous(), p.bp.contiguous().view(-1)]
         else:
             tensors.append(p.contiguous())
     return _SubgraphEmbedding.apply(mask.reshape(-1).contiguous(), int(B), int(C), list(pieces), *tensors)

@@ -78,7 +78,8 @@ CASES = [
     # 0..6 a tail iteration as well; one block of 64 rows wholly dead
     Case('many-rows-D64', 4200, 4, (InKernel(5, 64, ids=True, col='ld'), Tensor(2), InKernel(70, 64), InKernel(3, None)),
          dead_block=True, seed=8),
-    # the s-given form (sgnn_readout_sum_*): gradient of bp only, of s only, of both
+    # the s-given form (ReadoutPiece turns the scores into anchors X = s of width 1 with wp = 1; one launch group of three
+    # per case): gradient of bp only, of s only, of both
     Case('scores-three-trips', 33, 9, (Scores(65, grad=(False, True)), Tensor(3), Scores(5, 'ld', (True, False)), Scores(64)), seed=9),
     Case('scores-many-rows', 4200, 4, (Scores(5), Scores(3, 'ld', (False, True)), Scores(4, 'perm', (True, False))),
          dead_block=True, seed=10),
@@ -105,14 +106,15 @@ def row_blocks(case):
 
 
 def launch_groups(case):
-    """ops._readout_groups: the in-kernel pieces by anchor width (those without X ride with the smallest), each width in
-    launches of RO_MAX_PIECES -> the group sizes."""
-    many = [p for p in case.pieces if isinstance(p, InKernel)]
+    """ops._readout_groups: the read-out pieces by anchor width (those without X ride with the smallest; given scores are
+    anchors of width 1), each width in launches of RO_MAX_PIECES -> the group sizes."""
+    many = [p for p in case.pieces if not isinstance(p, Tensor)]
     if not many:
         return []
     by_d = {}
     for p in many:
-        by_d[p.D] = by_d.get(p.D, 0) + 1
+        d = 1 if isinstance(p, Scores) else p.D
+        by_d[d] = by_d.get(d, 0) + 1
     free = by_d.pop(None, 0)
     ds = sorted(by_d) or [1]
     by_d[ds[0]] = by_d.get(ds[0], 0) + free

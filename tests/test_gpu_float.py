@@ -330,8 +330,10 @@ def test_gather_rows_matches_embedding_with_padding_idx(det):
     assert float(Wg.grad[0].abs().max()) == 0.0
 
 
-@pytest.mark.parametrize('shape', [(17, 5, 37), (33, 3, 448), (50, 1, 64)])     # scalar form; 16-byte form (H % 4 == 0)
+@pytest.mark.parametrize('shape', [(17, 5, 37), (33, 3, 448), (50, 1, 64), (1, 1, 1), (3, 2, 4)])     # scalar form; 16-byte form (H % 4 == 0)
 def test_masked_sum(shape):
+    """ops.masked_sum (sgnn_masked_sum_slot_fwd / _bwd with a row stride equal to the width) against torch, and bit for bit:
+    the kernel adds a subgraph's live components in order, in float32, and the gradient is a copy or a zero."""
     ops = _ops()
     g = torch.Generator().manual_seed(0)
     x = torch.randn(*shape, generator=g)
@@ -345,6 +347,11 @@ def test_masked_sum(shape):
     (out * go.to(DEV)).sum().backward()
     assert_close(out, ref, 'masked_sum', norm_tol=1e-6)
     assert_close(xg.grad, xc.grad, 'masked_sum grad', norm_tol=1e-6)
+    acc = torch.zeros(shape[0], shape[2])
+    for c in range(shape[1]):
+        acc = torch.where(mask[:, c, None], acc + x[:, c], acc)
+    assert acc.dtype == torch.float32 and torch.equal(out.detach().cpu(), acc)
+    assert torch.equal(xg.grad.cpu(), go[:, None, :] * mask[..., None])
 
 
 @pytest.mark.parametrize('together', [True, False])
@@ -1293,7 +1300,8 @@ def test_device_side_batch_index_out_of_range_is_reported():
 def test_readout_pieces_with_scores_in_kernel(B, C):
     """Read-out pieces whose scores s = X wp (0 for a PAD anchor) are computed inside ops.subgraph_embedding's own launches
     (sgnn_readout_many_fwd / _bwd: all pieces of a step in two launches each way) against the same pieces with the scores made
-    by torch beforehand (one launch pair per piece + the autograd of s = X wp): embedding bit-equal, gradients of X, wp, bp and
+    by torch beforehand (given as ``s``: they travel as one-column anchors of weight 1 through the same launches, and the
+    autograd of s = X wp is torch's): embedding bit-equal, gradients of X, wp, bp and
     of the tensor pieces equal; two anchor widths in one call (two launch groups), a piece without anchors (all-zero
     similarities), nine pieces (more than one launch of eight)."""
     ops = _ops()

@@ -42,6 +42,8 @@ def test_cases_hold_what_the_kernels_branch_on():
     for shape in ((33, 9), (4200, 4)):
         grads = {p.grad for c in RC.CASES if (c.B, c.C) == shape for p in c.pieces if isinstance(p, RC.Scores)}
         assert grads >= {(True, False), (False, True), (True, True)}
+    # given scores travel as anchors of width 1: the three pieces of each such case share one launch group
+    assert all(RC.launch_groups(c) == [3] for c in RC.CASES if c.name in ('scores-three-trips', 'scores-many-rows'))
     grads = {p.grad for c in RC.CASES for p in c.pieces if isinstance(p, RC.InKernel) and p.D is not None}
     assert grads >= {(True, False, False), (False, True, False), (False, False, True), (True, True, True)}
     many = next(c for c in RC.CASES if c.name == 'many-slots')
