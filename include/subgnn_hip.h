@@ -410,6 +410,44 @@ int sgnn_insertion_write(const int64_t* set_ptr, const int32_t* set_nodes, int64
                          int32_t* out_parent, int32_t* out_cand, uint64_t* out_keys, void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Seeded walk sets: many connected candidate subgraphs around seed nodes, for finding further subgraphs of a class.  The
+ * reference has no counterpart; the nearest is its random-walk patch sampling (anchor_patch_samplers.py:20-113), whose walks
+ * are kept as sequences.  Here the SET of visited nodes is the result, ascending and with its content key, as the other set
+ * entries take it.
+ *
+ * The graph is rowptr (int64, max_id + 2) / col (int32): node ids 1 .. max_id, row 0 (PAD) empty, rows ascending, every edge
+ * in both rows.  seeds: int32[n_seeds].  sizes: int32[per_seed], the target size of candidate c of every seed; a value outside
+ * 1 .. width counts as clamped to it.  Item number q is item_ids[i] (int64[n_items]) if item_ids is given, else
+ * item_base + i; its seed is s = seeds[q / per_seed], its size sizes[q % per_seed].  Its draws come from
+ *     h1 = sgnn_tape_h1(sgnn_tape_h0(seed, stream), q)
+ * -- the item NUMBER, not the output row i: a chunk (item_base) or a list of items gives the bits of those rows of the whole
+ * call, so a caller may keep item numbers and regenerate their sets later.
+ *
+ * The walk: cur = s, set = {s}, t = 0.  A seed outside 1 .. max_id (or, with item_ids, q < 0 or q / per_seed >= n_seeds) gives
+ * the empty set with 0 steps; a seed without an edge gives {s} with 0 steps.  Otherwise, while |set| < size and t < max_steps:
+ *     r = (uint32)(sgnn_tape_draw(h1, 2t) >> 32)
+ *     (uint64) r < restart_thr:  cur = s
+ *     else:  d = rowptr[cur + 1] - rowptr[cur],  cur = col[rowptr[cur] + sgnn_choice_index(h1, 2t + 1, d)],  and cur joins
+ *            the set if it is no member (a row without entries, which only a one-way CSR has here, sends the walk to s)
+ *     t += 1
+ * cur is always a member, so every node that joins is adjacent to one: the set induces a connected subgraph that holds s.
+ * restart_thr is the restart probability in units of 2^-32, 0 .. 2^32 (the caller forms min(2^32, floor(p * 2^32)): no float
+ * arithmetic runs on the device).
+ *
+ * Row i of the outputs: out_nodes[i * width ..] the set ascending, then zeros up to width; out_len[i], out_steps[i] (the final
+ * t) int32; out_keys[i] = sgnn_set_key_finish(sum of sgnn_mix64(v), len): the bits sgnn_set_keys gives for the set.
+ * One wavefront per item; the set is held in four registers of every lane, width <= sgnn_seeded_walk_max_size() = 256.
+ * SGNN_ERR_BAD_ARG, with nothing written, for negative max_id, n_seeds, n_items, item_base or max_steps, width < 1 or above
+ * the maximum, per_seed < 1, restart_thr > 2^32, n_items or max_steps > 2^31 - 1, item_base + n_items > n_seeds * per_seed
+ * without item_ids, and a NULL pointer with items to write (seeds may be NULL for n_seeds = 0).  n_items = 0 writes nothing.
+ * ------------------------------------------------------------------------------------- */
+int64_t sgnn_seeded_walk_max_size(void);
+int sgnn_seeded_walk_sets(const int64_t* rowptr, const int32_t* col, int64_t max_id, const int32_t* seeds, int64_t n_seeds,
+                          const int32_t* sizes, int64_t per_seed, int64_t width, uint64_t restart_thr, int64_t max_steps,
+                          uint64_t seed, uint64_t stream, int64_t item_base, const int64_t* item_ids, int64_t n_items,
+                          int32_t* out_nodes, int32_t* out_len, int32_t* out_steps, uint64_t* out_keys, void* stream_handle);
+
+/* ---------------------------------------------------------------------------------------
  * a1-a3  Triangular random walks.
  * Replaces anchor_patch_samplers.triangular_random_walk / perform_random_walks /
  * sample_structure_anchor_patches (anchor_patch_samplers.py:20-158, 210-243).

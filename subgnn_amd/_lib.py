@@ -78,6 +78,9 @@ SIGNATURES = {
     'sgnn_insertion_count': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_ptr]),
     'sgnn_insertion_write': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_int, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
                                      c_ptr, c_ptr]),
+    'sgnn_seeded_walk_max_size': (c_i64, []),
+    'sgnn_seeded_walk_sets': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_u64, c_i64, c_u64, c_u64, c_i64,
+                                      c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sgnn_sample_anchors_ragged_keyed': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
     'sgnn_choice_ragged_keyed': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
     'sgnn_sample_border_anchors_keyed': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr,

@@ -111,6 +111,16 @@ __device__ __forceinline__ int32_t sgnn_wave_incl_scan(int32_t v) {
     return s;
 }
 
+// wrap-around sum of a uint64 over the 64 lanes, in every lane (the set keys' sums of sgnn_mix64)
+__device__ __forceinline__ uint64_t sgnn_wave_sum_u64(uint64_t acc) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)acc, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(acc >> 32), d);
+        acc += ((uint64_t)hi << 32) | lo;
+    }
+    return acc;
+}
+
 // ---- small device helpers ---------------------------------------------------------------
 __device__ static inline uint32_t sgnn_hash32(uint32_t x) { return x * 2654435761u; }
 

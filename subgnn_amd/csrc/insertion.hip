@@ -27,15 +27,6 @@ struct InsArgs {
     int64_t* out_ptr; int32_t* out_nodes; int32_t* out_parent; int32_t* out_cand; uint64_t* out_keys;
 };
 
-__device__ __forceinline__ uint64_t ins_wave_sum(uint64_t acc) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)acc, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(acc >> 32), d);
-        acc += ((uint64_t)hi << 32) | lo;
-    }
-    return acc;
-}
-
 template <int THREADS, int CAP, bool WRITE>
 __global__ __launch_bounds__(THREADS) void ins_kernel(const InsArgs a)
 {
@@ -64,7 +55,7 @@ __global__ __launch_bounds__(THREADS) void ins_kernel(const InsArgs a)
         if (WRITE) {
             uint64_t acc = 0;
             for (int i = tid; i < n; i += THREADS) acc += sgnn_mix64((uint64_t)(uint32_t)nodes[i]);
-            acc = ins_wave_sum(acc);
+            acc = sgnn_wave_sum_u64(acc);
             if (lane == 0) s_part[wave] = (unsigned long long)acc;
         }
         __syncthreads();

@@ -36,6 +36,7 @@ extern "C" int sgnn_warm_subgraph_props(void*);
 extern "C" int sgnn_warm_neighbors(void*);
 extern "C" int sgnn_warm_occlusion(void*);
 extern "C" int sgnn_warm_insertion(void*);
+extern "C" int sgnn_warm_seeded_sets(void*);
 extern "C" int sgnn_warm_up(void* stream)
 {
     int bad = 0;
@@ -61,5 +62,6 @@ extern "C" int sgnn_warm_up(void* stream)
     bad += sgnn_warm_neighbors(stream) != 0;
     bad += sgnn_warm_occlusion(stream) != 0;
     bad += sgnn_warm_insertion(stream) != 0;
+    bad += sgnn_warm_seeded_sets(stream) != 0;
     return bad == 0 ? SGNN_OK : SGNN_ERR_LAUNCH;
 }

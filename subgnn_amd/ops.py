@@ -949,6 +949,100 @@ def insertion_sets(sets, candidates, shared=False):
     return Insertion(Ragged(out_ptr, out_nodes, max_len=max_len + 1), parent, inserted, keys, variants)
 
 
+SEEDED_MAX_SIZE = 256          # csrc/seeded_sets.hip SGNN_SEEDED_MAX_SIZE (sgnn_seeded_walk_max_size): nodes of one sampled set
+
+
+class SeededSets:
+    """What ``seeded_walk_sets`` gives: ``nodes`` (n_items, width) int32, ``lengths``, ``steps`` int32, ``keys`` int64; ``sets``:
+    the non-empty rows as a Ragged, packed on first use."""
+
+    def __init__(self, nodes, lengths, steps, keys, may_be_empty):
+        self.nodes, self.lengths, self.steps, self.keys = nodes, lengths, steps, keys
+        self._may_be_empty, self._sets = may_be_empty, None
+
+    @property
+    def sets(self):
+        if self._sets is None:
+            dev = self.nodes.device
+            rows = self.nodes[self.lengths > 0] if self._may_be_empty else self.nodes
+            if rows.shape[0] == 0:
+                self._sets = Ragged(torch.zeros(1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev), max_len=0)
+            else:
+                packed = Ragged.from_padded(rows.long())
+                self._sets = Ragged(packed.ptr, packed.nodes, max_len=int(self.lengths.max()))
+        return self._sets
+
+
+def restart_threshold(restart):
+    """A restart probability in [0, 1] -> the integer the walk compares its 32-bit draw with: min(2^32, floor(p * 2^32))."""
+    p = float(restart)
+    if not 0.0 <= p <= 1.0:                                                             # (NaN fails both)
+        raise ValueError('restart must be in [0, 1], got %r' % (restart,))
+    return min(1 << 32, int(p * 4294967296.0))
+
+
+def _count(value, name, least=0):
+    if isinstance(value, bool) or int(value) != value or int(value) < least:
+        raise ValueError('%s must be an integer >= %d, got %r' % (name, least, value))
+    return int(value)
+
+
+def seeded_walk_sets(g, seeds, sizes, per_seed=None, restart=0.15, max_steps=None, seed=0, stream_id=0, item_base=0, n_items=None,
+                     item_ids=None):
+    """Connected candidate sets around seed nodes: the nodes a random walk with restarts from the seed visits until it holds its
+    target size or has taken ``max_steps`` steps (sgnn_seeded_walk_sets; include/subgnn_hip.h has the definition).  ``seeds``:
+    int32 device tensor of ids in 1 .. g.max_id.  ``sizes``: a sequence of ints in 1 .. SEEDED_MAX_SIZE, the target sizes of a
+    seed's ``per_seed`` candidates (default ``len(sizes)``; more candidates than sizes repeat them cyclically).  ``restart``: the
+    probability of a step back to the seed.  ``max_steps`` defaults to 16 * max(sizes).  Item q = ``item_base + i`` (or
+    ``item_ids[i]``, an int64 device tensor; an id outside 0 .. n_seeds * per_seed - 1 gives an empty row) is candidate
+    q % per_seed of seed q // per_seed, and its draws are those of item q on the tape (``seed``, ``stream_id``) whatever else the
+    call holds: a chunk or a list of items gives the rows of the whole call, bit for bit.
+    -> SeededSets: ``nodes`` (n_items, max(sizes)) int32, every row ascending and zero-filled; ``lengths``, ``steps`` int32;
+    ``keys`` (int64 holding the uint64 bits of ``set_keys``); ``sets``: the non-empty rows as a Ragged, packed on the device."""
+    sizes = [_count(v, 'sizes', 1) for v in sizes]
+    if not sizes or max(sizes) > SEEDED_MAX_SIZE:
+        raise ValueError('sizes: at least one, each in 1 .. %d' % SEEDED_MAX_SIZE)
+    per_seed = len(sizes) if per_seed is None else _count(per_seed, 'per_seed', 1)
+    thr = restart_threshold(restart)
+    width = max(sizes)
+    max_steps = 16 * width if max_steps is None else _count(max_steps, 'max_steps')
+    if max_steps > 0x7fffffff:
+        raise ValueError('max_steps: more than 2^31 - 1')
+    item_base = _count(item_base, 'item_base')
+    if n_items is not None:
+        n_items = _count(n_items, 'n_items')
+    if item_ids is not None and (n_items is not None or item_base != 0):
+        raise ValueError('item_ids stands in for item_base and n_items: give one or the other')
+    _req(seeds, torch.int32, 'seeds')
+    _req(item_ids, torch.int64, 'item_ids')
+    if seeds.dim() != 1 or (item_ids is not None and item_ids.dim() != 1):
+        raise ValueError('seeds and item_ids are one-dimensional')
+    n_seeds = seeds.numel()
+    if n_seeds and (int(seeds.min()) < 1 or int(seeds.max()) > g.max_id):
+        raise ValueError('seeds: ids outside 1 .. %d' % g.max_id)
+    if item_ids is not None:
+        n_items = item_ids.numel()
+    elif n_items is None:
+        n_items = max(n_seeds * per_seed - item_base, 0)
+    if item_ids is None and item_base + n_items > n_seeds * per_seed:
+        raise ValueError('items %d .. %d: beyond the %d x %d of the call' % (item_base, item_base + n_items - 1, n_seeds, per_seed))
+    if n_items > 0x7fffffff:
+        raise ValueError('%d items: more than 2^31 - 1 (send fewer at a time)' % n_items)
+    lib = _lib.load()
+    dev = g.device
+    size_row = torch.tensor([sizes[c % len(sizes)] for c in range(per_seed)], dtype=torch.int32, device=dev)
+    nodes = torch.empty((n_items, width), dtype=torch.int32, device=dev)
+    lengths = torch.empty(n_items, dtype=torch.int32, device=dev)
+    steps = torch.empty(n_items, dtype=torch.int32, device=dev)
+    keys = torch.empty(n_items, dtype=torch.int64, device=dev)
+    check(lib.sgnn_seeded_walk_sets(_ptr(g.rowptr), _ptr(g.col_sorted), g.max_id, _ptr(seeds), n_seeds, _ptr(size_row), per_seed,
+                                    width, thr, max_steps, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream_id) & 0xFFFFFFFFFFFFFFFF,
+                                    item_base, _ptr(item_ids), n_items, _ptr(nodes), _ptr(lengths), _ptr(steps), _ptr(keys),
+                                    _stream()), 'sgnn_seeded_walk_sets')
+    # (every seed is a node id, so only an item id beyond the call's leaves a row empty)
+    return SeededSets(nodes, lengths, steps, keys, may_be_empty=item_ids is not None)
+
+
 def _req_keys(keys, n, row_has_pad=None):
     _req(keys, torch.int64, 'keys')
     if keys.numel() != n:

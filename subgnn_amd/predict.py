@@ -97,10 +97,11 @@ class Predictor:
         return f
 
     # ------------------------------------------------------------------ a request --------
-    def map_subgraphs(self, subgraphs):
+    def map_subgraphs(self, subgraphs, allow_empty=False):
         """Node lists in the dataset's numbering -> the model's (read_data: id + 1), as sets: without the ids that are no nodes
         of the graph (beyond its ids, or without an edge: what subgraph_properties drops), without repeats, ascending ->
-        (ptr int64[n + 1], ids int32[total]) numpy arrays.  A list with nothing left is an error naming its index."""
+        (ptr int64[n + 1], ids int32[total]) numpy arrays.  A list with nothing left is an error naming its index (or, with
+        ``allow_empty``, an empty set)."""
         import itertools
         deg = self.freeze()['degree']
         max_id = deg.shape[0] - 1
@@ -117,7 +118,7 @@ class Predictor:
         first[1:] = (flat[1:] != flat[:-1]) | (rows[1:] != rows[:-1])
         flat, rows = flat[first], rows[first]
         counts = np.bincount(rows, minlength=n)
-        if n and int(counts.min()) == 0:
+        if n and not allow_empty and int(counts.min()) == 0:
             raise ValueError('subgraph %d holds no node of the graph' % int(np.argmin(counts != 0)))
         ptr = np.zeros(n + 1, dtype=np.int64)
         np.cumsum(counts, out=ptr[1:])
@@ -316,6 +317,14 @@ class Predictor:
         from . import suggest as _suggest
         return _suggest.grow(self, subgraphs, steps, target=target, min_gain=min_gain, candidates=candidates, hops=hops,
                              draws=draws, batch_size=batch_size)
+
+    def discover(self, seeds, sizes=(8,), per_seed=16, target=None, restart=0.15, max_steps=None, draws=1, top=100,
+                 top_per_seed=None, novel=False, batch_size=None, max_variants=65536, sample_seed=None):
+        """Connected candidate subgraphs sampled around seed nodes on the device, scored and ranked: ``discover.discover``."""
+        from . import discover as _discover
+        return _discover.discover(self, seeds, sizes=sizes, per_seed=per_seed, target=target, restart=restart, max_steps=max_steps,
+                                  draws=draws, top=top, top_per_seed=top_per_seed, novel=novel, batch_size=batch_size,
+                                  max_variants=max_variants, sample_seed=sample_seed)
 
     def nearest(self, index, subgraphs, k=10):
         """The ``k`` rows of ``index`` (a neighbors.SubgraphIndex) nearest to each requested subgraph: ``index.query``."""

@@ -23,6 +23,8 @@ STREAM_S_PICK = 9
 STREAM_NE_SPLIT = 10
 STREAM_NE_NEG = 11
 STREAM_NE_DROP = 12
+# candidate subgraphs around seed nodes (discover.py, ops.seeded_walk_sets): the item is the candidate's number
+STREAM_DISCOVER = 13
 
 # 'predict': requests outside the dataset (predict.py); their draws are keyed by content (set_key_np), not by row number
 SPLIT_CODE = {'train': 0, 'val': 1, 'test': 2, 'predict': 3}
