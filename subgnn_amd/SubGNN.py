@@ -229,8 +229,18 @@ class SubGNN(nn.Module):
         """The splits' subgraph lists were (re)read: what hotpath keeps per split of them (SplitFacts) is dropped."""
         from . import hotpath
         hotpath.forget_split_facts(self)
-        for sp in ('train', 'val', 'test'):
-            self.__dict__.pop('_subs_' + sp, None)
+
+    # For readers outside hotpath (bench.py's roofline measurements): the splits' kept set orders and border widths, as the
+    # plain dicts {split: order} and {(split, k, component rows, world): width} that once held them.  Built per read.
+    @property
+    def _degseq_order(self):
+        from . import hotpath
+        return hotpath.set_orders(self)
+
+    @property
+    def _border_width(self):
+        from . import hotpath
+        return hotpath.border_widths(self)
 
     def _read_memory(self, mem):
         """In-memory twin of read_data for synthetic inputs: ``mem`` = dict(graph=DeviceGraph,

@@ -325,6 +325,7 @@ class PassState:
         self.sim_cols = None       # (anchors_structure, {layer: device index tensor}) when new patches were drawn
         self.dtw_inputs = None     # between prepare_pass(defer_dtw=True) and finish_pass: what the DTW launches read
         self.x_fixed = False       # the component degree sequences among them are the split's kept ones (SplitFacts)
+        self.facts = None          # the split's record the pass worked from (SplitFacts): finish_pass reads its dtw_rows
         self.bfs_checks = []       # hinted position-channel searches to verify before the pass is consumed (_verify_bfs)
         self.pool_reused = False   # the pass re-picked from an earlier pass's structure-patch pool (prepare_pass(pool=...))
 
@@ -341,10 +342,290 @@ def pool_of(st):
             'int_sims': st.attrs[sp + '_int_struc_similarities'], 'bor_sims': st.attrs[sp + '_bor_struc_similarities']}
 
 
+class _Pass:
+    """One ``prepare_pass`` call: the locals that more than one of its stages reads.  The stages below fill it in as they run."""
+
+    def __init__(self, model, split, shard, pool, epoch, timer, main, side):
+        hp = model.hparams
+        self.model, self.hp, self.g, self.dev = model, hp, model.networkx_graph, model.device
+        self.split, self.shard, self.pool, self.main, self.side = split, shard, pool, main, side
+        self.dealt = shard is not None and shard.deal_shared
+        self.seed = int(hp.get('seed', 0)) & tape.MASK64
+        # the resample epoch of the draws (SubGNN.py:453-460: resample_anchor_patches draws fresh N / P anchors and re-picks the structure
+        # patches after every validation epoch; the patches and their walks are not drawn again): the model's, unless the caller says
+        self.ep = int(model.__dict__.get('_resample_epoch', 0)) if epoch is None else int(epoch)
+        self.base = shard.start if shard is not None else 0             # global number of this rank's first subgraph
+        self.det = bool(getattr(model, '_deterministic', ops.DETERMINISTIC))
+        self.L = hp['n_layers']
+        self.st, self.t = PassState(split), timer or StageTimer(False)
+        self.st.pool_reused = pool is not None
+        # What depends on the split's subgraph lists and the graph only -- the components with what hangs on them, the component
+        # sets, their sorted form and their degree sequences -- is computed by the split's first pass and kept (SplitFacts):
+        # a steady pass launches nothing for it.  hparams['keep_split_facts'] = False: every pass computes it, as before.
+        self.keep_facts = bool(hp.get('keep_split_facts', True))
+        # (a recording that finds nothing kept computes per pass: what it allocates belongs to the recording)
+        recording = torch.cuda.is_current_stream_capturing()
+        self.store_facts = self.keep_facts and not recording
+        self.rec = self.st.facts = _split_record(model, split, getattr(model, split + '_sub_G'), self.g, shard, store=not recording)
+        self.sims = {}
+        self.cc_ids = self.cc_sets = self.real = None                    # (S, C, Lc) component ids, their rows as sets, which are real
+        self.once = ''                                                   # '(first pass only)' on the marks of the pass that builds the facts
+        # The structure patches keep the walks' full width (no trim to the longest walk: that was a host round trip, and
+        # with a second prepared pass queued on this stream the host waited for that pass's DTW launch there).
+        self.new_patches = hp['use_structure'] and pool is None and (split != 'test' or getattr(model, 'structure_anchors', None) is None)
+        self.structure_anchors = getattr(model, 'structure_anchors', None) if pool is None else pool['structure_anchors']
+        self.a_sets = self.ai = self.ae = self.ci = self.ce = None       # the DTW operands: the patches' side and the components'
+        self.x_fixed = False                                             # the DTW launches' x side comes from kept facts (finish_pass)
+
+
+def _components(cx):
+    """Components (main): the device copy of the lists, the padded component ids with what hangs on them, the component sets
+    and their dispatch order -- taken from the split's record where it holds them."""
+    rec, g, shard, split, t = cx.rec, cx.g, cx.shard, cx.split, cx.t
+    if rec.subs is None:
+        rec.subs = ops.Ragged.from_lists(rec.sub_g, cx.dev)
+    subs = rec.subs
+    kept = cx.keep_facts and rec.cc_ids is not None
+    facts_new = cx.store_facts and not kept
+    cx.once = '(first pass only)' if facts_new else ''
+    if kept:
+        rec.wait(cx.main)
+        cc_ids, cc_sets, real = rec.cc_ids, rec.cc_sets, rec.real
+    else:
+        labels = ops.cc_labels(g, subs)
+        # the padded (components per subgraph, component length) is a property of the split's subgraph lists (and, sharded,
+        # of all ranks'): read back on the first pass, kept afterwards -- one statistics launch and one host round trip less
+        cc_ids = subgraph_utils.components_from_labels(subs.ptr, subs.nodes, labels, subs.max_len,
+                                                       dims_reduce=shard.reduce_max if shard is not None else None, dims=rec.dims)
+        rec.dims = tuple(cc_ids.shape[1:])
+    S, C, Lc = cc_ids.shape
+    cx.st.attrs[split + '_cc_ids'] = cc_ids
+    if cx.det:
+        # the component-embedding backward scatters per member id in sorted order: the members of a split's
+        # components are the same every pass, so their order is computed on the first pass and kept
+        if rec.member_order is None:
+            rec.member_order = ops.sort_edges_by_key(cc_ids.reshape(-1).to(torch.int32), g.max_id)
+        cc_ids._sgnn_member_order = rec.member_order
+    elif getattr(cc_ids, '_sgnn_member_order', None) is not None:
+        del cc_ids._sgnn_member_order                           # (kept components of a model that was deterministic before)
+    if not kept:
+        cc_ids._sgnn_ids32 = cc_ids.reshape(-1).to(torch.int32)        # what the component-embedding kernel reads
+        cc_sets = ops.Ragged.from_padded(cc_ids.reshape(S * C, Lc))
+        real = (cc_ids[:, :, 0] != 0)
+        # which component rows are real, as forward reads it (SubGNN._forward: bool (S, C) and its uint8 twin): made here, beside
+        # the sampling stages, and carried on the tensor -- two small launches less per training half
+        cc_ids._sgnn_mask = real
+        cc_ids._sgnn_mask_u8 = real.reshape(-1).to(torch.uint8)
+        if facts_new:
+            rec.keep_components(cc_ids, cc_sets, real)
+        t.mark('components' + cx.once)
+    # dispatch order of the component sets, heaviest (largest total degree) first: a property of the
+    # split's subgraphs and the graph, computed once per split and kept.  The set kernels whose cost is
+    # the members' degree sum (degree sequences, border BFS) take their sets in this order.
+    if rec.set_order is None:
+        rec.set_order = ops.heaviest_first(g, cc_sets)
+        t.mark('set_dispatch_order(first pass only)')
+    cx.cc_ids, cx.cc_sets, cx.real = cc_ids, cc_sets, real
+
+
+def _structure_patches(cx):
+    """Structure patches (side): the pool of patches the split's walks and DTW rows are made of."""
+    hp, g, dev, shard = cx.hp, cx.g, cx.dev, cx.shard
+    if cx.dealt and hp['structure_patch_type'] == 'triangular_random_walk':
+        # strong scaling: every rank walks an eighth of the shared patches (tape items = global walk numbers)
+        n_p = hp['max_sim_epochs'] * hp['n_anchor_patches_structure'] * hp['n_layers']
+        cx.structure_anchors = _deal_rows(shard, n_p, lambda lo, hi: aps.sample_structure_anchor_patches(
+            hp, g, dev, hp['max_sim_epochs'], trim=False, share=(lo, hi)), (hp['sample_walk_len'],), torch.int64, dev,
+            key=('S_patches', cx.split))
+    else:
+        cx.structure_anchors = aps.sample_structure_anchor_patches(hp, g, dev, hp['max_sim_epochs'], trim=False)
+    cx.st.attrs['structure_anchors'] = cx.structure_anchors
+
+
+def _position_channel(cx):
+    """Position channel: the shared P-border anchors, the per-subgraph P-internal draws and the multi-source BFS."""
+    model, hp, g, dev, split, shard, st, sims = cx.model, cx.hp, cx.g, cx.dev, cx.split, cx.shard, cx.st, cx.sims
+    cc_ids, cc_sets, real = cx.cc_ids, cx.cc_sets, cx.real
+    S, C, Lc = cc_ids.shape
+    anchors_pos_ext = getattr(model, 'anchors_pos_ext', None)
+    if anchors_pos_ext is None or split != 'test':
+        anchors_pos_ext = st.attrs['anchors_pos_ext'] = aps.init_anchors_pos_ext(hp, g, dev, epoch=cx.ep)
+        if cx.det:
+            for v in anchors_pos_ext.values():
+                ops.presort_ids(v, g.max_id)
+    pint = {l: ops.choice_ragged(cx.rec.subs, hp['n_anchor_patches_pos_in'], cx.seed,
+                                 tape.stream_id(tape.STREAM_P_INT, split, l, cx.ep), item_base=cx.base) for l in range(cx.L)}
+    st.per_split['anchors_pos_int'] = pint
+    until, cap = _position_until(hp), hp.get('max_bfs_hops', 32)
+    for l in range(cx.L):
+        if cx.dealt:
+            if getattr(shard, 'emulator', None) is not None:
+                w, status = _emulated_position_sims(g, anchors_pos_ext[l], cc_sets, cc_ids, shard, cap, (split, l))
+            else:
+                w, status = _dealt_position_sims(g, anchors_pos_ext[l], cc_sets, cc_ids, shard, cap)
+            w = w.view(S, C, -1)
+            # full cap, all ranks' worst status: verified before the pass is consumed like the hinted searches
+            # (nothing to repeat: running out of levels here means max_bfs_hops is too small)
+            model.__dict__.setdefault('_bfs_level_hint', {}).setdefault(('P_out_dealt', split, l), 0)
+            _bfs_note(model, st, ('P_out_dealt', split, l), status, cap, cap, None)
+        else:
+            cap = hp.get('max_bfs_hops', 32)
+            nlev = _bfs_levels(model, ('P_out', split, l), cap)
+            src = anchors_pos_ext[l].to(torch.int32).contiguous()
+            w, status = ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=nlev, want_status=True,
+                                                 push_levels=_bfs_push_levels(model, ('P_out', split, l)), until=until)
+
+            def redo(levels, src=src, l=l, sims=sims, until=until):
+                # the hinted search ran out of levels: the same search with the full cap, similarities replaced.
+                # It runs on the INSTALLING stream: what it reads was allocated on the preparation stream
+                _hand_over(torch.cuda.current_stream(), src, cc_sets)
+                w2, st2 = ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=levels, want_status=True, until=until)
+                sims[('P', 'out', l)] = w2.view(S, C, -1).contiguous()
+                return st2.tolist()
+            _bfs_note(model, st, ('P_out', split, l), status, cap, nlev, redo)
+            w = w.view(S, C, -1)
+        # (rows of padded components need no masking: an empty set receives no level in msbfs_set_reduce and
+        # keeps the 0 the output was cleared to -- test_sparse_prepare_equals_dense_prepare checks the raw rows)
+        sims[('P', 'out', l)] = w.contiguous()
+        if C == 1:
+            sims[('P', 'in', l)] = ops.ZeroSims((S, C, hp['n_anchor_patches_pos_in']), dev)
+        else:
+            uniq, inv = torch.unique(pint[l], return_inverse=True)
+            if uniq.numel() * (g.max_id + 1) <= MAX_PINT_BYTES:
+                d = ops.bfs_hops(g, uniq.to(torch.int32).contiguous(), max_hops=hp.get('max_bfs_hops', 32),
+                                 node_major=True)
+                full = ops.min_hops_to_sets(d, cc_sets, node_major=True).view(S, C, -1)     # (S, C, U)
+                w = torch.gather(full, 2, inv.view(S, 1, -1).expand(S, C, -1))
+            else:
+                w = _pint_sims_streamed(g, uniq, inv, cc_sets, S, C, hp.get('max_bfs_hops', 32))
+            sims[('P', 'in', l)] = (w * real.unsqueeze(-1)).contiguous()
+
+
+def _structure_walks(cx):
+    """Walks over the structure patches and the per-layer picks.  Which stream: see ``walks_on_side`` in prepare_pass."""
+    model, hp, g, dev, shard, st, pool = cx.model, cx.hp, cx.g, cx.dev, cx.shard, cx.st, cx.pool
+    structure_anchors = cx.structure_anchors
+    if cx.new_patches and cx.dealt:
+        # the walks over the shared patches, dealt: a rank builds the node views of ITS patches only
+        W_, T_ = hp['n_triangular_walks'], hp['random_walk_len']
+
+        def both(lo, hi):
+            mine = structure_anchors[lo:hi].contiguous()
+            v = aps.patch_node_views(mine)
+            iw, bw = aps.perform_random_walks_both(hp, g, mine, v, first_patch=lo)
+            return torch.stack([bw, iw], 1)
+        walks = _deal_rows(shard, structure_anchors.shape[0], both, (2, W_, T_), torch.int64, dev, key=('S_walks', cx.split))
+        bor_w = st.attrs['bor_structure_anchor_random_walks'] = walks[:, 0].contiguous()
+        int_w = st.attrs['int_structure_anchor_random_walks'] = walks[:, 1].contiguous()
+    elif cx.new_patches:
+        views = aps.patch_node_views(structure_anchors)
+        # (internal and border walks in ONE launch: 1050 + 1050 one-workgroup-per-CU walks fill the chip's rounds better)
+        int_w, bor_w = aps.perform_random_walks_both(hp, g, structure_anchors, views)
+        st.attrs['bor_structure_anchor_random_walks'], st.attrs['int_structure_anchor_random_walks'] = bor_w, int_w
+    if pool is not None:
+        int_w, bor_w = pool['int_w'], pool['bor_w']
+        st.attrs['structure_anchors'] = structure_anchors
+        st.attrs['int_structure_anchor_random_walks'], st.attrs['bor_structure_anchor_random_walks'] = int_w, bor_w
+    if cx.new_patches or pool is not None:
+        a_struct = st.attrs['anchors_structure'] = aps.init_anchors_structure(hp, structure_anchors, int_w, bor_w,
+                                                                              indices_on_device=True, epoch=cx.ep)
+        if cx.det:
+            # forward runs the LSTM once over a layer's internal AND border walks (SubGNN._structure_anchor_embeddings):
+            # the stacked walks and the sort their embedding lookup's backward needs are made here
+            for v in a_struct.values():
+                v[2]._sgnn_both = ops.presort_ids(torch.cat([v[2], v[3]], 0), g.max_id)
+            if cx.L > 1:                             # (forward runs ONE LSTM pass over the walks of all layers)
+                a_struct[0][2]._sgnn_all = ops.presort_ids(
+                    torch.cat([t for l in range(cx.L) for t in (a_struct[l][2], a_struct[l][3])], 0), g.max_id)
+        # the column upload is a blocking host->device copy: do it here, before the long DTW
+        # launches are queued, so that the host is free to queue forward/backward behind them
+        st.sim_cols = (a_struct, model.sim_cols_of(a_struct))
+
+
+def _patch_degree_sequences(cx):
+    """The structure patches' degree sequences: what the DTW launches read of the patches (not the walks).  A pass that reuses
+    a pool does not run this: the pool's similarity rows exist, no degree sequences, no DTW."""
+    cx.a_sets = ops.Ragged.from_padded(cx.structure_anchors)
+    cx.ai, cx.ae = ops.degree_sequence(cx.g, cx.a_sets, sort=True, use_degree_dict=cx.g.full_degree is not None)
+
+
+def _neighbourhood_channel(cx):
+    """Neighbourhood channel (main): the N-internal draws, the one-hop border anchors with their hop similarities, and the
+    border layer's edge plans."""
+    hp, g, dev, split, shard, rec, sims, seed, ep = cx.hp, cx.g, cx.dev, cx.split, cx.shard, cx.rec, cx.sims, cx.seed, cx.ep
+    cc_ids, cc_sets = cx.cc_ids, cx.cc_sets
+    S, C, Lc = cc_ids.shape
+    k = hp['neigh_sample_border_size']
+    if cx.keep_facts and rec.cc_canon is not None:
+        has_pad_c, cc_canon = rec.has_pad_c, rec.cc_canon
+    else:
+        has_pad_c = (cc_sets.lengths < Lc).to(torch.uint8)
+        cc_canon = ops.sort_ragged(cc_sets)                 # the draw ranks the ascending members
+        if cx.store_facts:
+            rec.has_pad_c, rec.cc_canon = has_pad_c, cc_canon
+            rec.built()
+    ni, nb, plans = {}, {}, {}
+    border = _kept_border(cx, k)
+    # the padded border matrix's width (the largest border: the PAD rule needs it) is a property of the split's
+    # components and the graph, not of the draw: reduced (over the ranks too) on the first pass, kept afterwards
+    widths = rec.border_width
+
+    def width_from(counts):
+        if k not in widths:
+            wmax = counts.max().view(1)
+            widths[k] = shard.reduce_max(wmax) if shard is not None else wmax
+    for l in range(cx.L):
+        ni[l] = ops.sample_anchors_ragged(cc_canon, hp['n_anchor_patches_N_in'], seed,
+                                          tape.stream_id(tape.STREAM_N_INT, split, l, ep), has_pad_c,
+                                          canonical=True, item_base=cx.base * C).view(S, C, -1)
+        sims[('N', 'in', l)] = ops.ZeroSims(ni[l].shape, dev)
+        # border BFS fused with the border-anchor draw (rank query on the visited bitmap): the
+        # border is never materialised
+        # the one-hop border itself is a property of the split too: written once per split, sorted (_kept_border), and every pass,
+        # layer and resample epoch draws from the kept ids -- the draw is all that changes
+        if border is not None:
+            width_from(border.counts)
+            a, w, counts = ops.draw_border_anchors(border, hp['n_anchor_patches_N_out'], seed,
+                                                   tape.stream_id(tape.STREAM_N_BOR, split, l, ep), item_base=cx.base * C,
+                                                   width=widths[k])
+        else:
+            a, w, counts = ops.khop_border_sample(g, cc_sets, k, hp['n_anchor_patches_N_out'], seed,
+                                                  tape.stream_id(tape.STREAM_N_BOR, split, l, ep),     # taken dynamically: a dispatch order buys nothing here
+                                                  item_base=cx.base * C,
+                                                  count_reduce=shard.reduce_max if shard is not None else None,
+                                                  width=widths.get(k))
+        width_from(counts)
+        nb[l] = a.view(S, C, -1)
+        sims[('N', 'out', l)] = w.view(S, C, -1).contiguous()
+        D = hp['node_embed_size']
+        if cx.det and hp.get('fused_forward', True) and D % 4 == 0 and D <= 256 and (D // 4) & (D // 4 - 1) == 0:
+            # the border layer's table gradient is a sorted scatter: its edge list and order are known here
+            plan = ops.mpn_edge_plan(sims[('N', 'out', l)], nb[l], cc_ids._sgnn_mask_u8, R=S * C,
+                                     A=nb[l].shape[-1], D=D, max_key=g.max_id, sims_per_edge=True)
+            plan['anchors'] = nb[l]
+            plans[('N', False, l)] = plan
+    cx.st.per_split['anchors_neigh_int'], cx.st.per_split['anchors_neigh_border'] = ni, nb
+    cx.st.per_split['_mpn_edge_plans'] = plans
+
+
+def _component_degree_sequences(cx):
+    """The components' degree sequences (main): the x side of the DTW launches, kept with the split's facts."""
+    rec = cx.rec
+    if cx.keep_facts and rec.ci is not None:
+        cx.ci, cx.ce, cx.x_fixed = rec.ci, rec.ce, True
+        return
+    cx.ci, cx.ce = ops.degree_sequence(cx.g, cx.cc_sets, sort=True, use_degree_dict=cx.g.full_degree is not None,
+                                       order=rec.set_order)
+    if cx.store_facts:
+        rec.ci, rec.ce, cx.x_fixed = cx.ci, cx.ce, True
+        rec.built()
+    cx.t.mark('degree_sequences' + cx.once)
+
+
 def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, pool=None, epoch=None):
     """The sampling + similarity half of a pass (everything that does not read the embedding table), for one split
     (SubGNN.py:1024-1063 semantics, sparse similarities) -> PassState.  The model's per-pass attributes are left
-    alone (only its per-split caches of pass-invariant facts are filled), so the pass can be prepared while the
+    alone (only the split's record of pass-invariant facts, SplitFacts, is filled), so the pass can be prepared while the
     previous one is still training on the model (PassPipeline).
     ``shard`` (dist.Shard): the model holds one rank's block of the split's subgraphs; draws then read the
     tape items of the GLOBAL subgraph numbers and padded widths are reduced over ranks, so that the
@@ -362,366 +643,128 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
     sequences or DTW launches; the pass re-picks its layers' patches from the pool (init_anchors_structure) and reads the
     pool's similarity rows.  The reference's design: max_sim_epochs x n_anchor_patches_structure x n_layers patches are sampled
     and scored once (SubGNN.py:783-833, anchor_patch_samplers.py:210-243) so that re-picking is free (aps:316-328)."""
-    hp, g, dev = model.hparams, model.networkx_graph, model.device
-    if pool is not None and (shard is not None and shard.deal_shared):
+    hp = model.hparams
+    structure, position = hp['use_structure'], hp['use_position']
+    dealt = shard is not None and shard.deal_shared
+    if pool is not None and dealt:
         raise ValueError('pool reuse is not combined with the dealt (strong-scaling) form')
-    seed = int(hp.get('seed', 0)) & tape.MASK64
-    # the resample epoch of the draws (SubGNN.py:453-460: resample_anchor_patches draws fresh N / P anchors and re-picks the structure
-    # patches after every validation epoch; the patches and their walks are not drawn again): the model's, unless the caller says
-    ep = int(model.__dict__.get('_resample_epoch', 0)) if epoch is None else int(epoch)
-    st = PassState(split)
-    st.pool_reused = pool is not None
-    t = timer or StageTimer(False)
-    L = hp['n_layers']
     main = torch.cuda.current_stream()
     # (the dealt -- strong-scaling -- form overlaps too: its exchanges are issued by this one host thread in one fixed order on
     # every rank, and torch's process group runs them on its own stream behind whichever stream issued them: the position search
     # with its all-to-all on the side stream beside the border / walks / DTW chain.  hparams['overlap_streams_dealt'] = False
     # keeps the dealt form on one stream, as rounds 2-5 ran it)
-    if hp.get('overlap_streams', True) and (hp.get('overlap_streams_dealt', True) or not (shard is not None and shard.deal_shared)):
+    if hp.get('overlap_streams', True) and (hp.get('overlap_streams_dealt', True) or not dealt):
         if getattr(model, '_side_stream', None) is None:
             model._side_stream = torch.cuda.Stream()
         side = model._side_stream
     else:
         side = main
+    two = side is not main
+    # Where the position search runs.  It is memory-bound (pull levels gather a 32-byte row per edge) and the DTW launches are
+    # bound by fp64 vector issue: started TOGETHER the two share the chip (tools/dtw_overlap_probe.py: DTW 4.6 ms + search
+    # 1.5 ms take 5.0 ms side by side, 69 % of the search hidden; degree sequences, walks and the table's Adam hide
+    # completely, the one-hop border kernel 38 %).  hparams['bfs_beside_dtw'] queues the search behind an event the main
+    # stream records right before the DTW launches.  Measured in the pipelined schedule (round 4): the border stage drops
+    # from 2.66 to 1.90 ms and the DTW stage grows from 5.2 to 6.2 -- the step stays at 9.4-9.5 ms, because the training
+    # half of the previous pass already fills what the DTW launch leaves free: the device is saturated by total work, the
+    # schedule only moves it around.  Default False (the search beside the border kernel, as before).
+    late_bfs = bool(hp.get('bfs_beside_dtw', False)) and two and structure and position and not defer_dtw and not dealt
+    cx = _Pass(model, split, shard, pool, epoch, timer, main, side)
+    st, t = cx.st, cx.t
     t.mark('start')
     # ---- components (main) ---------------------------------------------------------------
-    sub_g = getattr(model, split + '_sub_G')
-    srcs = model.__dict__.setdefault('_subs_src', {})
-    if not hasattr(model, '_subs_' + split) or srcs.get(split, sub_g) is not sub_g or getattr(model, '_subs_' + split).n != len(sub_g):
-        setattr(model, '_subs_' + split, ops.Ragged.from_lists(sub_g, dev))
-    srcs[split] = sub_g                                         # (the list the device copy was made from: another, or one
-    #                                                             that changed its length, is uploaded again)
-    subs = getattr(model, '_subs_' + split)
-    # What depends on the split's subgraph lists and the graph only -- the components with what hangs on them, the component
-    # sets, their sorted form and their degree sequences -- is computed by the split's first pass and kept (SplitFacts):
-    # a steady pass launches nothing for it.  hparams['keep_split_facts'] = False: every pass computes it, as before.
-    keep_facts = bool(hp.get('keep_split_facts', True))
-    facts = _split_facts(model, split, sub_g, subs.n, g, shard) if keep_facts else None
-    # (a recording that finds nothing kept computes per pass: what it allocates belongs to the recording)
-    facts_new = keep_facts and facts is None and not torch.cuda.is_current_stream_capturing()
-    once = '(first pass only)' if facts_new else ''
-    det = bool(getattr(model, '_deterministic', ops.DETERMINISTIC))
-    if facts is not None:
-        facts.wait(main)
-        cc_ids, cc_sets, real = facts.cc_ids, facts.cc_sets, facts.real
-        S, C, Lc = cc_ids.shape
-    else:
-        labels = ops.cc_labels(g, subs)
-        # the padded (components per subgraph, component length) is a property of the split's subgraph lists (and, sharded,
-        # of all ranks'): read back on the first pass, kept afterwards -- one statistics launch and one host round trip less
-        kept = model.__dict__.setdefault('_cc_dims', {})
-        tag = (id(sub_g), subs.n)
-        hit = kept.get(split)
-        cc_ids = subgraph_utils.components_from_labels(subs.ptr, subs.nodes, labels, subs.max_len,
-                                                       dims_reduce=shard.reduce_max if shard is not None else None,
-                                                       dims=hit[1] if hit is not None and hit[0] == tag else None)
-        kept[split] = (tag, tuple(cc_ids.shape[1:]))
-        S, C, Lc = cc_ids.shape
-    st.attrs[split + '_cc_ids'] = cc_ids
-    if det:
-        # the component-embedding backward scatters per member id in sorted order: the members of a split's
-        # components are the same every pass, so their order is computed on the first pass and kept
-        mo = model.__dict__.setdefault('_cc_member_order', {})
-        if facts_new:
-            mo.pop(split, None)                                 # (new facts: maybe another list of the same size)
-        if mo.get(split) is None or mo[split][0].numel() != cc_ids.numel():
-            mo[split] = ops.sort_edges_by_key(cc_ids.reshape(-1).to(torch.int32), g.max_id)
-        cc_ids._sgnn_member_order = mo[split]
-    elif getattr(cc_ids, '_sgnn_member_order', None) is not None:
-        del cc_ids._sgnn_member_order                           # (kept components of a model that was deterministic before)
-    base = shard.start if shard is not None else 0             # global number of this rank's first subgraph
-    if facts is None:
-        cc_ids._sgnn_ids32 = cc_ids.reshape(-1).to(torch.int32)        # what the component-embedding kernel reads
-        cc_sets = ops.Ragged.from_padded(cc_ids.reshape(S * C, Lc))
-        real = (cc_ids[:, :, 0] != 0)
-        # which component rows are real, as forward reads it (SubGNN._forward: bool (S, C) and its uint8 twin): made here, beside
-        # the sampling stages, and carried on the tensor -- two small launches less per training half
-        cc_ids._sgnn_mask = real
-        cc_ids._sgnn_mask_u8 = real.reshape(-1).to(torch.uint8)
-        if facts_new:
-            facts = _keep_split_facts(model, split, SplitFacts(sub_g, subs.n, g, shard, cc_ids, cc_sets, real))
-        t.mark('components' + once)
-    # dispatch order of the component sets, heaviest (largest total degree) first: a property of the
-    # split's subgraphs and the graph, computed once per split and kept.  The set kernels whose cost is
-    # the members' degree sum (degree sequences, border BFS) take their sets in this order.
-    orders = model.__dict__.setdefault('_degseq_order', {})
-    if orders.get(split) is None or orders[split].numel() != cc_sets.n:
-        orders[split] = ops.heaviest_first(g, cc_sets)
-        t.mark('set_dispatch_order(first pass only)')
-    set_order = orders[split]
-    sims = {}
-    a_sets = ai = ae = None
-    # ---- side stream: position channel + structure patches / walks -------------------------
+    _components(cx)
+    # Where the walks run (decided here, not above: by the number of component rows).  For shards of up to
+    # WALKS_ON_SIDE_MAX_SETS component rows (round 6): on the SIDE stream, right behind the patches and AHEAD of the position
+    # search.  Nothing on the main chain reads the walks -- the DTW launches read the patches' degree sequences only -- so they leave it; and they no longer run BESIDE the search: a walk is one
+    # 1024-thread workgroup around a 125 KB LDS bitmap, it needs 16 free wavefront slots on one CU at once, and the search's
+    # small workgroups kept every CU's slots busy -- at 6 250 subgraphs the walks' stage took 1.3-1.45 ms on the main chain
+    # for 0.27 ms of kernel: the pass 3.08 -> 2.79 ms (same box, back to back).  At the benchmark's 50k subgraphs the main
+    # chain is the long one either way and the walks hide better there (8.82 vs 8.87 ms pipelined, 9.31 vs 9.60 sequential):
+    # they stay on the main chain, as rounds 3-5 had them.  hparams['walks_on_side_stream'] = True / False forces either.
+    wos = hp.get('walks_on_side_stream')            # None: by size; True / False: forced
+    walks_on_side = (bool(wos) if wos is not None else cx.cc_sets.n <= WALKS_ON_SIDE_MAX_SETS) and two and structure
+    # ---- side stream: structure patches, position channel (+ the walks, see above) ------------
     side.wait_stream(main)
-    if facts is not None and side is not main:
-        facts.wait(side)
+    if two and cx.keep_facts and cx.rec.cc_ids is not None:
+        cx.rec.wait(side)
+    patch_ev = None
     with torch.cuda.stream(side):
-        # The structure patches keep the walks' full width (no trim to the longest walk: that was a host round trip, and
-        # with a second prepared pass queued on this stream the host waited for that pass's DTW launch there).
-        new_patches = hp['use_structure'] and pool is None and (split != 'test' or getattr(model, 'structure_anchors', None) is None)
-        structure_anchors = getattr(model, 'structure_anchors', None) if pool is None else pool['structure_anchors']
-        if new_patches:
-            if shard is not None and shard.deal_shared and hp['structure_patch_type'] == 'triangular_random_walk':
-                # strong scaling: every rank walks an eighth of the shared patches (tape items = global walk numbers)
-                n_p = hp['max_sim_epochs'] * hp['n_anchor_patches_structure'] * hp['n_layers']
-                structure_anchors = _deal_rows(shard, n_p, lambda lo, hi: aps.sample_structure_anchor_patches(
-                    hp, g, dev, hp['max_sim_epochs'], trim=False, share=(lo, hi)), (hp['sample_walk_len'],), torch.int64, dev,
-                    key=('S_patches', split))
-                st.attrs['structure_anchors'] = structure_anchors
-            else:
-                structure_anchors = st.attrs['structure_anchors'] = aps.sample_structure_anchor_patches(hp, g, dev, hp['max_sim_epochs'], trim=False)
-            if side is main:
+        if cx.new_patches:
+            _structure_patches(cx)
+            if not two:
                 t.mark('S_patches_walks')
-        patch_ev = None
-        if hp['use_structure'] and side is not main:
+        if structure and two:
             patch_ev = torch.cuda.Event()
             patch_ev.record(side)                       # the patches exist: their walks run on the main stream (below) and
             #                                             wait for the patches only, not for the position BFS queued next
-        def position_block():
-            """Position channel: the shared P-border anchors, the per-subgraph P-internal draws and the multi-source BFS."""
-            if hp['use_position']:
-                anchors_pos_ext = getattr(model, 'anchors_pos_ext', None)
-                if anchors_pos_ext is None or split != 'test':
-                    anchors_pos_ext = st.attrs['anchors_pos_ext'] = aps.init_anchors_pos_ext(hp, g, dev, epoch=ep)
-                    if det:
-                        for v in anchors_pos_ext.values():
-                            ops.presort_ids(v, g.max_id)
-                pint = {l: ops.choice_ragged(subs, hp['n_anchor_patches_pos_in'], seed,
-                                             tape.stream_id(tape.STREAM_P_INT, split, l, ep), item_base=base) for l in range(L)}
-                st.per_split['anchors_pos_int'] = pint
-                until = _position_until(hp)
-                for l in range(L):
-                    if shard is not None and shard.deal_shared:
-                        cap = hp.get('max_bfs_hops', 32)
-                        if getattr(shard, 'emulator', None) is not None:
-                            w, status = _emulated_position_sims(g, anchors_pos_ext[l], cc_sets, cc_ids, shard, cap, (split, l))
-                        else:
-                            w, status = _dealt_position_sims(g, anchors_pos_ext[l], cc_sets, cc_ids, shard, cap)
-                        w = w.view(S, C, -1)
-                        # full cap, all ranks' worst status: verified before the pass is consumed like the hinted searches
-                        # (nothing to repeat: running out of levels here means max_bfs_hops is too small)
-                        model.__dict__.setdefault('_bfs_level_hint', {}).setdefault(('P_out_dealt', split, l), 0)
-                        _bfs_note(model, st, ('P_out_dealt', split, l), status, cap, cap, None)
-                    else:
-                        cap = hp.get('max_bfs_hops', 32)
-                        nlev = _bfs_levels(model, ('P_out', split, l), cap)
-                        src = anchors_pos_ext[l].to(torch.int32).contiguous()
-                        w, status = ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=nlev, want_status=True,
-                                                             push_levels=_bfs_push_levels(model, ('P_out', split, l)), until=until)
-
-                        def redo(levels, src=src, l=l, sims=sims, until=until):
-                            # the hinted search ran out of levels: the same search with the full cap, similarities replaced.
-                            # It runs on the INSTALLING stream: what it reads was allocated on the preparation stream
-                            _hand_over(torch.cuda.current_stream(), src, cc_sets)
-                            w2, st2 = ops.bfs_min_hops_to_sets(g, src, cc_sets, max_hops=levels, want_status=True, until=until)
-                            sims[('P', 'out', l)] = w2.view(S, C, -1).contiguous()
-                            return st2.tolist()
-                        _bfs_note(model, st, ('P_out', split, l), status, cap, nlev, redo)
-                        w = w.view(S, C, -1)
-                    # (rows of padded components need no masking: an empty set receives no level in msbfs_set_reduce and
-                    # keeps the 0 the output was cleared to -- test_sparse_prepare_equals_dense_prepare checks the raw rows)
-                    sims[('P', 'out', l)] = w.contiguous()
-                    if C == 1:
-                        sims[('P', 'in', l)] = ops.ZeroSims((S, C, hp['n_anchor_patches_pos_in']), dev)
-                    else:
-                        uniq, inv = torch.unique(pint[l], return_inverse=True)
-                        if uniq.numel() * (g.max_id + 1) <= MAX_PINT_BYTES:
-                            d = ops.bfs_hops(g, uniq.to(torch.int32).contiguous(), max_hops=hp.get('max_bfs_hops', 32),
-                                             node_major=True)
-                            full = ops.min_hops_to_sets(d, cc_sets, node_major=True).view(S, C, -1)     # (S, C, U)
-                            w = torch.gather(full, 2, inv.view(S, 1, -1).expand(S, C, -1))
-                        else:
-                            w = _pint_sims_streamed(g, uniq, inv, cc_sets, S, C, hp.get('max_bfs_hops', 32))
-                        sims[('P', 'in', l)] = (w * real.unsqueeze(-1)).contiguous()
-                if side is main:
-                    t.mark('P_bfs_sims')
-        # Where the position search runs.  It is memory-bound (pull levels gather a 32-byte row per edge) and the DTW launches are
-        # bound by fp64 vector issue: started TOGETHER the two share the chip (tools/dtw_overlap_probe.py: DTW 4.6 ms + search
-        # 1.5 ms take 5.0 ms side by side, 69 % of the search hidden; degree sequences, walks and the table's Adam hide
-        # completely, the one-hop border kernel 38 %).  hparams['bfs_beside_dtw'] queues the search behind an event the main
-        # stream records right before the DTW launches.  Measured in the pipelined schedule (round 4): the border stage drops
-        # from 2.66 to 1.90 ms and the DTW stage grows from 5.2 to 6.2 -- the step stays at 9.4-9.5 ms, because the training
-        # half of the previous pass already fills what the DTW launch leaves free: the device is saturated by total work, the
-        # schedule only moves it around.  Default False (the search beside the border kernel, as before).
-        late_bfs = bool(hp.get('bfs_beside_dtw', False)) and side is not main and hp['use_structure'] and hp['use_position'] \
-            and not defer_dtw and not (shard is not None and shard.deal_shared)
-        wos = hp.get('walks_on_side_stream')            # None: by size (below); True / False: forced
-        walks_on_side = (bool(wos) if wos is not None else cc_sets.n <= WALKS_ON_SIDE_MAX_SETS) and side is not main and hp['use_structure']
-
-        def structure_walks(degree_sequences=True):
-            """Walks over the structure patches and the per-layer picks (+ the patches' degree sequences unless the caller runs
-            them elsewhere).  Which stream: see ``walks_on_side`` below."""
-            nonlocal a_sets, ai, ae
-            if new_patches and shard is not None and shard.deal_shared:
-                # the walks over the shared patches, dealt: a rank builds the node views of ITS patches only
-                W_, T_ = hp['n_triangular_walks'], hp['random_walk_len']
-
-                def both(lo, hi):
-                    mine = structure_anchors[lo:hi].contiguous()
-                    v = aps.patch_node_views(mine)
-                    iw, bw = aps.perform_random_walks_both(hp, g, mine, v, first_patch=lo)
-                    return torch.stack([bw, iw], 1)
-                walks = _deal_rows(shard, structure_anchors.shape[0], both, (2, W_, T_), torch.int64, dev, key=('S_walks', split))
-                bor_w = st.attrs['bor_structure_anchor_random_walks'] = walks[:, 0].contiguous()
-                int_w = st.attrs['int_structure_anchor_random_walks'] = walks[:, 1].contiguous()
-            elif new_patches:
-                views = aps.patch_node_views(structure_anchors)
-                # (internal and border walks in ONE launch: 1050 + 1050 one-workgroup-per-CU walks fill the chip's rounds better)
-                int_w, bor_w = aps.perform_random_walks_both(hp, g, structure_anchors, views)
-                st.attrs['bor_structure_anchor_random_walks'], st.attrs['int_structure_anchor_random_walks'] = bor_w, int_w
-            if pool is not None:
-                int_w, bor_w = pool['int_w'], pool['bor_w']
-                st.attrs['structure_anchors'] = structure_anchors
-                st.attrs['int_structure_anchor_random_walks'], st.attrs['bor_structure_anchor_random_walks'] = int_w, bor_w
-            if new_patches or pool is not None:
-                a_struct = st.attrs['anchors_structure'] = aps.init_anchors_structure(hp, structure_anchors, int_w, bor_w,
-                                                                                      indices_on_device=True, epoch=ep)
-                if det:
-                    # forward runs the LSTM once over a layer's internal AND border walks (SubGNN._structure_anchor_embeddings):
-                    # the stacked walks and the sort their embedding lookup's backward needs are made here
-                    for v in a_struct.values():
-                        v[2]._sgnn_both = ops.presort_ids(torch.cat([v[2], v[3]], 0), g.max_id)
-                    if L > 1:                            # (forward runs ONE LSTM pass over the walks of all layers)
-                        a_struct[0][2]._sgnn_all = ops.presort_ids(
-                            torch.cat([t for l in range(L) for t in (a_struct[l][2], a_struct[l][3])], 0), g.max_id)
-                # the column upload is a blocking host->device copy: do it here, before the long DTW
-                # launches are queued, so that the host is free to queue forward/backward behind them
-                st.sim_cols = (a_struct, model.sim_cols_of(a_struct))
-            if pool is not None or not degree_sequences:
-                return                                   # the pool's similarity rows exist: no degree sequences, no DTW
-            patch_degree_sequences()
-
-        def patch_degree_sequences():
-            """The structure patches' degree sequences: what the DTW launches read of the patches (not the walks)."""
-            nonlocal a_sets, ai, ae
-            a_sets = ops.Ragged.from_padded(structure_anchors)
-            ai, ae = ops.degree_sequence(g, a_sets, sort=True, use_degree_dict=g.full_degree is not None)
-        # Where the walks run.  For shards of up to WALKS_ON_SIDE_MAX_SETS component rows (round 6): on the SIDE stream, right
-        # behind the patches and AHEAD of the position search.  Nothing on the main chain reads the walks -- the DTW launches read
-        # the patches' degree sequences only -- so they leave it; and they no longer run BESIDE the search: a walk is one
-        # 1024-thread workgroup around a 125 KB LDS bitmap, it needs 16 free wavefront slots on one CU at once, and the search's
-        # small workgroups kept every CU's slots busy -- at 6 250 subgraphs the walks' stage took 1.3-1.45 ms on the main chain
-        # for 0.27 ms of kernel: the pass 3.08 -> 2.79 ms (same box, back to back).  At the benchmark's 50k subgraphs the main
-        # chain is the long one either way and the walks hide better there (8.82 vs 8.87 ms pipelined, 9.31 vs 9.60 sequential):
-        # they stay on the main chain, as rounds 3-5 had them.  hparams['walks_on_side_stream'] = True / False forces either.
         if walks_on_side:
-            structure_walks(degree_sequences=False)
-        if not late_bfs:
-            position_block()
-        if hp['use_structure'] and side is main:
-            structure_walks()
-            t.mark('S_patches_walks')
-    # ---- main stream: neighbourhood channel + component degree sequences --------------------
-    if hp['use_neighborhood']:
-        k = hp['neigh_sample_border_size']
-        if facts is not None and facts.cc_canon is not None:
-            has_pad_c, cc_canon = facts.has_pad_c, facts.cc_canon
-        else:
-            has_pad_c = (cc_sets.lengths < Lc).to(torch.uint8)
-            cc_canon = ops.sort_ragged(cc_sets)                 # the draw ranks the ascending members
-            if facts is not None and not torch.cuda.is_current_stream_capturing():
-                facts.has_pad_c, facts.cc_canon = has_pad_c, cc_canon
-                facts.built()
-        ni, nb, plans = {}, {}, {}
-        border = _kept_border(model, split, subs, cc_sets, k)
-        for l in range(L):
-            ni[l] = ops.sample_anchors_ragged(cc_canon, hp['n_anchor_patches_N_in'], seed,
-                                              tape.stream_id(tape.STREAM_N_INT, split, l, ep), has_pad_c,
-                                              canonical=True, item_base=base * C).view(S, C, -1)
-            sims[('N', 'in', l)] = ops.ZeroSims(ni[l].shape, dev)
-            # border BFS fused with the border-anchor draw (rank query on the visited bitmap): the
-            # border is never materialised
-            # the padded border matrix's width (the largest border: the PAD rule needs it) is a property of the split's
-            # components and the graph, not of the draw: reduced (over the ranks too) on the first pass, kept afterwards
-            widths = model.__dict__.setdefault('_border_width', {})
-            wkey = (split, k, cc_sets.n, shard.world if shard is not None else 1)
-            # the one-hop border itself is such a property too: written once per split, sorted (_kept_border), and every pass,
-            # layer and resample epoch draws from the kept ids -- the draw is all that changes
-            if border is not None:
-                if wkey not in widths:
-                    wmax = border.counts.max().view(1)
-                    widths[wkey] = shard.reduce_max(wmax) if shard is not None else wmax
-                a, w, counts = ops.draw_border_anchors(border, hp['n_anchor_patches_N_out'], seed,
-                                                       tape.stream_id(tape.STREAM_N_BOR, split, l, ep), item_base=base * C,
-                                                       width=widths[wkey])
-            else:
-                a, w, counts = ops.khop_border_sample(g, cc_sets, k, hp['n_anchor_patches_N_out'], seed,
-                                                      tape.stream_id(tape.STREAM_N_BOR, split, l, ep),     # taken dynamically: a dispatch order buys nothing here
-                                                      item_base=base * C,
-                                                      count_reduce=shard.reduce_max if shard is not None else None,
-                                                      width=widths.get(wkey))
-            if wkey not in widths:
-                wmax = counts.max().view(1)
-                widths[wkey] = shard.reduce_max(wmax) if shard is not None else wmax
-            nb[l] = a.view(S, C, -1)
-            sims[('N', 'out', l)] = w.view(S, C, -1).contiguous()
-            D = hp['node_embed_size']
-            if det and hp.get('fused_forward', True) and D % 4 == 0 and D <= 256 and (D // 4) & (D // 4 - 1) == 0:
-                # the border layer's table gradient is a sorted scatter: its edge list and order are known here
-                plan = ops.mpn_edge_plan(sims[('N', 'out', l)], nb[l], cc_ids._sgnn_mask_u8, R=S * C,
-                                         A=nb[l].shape[-1], D=D, max_key=g.max_id, sims_per_edge=True)
-                plan['anchors'] = nb[l]
-                plans[('N', False, l)] = plan
-        st.per_split['anchors_neigh_int'], st.per_split['anchors_neigh_border'] = ni, nb
-        st.per_split['_mpn_edge_plans'] = plans
-        t.mark('border_bfs+N_anchors')
-    ci = ce = None
-    x_fixed = False                                             # the DTW launches' x side comes from kept facts (finish_pass)
-    if hp['use_structure'] and pool is None:
-        if facts is not None and facts.ci is not None:
-            ci, ce, x_fixed = facts.ci, facts.ce, True
-        else:
-            ci, ce = ops.degree_sequence(g, cc_sets, sort=True, use_degree_dict=g.full_degree is not None,
-                                         order=set_order)
-            if facts is not None and not torch.cuda.is_current_stream_capturing():
-                facts.ci, facts.ce, x_fixed = ci, ce, True
-                facts.built()
-            t.mark('degree_sequences' + once)
-    if hp['use_structure'] and side is not main:
-        main.wait_event(patch_ev)
-        _hand_over(main, structure_anchors)
-        if walks_on_side:
+            _structure_walks(cx)
+        if position and not late_bfs:
+            _position_channel(cx)
+            if not two:
+                t.mark('P_bfs_sims')
+        if structure and not two:
+            _structure_walks(cx)
             if pool is None:
-                patch_degree_sequences()
-            t.mark('S_patch_degree_sequences')
-        else:
-            structure_walks()
-            t.mark('S_walks')
+                _patch_degree_sequences(cx)
+            t.mark('S_patches_walks')
+    # ---- main stream: neighbourhood channel, component degree sequences, the patches' side -----
+    if hp['use_neighborhood']:
+        _neighbourhood_channel(cx)
+        t.mark('border_bfs+N_anchors')
+    if structure and pool is None:
+        _component_degree_sequences(cx)
+    if structure and two:
+        main.wait_event(patch_ev)
+        _hand_over(main, cx.structure_anchors)
+        if not walks_on_side:
+            _structure_walks(cx)
+        if pool is None:
+            _patch_degree_sequences(cx)
+        t.mark('S_patch_degree_sequences' if walks_on_side else 'S_walks')
     # ---- structure similarities (main), then the join ---------------------------------------
     # The DTW launches read the degree sequences only, nothing the side stream computes: they are queued BEFORE the join, so a
     # position search that is still running (small shards: the search does not shrink with the shard, everything else does)
     # overlaps with them instead of delaying them (6 250 subgraphs: the main chain reaches this point after ~1.3 ms, the search
     # ends at ~1.6).  At the benchmark's 50k subgraphs the search has long finished when the main chain gets here.
-    st.dtw_inputs = (cc_sets, ci, ce, a_sets, ai, ae, (S, C)) if (hp['use_structure'] and pool is None) else None
-    st.x_fixed = x_fixed
-    if pool is not None and hp['use_structure']:
+    st.dtw_inputs = (cx.cc_sets, cx.ci, cx.ce, cx.a_sets, cx.ai, cx.ae, tuple(cx.cc_ids.shape[:2])) if (structure and pool is None) else None
+    st.x_fixed = cx.x_fixed
+    if pool is not None and structure:
         st.attrs[split + '_int_struc_similarities'], st.attrs[split + '_bor_struc_similarities'] = pool['int_sims'], pool['bor_sims']
     if late_bfs:
         dtw_ev = torch.cuda.Event()
         dtw_ev.record(main)                                 # the DTW launches are queued right behind this ...
         with torch.cuda.stream(side):
             side.wait_event(dtw_ev)                         # ... and the position search starts with them
-            position_block()
+            _position_channel(cx)
     if not defer_dtw:
         finish_pass(model, st, t)
-    if side is not main:
+    if two:
         main.wait_stream(side)
-        _hand_over(main, sims, st.attrs.get('anchors_pos_ext'), st.per_split.get('anchors_pos_int'),
+        _hand_over(main, cx.sims, st.attrs.get('anchors_pos_ext'), st.per_split.get('anchors_pos_int'),
                    st.attrs.get('structure_anchors'), st.attrs.get('int_structure_anchor_random_walks'),
                    st.attrs.get('bor_structure_anchor_random_walks'), st.sim_cols[1] if st.sim_cols else None)
         for v in (st.attrs.get('anchors_structure') or {}).values():
             _hand_over(main, v[0], v[2], v[3])
-    if side is not main:
         t.mark('side_stream_join(S_patches,P_bfs)')
-    st.attrs[split + '_neigh_pos_similarities'] = sims if sims else None
+    st.attrs[split + '_neigh_pos_similarities'] = cx.sims if cx.sims else None
     st.attrs[split + '_N_border'] = None
     return st
 
 
 class SplitFacts:
-    """What a pass computes from a split's subgraph lists and the graph ALONE -- no draw, no resample epoch, no embedding table
-    enters it -- built by the split's first pass and taken by every later one (model.__dict__['_split_facts'][split]):
+    """The one record of what a pass computes from a split's subgraph lists, the graph and the shard ALONE -- no draw, no resample
+    epoch, no embedding table enters it -- filled by the split's first passes and taken by every later one
+    (model.__dict__['_split_facts'][split]; every field None or empty until a pass has made it):
+
+        subs, dims          the device copy (ops.Ragged) of the lists; the padded (C, Lc) of the component ids
+        member_order        the members' sort for the deterministic component-embedding backward
+        set_order           the component sets' dispatch order, heaviest first
+        border_width        {border size k: width of the padded border matrix}
+        borders             {(k, byte budget): ops.KeptBorders, or None for a remembered "no"}  (``_kept_border``)
+        dtw_rows            ``_DtwRows``: the DTW calls' component side (grouping decision, ops.DtwRowPrep)
+    and, only where hparams['keep_split_facts'] is on (otherwise every pass computes them), the component tensors:
 
         cc_ids (S, C, Lc)   with what hangs on it: _sgnn_ids32, _sgnn_mask, _sgnn_mask_u8 (and _sgnn_member_order)
         cc_sets, real       the component rows as ragged sets; which rows are real
@@ -729,17 +772,25 @@ class SplitFacts:
         ci, ce              the components' internal / external degree sequences        (None until a pass needs them)
 
     The key: the subgraph LIST OBJECT (held here and compared by identity -- an ``id()`` alone is recycled once a list is
-    freed), the subgraph count, the graph object and, sharded, (start, world).  Anything else builds new facts.
-    ``ready``: the event behind the launches that wrote the tensors; a pass on another stream waits for it once and tells the
-    allocator (``wait``), like ops.KeptBorders."""
+    freed), the subgraph count, the graph object and, sharded, (start, world).  Anything else gets a new record: nothing of the
+    old one survives, and ``forget_split_facts`` drops it for a change the key cannot see.
+    ``ready``: the event behind the launches that wrote the component tensors; a pass on another stream waits for it once and
+    tells the allocator (``wait``), like ops.KeptBorders."""
 
-    def __init__(self, sub_g, n, graph, shard, cc_ids, cc_sets, real):
+    def __init__(self, sub_g, n, graph, shard, cc_ids=None, cc_sets=None, real=None):
         self.sub_g, self.n, self.graph = sub_g, n, graph
         self.shard_key = self.shard_key_of(shard)
-        self.cc_ids, self.cc_sets, self.real = cc_ids, cc_sets, real
+        self.subs = self.dims = self.member_order = self.set_order = self.dtw_rows = None
+        self.border_width, self.borders = {}, {}
         self.has_pad_c = self.cc_canon = self.ci = self.ce = None
         self.ready, self._waited = None, set()
-        self.built()
+        self.keep_components(cc_ids, cc_sets, real)
+
+    def keep_components(self, cc_ids, cc_sets, real):
+        """The component tensors, where they are kept (None: not, or not yet)."""
+        self.cc_ids, self.cc_sets, self.real = cc_ids, cc_sets, real
+        if cc_ids is not None:
+            self.built()
 
     @staticmethod
     def shard_key_of(shard):
@@ -751,6 +802,8 @@ class SplitFacts:
 
     def tensors(self):
         cc = self.cc_ids
+        if cc is None:
+            return []
         out = [cc, self.real, self.has_pad_c, self.ci, self.ce, self.cc_sets.ptr, self.cc_sets.nodes]
         out += [getattr(cc, nm, None) for nm in ('_sgnn_ids32', '_sgnn_mask_u8')]
         if self.cc_canon is not None:
@@ -785,64 +838,67 @@ class SplitFacts:
             stream.wait_event(self.ready)
 
 
-def _split_facts(model, split, sub_g, n, graph, shard):
-    """The split's kept facts if they are those of THIS list, count, graph and shard, else None (the caller builds)."""
-    facts = model.__dict__.get('_split_facts', {}).get(split)
-    return facts if facts is not None and facts.matches(sub_g, n, graph, shard) else None
-
-
-def _keep_split_facts(model, split, facts):
+def _split_record(model, split, sub_g, graph, shard, store=True):
+    """The split's record if it is that of THIS list, count, graph and shard; else a new, empty one, which replaces it whole --
+    unless ``store`` is False (the stream is capturing: the pass works from a temporary record, nothing new is kept)."""
     kept = model.__dict__.setdefault('_split_facts', {})
-    if kept.get(split) is not None:
-        # other lists than the kept ones: whatever else was derived from the old components goes with them
-        for name in ('_dtw_group_rows', '_degseq_order'):
-            model.__dict__.get(name, {}).pop(split, None)
-        widths = model.__dict__.get('_border_width', {})
-        for k in [k for k in widths if k[0] == split]:
-            widths.pop(k)
-    kept[split] = facts
-    return facts
+    rec = kept.get(split)
+    if rec is None or not rec.matches(sub_g, len(sub_g), graph, shard):
+        rec = SplitFacts(sub_g, len(sub_g), graph, shard)
+        if store:
+            kept[split] = rec
+    return rec
 
 
 def forget_split_facts(model, split=None):
-    """Drop the kept facts of ``split`` (None: of every split): the next pass computes them again.  For code that changes a
-    split's subgraphs in a way the key cannot see (editing the list in place)."""
-    kept = model.__dict__.get('_split_facts')
-    if kept:
-        for sp in ([split] if split is not None else list(kept)):
-            kept.pop(sp, None)
+    """Drop everything kept for ``split`` (None: for every split) -- its record and the learned depths of its position searches:
+    the next pass uploads the lists and computes all of it again.  For code that changes a split's subgraphs in a way the key
+    cannot see (editing the list in place)."""
+    kept = model.__dict__.get('_split_facts') or {}
+    for sp in ([split] if split is not None else list(kept)):
+        kept.pop(sp, None)
+    for name in ('_bfs_level_hint', '_bfs_push_hint'):                          # keyed by (kind, split, layer)
+        hints = model.__dict__.get(name) or {}
+        for k in [k for k in hints if split is None or k[1] == split]:
+            hints.pop(k)
 
 
 def split_facts_bytes(model, split='train'):
     """Device bytes kept for a split: (the facts' tensors, the DTW row sides' grouped values and prepared rows)."""
-    facts = model.__dict__.get('_split_facts', {}).get(split)
-    rec = model.__dict__.get('_dtw_group_rows', {}).get(split)
-    return (facts.nbytes if facts is not None else 0,
-            sum(s.prep.nbytes for s in (rec.internal, rec.external)) if rec is not None else 0)
+    rec = model.__dict__.get('_split_facts', {}).get(split)
+    rows = rec.dtw_rows if rec is not None else None
+    return (rec.nbytes if rec is not None else 0,
+            sum(s.prep.nbytes for s in (rows.internal, rows.external)) if rows is not None else 0)
+
+
+def set_orders(model):
+    """{split: set_order} of the records: what ``SubGNN._degseq_order`` returns."""
+    return {sp: r.set_order for sp, r in model.__dict__.get('_split_facts', {}).items() if r.set_order is not None}
+
+
+def border_widths(model):
+    """{(split, k, component rows, world): width} of the records: what ``SubGNN._border_width`` returns."""
+    return {(sp, k, r.n * r.dims[0], r.shard_key[1] if r.shard_key else 1): w
+            for sp, r in model.__dict__.get('_split_facts', {}).items() for k, w in r.border_width.items()}
 
 
 KEPT_BORDER_BYTES = 4 << 30        # ids of a split's kept one-hop borders (hparams['kept_border_bytes']; 0: never keep)
 
 
-def _kept_border(model, split, subs, cc_sets, k):
+def _kept_border(cx, k):
     """The split's sorted one-hop borders (ops.KeptBorders), built by its first pass and kept: they depend on the split's
     components and the graph only.  None where the pass takes the fused border + draw kernel instead: k != 1, a graph the one-hop
     kernel does not serve, a budget of 0 or a border beyond the budget (decided once: the count is not repeated), and a
     recording that finds nothing kept -- building reads a size back, which a capture cannot (an eager pass builds first)."""
-    hp, g = model.hparams, model.networkx_graph
-    budget = int(hp.get('kept_border_bytes', KEPT_BORDER_BYTES))
+    budget = int(cx.hp.get('kept_border_bytes', KEPT_BORDER_BYTES))
     if k != 1 or budget <= 0:
         return None
-    kept = model.__dict__.setdefault('_kept_borders', {})
-    sub_g = getattr(model, split + '_sub_G')
-    tag = (id(sub_g), subs.n, cc_sets.n, id(g), budget)
-    rec = kept.get(split)
-    if rec is None or rec[0] != tag:
+    borders, key = cx.rec.borders, (k, budget)
+    if key not in borders:
         if torch.cuda.is_current_stream_capturing():
             return None
-        border = ops.khop1_borders_sorted(g, cc_sets, max_bytes=budget) if ops.khop1_applies(g, cc_sets.n) else None
-        rec = kept[split] = (tag, border, sub_g, g)              # (the list and the graph are held: their ids stay theirs)
-    border = rec[1]
+        borders[key] = ops.khop1_borders_sorted(cx.g, cx.cc_sets, max_bytes=budget) if ops.khop1_applies(cx.g, cx.cc_sets.n) else None
+    border = borders[key]
     if border is not None:
         border.wait(torch.cuda.current_stream())
     return border
@@ -866,13 +922,12 @@ def finish_pass(model, st, timer=None):
         # Grouping repeated component sequences pays on the internal side (2.7k distinct rows among the
         # benchmark's 50k) and is pure overhead on the external side (nearly all distinct).  Which it is
         # depends only on the split's components and the graph: decided on the first pass, kept.
-        group = model.__dict__.setdefault('_dtw_group_rows', {})
-        rec = group.get(split)
-        if rec is None or rec.n != cc_sets.n:
+        rec = st.facts.dtw_rows
+        if rec is None:
             # the first pass of a split does not group (a choice of kernels, never of values) and does not WAIT for the answer
             # either: the distinct-row counts travel to pinned memory behind its launches (75 ms of read-back on the driver's
             # box in round 5) and a later pass picks them up
-            rec = group[split] = _DtwRows(cc_sets.n, *(_DtwSide(ops.distinct_rows_async(cc_sets.ptr, x, mx)) for x in (ci, ce)))
+            rec = st.facts.dtw_rows = _DtwRows(*(_DtwSide(ops.distinct_rows_async(cc_sets.ptr, x, mx)) for x in (ci, ce)))
             t.mark('dtw_row_grouping_counts_queued(first pass only)')
         elif rec.internal.group is None and not torch.cuda.is_current_stream_capturing():
             _settle_dtw_grouping(model, split, wait=False)
@@ -898,14 +953,14 @@ class _DtwSide:
         self.group, self.pending, self.prep = None, pending, ops.DtwRowPrep()
 
 
-_DtwRows = collections.namedtuple('_DtwRows', 'n internal external')        # model.__dict__['_dtw_group_rows'][split]
+_DtwRows = collections.namedtuple('_DtwRows', 'internal external')          # SplitFacts.dtw_rows
 
 
 def _settle_dtw_grouping(model, split, wait):
     """Pick up the distinct-row counts the split's first pass sent to pinned memory and decide which DTW side groups repeated
     rows (a choice of kernels, never of values; the kept preparations start over).  ``wait``: block until the copies have
     landed -- what a recording of the preparation does BEFORE its capture starts (an event wait inside a capture invalidates it)."""
-    rec = model.__dict__.get('_dtw_group_rows', {}).get(split)
+    rec = getattr(model.__dict__.get('_split_facts', {}).get(split), 'dtw_rows', None)
     if rec is None or rec.internal.group is not None:
         return
     sides = (rec.internal, rec.external)

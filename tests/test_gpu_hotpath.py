@@ -191,9 +191,7 @@ def test_sharded_passes_reproduce_the_single_rank_pass(name, world, tmp_path):
         sh = PlayedShard(S, r, world, collectives=False)
         a, b = sh.start, sh.stop
         part.train_sub_G, part.train_sub_G_label = all_subs[a:b], all_labels[a:b]
-        part.__dict__.pop('_subs_train', None)
-        for k in ('_degseq_order', '_dtw_group_rows'):
-            part.__dict__.pop(k, None)
+        hotpath.forget_split_facts(part, 'train')
         hotpath.prepare_sparse(part, 'train', shard=sh)
         assert torch.equal(part.train_cc_ids, full.train_cc_ids[a:b])
         for l in range(hp['n_layers']):

@@ -252,19 +252,20 @@ def test_a_pass_draws_from_kept_borders_like_the_fused_call(tmp_path):
     _same(firsts['pass 2']['anchors'], firsts['pass 1']['anchors'], 'same epoch, same draws')
     assert any(not torch.equal(firsts['epoch 1']['anchors'][l], firsts['pass 1']['anchors'][l]) for l in range(L))
     # what is kept: one object for the split under the default budget, a remembered "no" otherwise
-    rec = kept_m.__dict__['_kept_borders']['train']
-    assert isinstance(rec[1], ops.KeptBorders) and rec[1].n == firsts['pass 1']['anchors'][0].shape[0] * firsts['pass 1']['anchors'][0].shape[1]
-    assert '_kept_borders' not in fused_m.__dict__ or 'train' not in fused_m.__dict__['_kept_borders']
-    assert tiny_m.__dict__['_kept_borders']['train'][1] is None
-    # the split's subgraph list replaced by a different one: the kept object is rebuilt
+    def borders(m):
+        return list(m.__dict__['_split_facts']['train'].borders.values())
+    (rec,) = borders(kept_m)
+    assert isinstance(rec, ops.KeptBorders) and rec.n == firsts['pass 1']['anchors'][0].shape[0] * firsts['pass 1']['anchors'][0].shape[1]
+    assert borders(fused_m) == []
+    assert borders(tiny_m) == [None]
+    # the split's subgraph list replaced by a different one: the kept object is rebuilt (another list object is another
+    # record: nothing has to be forgotten by hand)
     for m in (kept_m, fused_m):
         m.train_sub_G = list(m.train_sub_G)[::-1]
-        for k in ('_subs_train', '_degseq_order', '_dtw_group_rows', '_cc_member_order'):
-            m.__dict__.pop(k, None)
     got = _border_half(hotpath.prepare_pass(kept_m, 'train'), L)
     want = _border_half(hotpath.prepare_pass(fused_m, 'train'), L)
     _same(got, want, 'replaced subgraph list')
-    assert kept_m.__dict__['_kept_borders']['train'][1] is not rec[1]
+    assert len(borders(kept_m)) == 1 and isinstance(borders(kept_m)[0], ops.KeptBorders) and borders(kept_m)[0] is not rec
     assert any(not torch.equal(got['anchors'][l], firsts['pass 1']['anchors'][l]) for l in range(L))
     # a pass prepared on a second stream after one prepared on the first
     second = torch.cuda.Stream()
@@ -273,7 +274,7 @@ def test_a_pass_draws_from_kept_borders_like_the_fused_call(tmp_path):
         got2 = _border_half(hotpath.prepare_pass(kept_m, 'train'), L)
     _same(got2, want, 'second stream')
     # ... and one whose first pass (the build) ran on a stream other than the consumer's
-    kept_m.__dict__.pop('_kept_borders')
+    kept_m.__dict__['_split_facts']['train'].borders.clear()
     with torch.cuda.stream(second):
         st3 = hotpath.prepare_pass(kept_m, 'train')
     st4 = hotpath.prepare_pass(kept_m, 'train')          # (no synchronisation in between: the kept border's event orders it)

@@ -137,7 +137,9 @@ def test_passes_from_kept_facts_equal_recomputed_passes(variant):
         assert cc.shape[0] == N_TRAIN and cc.shape[1] > 1 and bool((cc[:, 1:, 0] == 0).any())       # C > 1, padded rows
         now = kept_m.__dict__['_split_facts']['train']
         assert (facts is None or now is facts) and cc is now.cc_ids and now.sub_g is kept_m.train_sub_G
-        assert a.x_fixed and not b.x_fixed and '_split_facts' not in off_m.__dict__
+        off = off_m.__dict__['_split_facts']['train']            # its record holds none of the component tensors
+        assert a.x_fixed and not b.x_fixed and off.tensors() == [] and off.nbytes == 0
+        assert all(getattr(off, nm) is None for nm in ('cc_ids', 'cc_sets', 'real', 'has_pad_c', 'cc_canon', 'ci', 'ce'))
         facts = now
         draws.append(a.per_split['anchors_neigh_border'][0].clone())
         hotpath.install_pass(kept_m, a)
@@ -148,9 +150,15 @@ def test_passes_from_kept_facts_equal_recomputed_passes(variant):
     else:
         assert torch.equal(draws[0], draws[2])
     # the prepared x side of the DTW launches was built once the preparations settled, and is the one the last pass used
-    rec = kept_m.__dict__['_dtw_group_rows']['train']
+    rec = facts.dtw_rows
     assert all(s.prep.rows is not None and s.prep.fixed_src is f for s, f in ((rec.internal, facts.ci), (rec.external, facts.ce)))
-    assert all(s.prep.rows is None for s in (lambda r: (r.internal, r.external))(off_m.__dict__['_dtw_group_rows']['train']))
+    assert all(s.prep.rows is None for s in (lambda r: (r.internal, r.external))(off_m.__dict__['_split_facts']['train'].dtw_rows))
+    # what readers outside hotpath see of the records (the benchmark's rooflines): dictionaries of the earlier shapes
+    rows, k = facts.cc_sets.n, kept_m.hparams['neigh_sample_border_size']
+    for m in (kept_m, off_m):
+        r = m.__dict__['_split_facts']['train']
+        assert list(m._degseq_order) == ['train'] and m._degseq_order['train'] is r.set_order and r.set_order.numel() == rows
+        assert list(m._border_width) == [('train', k, rows, 1)] and m._border_width[('train', k, rows, 1)] is r.border_width[k]
 
 
 def _counted(monkeypatch):
@@ -249,6 +257,35 @@ def test_another_list_count_or_split_never_reads_kept_facts(monkeypatch):
     hotpath.forget_split_facts(m)
     assert not m.__dict__['_split_facts']
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize('deterministic', [False, True])
+def test_lists_edited_in_place_are_read_again_once_forgotten(deterministic):
+    """A change the record's key cannot see -- some of the split's lists overwritten in place: same list object, same length --
+    followed by forget_split_facts: the next pass is the pass of a fresh model on the edited lists (device lists uploaded
+    again, components, kept border, widths and orders computed again), not the pass the old record would have served."""
+    from subgnn_amd import hotpath
+    c = _case()
+    m = _model(keep=True)
+    m._deterministic = deterministic
+    for _ in range(2):
+        before = hotpath.prepare_pass(m, 'train')
+        hotpath.install_pass(m, before)
+    lists = m.train_sub_G
+    for i in (1, 3, 4, 11, 40):                              # (3 and 11: lists of several disconnected pieces)
+        assert lists[i] != c['other'][i]
+        lists[i] = list(c['other'][i])
+    assert m.train_sub_G is lists and len(lists) == N_TRAIN
+    hotpath.forget_split_facts(m, 'train')
+    after = hotpath.prepare_pass(m, 'train')
+    fresh = _model(train=lists, keep=False)
+    fresh._deterministic = deterministic
+    _same_pass(after, hotpath.prepare_pass(fresh, 'train'), 'edited in place, then forgotten')
+    # ... and not because the edit changed nothing
+    cc0, cc1 = before.attrs['train_cc_ids'], after.attrs['train_cc_ids']
+    assert cc0.shape != cc1.shape or not torch.equal(cc0, cc1)
+    nb0, nb1 = before.per_split['anchors_neigh_border'], after.per_split['anchors_neigh_border']
+    assert any(nb0[l].shape != nb1[l].shape or not torch.equal(nb0[l], nb1[l]) for l in nb0)
 
 
 def test_facts_built_on_one_stream_serve_a_pass_on_another():

@@ -13,6 +13,20 @@ def _facts(sub_g, graph, shard=None):
     return hotpath.SplitFacts(sub_g, len(sub_g), graph, shard, cc, None, cc[:, :, 0] != 0)
 
 
+_FIELDS = ('subs', 'dims', 'member_order', 'set_order', 'dtw_rows', 'cc_ids', 'cc_sets', 'real', 'has_pad_c', 'cc_canon', 'ci', 'ce')
+
+
+def _filled(m, split, sub_g, graph, shard=None):
+    """The split's record as a pass gets it, every field a sentinel of its own."""
+    from subgnn_amd import hotpath
+    rec = hotpath._split_record(m, split, sub_g, graph, shard)
+    for nm in _FIELDS:
+        setattr(rec, nm, (split, nm))
+    rec.dims = (3, 7)
+    rec.border_width, rec.borders = {1: (split, 'width')}, {(1, 4 << 30): (split, 'border'), (1, 1): None}
+    return rec
+
+
 def test_facts_are_those_of_one_list_object_count_graph_and_shard():
     from subgnn_amd import hotpath
     g, g2 = object(), object()
@@ -42,23 +56,71 @@ def test_facts_are_kept_per_split_and_forgotten_on_request():
     m = types.SimpleNamespace()
     g = object()
     train, val = [[1]], [[2]]
-    assert hotpath._split_facts(m, 'train', train, 1, g, None) is None
-    ft = hotpath._keep_split_facts(m, 'train', _facts(train, g))
-    fv = hotpath._keep_split_facts(m, 'val', _facts(val, g))
-    assert hotpath._split_facts(m, 'train', train, 1, g, None) is ft and hotpath._split_facts(m, 'val', val, 1, g, None) is fv
-    assert hotpath._split_facts(m, 'train', val, 1, g, None) is None
-    # replacing a split's facts drops what else was derived from the old components; the other split's stay
-    m._dtw_group_rows, m._degseq_order = {'train': 1, 'val': 2}, {'train': 1, 'val': 2}
-    m._border_width = {('train', 1, 5, 1): 3, ('val', 1, 5, 1): 4}
+    ft, fv = _filled(m, 'train', train, g), _filled(m, 'val', val, g)
+    assert m._split_facts == {'train': ft, 'val': fv} and ft is not fv
+    assert hotpath._split_record(m, 'train', train, g, None) is ft and hotpath._split_record(m, 'val', val, g, None) is fv
+    # replacing a split's record leaves no field of the old one reachable -- everything hangs on the one record; the other
+    # split's stays
     other = [[3]]
-    f2 = hotpath._keep_split_facts(m, 'train', _facts(other, g))
-    assert hotpath._split_facts(m, 'train', train, 1, g, None) is None and hotpath._split_facts(m, 'train', other, 1, g, None) is f2
-    assert m._dtw_group_rows == {'val': 2} and m._degseq_order == {'val': 2} and m._border_width == {('val', 1, 5, 1): 4}
+    f2 = hotpath._split_record(m, 'train', other, g, None)
+    assert f2 is not ft and f2.matches(other, 1, g, None) and m._split_facts == {'train': f2, 'val': fv}
+    assert all(getattr(f2, nm) is None for nm in _FIELDS) and f2.border_width == {} and f2.borders == {} and f2.nbytes == 0
+    assert all(getattr(fv, nm) == ('val', nm) for nm in _FIELDS if nm != 'dims') and fv.border_width == {1: ('val', 'width')}
+    assert hotpath._split_record(m, 'train', other, g, None) is f2
+    assert hotpath._split_record(m, 'train', other, g, types.SimpleNamespace(start=0, world=2)) is not f2      # another shard
+    # a pass that is being recorded and finds no matching record works from a temporary one: nothing new is kept
+    f3 = m._split_facts['train']
+    tmp = hotpath._split_record(m, 'train', train, g, None, store=False)
+    assert tmp is not f3 and tmp.matches(train, 1, g, None) and tmp.subs is None and m._split_facts == {'train': f3, 'val': fv}
+    assert hotpath._split_record(m, 'val', val, g, None, store=False) is fv
     hotpath.forget_split_facts(m, 'train')
-    assert hotpath._split_facts(m, 'train', other, 1, g, None) is None and hotpath._split_facts(m, 'val', val, 1, g, None) is fv
+    assert m._split_facts == {'val': fv}
     hotpath.forget_split_facts(m)
     assert m._split_facts == {}
     hotpath.forget_split_facts(types.SimpleNamespace())               # (a model that never kept any)
+
+
+def test_forgetting_a_split_leaves_nothing_of_it_and_all_of_the_other():
+    from subgnn_amd import hotpath
+    g = object()
+
+    def model():
+        m = types.SimpleNamespace()
+        recs = {sp: _filled(m, sp, [[i + 1]], g) for i, sp in enumerate(('train', 'val'))}
+        m._bfs_level_hint = {(kind, sp, l): 5 for kind in ('P_out', 'P_out_dealt') for sp in ('train', 'val') for l in (0, 1)}
+        m._bfs_push_hint = {('P_out', sp, l): 2 for sp in ('train', 'val') for l in (0, 1)}
+        m._bfs_status_pool, m._device_label_cache = ['buffer'], {'train': 'labels'}           # keyed by other things: they stay
+        return m, recs
+    m, recs = model()
+    before = {k: v for k, v in vars(recs['val']).items()}
+    hotpath.forget_split_facts(m, 'train')
+    assert m._split_facts == {'val': recs['val']} and vars(recs['val']) == before
+    assert m._bfs_level_hint == {(kind, 'val', l): 5 for kind in ('P_out', 'P_out_dealt') for l in (0, 1)}
+    assert m._bfs_push_hint == {('P_out', 'val', l): 2 for l in (0, 1)}
+    assert m._bfs_status_pool == ['buffer'] and m._device_label_cache == {'train': 'labels'}
+    assert hotpath.split_facts_bytes(m, 'train') == (0, 0)
+    # the next pass of the split starts from an empty record
+    again = hotpath._split_record(m, 'train', recs['train'].sub_g, g, None)
+    assert again is not recs['train'] and again.subs is None and again.borders == {} and again.dtw_rows is None
+    m, recs = model()
+    hotpath.forget_split_facts(m)
+    assert m._split_facts == {} and m._bfs_level_hint == {} and m._bfs_push_hint == {} and m._bfs_status_pool == ['buffer']
+
+
+def test_the_compatibility_views_have_the_shapes_of_the_dictionaries_they_replace():
+    """What SubGNN._degseq_order and SubGNN._border_width return (hotpath.set_orders, hotpath.border_widths): {split: order}
+    and {(split, k, component rows, world): width}, built from the records."""
+    from subgnn_amd import hotpath
+    m, g = types.SimpleNamespace(), object()
+    assert hotpath.set_orders(m) == {} and hotpath.border_widths(m) == {}
+    train = _filled(m, 'train', [[1], [2], [3], [4], [5]], g)                        # 5 subgraphs x dims[0] = 3 component rows each
+    val = _filled(m, 'val', [[1], [2]], g, types.SimpleNamespace(start=2, world=4))
+    val.border_width[2] = 'two hops'
+    hotpath._split_record(m, 'test', [], g, None)                                    # (prepared by no pass yet: in neither view)
+    assert hotpath.set_orders(m) == {'train': ('train', 'set_order'), 'val': ('val', 'set_order')}
+    assert hotpath.border_widths(m) == {('train', 1, 15, 1): ('train', 'width'), ('val', 1, 6, 4): ('val', 'width'),
+                                        ('val', 2, 6, 4): 'two hops'}
+    assert train.n == 5 and val.shard_key == (2, 4)
 
 
 def test_row_prep_forgets_on_another_shape_and_on_another_fixed_tensor():

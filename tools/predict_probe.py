@@ -50,13 +50,7 @@ def as_test_split(lists):
     """The route before predict.py: the lists as the model's test split (every per-split fact kept for 'test' dropped first)."""
     model.test_sub_G = lists
     model.test_sub_G_label = torch.zeros(len(lists), dtype=torch.int64)
-    model.__dict__.pop('_subs_test', None)
-    for name in ('_cc_dims', '_degseq_order', '_dtw_group_rows', '_kept_borders', '_cc_member_order', '_device_label_cache'):
-        model.__dict__.get(name, {}).pop('test', None)
-    for k in [k for k in model.__dict__.get('_border_width', {}) if k[0] == 'test']:
-        model.__dict__['_border_width'].pop(k)
-    for k in [k for k in model.__dict__.get('_bfs_level_hint', {}) if 'test' in k]:
-        model.__dict__['_bfs_level_hint'].pop(k)
+    hotpath.forget_split_facts(model, 'test')
 
 
 def test_split_call():

@@ -39,7 +39,7 @@ def main():
         hotpath.install_pass(kept_m, a)
         hotpath.install_pass(off_m, b)
     facts = kept_m.__dict__['_split_facts']['train']
-    rec = kept_m.__dict__['_dtw_group_rows']['train']
+    rec = facts.dtw_rows
     facts_bytes, dtw_bytes = hotpath.split_facts_bytes(kept_m, 'train')
     each = {nm: t.numel() * t.element_size() for nm, t in (
         ('cc_ids', facts.cc_ids), ('cc_ids._sgnn_ids32', facts.cc_ids._sgnn_ids32), ('cc_ids._sgnn_mask_u8', facts.cc_ids._sgnn_mask_u8),
