@@ -887,6 +887,31 @@ int sgnn_bce_logits_fwd(const float* logits, const int64_t* targets, int64_t B, 
 int sgnn_bce_logits_bwd(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K,
                         float* grad_logits, void* stream);
 
+/* ---------------------------------------------------------------------------------------
+ * The two pairs above with class weights: torch's `weight` of nn.CrossEntropyLoss and `weight` / `pos_weight` of
+ * nn.BCEWithLogitsLoss, the two loss modules built at SubGNN/SubGNN.py:133 (mean reduction).  The argument lists are those of
+ * the bare entries plus the weight rows at the end: DEVICE pointers to K floats each, nullable -- with every row null the call IS
+ * the bare entry (the same kernel).  The bare entries forward here with nulls.
+ *   single-label   loss = sum_i w[y_i] (lse_i - x[i, y_i]) / sum_i w[y_i] over the rows with y_i != -100;
+ *                  grad_logits[i, :] = w[y_i] (softmax_i - onehot(y_i)) grad_loss[0] / lse[B]; lse[B] = sum_i w[y_i], the divisor
+ *                  (0 gives NaN, as torch does).  A label outside [0, K) other than -100 makes the loss NaN as before, and
+ *                  w[y] is never read for it.  The accuracy stays unweighted, over all B rows.
+ *   multi-label    with y in {0, 1}, c = weight, p = pos_weight, L = 1 + (p_k - 1) y: element loss
+ *                  c_k [(1 - y) x + L (log1p(exp(-|x|)) + max(-x, 0))], mean over B K;
+ *                  grad_logits = c_k [(1 - y) - L (1 - sigmoid(x))] grad_loss[0] / (B K), evaluated without overflow.
+ * Workspaces, partials and the fixed summation order are those of the bare entries: bit-reproducible.
+ * ------------------------------------------------------------------------------------- */
+int sgnn_cross_entropy_fwd_weighted(const float* logits, const int64_t* labels, int64_t B, int64_t K, float* lse, float* loss,
+                                    float* accuracy, void* workspace, int64_t workspace_bytes, void* stream,
+                                    const float* class_weight);
+int sgnn_cross_entropy_bwd_weighted(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss,
+                                    int64_t B, int64_t K, float* grad_logits, void* stream, const float* class_weight);
+int sgnn_bce_logits_fwd_weighted(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
+                                 void* workspace, int64_t workspace_bytes, void* stream, const float* weight,
+                                 const float* pos_weight);
+int sgnn_bce_logits_bwd_weighted(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K,
+                                 float* grad_logits, void* stream, const float* weight, const float* pos_weight);
+
 /* Column sums of a row-major matrix x (R rows of A floats, row stride ld): out[a] = sum_r x[r, a] -- the bias gradients of the
  * head's Linear layers over a shard's rows (autograd of SubGNN/SubGNN.py:304-312).  Row-block partials added in block order:
  * bit-reproducible.  workspace: sgnn_column_sum_workspace_bytes. */
@@ -1125,6 +1150,31 @@ int sgnn_head_fwd_ml(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t
 int sgnn_head_bwd_ml(const float* logits, const int64_t* targets, const float* grad_loss, const float* grad_logits,
                      const float* rows, const float* a1, const float* a2, const float* W2, const float* W3, int64_t B,
                      int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream);
+
+/* The head's four launches with class weights (torch's `weight` of nn.CrossEntropyLoss, `weight` / `pos_weight` of
+ * nn.BCEWithLogitsLoss: the loss modules built at SubGNN/SubGNN.py:133; semantics as stated at sgnn_cross_entropy_fwd_weighted).
+ * The argument lists are those of the four entries above plus the weight rows at the end: DEVICE pointers to K <= 32 floats,
+ * nullable; with every row null -- or without labels / grad_loss -- the call IS the bare entry, and the bare entries forward here
+ * with nulls.  Otherwise kernels of their own run (the bare kernels carry no argument and no branch for weights): the rows are
+ * loaded into LDS once per workgroup.  Single-label: out[2] = lse[B] = the sum of the counted rows' weights, which is what
+ * sgnn_head_bwd_weighted divides by through `rows`; class weights of 1.0 give the bare result bit for bit.  Multi-label: out[2] = B K
+ * as before.  Accuracy, logits, saved activations, dropout masks and the {seed, step} state do not depend on the weights. */
+int sgnn_head_fwd_weighted(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                           const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1, float* a2,
+                           float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream,
+                           const float* class_weight);
+int sgnn_head_bwd_weighted(const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,
+                           const float* grad_logits, const float* rows, const float* a1, const float* a2, const float* W2,
+                           const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial,
+                           void* stream, const float* class_weight);
+int sgnn_head_fwd_ml_weighted(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                              const float* W3, const float* b3, const int64_t* targets, float p, int64_t* rng, float* a1,
+                              float* a2, float* logits, float* out, void* workspace, int64_t workspace_bytes, void* stream,
+                              const float* weight, const float* pos_weight);
+int sgnn_head_bwd_ml_weighted(const float* logits, const int64_t* targets, const float* grad_loss, const float* grad_logits,
+                              const float* rows, const float* a1, const float* a2, const float* W2, const float* W3, int64_t B,
+                              int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream,
+                              const float* weight, const float* pos_weight);
 
 /* A^T B for tall operands (the weight gradients of Linear / LSTM layers: outputs of a few thousand elements contracted over
  * thousands of rows -- a library GEMM runs them on a handful of workgroups): job k contracts A[k] (R[k], M[k]) with B[k]

@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.parameter import Parameter
 
-from . import config, gamma, ops, subgraph_utils
+from . import config, gamma, loss_weights, ops, subgraph_utils
 from . import anchor_patch_samplers as aps
 from .datasets import SubgraphDataset
 from .graph import load_graph
@@ -164,7 +164,11 @@ class SubGNN(nn.Module):
         self.lin3 = nn.Linear(hp['linear_hidden_dim_2'], self.num_classes)
         self.lin_dropout = nn.Dropout(p=hp['lin_dropout'])
         self.lin_dropout2 = nn.Dropout(p=hp['lin_dropout'])
-        self.loss = nn.BCEWithLogitsLoss() if self.multilabel else nn.CrossEntropyLoss()
+        # hparams['class_weight'] / ['pos_weight'] (None, K numbers, {label: number} or 'balanced' from the training split):
+        # the module carries them as non-persistent buffers, so the kernels of a training step, the library path and the
+        # validation loss all apply the same weights and the state_dict keeps its keys
+        self.loss = loss_weights.make_loss(self.multilabel, *self._loss_weights())
+        loss_weights.refuse_multi_rank(self.loss)
         self.lstm = LSTM(D, D, dropout=hp['lstm_dropout'], num_layers=hp['lstm_n_layers'],
                          aggregator=hp['lstm_aggregator'])
         if hp.get('ff_attn', False):                                   # S.py:179-183
@@ -224,6 +228,18 @@ class SubGNN(nn.Module):
         table = torch.cat((torch.zeros(1, pre.shape[1]), pre.float()), 0)
         self.node_embeddings = nn.Embedding.from_pretrained(table, freeze=self.hparams['freeze_node_embeds'],
                                                             padding_idx=config.PAD_VALUE)
+
+    def _loss_weights(self):
+        """(class_weight, pos_weight) of the hyper-parameters as lists of num_classes floats or None (loss_weights.resolve):
+        'balanced' counts the training split's labels, a dict names classes by their label strings in ``subgraphs.pth``."""
+        hp = self.hparams
+        if hp.get('class_weight') is None and hp.get('pos_weight') is None:
+            return None, None
+        names = None
+        if self._memory is None and any(isinstance(hp.get(k), dict) for k in loss_weights.KINDS):
+            names = subgraph_utils.label_names(Path(config.PROJECT_ROOT) / self.subgraph_path)
+        return tuple(loss_weights.resolve(hp.get(k), k, self.num_classes, self.multilabel, labels=self.train_sub_G_label, names=names)
+                     for k in loss_weights.KINDS)
 
     def _forget_split_caches(self):
         """The splits' subgraph lists were (re)read: what hotpath keeps per split of them (SplitFacts) is dropped."""
@@ -894,6 +910,7 @@ class SubGNN(nn.Module):
         hp = self.hparams
         labels = self.__dict__.pop('_head_labels', None)
         targets = self.__dict__.pop('_head_targets', None)
+        class_weight, pos_weight = self.__dict__.pop('_head_weights', None) or (None, None)
         x = subgraph_embedding
         keep = self.__dict__.get('_head_inputs')        # (predict.Predictor: the subgraph embeddings of a request, per chunk)
         if keep is not None:
@@ -907,8 +924,10 @@ class SubGNN(nn.Module):
             if targets is not None and (targets.dim() != 2 or targets.shape[0] != x.shape[0] or targets.dtype != torch.int64
                                         or targets.shape[1] != self.lin3.out_features):
                 targets = None
+            if labels is None and targets is None:
+                class_weight = pos_weight = None
             logits, loss, acc = ops.fused_head(x, self.lin, self.lin2, self.lin3, labels, p, self._dropout_rng() if p > 0 else None,
-                                               targets=targets)
+                                               targets=targets, class_weight=class_weight, pos_weight=pos_weight)
             if labels is not None or targets is not None:
                 self.__dict__['_head_result'] = (loss, acc)
             return logits
@@ -928,42 +947,63 @@ class SubGNN(nn.Module):
     def _loss(self, logits, labels):
         if labels.dim() == 0:
             labels = labels.unsqueeze(-1)
+        loss = self._loss_module_on(logits.device)
         if self.multilabel:
-            return self.loss(logits.squeeze(1), labels.type_as(logits)), labels
-        return self.loss(logits, labels), labels
+            return loss(logits.squeeze(1), labels.type_as(logits)), labels
+        return loss(logits, labels), labels
+
+    def _loss_module_on(self, device):
+        """``self.loss``, or -- when it carries weights that live on another device than the logits (the trainer hands
+        val_test_outputs host copies of an epoch's logits) -- a copy of it on ``device``, kept until the module or one of its
+        weight tensors is replaced."""
+        rows = [w for w in (getattr(self.loss, 'weight', None), getattr(self.loss, 'pos_weight', None)) if torch.is_tensor(w)]
+        if all(w.device == device for w in rows):
+            return self.loss
+        key = (id(self.loss), str(device)) + tuple((id(w), w._version) for w in rows)
+        kept = self.__dict__.get('_loss_copy')
+        if kept is None or kept[0] != key:
+            import copy
+            kept = self.__dict__['_loss_copy'] = (key, copy.deepcopy(self.loss).to(device))
+        return kept[1]
 
     def training_step(self, train_batch, batch_idx):
         labels = train_batch['label'].squeeze(-1)
-        fusable = not self.multilabel and labels.is_cuda and labels.dim() == 1 and type(self.loss) is nn.CrossEntropyLoss \
-            and self.hparams.get('fused_forward', True)
+        # what the loss kernels can compute of self.loss (loss_weights.kernel_plan): its weight rows, (None, None) for a bare
+        # module -- or None: a module with another reduction / ignore_index / label_smoothing, a subclass, or weights of another
+        # shape, dtype or device go through the library.  Weights the user assigned to self.loss count like the hyper-parameters'.
+        plan = loss_weights.kernel_plan(self.loss, self.multilabel, self.lin3.out_features, labels.device) \
+            if self.hparams.get('fused_forward', True) else None
+        fusable = plan is not None and not self.multilabel and labels.is_cuda and labels.dim() == 1
         # multi-label (HPO-NEURO): BCE with logits + exact-match accuracy in the head's launch too, straight from the int64 (B, K)
         # indicator matrix the split keeps on the device; hparams['fused_multilabel_loss'] = False is the library path
-        fusable_ml = self.multilabel and labels.is_cuda and labels.dim() == 2 and labels.dtype == torch.int64 \
-            and labels.shape[1] == self.lin3.out_features and type(self.loss) is nn.BCEWithLogitsLoss \
-            and self.hparams.get('fused_forward', True) and self.hparams.get('fused_multilabel_loss', True)
+        fusable_ml = plan is not None and self.multilabel and labels.is_cuda and labels.dim() == 2 and labels.dtype == torch.int64 \
+            and labels.shape[1] == self.lin3.out_features and self.hparams.get('fused_multilabel_loss', True)
         self.__dict__.pop('_head_result', None)
         if fusable:
             self.__dict__['_head_labels'] = labels          # the head computes loss + accuracy in its own launch (_head)
         elif fusable_ml:
             self.__dict__['_head_targets'] = labels
+        if fusable or fusable_ml:
+            self.__dict__['_head_weights'] = plan
         try:
             logits = self._forward_batch('train', train_batch)
         finally:
             self.__dict__.pop('_head_labels', None)
             self.__dict__.pop('_head_targets', None)
+            self.__dict__.pop('_head_weights', None)
         done = self.__dict__.pop('_head_result', None)
         if done is not None:
             loss, acc = done
             return {'loss': loss, 'log': {'train_loss': loss, 'train_acc': acc}}
         if fusable_ml and logits.is_cuda and logits.dtype == torch.float32 and logits.shape == labels.shape:
             # a head the fused kernel does not take (widths above 128, K above 32, fused_head: false): one pass over the logits
-            loss, acc = ops.bce_with_logits_and_accuracy(logits, labels)
+            loss, acc = ops.bce_with_logits_and_accuracy(logits, labels, weight=plan[0], pos_weight=plan[1])
             return {'loss': loss, 'log': {'train_loss': loss, 'train_acc': acc}}
         if not self.multilabel and logits.is_cuda and logits.dim() == 2 and labels.dim() == 1 and logits.dtype == torch.float32 \
-                and type(self.loss) is nn.CrossEntropyLoss and self.hparams.get('fused_forward', True):
+                and plan is not None:
             # cross entropy + accuracy in one pass over the logits (ops.cross_entropy_with_accuracy): the library's nll
             # reduction runs on one workgroup (48 us at 50k rows) and the pair is 12 launches
-            loss, acc = ops.cross_entropy_with_accuracy(logits, labels)
+            loss, acc = ops.cross_entropy_with_accuracy(logits, labels, weight=plan[0])
             return {'loss': loss, 'log': {'train_loss': loss, 'train_acc': acc}}
         loss, labels = self._loss(logits, labels)
         acc = subgraph_utils.calc_accuracy(logits, labels, multilabel_binarizer=self.multilabel_binarizer)

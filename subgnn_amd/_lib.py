@@ -164,6 +164,11 @@ SIGNATURES = {
     'sgnn_bce_logits_workspace_bytes': (c_i64, [c_i64]),
     'sgnn_bce_logits_fwd': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_bce_logits_bwd': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr]),
+    # the class-weighted forms: the bare argument lists + the weight rows (device pointers, nullable) at the end
+    'sgnn_cross_entropy_fwd_weighted': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    'sgnn_cross_entropy_bwd_weighted': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
+    'sgnn_bce_logits_fwd_weighted': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    'sgnn_bce_logits_bwd_weighted': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sgnn_column_sum_workspace_bytes': (c_i64, [c_i64, c_i64]),
     'sgnn_column_sum': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_gather_rows_many_max': (c_i64, []),
@@ -190,6 +195,14 @@ SIGNATURES = {
                                  c_ptr, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_head_bwd_ml': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64,
                                  ctypes.c_float, c_ptr, c_ptr, c_ptr]),
+    'sgnn_head_fwd_weighted': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float, c_ptr, c_ptr,
+                                       c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    'sgnn_head_bwd_weighted': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64,
+                                       ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sgnn_head_fwd_ml_weighted': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float, c_ptr, c_ptr,
+                                          c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
+    'sgnn_head_bwd_ml_weighted': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64,
+                                          ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     'sgnn_contract_rows_max_jobs': (c_i64, []),
     'sgnn_contract_rows_blocks': (c_i64, [c_i64, c_i64, c_i64]),
     'sgnn_contract_rows_partial': (c_int, [c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),

@@ -27,6 +27,15 @@
 // 1), a row's loss the sum over k of max(x, 0) - x y + log1p(exp(-|x|)), a row a hit when 1 / (1 + exp(-x)) > 0.5 (float32, as
 // torch.sigmoid(x) > 0.5 evaluates it: NOT x > 0) equals y in every column; out = [sum / (B K), hits / B, B K].  Nothing is saved
 // for the backward (no lse): dlogits = (sigmoid(x) - y) g / (B K) is recomputed from the logits.
+//
+// Class weights (torch's `weight` / `pos_weight` of the two loss modules built at SubGNN.py:133): the same two bodies with WT = 1,
+// again kernels of their own (headw_fwd_kernel, headw_fwd_ml_kernel, headw_bwd_kernel<NB>, headw_bwd_ml_kernel<NB>) that take the
+// weight rows as a SECOND argument -- the bare launches keep their argument block and their code.  The rows (K <= 32 floats each,
+// an absent one stands as ones) are loaded into LDS once per workgroup.  Single-label: a counted row's loss and its count are
+// multiplied by w[y], so out[2] = lse[B] = the sum of the counted rows' weights, which is what the backward divides by (weights of
+// 1.0 reproduce the bare launch bit for bit); w[y] is read only for y in [0, K).  Multi-label: the element loss is
+// c_k [(1 - y) x + L (log1p(exp(-|x|)) + max(-x, 0))] with L = 1 + (p_k - 1) y, its gradient c_k [(1 - y) - L sigmoid(-x)] g / (B K);
+// out[2] stays B K.  The accuracy is unweighted in both modes, and the dropout masks do not depend on the mode.
 #include "common.h"
 
 #define HEAD_RB 32
@@ -42,6 +51,8 @@ struct HeadFwd {
     int64_t B; int H1, H2, K; float p;
     float* a1; float* a2; float* logits; float* lse; float* partial; unsigned* ticket; float* out;
 };
+
+struct HeadWeights { const float* w; const float* pw; };     // the weighted launches' class weight rows (either nullable)
 
 struct HeadBwd {
     const float* logits; const float* lse; const int64_t* labels; const float* g_loss; const float* g_logits; const float* rows;
@@ -76,8 +87,8 @@ __device__ __forceinline__ float head_sigmoid(float x)
     return e / (1.f + e);
 }
 
-template <int ML>
-__device__ __forceinline__ void head_fwd_body(const HeadFwd A)
+template <int ML, int WT>
+__device__ __forceinline__ void head_fwd_body(const HeadFwd A, const HeadWeights Wt)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H1 = A.H1, H2 = A.H2, K = A.K, tid = threadIdx.x;
@@ -87,6 +98,7 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwd A)
     float* a1s = W3s + K * ld3;                          // [RB][H1p]
     float* a2s = a1s + HEAD_RB * H1p;                    // [RB][H2p]
     float* lgs = a2s + HEAD_RB * H2p;                    // [RB][K]
+    float* wts = lgs + HEAD_RB * K;                      // [2][K]: weight | pos_weight (WT only)
     __shared__ int s_last;
     for (int idx = tid; idx < H2e * ld2; idx += HEAD_THREADS) {
         const int j = idx / ld2, k = idx - j * ld2;
@@ -97,6 +109,9 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwd A)
         W3s[idx] = k < H2 ? A.W3[c * H2 + k] : 0.f;
     }
     for (int idx = tid; idx < HEAD_RB * (H1p + H2p); idx += HEAD_THREADS) a1s[idx] = 0.f;      // (a1s and a2s are adjacent: pads stay zero)
+    if (WT) {
+        for (int idx = tid; idx < K; idx += HEAD_THREADS) { wts[idx] = Wt.w ? Wt.w[idx] : 1.f; wts[K + idx] = Wt.pw ? Wt.pw[idx] : 1.f; }
+    }
     const bool drop = A.p > 0.f && A.rng != nullptr;
     uint64_t h01 = 0, h02 = 0;
     if (drop) {
@@ -175,7 +190,8 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwd A)
                 for (int k = 0; k < K; ++k) {
                     const float v = x[k];
                     const bool t = y[k] != 0;
-                    l += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
+                    if (WT) l += wts[k] * ((t ? 0.f : v) + (t ? wts[K + k] : 1.f) * (log1pf(expf(-fabsf(v))) + fmaxf(-v, 0.f)));
+                    else l += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
                     all = all && ((1.f / (1.f + expf(-v)) > 0.5f) == t);           // torch.sigmoid(x) > 0.5 in float32
                 }
                 loss += l; hit += all ? 1.f : 0.f; cnt += (float)K;
@@ -190,7 +206,11 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwd A)
             const float l = m + logf(sum);
             A.lse[row0 + tid] = l;
             const int64_t y = A.labels[row0 + tid];
-            if (y >= 0 && y < K) { loss += l - x[y]; hit += (am == (int)y) ? 1.f : 0.f; cnt += 1.f; }
+            if (y >= 0 && y < K) {
+                const float wy = WT ? wts[y] : 1.f;
+                if (WT) loss += wy * (l - x[y]); else loss += l - x[y];
+                hit += (am == (int)y) ? 1.f : 0.f; cnt += wy;
+            }
             else if (y != -100ll) { loss = __builtin_nanf(""); cnt += 1.f; }
         }
         __syncthreads();
@@ -232,15 +252,17 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwd A)
     }
 }
 
-__global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const HeadFwd A) { head_fwd_body<0>(A); }
-__global__ __launch_bounds__(HEAD_THREADS) void head_fwd_ml_kernel(const HeadFwd A) { head_fwd_body<1>(A); }
+__global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const HeadFwd A) { head_fwd_body<0, 0>(A, HeadWeights{nullptr, nullptr}); }
+__global__ __launch_bounds__(HEAD_THREADS) void head_fwd_ml_kernel(const HeadFwd A) { head_fwd_body<1, 0>(A, HeadWeights{nullptr, nullptr}); }
+__global__ __launch_bounds__(HEAD_THREADS) void headw_fwd_kernel(const HeadFwd A, const HeadWeights Wt) { head_fwd_body<0, 1>(A, Wt); }
+__global__ __launch_bounds__(HEAD_THREADS) void headw_fwd_ml_kernel(const HeadFwd A, const HeadWeights Wt) { head_fwd_body<1, 1>(A, Wt); }
 
 // partial layout of one workgroup: [gW3 (K H2) | gb3 (K) | gW2 (H2 H1) | gb2 (H2) | gb1 (H1)]
 __host__ __device__ static inline int64_t head_partial_floats(int H1, int H2, int K) { return (int64_t)K * H2 + K + (int64_t)H2 * H1 + H2 + H1; }
 
 // NB: 4 x 4 blocks of gW2 a thread keeps in registers (1: up to 64 x 64 weights, 2: 128 x 64, 4: 128 x 128)
-template <int NB, int ML>
-__device__ __forceinline__ void head_bwd_body(const HeadBwd A)
+template <int NB, int ML, int WT>
+__device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights Wt)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H1 = A.H1, H2 = A.H2, K = A.K, tid = threadIdx.x;
@@ -252,6 +274,7 @@ __device__ __forceinline__ void head_bwd_body(const HeadBwd A)
     float* a2s = dz2s + HEAD_RB * H2p;                   // [RB][H2p]
     float* a1s = a2s + HEAD_RB * H2p;                    // [RB][H1p]
     float* dz1s = a1s + HEAD_RB * H1p;                   // [RB][H1p]
+    float* wts = dz1s + HEAD_RB * H1p;                   // [2][K]: weight | pos_weight (WT only)
     for (int idx = tid; idx < H1e * ldt; idx += HEAD_THREADS) {
         const int k = idx / ldt, j = idx - k * ldt;
         W2t[idx] = (k < H1 && j < H2) ? A.W2[j * H1 + k] : 0.f;
@@ -261,6 +284,9 @@ __device__ __forceinline__ void head_bwd_body(const HeadBwd A)
         W3s[idx] = k < H2 ? A.W3[c * H2 + k] : 0.f;
     }
     for (int idx = tid; idx < HEAD_RB * (2 * H2p + 2 * H1p); idx += HEAD_THREADS) dz2s[idx] = 0.f;    // (adjacent: all pads zero)
+    if (WT) {
+        for (int idx = tid; idx < K; idx += HEAD_THREADS) { wts[idx] = Wt.w ? Wt.w[idx] : 1.f; wts[K + idx] = Wt.pw ? Wt.pw[idx] : 1.f; }
+    }
     const int64_t P = head_partial_floats(H1, H2, K);
     float* part = A.partial + (int64_t)blockIdx.x * P;
     const float gscale = (A.labels && A.g_loss) ? A.g_loss[0] / A.rows[0] : 0.f;
@@ -282,11 +308,19 @@ __device__ __forceinline__ void head_bwd_body(const HeadBwd A)
             const int r = idx / K, c = idx - r * K;
             float v = 0.f;
             if (ML) {
-                if (A.labels && A.g_loss)
+                if (WT) {
+                    if (A.labels && A.g_loss) {
+                        const bool t = A.labels[row0 * K + idx] != 0;
+                        v = wts[c] * ((t ? 0.f : 1.f) - (t ? wts[K + c] : 1.f) * head_sigmoid(-A.logits[row0 * K + idx])) * gscale;
+                    }
+                } else if (A.labels && A.g_loss)
                     v = (head_sigmoid(A.logits[row0 * K + idx]) - (A.labels[row0 * K + idx] != 0 ? 1.f : 0.f)) * gscale;
             } else if (A.labels && A.g_loss) {
                 const int64_t y = A.labels[row0 + r];
-                if (y >= 0 && y < K) v = (expf(A.logits[row0 * K + idx] - A.lse[row0 + r]) - (c == (int)y ? 1.f : 0.f)) * gscale;
+                if (y >= 0 && y < K) {
+                    v = (expf(A.logits[row0 * K + idx] - A.lse[row0 + r]) - (c == (int)y ? 1.f : 0.f)) * gscale;
+                    if (WT) v *= wts[y];
+                }
             }
             if (A.g_logits) v += A.g_logits[row0 * K + idx];
             dls[idx] = v;
@@ -386,8 +420,10 @@ __device__ __forceinline__ void head_bwd_body(const HeadBwd A)
     }
 }
 
-template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(const HeadBwd A) { head_bwd_body<NB, 0>(A); }
-template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_ml_kernel(const HeadBwd A) { head_bwd_body<NB, 1>(A); }
+template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kernel(const HeadBwd A) { head_bwd_body<NB, 0, 0>(A, HeadWeights{nullptr, nullptr}); }
+template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_ml_kernel(const HeadBwd A) { head_bwd_body<NB, 1, 0>(A, HeadWeights{nullptr, nullptr}); }
+template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void headw_bwd_kernel(const HeadBwd A, const HeadWeights Wt) { head_bwd_body<NB, 0, 1>(A, Wt); }
+template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void headw_bwd_ml_kernel(const HeadBwd A, const HeadWeights Wt) { head_bwd_body<NB, 1, 1>(A, Wt); }
 
 // ---- A^T B for tall operands: partial sums over row blocks (fp32 MFMA) ----------------------------------------------------------
 // part[blk][m][n] = sum over the block's rows r of A[r][m] B[r][n].  blockIdx.x = row block (four wavefronts of `wr` rows each),
@@ -544,15 +580,20 @@ static int head_set_lds(const void* kernel, size_t bytes)
     return 0;
 }
 
-// ml: `labels` is the (B, K) indicator matrix and the launch is head_fwd_ml_kernel (no lse)
-static int head_fwd_launch(bool ml, const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+// ml: `labels` is the (B, K) indicator matrix and the launch is head_fwd_ml_kernel (no lse).  cw / pw: DEVICE rows of K class
+// weights, nullable; with labels and either of them the launch is the weighted kernel (pw: multi-label only)
+static int head_fwd_launch(bool ml, const float* cw, const float* pw, const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
                            const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1, float* a2,
                            float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream)
 {
     if (!z1 || !W2 || !W3 || !a1 || !a2 || !logits || B < 1 || !(p >= 0.f && p < 1.f)) return SGNN_ERR_BAD_ARG;
     if (!sgnn_head_supported(H1, H2, K)) return SGNN_ERR_UNSUPPORTED_D;
     if (labels && ((!ml && !lse) || !out)) return SGNN_ERR_BAD_ARG;
+    if (pw && !ml) return SGNN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < sgnn_head_fwd_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
+    const bool weighted = labels && (cw || pw);
+    HeadWeights Wt;
+    Wt.w = cw; Wt.pw = pw;
     HeadFwd A;
     A.z1 = z1; A.W2 = W2; A.b2 = b2; A.W3 = W3; A.b3 = b3; A.labels = labels; A.rng = (p > 0.f) ? rng : nullptr;
     A.B = B; A.H1 = (int)H1; A.H2 = (int)H2; A.K = (int)K; A.p = p;
@@ -561,8 +602,14 @@ static int head_fwd_launch(bool ml, const float* z1, int64_t B, int64_t H1, int6
     A.partial = (float*)workspace;
     A.ticket = (unsigned*)((char*)workspace + 3 * nb * 4);
     const int64_t H1p = (H1 + 3) & ~3ll, H2p = (H2 + 3) & ~3ll, H2e = (H2 + 1) & ~1ll;
-    const size_t lds = (size_t)(H2e * (H1p + 4) + K * (H2p + 4) + HEAD_RB * (H1p + H2p + K)) * 4;
-    if (ml) {
+    const size_t lds = (size_t)(H2e * (H1p + 4) + K * (H2p + 4) + HEAD_RB * (H1p + H2p + K) + (weighted ? 2 * K : 0)) * 4;
+    if (weighted && ml) {
+        if (head_set_lds((const void*)headw_fwd_ml_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
+        hipLaunchKernelGGL(headw_fwd_ml_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt);
+    } else if (weighted) {
+        if (head_set_lds((const void*)headw_fwd_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
+        hipLaunchKernelGGL(headw_fwd_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt);
+    } else if (ml) {
         if (head_set_lds((const void*)head_fwd_ml_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
         hipLaunchKernelGGL(head_fwd_ml_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A);
     } else {
@@ -577,8 +624,17 @@ extern "C" int sgnn_head_fwd(const float* z1, int64_t B, int64_t H1, int64_t H2,
                              const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1, float* a2,
                              float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream)
 {
-    return head_fwd_launch(false, z1, B, H1, H2, K, W2, b2, W3, b3, labels, p, rng, a1, a2, logits, lse, out, workspace, workspace_bytes,
-                           stream);
+    return head_fwd_launch(false, nullptr, nullptr, z1, B, H1, H2, K, W2, b2, W3, b3, labels, p, rng, a1, a2, logits, lse, out, workspace,
+                           workspace_bytes, stream);
+}
+
+extern "C" int sgnn_head_fwd_weighted(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                                      const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1,
+                                      float* a2, float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes,
+                                      void* stream, const float* class_weight)
+{
+    return head_fwd_launch(false, class_weight, nullptr, z1, B, H1, H2, K, W2, b2, W3, b3, labels, p, rng, a1, a2, logits, lse, out,
+                           workspace, workspace_bytes, stream);
 }
 
 extern "C" int sgnn_head_fwd_ml(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
@@ -586,11 +642,21 @@ extern "C" int sgnn_head_fwd_ml(const float* z1, int64_t B, int64_t H1, int64_t 
                                 float* logits, float* out, void* workspace, int64_t workspace_bytes, void* stream)
 {
     if (!targets) return SGNN_ERR_BAD_ARG;
-    return head_fwd_launch(true, z1, B, H1, H2, K, W2, b2, W3, b3, targets, p, rng, a1, a2, logits, nullptr, out, workspace,
-                           workspace_bytes, stream);
+    return head_fwd_launch(true, nullptr, nullptr, z1, B, H1, H2, K, W2, b2, W3, b3, targets, p, rng, a1, a2, logits, nullptr, out,
+                           workspace, workspace_bytes, stream);
 }
 
-static int head_bwd_launch(bool ml, const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,
+extern "C" int sgnn_head_fwd_ml_weighted(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2,
+                                         const float* b2, const float* W3, const float* b3, const int64_t* targets, float p,
+                                         int64_t* rng, float* a1, float* a2, float* logits, float* out, void* workspace,
+                                         int64_t workspace_bytes, void* stream, const float* weight, const float* pos_weight)
+{
+    if (!targets) return SGNN_ERR_BAD_ARG;
+    return head_fwd_launch(true, weight, pos_weight, z1, B, H1, H2, K, W2, b2, W3, b3, targets, p, rng, a1, a2, logits, nullptr, out,
+                           workspace, workspace_bytes, stream);
+}
+
+static int head_bwd_launch(bool ml, const float* cw, const float* pw, const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,
                            const float* grad_logits, const float* rows, const float* a1, const float* a2, const float* W2,
                            const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial,
                            void* stream)
@@ -598,22 +664,33 @@ static int head_bwd_launch(bool ml, const float* logits, const float* lse, const
     if (!a1 || !a2 || !W2 || !W3 || !dz1 || !partial || B < 1 || !(p >= 0.f && p < 1.f)) return SGNN_ERR_BAD_ARG;
     if (!sgnn_head_supported(H1, H2, K)) return SGNN_ERR_UNSUPPORTED_D;
     if (grad_loss && (!labels || !logits || (!ml && !lse) || !rows)) return SGNN_ERR_BAD_ARG;
+    if (pw && !ml) return SGNN_ERR_BAD_ARG;
+    const bool weighted = grad_loss && (cw || pw);
+    HeadWeights Wt;
+    Wt.w = cw; Wt.pw = pw;
     HeadBwd A;
     A.logits = logits; A.lse = lse; A.labels = labels; A.g_loss = grad_loss; A.g_logits = grad_logits; A.rows = rows;
     A.a1 = a1; A.a2 = a2; A.W2 = W2; A.W3 = W3; A.B = B; A.H1 = (int)H1; A.H2 = (int)H2; A.K = (int)K;
     A.scale = 1.f / (1.f - p);
     A.dz1 = dz1; A.partial = partial;
     const int64_t H1p = (H1 + 3) & ~3ll, H2p = (H2 + 3) & ~3ll, H1e = (H1 + 1) & ~1ll;
-    const size_t lds = (size_t)(H1e * (H2p + 4) + K * H2p + HEAD_RB * (K + 2 * H2p + 2 * H1p)) * 4;
+    const size_t lds = (size_t)(H1e * (H2p + 4) + K * H2p + HEAD_RB * (K + 2 * H2p + 2 * H1p) + (weighted ? 2 * K : 0)) * 4;
     const int64_t nblocks = (H2p / 4) * (H1p / 4);
 #define HEAD_BWD(KERNEL, NB) do { if (head_set_lds((const void*)KERNEL<NB>, lds) != 0) return SGNN_ERR_LAUNCH; \
                                   hipLaunchKernelGGL(KERNEL<NB>, dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A); } while (0)
-    if (ml) {
+#define HEAD_BWD_W(KERNEL, NB) do { if (head_set_lds((const void*)KERNEL<NB>, lds) != 0) return SGNN_ERR_LAUNCH; \
+                                    hipLaunchKernelGGL(KERNEL<NB>, dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt); } while (0)
+    if (weighted && ml) {
+        if (nblocks <= HEAD_THREADS) HEAD_BWD_W(headw_bwd_ml_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD_W(headw_bwd_ml_kernel, 2); else HEAD_BWD_W(headw_bwd_ml_kernel, 4);
+    } else if (weighted) {
+        if (nblocks <= HEAD_THREADS) HEAD_BWD_W(headw_bwd_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD_W(headw_bwd_kernel, 2); else HEAD_BWD_W(headw_bwd_kernel, 4);
+    } else if (ml) {
         if (nblocks <= HEAD_THREADS) HEAD_BWD(head_bwd_ml_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD(head_bwd_ml_kernel, 2); else HEAD_BWD(head_bwd_ml_kernel, 4);
     } else {
         if (nblocks <= HEAD_THREADS) HEAD_BWD(head_bwd_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD(head_bwd_kernel, 2); else HEAD_BWD(head_bwd_kernel, 4);
     }
 #undef HEAD_BWD
+#undef HEAD_BWD_W
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
@@ -623,15 +700,34 @@ extern "C" int sgnn_head_bwd(const float* logits, const float* lse, const int64_
                              const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial,
                              void* stream)
 {
-    return head_bwd_launch(false, logits, lse, labels, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K, p, dz1, partial, stream);
+    return head_bwd_launch(false, nullptr, nullptr, logits, lse, labels, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K, p, dz1,
+                           partial, stream);
+}
+
+extern "C" int sgnn_head_bwd_weighted(const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,
+                                      const float* grad_logits, const float* rows, const float* a1, const float* a2, const float* W2,
+                                      const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1,
+                                      float* partial, void* stream, const float* class_weight)
+{
+    return head_bwd_launch(false, class_weight, nullptr, logits, lse, labels, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K, p,
+                           dz1, partial, stream);
 }
 
 extern "C" int sgnn_head_bwd_ml(const float* logits, const int64_t* targets, const float* grad_loss, const float* grad_logits,
                                 const float* rows, const float* a1, const float* a2, const float* W2, const float* W3, int64_t B,
                                 int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream)
 {
-    return head_bwd_launch(true, logits, nullptr, targets, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K, p, dz1, partial,
-                           stream);
+    return head_bwd_launch(true, nullptr, nullptr, logits, nullptr, targets, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K, p,
+                           dz1, partial, stream);
+}
+
+extern "C" int sgnn_head_bwd_ml_weighted(const float* logits, const int64_t* targets, const float* grad_loss, const float* grad_logits,
+                                         const float* rows, const float* a1, const float* a2, const float* W2, const float* W3,
+                                         int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream,
+                                         const float* weight, const float* pos_weight)
+{
+    return head_bwd_launch(true, weight, pos_weight, logits, nullptr, targets, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K,
+                           p, dz1, partial, stream);
 }
 
 // rows per wavefront of a job: enough row blocks that blocks x output tiles fill the chip twice (~512 workgroups), no more -- every

@@ -3,14 +3,22 @@
 // (subgraph_utils.calc_accuracy, SubGNN/subgraph_utils.py:108-124).  The library form is log_softmax, an nll reduction
 // that runs on ONE workgroup (48 us for 50k rows), argmax, compare, cast, mean, and in the backward two fills, the nll
 // backward and the softmax backward: 12 launches.  Here: one kernel per direction + a one-wavefront finish.
+//
+// Class weights (torch's `weight` / `pos_weight` of the two loss modules built at SubGNN.py:133): every kernel body below is a
+// template on WT; the bare kernels are its WT = 0 instantiations under their old names and argument lists, the weighted ones
+// (ce_fwd_weighted_kernel, ...) kernels of their own that read the weight rows from global memory (any K).  Single-label: a
+// counted row's loss and count are multiplied by w[y] -- the third partial becomes the sum of weights, which the finish writes
+// to lse[B] as before; w[y] is read only for y in [0, K).  Multi-label: c_k [(1 - y) x + L (log1p(exp(-|x|)) + max(-x, 0))] with
+// L = 1 + (p_k - 1) y; the mean stays over B K.
 #include "common.h"
 
 #define SGNN_CE_IGNORE_INDEX (-100ll)
 
 // thread per row; per-workgroup partial sums added in a fixed order (bit-reproducible)
-__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int64_t B,
-                                                     int32_t K, float* __restrict__ lse, float* __restrict__ partial_loss,
-                                                     float* __restrict__ partial_hits, float* __restrict__ partial_rows)
+template <int WT>
+__device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, const int64_t* __restrict__ labels, int64_t B, int32_t K,
+                                            const float* __restrict__ weight, float* __restrict__ lse, float* __restrict__ partial_loss,
+                                            float* __restrict__ partial_hits, float* __restrict__ partial_rows)
 {
     __shared__ float sh_l[256], sh_h[256], sh_n[256];
     const int64_t r = blockIdx.x * 256ll + threadIdx.x;
@@ -25,7 +33,10 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
         const float l = m + logf(sum);
         lse[r] = l;
         const int64_t y = labels[r];
-        if (y >= 0 && y < K) { loss = l - x[y]; hit = (am == (int32_t)y) ? 1.f : 0.f; cnt = 1.f; }
+        if (y >= 0 && y < K) {
+            hit = (am == (int32_t)y) ? 1.f : 0.f;
+            if (WT) { cnt = weight[y]; loss = cnt * (l - x[y]); } else { loss = l - x[y]; cnt = 1.f; }
+        }
         else if (y != SGNN_CE_IGNORE_INDEX) { loss = __builtin_nanf(""); cnt = 1.f; }
     }
     sh_l[threadIdx.x] = loss;
@@ -40,6 +51,21 @@ __global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ l
         for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); h += __shfl_xor(h, o, 64); n += __shfl_xor(n, o, 64); }
         if (threadIdx.x == 0) { partial_loss[blockIdx.x] = a; partial_hits[blockIdx.x] = h; partial_rows[blockIdx.x] = n; }
     }
+}
+
+__global__ __launch_bounds__(256) void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels, int64_t B,
+                                                     int32_t K, float* __restrict__ lse, float* __restrict__ partial_loss,
+                                                     float* __restrict__ partial_hits, float* __restrict__ partial_rows)
+{
+    ce_fwd_body<0>(logits, labels, B, K, nullptr, lse, partial_loss, partial_hits, partial_rows);
+}
+
+__global__ __launch_bounds__(256) void ce_fwd_weighted_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                              int64_t B, int32_t K, const float* __restrict__ weight,
+                                                              float* __restrict__ lse, float* __restrict__ partial_loss,
+                                                              float* __restrict__ partial_hits, float* __restrict__ partial_rows)
+{
+    ce_fwd_body<1>(logits, labels, B, K, weight, lse, partial_loss, partial_hits, partial_rows);
 }
 
 __global__ __launch_bounds__(64) void ce_finish_kernel(const float* __restrict__ partial_loss, const float* __restrict__ partial_hits,
@@ -57,10 +83,11 @@ __global__ __launch_bounds__(64) void ce_finish_kernel(const float* __restrict__
     }
 }
 
-// d loss / d logits[r, k] = (softmax(r)[k] - [k == label r]) * grad_loss / (rows not ignored)
-__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
-                                                     const float* __restrict__ lse, const float* __restrict__ grad_loss, int64_t B,
-                                                     int32_t K, float* __restrict__ grad_logits)
+// d loss / d logits[r, k] = (softmax(r)[k] - [k == label r]) * grad_loss / (rows not ignored)   [WT: * w[label r] / (sum of weights)]
+template <int WT>
+__device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                            const float* __restrict__ lse, const float* __restrict__ grad_loss, int64_t B, int32_t K,
+                                            const float* __restrict__ weight, float* __restrict__ grad_logits)
 {
     const int64_t t = blockIdx.x * 256ll + threadIdx.x;
     if (t >= B * K) return;
@@ -69,8 +96,26 @@ __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ l
     const int64_t y = labels[r];
     const float scale = grad_loss[0] / lse[B];
     float v = 0.f;
-    if (y >= 0 && y < K) v = (expf(logits[t] - lse[r]) - (k == (int32_t)y ? 1.f : 0.f)) * scale;
+    if (y >= 0 && y < K) {
+        v = (expf(logits[t] - lse[r]) - (k == (int32_t)y ? 1.f : 0.f)) * scale;
+        if (WT) v *= weight[y];
+    }
     grad_logits[t] = v;
+}
+
+__global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                     const float* __restrict__ lse, const float* __restrict__ grad_loss, int64_t B,
+                                                     int32_t K, float* __restrict__ grad_logits)
+{
+    ce_bwd_body<0>(logits, labels, lse, grad_loss, B, K, nullptr, grad_logits);
+}
+
+__global__ __launch_bounds__(256) void ce_bwd_weighted_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                              const float* __restrict__ lse, const float* __restrict__ grad_loss,
+                                                              int64_t B, int32_t K, const float* __restrict__ weight,
+                                                              float* __restrict__ grad_logits)
+{
+    ce_bwd_body<1>(logits, labels, lse, grad_loss, B, K, weight, grad_logits);
 }
 
 static inline int64_t ce_blocks(int64_t B) { return (B + 255) / 256; }
@@ -81,8 +126,9 @@ extern "C" int64_t sgnn_cross_entropy_workspace_bytes(int64_t B)
     return 3 * ce_blocks(B) * (int64_t)sizeof(float) + 16;
 }
 
-extern "C" int sgnn_cross_entropy_fwd(const float* logits, const int64_t* labels, int64_t B, int64_t K, float* lse, float* loss,
-                                      float* accuracy, void* workspace, int64_t workspace_bytes, void* stream)
+// weight: DEVICE row of K class weights, nullable (null: the bare kernel)
+static int ce_fwd_launch(const float* logits, const int64_t* labels, int64_t B, int64_t K, float* lse, float* loss, float* accuracy,
+                         void* workspace, int64_t workspace_bytes, void* stream, const float* weight)
 {
     if (!logits || !labels || !lse || !loss || B < 1 || K < 1 || K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < sgnn_cross_entropy_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
@@ -92,9 +138,36 @@ extern "C" int sgnn_cross_entropy_fwd(const float* logits, const int64_t* labels
     float* ph = pl + nblk;
     float* pn = ph + nblk;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, lse, pl, ph, pn);
+    if (weight) hipLaunchKernelGGL(ce_fwd_weighted_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, weight, lse, pl, ph, pn);
+    else hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, lse, pl, ph, pn);
     SGNN_CHECK_LAUNCH();
     hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, st, pl, ph, pn, nblk, B, loss, accuracy, lse + B);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
+extern "C" int sgnn_cross_entropy_fwd(const float* logits, const int64_t* labels, int64_t B, int64_t K, float* lse, float* loss,
+                                      float* accuracy, void* workspace, int64_t workspace_bytes, void* stream)
+{
+    return ce_fwd_launch(logits, labels, B, K, lse, loss, accuracy, workspace, workspace_bytes, stream, nullptr);
+}
+
+extern "C" int sgnn_cross_entropy_fwd_weighted(const float* logits, const int64_t* labels, int64_t B, int64_t K, float* lse, float* loss,
+                                               float* accuracy, void* workspace, int64_t workspace_bytes, void* stream,
+                                               const float* class_weight)
+{
+    return ce_fwd_launch(logits, labels, B, K, lse, loss, accuracy, workspace, workspace_bytes, stream, class_weight);
+}
+
+static int ce_bwd_launch(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss, int64_t B, int64_t K,
+                         float* grad_logits, void* stream, const float* weight)
+{
+    if (!logits || !labels || !lse || !grad_loss || !grad_logits || B < 1 || K < 1 || K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
+    if ((B * K + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
+    if (weight) hipLaunchKernelGGL(ce_bwd_weighted_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits,
+                                   labels, lse, grad_loss, B, (int32_t)K, weight, grad_logits);
+    else hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, labels, lse,
+                            grad_loss, B, (int32_t)K, grad_logits);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
@@ -102,20 +175,23 @@ extern "C" int sgnn_cross_entropy_fwd(const float* logits, const int64_t* labels
 extern "C" int sgnn_cross_entropy_bwd(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss, int64_t B,
                                       int64_t K, float* grad_logits, void* stream)
 {
-    if (!logits || !labels || !lse || !grad_loss || !grad_logits || B < 1 || K < 1 || K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-    if ((B * K + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-    hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, labels, lse,
-                       grad_loss, B, (int32_t)K, grad_logits);
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
+    return ce_bwd_launch(logits, labels, lse, grad_loss, B, K, grad_logits, stream, nullptr);
+}
+
+extern "C" int sgnn_cross_entropy_bwd_weighted(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss,
+                                               int64_t B, int64_t K, float* grad_logits, void* stream, const float* class_weight)
+{
+    return ce_bwd_launch(logits, labels, lse, grad_loss, B, K, grad_logits, stream, class_weight);
 }
 
 // ---- multi-label: nn.BCEWithLogitsLoss() (mean over B x K, SubGNN.py:133 with several labels per subgraph) + the exact-match
 // accuracy of su:108-124, for any K.  targets: int64 (B, K) indicator matrix, non-zero counts as 1.  A thread walks its row in k
 // order: l = max(x, 0) - x y + log1p(exp(-|x|)); the row is a hit when 1 / (1 + exp(-x)) > 0.5 (float32, as torch.sigmoid(x) >
 // 0.5 evaluates it -- not x > 0) equals y in every column.  Same partials and the same fixed order as the single-label pair.
-__global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets, int64_t B,
-                                                      int32_t K, float* __restrict__ partial_loss, float* __restrict__ partial_hits)
+template <int WT>
+__device__ __forceinline__ void bce_fwd_body(const float* __restrict__ logits, const int64_t* __restrict__ targets, int64_t B, int32_t K,
+                                             const float* __restrict__ weight, const float* __restrict__ pos_weight,
+                                             float* __restrict__ partial_loss, float* __restrict__ partial_hits)
 {
     __shared__ float sh_l[256], sh_h[256];
     const int64_t r = blockIdx.x * 256ll + threadIdx.x;
@@ -127,7 +203,10 @@ __global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ 
         for (int32_t k = 0; k < K; ++k) {
             const float v = x[k];
             const bool t = y[k] != 0;
-            loss += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
+            if (WT) {                                     // (either row may be absent: it stands as ones)
+                const float c = weight ? weight[k] : 1.f, L = (t && pos_weight) ? pos_weight[k] : 1.f;
+                loss += c * ((t ? 0.f : v) + L * (log1pf(expf(-fabsf(v))) + fmaxf(-v, 0.f)));
+            } else loss += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
             all = all && ((1.f / (1.f + expf(-v)) > 0.5f) == t);
         }
         hit = all ? 1.f : 0.f;
@@ -142,6 +221,20 @@ __global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ 
         for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o, 64); h += __shfl_xor(h, o, 64); }
         if (threadIdx.x == 0) { partial_loss[blockIdx.x] = a; partial_hits[blockIdx.x] = h; }
     }
+}
+
+__global__ __launch_bounds__(256) void bce_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets, int64_t B,
+                                                      int32_t K, float* __restrict__ partial_loss, float* __restrict__ partial_hits)
+{
+    bce_fwd_body<0>(logits, targets, B, K, nullptr, nullptr, partial_loss, partial_hits);
+}
+
+__global__ __launch_bounds__(256) void bce_fwd_weighted_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                               int64_t B, int32_t K, const float* __restrict__ weight,
+                                                               const float* __restrict__ pos_weight, float* __restrict__ partial_loss,
+                                                               float* __restrict__ partial_hits)
+{
+    bce_fwd_body<1>(logits, targets, B, K, weight, pos_weight, partial_loss, partial_hits);
 }
 
 __global__ __launch_bounds__(64) void bce_finish_kernel(const float* __restrict__ partial_loss, const float* __restrict__ partial_hits,
@@ -159,14 +252,39 @@ __global__ __launch_bounds__(64) void bce_finish_kernel(const float* __restrict_
 }
 
 // d loss / d logits[r, k] = (sigmoid(x) - y) * grad_loss / (B K); the sigmoid takes exp of a non-positive argument only
-__global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
-                                                      const float* __restrict__ grad_loss, int64_t n, float* __restrict__ grad_logits)
+// WT: c_k [(1 - y) - L (1 - sigmoid(x))] * grad_loss / (B K), L = 1 + (p_k - 1) y; 1 - sigmoid(x) = sigmoid(-x), from the same exp
+template <int WT>
+__device__ __forceinline__ void bce_bwd_body(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                             const float* __restrict__ grad_loss, int64_t n, int32_t K, const float* __restrict__ weight,
+                                             const float* __restrict__ pos_weight, float* __restrict__ grad_logits)
 {
     const int64_t t = blockIdx.x * 256ll + threadIdx.x;
     if (t >= n) return;
     const float x = logits[t], e = expf(-fabsf(x));
+    if (WT) {
+        const int32_t k = (int32_t)(t % K);
+        const bool y = targets[t] != 0;
+        const float nsig = x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);
+        const float c = weight ? weight[k] : 1.f, L = (y && pos_weight) ? pos_weight[k] : 1.f;
+        grad_logits[t] = c * ((y ? 0.f : 1.f) - L * nsig) * (grad_loss[0] / (float)n);
+        return;
+    }
     const float sig = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
     grad_logits[t] = (sig - (targets[t] != 0 ? 1.f : 0.f)) * (grad_loss[0] / (float)n);
+}
+
+__global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                      const float* __restrict__ grad_loss, int64_t n, float* __restrict__ grad_logits)
+{
+    bce_bwd_body<0>(logits, targets, grad_loss, n, 1, nullptr, nullptr, grad_logits);
+}
+
+__global__ __launch_bounds__(256) void bce_bwd_weighted_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                               const float* __restrict__ grad_loss, int64_t n, int32_t K,
+                                                               const float* __restrict__ weight, const float* __restrict__ pos_weight,
+                                                               float* __restrict__ grad_logits)
+{
+    bce_bwd_body<1>(logits, targets, grad_loss, n, K, weight, pos_weight, grad_logits);
 }
 
 extern "C" int64_t sgnn_bce_logits_workspace_bytes(int64_t B)
@@ -175,8 +293,9 @@ extern "C" int64_t sgnn_bce_logits_workspace_bytes(int64_t B)
     return 2 * ce_blocks(B) * (int64_t)sizeof(float) + 16;
 }
 
-extern "C" int sgnn_bce_logits_fwd(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
-                                   void* workspace, int64_t workspace_bytes, void* stream)
+// weight / pos_weight: DEVICE rows of K floats, either nullable (both null: the bare kernel)
+static int bce_fwd_launch(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
+                          void* workspace, int64_t workspace_bytes, void* stream, const float* weight, const float* pos_weight)
 {
     if (!logits || !targets || !loss || B < 1 || K < 1 || K > 0x7fffffff || B > (int64_t)0x7fffffffffffffffll / K) return SGNN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < sgnn_bce_logits_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
@@ -185,9 +304,40 @@ extern "C" int sgnn_bce_logits_fwd(const float* logits, const int64_t* targets, 
     float* pl = (float*)workspace;
     float* ph = pl + nblk;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(bce_fwd_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, pl, ph);
+    if (weight || pos_weight)
+        hipLaunchKernelGGL(bce_fwd_weighted_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, weight, pos_weight, pl, ph);
+    else hipLaunchKernelGGL(bce_fwd_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, pl, ph);
     SGNN_CHECK_LAUNCH();
     hipLaunchKernelGGL(bce_finish_kernel, dim3(1), dim3(64), 0, st, pl, ph, nblk, B, K, loss, accuracy);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
+extern "C" int sgnn_bce_logits_fwd(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
+                                   void* workspace, int64_t workspace_bytes, void* stream)
+{
+    return bce_fwd_launch(logits, targets, B, K, loss, accuracy, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+extern "C" int sgnn_bce_logits_fwd_weighted(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
+                                            void* workspace, int64_t workspace_bytes, void* stream, const float* weight,
+                                            const float* pos_weight)
+{
+    return bce_fwd_launch(logits, targets, B, K, loss, accuracy, workspace, workspace_bytes, stream, weight, pos_weight);
+}
+
+static int bce_bwd_launch(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K, float* grad_logits,
+                          void* stream, const float* weight, const float* pos_weight)
+{
+    if (!logits || !targets || !grad_loss || !grad_logits || B < 1 || K < 1 || B > (int64_t)0x7fffffffffffffffll / K) return SGNN_ERR_BAD_ARG;
+    if ((B * K + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
+    if (weight || pos_weight) {
+        if (K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
+        hipLaunchKernelGGL(bce_bwd_weighted_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, targets,
+                           grad_loss, B * K, (int32_t)K, weight, pos_weight, grad_logits);
+    } else
+        hipLaunchKernelGGL(bce_bwd_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, targets,
+                           grad_loss, B * K, grad_logits);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
@@ -195,12 +345,13 @@ extern "C" int sgnn_bce_logits_fwd(const float* logits, const int64_t* targets, 
 extern "C" int sgnn_bce_logits_bwd(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K,
                                    float* grad_logits, void* stream)
 {
-    if (!logits || !targets || !grad_loss || !grad_logits || B < 1 || K < 1 || B > (int64_t)0x7fffffffffffffffll / K) return SGNN_ERR_BAD_ARG;
-    if ((B * K + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-    hipLaunchKernelGGL(bce_bwd_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, targets,
-                       grad_loss, B * K, grad_logits);
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
+    return bce_bwd_launch(logits, targets, grad_loss, B, K, grad_logits, stream, nullptr, nullptr);
+}
+
+extern "C" int sgnn_bce_logits_bwd_weighted(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K,
+                                            float* grad_logits, void* stream, const float* weight, const float* pos_weight)
+{
+    return bce_bwd_launch(logits, targets, grad_loss, B, K, grad_logits, stream, weight, pos_weight);
 }
 
 SGNN_DEFINE_WARM(loss)

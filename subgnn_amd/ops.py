@@ -2721,22 +2721,40 @@ def subgraph_embedding(pieces, mask, B, C):
     return _SubgraphEmbedding.apply(mask.reshape(-1).contiguous(), int(B), int(C), list(pieces), *tensors)
 
 
+def _class_weights(w, K, like, name):
+    """A loss weight row (torch's ``weight`` / ``pos_weight`` of nn.CrossEntropyLoss / nn.BCEWithLogitsLoss): None, or a float32
+    tensor of K elements on the logits' device -> the detached contiguous row (no gradient flows to a weight)."""
+    if w is None:
+        return None
+    if not torch.is_tensor(w) or w.dtype != torch.float32 or w.dim() != 1 or w.shape[0] != int(K):
+        raise ValueError('%s must be a float32 tensor of %d elements (one per class)' % (name, int(K)))
+    if w.device != like.device or not w.is_cuda:
+        raise ValueError('%s must live on the device of the logits (%s), not on %s' % (name, like.device, w.device))
+    return w.detach().contiguous()
+
+
 class _CrossEntropy(torch.autograd.Function):
-    """(mean cross entropy, accuracy) of logits (B, K) against int64 labels (sgnn_cross_entropy_fwd / _bwd)."""
+    """(mean cross entropy, accuracy) of logits (B, K) against int64 labels (sgnn_cross_entropy_fwd / _bwd; with a class weight
+    row their ``_weighted`` forms: the mean is over the sum of the counted rows' weights, the accuracy stays unweighted)."""
 
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, weight):
         lib = _lib.load()
         _req(logits, torch.float32, 'logits')
         _req(labels, torch.int64, 'labels')
         B, K = logits.shape
-        lse = torch.empty(B + 1, dtype=torch.float32, device=logits.device)      # [B]: rows not ignored (label -100)
+        lse = torch.empty(B + 1, dtype=torch.float32, device=logits.device)      # [B]: rows not ignored (label -100), or their weights' sum
         res = torch.empty(2, dtype=torch.float32, device=logits.device)
         wsb = lib.sgnn_cross_entropy_workspace_bytes(B)
         ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=logits.device)
-        check(lib.sgnn_cross_entropy_fwd(_ptr(logits), _ptr(labels), B, K, _ptr(lse), _ptr(res), ctypes.c_void_p(res.data_ptr() + 4),
-                                         _ptr(ws), wsb, _stream()), 'sgnn_cross_entropy_fwd')
-        ctx.save_for_backward(logits, labels, lse)
+        if weight is None:
+            check(lib.sgnn_cross_entropy_fwd(_ptr(logits), _ptr(labels), B, K, _ptr(lse), _ptr(res), ctypes.c_void_p(res.data_ptr() + 4),
+                                             _ptr(ws), wsb, _stream()), 'sgnn_cross_entropy_fwd')
+        else:
+            check(lib.sgnn_cross_entropy_fwd_weighted(_ptr(logits), _ptr(labels), B, K, _ptr(lse), _ptr(res),
+                                                      ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb, _stream(), _ptr(weight)),
+                  'sgnn_cross_entropy_fwd_weighted')
+        ctx.save_for_backward(logits, labels, lse, weight)
         loss, acc = res[0], res[1:2]
         ctx.mark_non_differentiable(acc)
         return loss, acc
@@ -2744,17 +2762,24 @@ class _CrossEntropy(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_acc):
         lib = _lib.load()
-        logits, labels, lse = ctx.saved_tensors
+        logits, labels, lse, weight = ctx.saved_tensors
         B, K = logits.shape
         g = torch.empty_like(logits)
-        check(lib.sgnn_cross_entropy_bwd(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss.reshape(1).contiguous().float()), B, K,
-                                         _ptr(g), _stream()), 'sgnn_cross_entropy_bwd')
-        return g, None
+        if weight is None:
+            check(lib.sgnn_cross_entropy_bwd(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss.reshape(1).contiguous().float()), B, K,
+                                             _ptr(g), _stream()), 'sgnn_cross_entropy_bwd')
+        else:
+            check(lib.sgnn_cross_entropy_bwd_weighted(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss.reshape(1).contiguous().float()),
+                                                      B, K, _ptr(g), _stream(), _ptr(weight)), 'sgnn_cross_entropy_bwd_weighted')
+        return g, None, None
 
 
-def cross_entropy_with_accuracy(logits, labels):
-    """nn.CrossEntropyLoss()(logits, labels) and calc_accuracy(logits, labels) -> (0-d loss, (1,) accuracy) in one pass."""
-    return _CrossEntropy.apply(logits.contiguous(), labels.contiguous())
+def cross_entropy_with_accuracy(logits, labels, weight=None):
+    """nn.CrossEntropyLoss(weight=weight)(logits, labels) and calc_accuracy(logits, labels) -> (0-d loss, (1,) accuracy) in one
+    pass.  ``weight``: None or a float32 device tensor of K class weights (torch's semantics: the mean is taken over the sum of the
+    counted rows' weights; the accuracy is over all rows, unweighted)."""
+    return _CrossEntropy.apply(logits.contiguous(), labels.contiguous(),
+                               _class_weights(weight, logits.shape[-1], logits, 'cross_entropy_with_accuracy: weight'))
 
 
 class _BCEWithLogits(torch.autograd.Function):
@@ -2762,7 +2787,7 @@ class _BCEWithLogits(torch.autograd.Function):
     (sgnn_bce_logits_fwd / _bwd).  Nothing but the two inputs is saved: the backward recomputes the sigmoid."""
 
     @staticmethod
-    def forward(ctx, logits, targets):
+    def forward(ctx, logits, targets, weight, pos_weight):
         lib = _lib.load()
         _req(logits, torch.float32, 'logits')
         _req(targets, torch.int64, 'targets')
@@ -2773,9 +2798,14 @@ class _BCEWithLogits(torch.autograd.Function):
         res = torch.empty(2, dtype=torch.float32, device=logits.device)
         wsb = lib.sgnn_bce_logits_workspace_bytes(B)
         ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=logits.device)
-        check(lib.sgnn_bce_logits_fwd(_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb,
-                                      _stream()), 'sgnn_bce_logits_fwd')
-        ctx.save_for_backward(logits, targets)
+        if weight is None and pos_weight is None:
+            check(lib.sgnn_bce_logits_fwd(_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb,
+                                          _stream()), 'sgnn_bce_logits_fwd')
+        else:
+            check(lib.sgnn_bce_logits_fwd_weighted(_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4),
+                                                   _ptr(ws), wsb, _stream(), _ptr(weight), _ptr(pos_weight)),
+                  'sgnn_bce_logits_fwd_weighted')
+        ctx.save_for_backward(logits, targets, weight, pos_weight)
         loss, acc = res[0], res[1:2]
         ctx.mark_non_differentiable(acc)
         return loss, acc
@@ -2783,19 +2813,27 @@ class _BCEWithLogits(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_loss, _g_acc):
         lib = _lib.load()
-        logits, targets = ctx.saved_tensors
+        logits, targets, weight, pos_weight = ctx.saved_tensors
         B, K = logits.shape
         g = torch.empty_like(logits)
-        check(lib.sgnn_bce_logits_bwd(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K, _ptr(g),
-                                      _stream()), 'sgnn_bce_logits_bwd')
-        return g, None
+        if weight is None and pos_weight is None:
+            check(lib.sgnn_bce_logits_bwd(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K, _ptr(g),
+                                          _stream()), 'sgnn_bce_logits_bwd')
+        else:
+            check(lib.sgnn_bce_logits_bwd_weighted(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K,
+                                                   _ptr(g), _stream(), _ptr(weight), _ptr(pos_weight)), 'sgnn_bce_logits_bwd_weighted')
+        return g, None, None, None
 
 
-def bce_with_logits_and_accuracy(logits, targets):
-    """nn.BCEWithLogitsLoss()(logits, targets.float()) and the exact-match accuracy calc_accuracy logs for a multi-label batch
-    (every sigmoid(x) > 0.5 of a row equal to its target) -> (0-d loss, (1,) accuracy) in one pass.  ``targets``: int64 (B, K)
-    indicator matrix, as the data loader keeps it (no float copy is made); any K."""
-    return _BCEWithLogits.apply(logits.contiguous(), targets.contiguous())
+def bce_with_logits_and_accuracy(logits, targets, weight=None, pos_weight=None):
+    """nn.BCEWithLogitsLoss(weight=, pos_weight=)(logits, targets.float()) and the exact-match accuracy calc_accuracy logs for a
+    multi-label batch (every sigmoid(x) > 0.5 of a row equal to its target) -> (0-d loss, (1,) accuracy) in one pass.  ``targets``:
+    int64 (B, K) indicator matrix, as the data loader keeps it (no float copy is made); any K.  ``weight`` / ``pos_weight``: None
+    or float32 device tensors of K per-class factors (torch's: weight scales a column's loss, pos_weight its positive term)."""
+    logits = logits.contiguous()
+    K = logits.shape[-1]
+    return _BCEWithLogits.apply(logits, targets.contiguous(), _class_weights(weight, K, logits, 'bce_with_logits_and_accuracy: weight'),
+                                _class_weights(pos_weight, K, logits, 'bce_with_logits_and_accuracy: pos_weight'))
 
 
 # ---------------------------------------------------------------------------------------
@@ -2904,7 +2942,7 @@ class _FusedHead(torch.autograd.Function):
     every weight and bias gradient of the head.  9 + 22 launches -> 2 + 4."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, W3, b3, labels, p, rng, ml):
+    def forward(ctx, x, W1, b1, W2, b2, W3, b3, labels, p, rng, ml, class_weight=None, pos_weight=None):
         lib = _lib.load()
         for t, nm in ((x, 'x'), (W1, 'W1'), (b1, 'b1'), (W2, 'W2'), (b2, 'b2'), (W3, 'W3'), (b3, 'b3')):
             _req(t, torch.float32, nm)
@@ -2921,7 +2959,16 @@ class _FusedHead(torch.autograd.Function):
         lse = torch.empty(B + 1, dtype=torch.float32, device=dev) if (labels is not None and not ml) else None
         out = torch.empty(3, dtype=torch.float32, device=dev) if labels is not None else None
         ws = _head_workspace(dev, B)
-        if ml:                                               # multi-label: ``labels`` is the (B, K) indicator matrix; no lse
+        weighted = labels is not None and (class_weight is not None or pos_weight is not None)
+        if weighted and ml:                                  # the weighted launches (headw_*): the bare ones below stay as they are
+            check(lib.sgnn_head_fwd_ml_weighted(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p),
+                                                _ptr(rng), _ptr(a1), _ptr(a2), _ptr(logits), _ptr(out), _ptr(ws), ws.numel() * 4,
+                                                _stream(), _ptr(class_weight), _ptr(pos_weight)), 'sgnn_head_fwd_ml_weighted')
+        elif weighted:
+            check(lib.sgnn_head_fwd_weighted(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p),
+                                             _ptr(rng), _ptr(a1), _ptr(a2), _ptr(logits), _ptr(lse), _ptr(out), _ptr(ws),
+                                             ws.numel() * 4, _stream(), _ptr(class_weight)), 'sgnn_head_fwd_weighted')
+        elif ml:                                             # multi-label: ``labels`` is the (B, K) indicator matrix; no lse
             check(lib.sgnn_head_fwd_ml(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p), _ptr(rng),
                                        _ptr(a1), _ptr(a2), _ptr(logits), _ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
                   'sgnn_head_fwd_ml')
@@ -2929,7 +2976,8 @@ class _FusedHead(torch.autograd.Function):
             check(lib.sgnn_head_fwd(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p), _ptr(rng),
                                     _ptr(a1), _ptr(a2), _ptr(logits), _ptr(lse), _ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
                   'sgnn_head_fwd')
-        ctx.save_for_backward(x, W1, W2, W3, a1, a2, logits, lse, labels, out)
+        ctx.save_for_backward(x, W1, W2, W3, a1, a2, logits, lse, labels, out, class_weight if weighted else None,
+                              pos_weight if weighted else None)
         ctx.p, ctx.dims, ctx.ml = float(p), (B, H1, H2, K), bool(ml)
         ctx.has_bias = (b1 is not None, b2 is not None, b3 is not None)
         ctx.set_materialize_grads(False)
@@ -2942,11 +2990,11 @@ class _FusedHead(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_logits, g_loss, _g_acc):
         lib = _lib.load()
-        x, W1, W2, W3, a1, a2, logits, lse, labels, out = ctx.saved_tensors
+        x, W1, W2, W3, a1, a2, logits, lse, labels, out, class_weight, pos_weight = ctx.saved_tensors
         B, H1, H2, K = ctx.dims
         dev = x.device
         if g_logits is None and g_loss is None:
-            return (None,) * 11
+            return (None,) * 13
         g_logits = g_logits.contiguous() if g_logits is not None else None
         g_loss = g_loss.reshape(1).contiguous().float() if g_loss is not None else None
         P = int(lib.sgnn_head_partial_floats(H1, H2, K))
@@ -2954,7 +3002,16 @@ class _FusedHead(torch.autograd.Function):
         dz1 = torch.empty((B, H1), dtype=torch.float32, device=dev)
         partial = torch.empty((nb, P), dtype=torch.float32, device=dev)
         rows = ctypes.c_void_p(out.data_ptr() + 8) if out is not None else None
-        if ctx.ml:
+        weighted = class_weight is not None or pos_weight is not None
+        if weighted and ctx.ml:
+            check(lib.sgnn_head_bwd_ml_weighted(_ptr(logits), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2),
+                                                _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream(),
+                                                _ptr(class_weight), _ptr(pos_weight)), 'sgnn_head_bwd_ml_weighted')
+        elif weighted:
+            check(lib.sgnn_head_bwd_weighted(_ptr(logits), _ptr(lse), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1),
+                                             _ptr(a2), _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream(),
+                                             _ptr(class_weight)), 'sgnn_head_bwd_weighted')
+        elif ctx.ml:
             check(lib.sgnn_head_bwd_ml(_ptr(logits), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2), _ptr(W2),
                                        _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream()), 'sgnn_head_bwd_ml')
         else:
@@ -2990,26 +3047,37 @@ class _FusedHead(torch.autograd.Function):
         need = ctx.needs_input_grad
         dx = dz1 @ W1 if need[0] else None
         return (dx, gW1, gb1 if (hb[0] and need[2]) else None, gW2 if need[3] else None, gb2 if (hb[1] and need[4]) else None,
-                gW3 if need[5] else None, gb3 if (hb[2] and need[6]) else None, None, None, None, None)
+                gW3 if need[5] else None, gb3 if (hb[2] and need[6]) else None, None, None, None, None, None, None)
 
 
-def fused_head(x, lin, lin2, lin3, labels=None, p=0.0, rng=None, targets=None):
+def fused_head(x, lin, lin2, lin3, labels=None, p=0.0, rng=None, targets=None, class_weight=None, pos_weight=None):
     """The head's three Linear layers with relu + dropout(p) between them, and -- with ``labels`` (int64 (B,)) -- the mean cross
     entropy and the accuracy of the logits, or -- with ``targets`` (int64 (B, K) indicator matrix, multi-label) -- the mean binary
     cross entropy with logits and the exact-match accuracy (``lin*``: nn.Linear modules).
     -> (logits, loss or None, accuracy (1,) or None).
-    ``rng``: int64 (2,) device tensor {seed, step} when p > 0 (the launch advances step)."""
+    ``rng``: int64 (2,) device tensor {seed, step} when p > 0 (the launch advances step).
+    ``class_weight``: float32 device tensor of K class weights -- nn.CrossEntropyLoss's ``weight`` with ``labels`` (the mean is over
+    the sum of the counted rows' weights), nn.BCEWithLogitsLoss's ``weight`` with ``targets``; ``pos_weight`` (``targets`` only):
+    nn.BCEWithLogitsLoss's.  Either selects the weighted launches; no gradient flows to them; the accuracy is unweighted."""
     if labels is not None and targets is not None:
         raise ValueError('fused_head: labels (single-label) and targets (multi-label) exclude each other')
     if p > 0 and rng is None:
         raise ValueError('fused_head: dropout needs the {seed, step} tensor')
     if x.stride(1) != 1 or x.stride(0) != x.shape[1]:
         x = x.contiguous()
+    if pos_weight is not None and targets is None:
+        raise ValueError('fused_head: pos_weight belongs to the multi-label loss (targets=)')
+    if class_weight is not None and labels is None and targets is None:
+        raise ValueError('fused_head: class_weight without labels or targets')
+    K = lin3.weight.shape[0]
+    class_weight = _class_weights(class_weight, K, x, 'fused_head: class_weight')
+    pos_weight = _class_weights(pos_weight, K, x, 'fused_head: pos_weight')
     if targets is not None:
         return _FusedHead.apply(x, lin.weight, lin.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias, targets.contiguous(),
-                                float(p), rng if p > 0 else None, True)
+                                float(p), rng if p > 0 else None, True, class_weight, pos_weight)
     return _FusedHead.apply(x, lin.weight, lin.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias,
-                            labels.contiguous() if labels is not None else None, float(p), rng if p > 0 else None, False)
+                            labels.contiguous() if labels is not None else None, float(p), rng if p > 0 else None, False,
+                            class_weight, None)
 
 
 class _GatherRows(torch.autograd.Function):

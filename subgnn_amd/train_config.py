@@ -429,6 +429,15 @@ class Trainer:
             return model.test_epoch_end(outs)
 
 
+def write_hyperparams(results_dir, hp):
+    """``results_dir/hyperparams.json``: the run's hyper-parameters as configured (train.py:174-183) -- what ``restore_path``
+    reads back.  Values stay in their configured form ('balanced' for a loss weight stays the word: the weights are rebuilt from
+    it and the training split)."""
+    Path(results_dir).mkdir(parents=True, exist_ok=True)
+    with open(Path(results_dir) / 'hyperparams.json', 'w') as f:
+        json.dump({k: v for k, v in hp.items()}, f, indent=2, default=str)
+
+
 def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_k=0, restore_path=None, restore_name=None,
                 no_train=False, run_test=False, resume=False, max_epochs=None, epoch_callback=None, similarities_subdir=None,
                 auto_lr_find=False):
@@ -462,9 +471,7 @@ def train_model(run_config, trial=None, results_dir=None, log=print, checkpoint_
                       checkpoint_k=0 if no_train else checkpoint_k,
                       auto_lr_find=hp.get('auto_lr_find', False) if auto_lr_find else False)
     if results_dir is not None and not no_train:
-        Path(results_dir).mkdir(parents=True, exist_ok=True)
-        with open(Path(results_dir) / 'hyperparams.json', 'w') as f:
-            json.dump({k: v for k, v in hp.items()}, f, indent=2, default=str)
+        write_hyperparams(results_dir, hp)
     prepared = False
     if restore_name is not None:
         model.prepare_data()
