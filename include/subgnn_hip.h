@@ -686,6 +686,43 @@ int sgnn_topk_rows(const float* q, int64_t q_stride, int64_t Q, const float* ban
                    void* stream);
 
 /* ---------------------------------------------------------------------------------------
+ * n2   k-means over a bank of embeddings: one Lloyd iteration = sgnn_kmeans_step + sgnn_kmeans_finish, no (N, K) matrix,
+ * no atomics on floats, nothing returned to the host.  Replaces no reference function.
+ *   x (N, D) and c (K, D) float32, row-major with row strides x_stride / c_stride >= D (in elements); x_aux (N) / c_aux (K)
+ *   the vectors sgnn_topk_rows takes beside them.  metric: SGNN_TOPK_L2 (k-means) or SGNN_TOPK_COSINE (spherical k-means on
+ *   rows the caller has normalised); SGNN_TOPK_DOT is refused.
+ * sgnn_kmeans_step
+ *   assign[i] (int32) / score[i]: exactly index and score of sgnn_topk_rows(x, c, k = 1, metric, x_aux, c_aux) -- the same
+ *   fmaf chain, epilogue and total order (better score, then the smaller centre, NaN last), for every grid.
+ *   The rows are dealt to S = sgnn_kmeans_slots(N, K, D) workgroups as contiguous ranges of 32-row tiles:
+ *   S = min(ceil(N / 32), 1024, max(1, 64 MiB / (4 K D))), then evened so that no slot is empty.  Slot s leaves in the
+ *   workspace: per cluster the float32 chain acc = acc + x[i][d] from +0 over its rows of the cluster in ascending i; the
+ *   rows' count; the number of its rows with assign[i] != prev_assign[i] (prev_assign NULL: all of them; it must not be the
+ *   array `assign`); and the double sum of its scores -- per 32-row tile the butterfly t[r] += t[r ^ 16], ^ 8, ^ 4, ^ 2, ^ 1
+ *   (rows past N count 0), the tiles added in ascending order.
+ * sgnn_kmeans_finish (same N, K, D, metric and workspace; c = the centres the step used)
+ *   sums (K, D) = the chain acc = acc + partial over the slots in slot order from +0; counts (K) int32; *inertia (double)
+ *   and changed[it] (int32; `it` >= 0 indexes a device array, so a loop of iterations needs no read-back) the slots' sums in
+ *   slot order; c_next (K, D, contiguous; may be c itself) = sums / (float)counts, one correctly rounded division, or the
+ *   row of c for a cluster without rows; *empty (int32) the number of such clusters; c_aux_next (K): with
+ *   q = the chain fmaf(v, v, q) of thread t over d = t, t + 256, ... and then q[t] += q[t + 128], q[t + 64], ..., q[t + 1],
+ *   q[0] for l2 and 1 / sqrt(max(q[0], 1e-30)) (both correctly rounded) for cosine.
+ * Limits: 1 <= K <= sgnn_kmeans_max_k() (1024); 1 <= N < 2^31 - 256; 1 <= D; strides < 2^23 (topk_rows' limits); float32.
+ * Anything else -- a refused metric, a NULL array other than prev_assign, a workspace smaller than
+ * sgnn_kmeans_workspace_bytes(N, K, D) (< 0 for sizes the calls refuse) -- returns SGNN_ERR_BAD_ARG before any launch, with
+ * nothing written.  A call repeats bit for bit; a step whose assignment equals prev_assign's yields the same c_next bits.
+ * ------------------------------------------------------------------------------------- */
+int64_t sgnn_kmeans_max_k(void);
+int64_t sgnn_kmeans_slots(int64_t N, int64_t K, int64_t D);
+int64_t sgnn_kmeans_workspace_bytes(int64_t N, int64_t K, int64_t D);
+int sgnn_kmeans_step(const float* x, int64_t x_stride, int64_t N, const float* c, int64_t c_stride, int64_t K, int64_t D,
+                     int metric, const float* x_aux, const float* c_aux, const int32_t* prev_assign, int32_t* assign,
+                     float* score, void* workspace, int64_t workspace_bytes, void* stream);
+int sgnn_kmeans_finish(const void* workspace, int64_t workspace_bytes, int64_t N, int64_t K, int64_t D, int metric,
+                       const float* c, int64_t c_stride, float* sums, int32_t* counts, double* inertia, int32_t* empty,
+                       float* c_next, float* c_aux_next, int32_t* changed, int64_t it, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * a12  CC embedding initialisation: sum or max of member node embeddings.
  * Replaces SubGNN.initialize_cc_embeddings (SubGNN/SubGNN.py:609-622).  E: (n_emb_rows, D) f32.
  * aggregator 0 = sum, 1 = max.  For max, a row shorter than padded_len also competes with the

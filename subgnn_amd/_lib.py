@@ -127,6 +127,13 @@ SIGNATURES = {
     'sgnn_topk_rows_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     'sgnn_topk_rows': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_i64, c_ptr,
                                c_ptr, c_ptr, c_i64, c_ptr]),
+    'sgnn_kmeans_max_k': (c_i64, []),
+    'sgnn_kmeans_slots': (c_i64, [c_i64, c_i64, c_i64]),
+    'sgnn_kmeans_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64]),
+    'sgnn_kmeans_step': (c_int, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                 c_i64, c_ptr]),
+    'sgnn_kmeans_finish': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_int, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                   c_ptr, c_i64, c_ptr]),
     'sgnn_dtw_exact_workspace_bytes': (c_i64, [c_i64, c_i64, c_i64, c_i64]),
     'sgnn_dtw_exact_similarity': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_i64, c_int, c_ptr, c_ptr, c_ptr,
                                           c_i64, c_ptr]),

@@ -16,38 +16,17 @@
 // Keys are distinct (the row is in them), so the order is strict and total and the result cannot depend on tiles, slices or the
 // order of insertions.  The score is read back out of the key: a zero comes back as +0, a NaN as the quiet NaN 0x7FC00000.
 #include "common.h"
+#include "topk_order.h"
 #include <math.h>
 
 #define TK_MAX_K      64
 #define TK_TQ         32          // queries per workgroup
 #define TK_TB         128         // bank rows per tile: one 32-row sub-tile per wave
-#define TK_KC         32          // columns per staged chunk
-#define TK_LD         (TK_KC + 1) // LDS row stride of the staged chunks: a lane's 32 rows fall on 32 banks
 #define TK_THREADS    256
 #define TK_QPW        (TK_TQ / (TK_THREADS / 64))   // queries per wave in the selection
 #define TK_MAX_SPLITS 1024
-#define TK_MAX_ROWS   0x7FFFFF00ll // rows of either matrix: a row index, rounded up to its tile, is an int
-#define TK_MAX_STRIDE (1ll << 23)   // row stride in elements: a tile's offsets stay within 32 bits
 #define TK_WANT_BLOCKS 1024       // four workgroups per CU
-#define TK_FILLER     0xFFFFFFFFFFFFFFFFull
-#define TK_KEY_NAN    0xFFFFFFFEu
-
-typedef float tk_f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ uint32_t tk_order_key(float s, bool lower_better) {
-    if (s != s) return TK_KEY_NAN;
-    uint32_t u = __float_as_uint(s);
-    if (u == 0x80000000u) u = 0u;                                  // -0 == +0
-    const uint32_t m = u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);  // ascending with the float
-    return lower_better ? m : ~m;
-}
-
-__device__ __forceinline__ float tk_key_score(uint32_t key, bool lower_better) {
-    if (key == 0xFFFFFFFFu) return lower_better ? INFINITY : -INFINITY;
-    if (key == TK_KEY_NAN) return __uint_as_float(0x7FC00000u);
-    const uint32_t m = lower_better ? key : ~key;
-    return __uint_as_float((m >> 31) ? (m ^ 0x80000000u) : ~m);
-}
+// (the staged-chunk geometry, the limits, the order key and its inverse: topk_order.h, shared with kmeans.hip)
 
 __device__ __forceinline__ uint64_t tk_readlane(uint64_t v, int src) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);

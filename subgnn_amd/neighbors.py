@@ -158,6 +158,12 @@ class SubgraphIndex:
         me = torch.arange(len(self), dtype=torch.int64, device=self.embeddings.device)
         return self.query_embeddings(self.embeddings, k, exclude=me)
 
+    def cluster(self, n_clusters, metric=None, medoids=5, **kmeans_args):
+        """k-means of the index's rows on the device (ops.kmeans) -> ``subgnn_amd.cluster.Clustering``.  ``metric`` None: the
+        index's own ('dot' is refused); ``medoids``: typical rows kept per cluster; further arguments go to ops.kmeans."""
+        from .cluster import cluster_index
+        return cluster_index(self, n_clusters, metric, medoids, **kmeans_args)
+
     def describe(self, row):
         """(split, row within the split, node list, label strings) of a row of the index."""
         return self.splits[row], self.rows[row], self.subgraphs[row], self.labels[row]

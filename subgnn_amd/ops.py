@@ -3722,3 +3722,184 @@ def topk_rows(queries, bank, k, metric='cosine', exclude=None, splits=0, q_aux=N
                                  _ptr(b_aux) if N else None, _ptr(exclude), int(splits), _ptr(scores), _ptr(indices), _ptr(ws),
                                  nbytes, _stream()), 'sgnn_topk_rows')
     return scores, indices
+
+
+# ---------------------------------------------------------------------------------------
+# k-means over a bank of embeddings (csrc/kmeans.hip)
+# ---------------------------------------------------------------------------------------
+KMEANS_METRICS = ('l2', 'cosine')
+KMEANS_INITS = ('k-means++', 'random')
+
+
+def _kmeans_check(X, C, metric):
+    if metric not in KMEANS_METRICS:
+        raise ValueError('metric must be one of %s, got %r' % (KMEANS_METRICS, metric))
+    for name, t in (('X', X), ('C', C)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError('%s must be a 2-d float32 CUDA/HIP tensor' % name)
+        if t.shape[0] > 0 and t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError('%s must have unit column stride' % name)
+    (N, D), K = X.shape, C.shape[0]
+    if C.shape[1] != D:
+        raise ValueError('X is %d wide, the centres %d' % (D, C.shape[1]))
+    if X.device != C.device:
+        raise ValueError('X and C must be on one device')
+    max_k = int(_lib.load().sgnn_kmeans_max_k())
+    if N < 1 or D < 1 or K < 1 or K > max_k:
+        raise ValueError('k-means needs N >= 1, D >= 1 and 1 <= K <= %d, got N=%d D=%d K=%d' % (max_k, N, D, K))
+    xs = X.stride(0) if N > 1 else max(D, X.stride(0))
+    cs = C.stride(0) if K > 1 else max(D, C.stride(0))
+    if xs < D or cs < D:
+        raise ValueError('rows must not overlap (row stride >= width)')
+    return N, K, D, xs, cs
+
+
+class _KMeansState:
+    """The device buffers of a run of Lloyd iterations over one (X, K): two sets of centres and assignments used in turn,
+    the workspace, and the ``changed`` array the iterations fill."""
+
+    def __init__(self, X, K, metric, x_aux, slots):
+        N, D = X.shape
+        dev = X.device
+        self.lib = _lib.load()
+        self.X, self.metric, self.code, self.x_aux = X, metric, TOPK_METRICS[metric], x_aux
+        self.N, self.K, self.D = N, K, D
+        self.xs = X.stride(0) if N > 1 else max(D, X.stride(0))
+        self.nbytes = int(self.lib.sgnn_kmeans_workspace_bytes(N, K, D))
+        if self.nbytes < 0:
+            raise ValueError('sgnn_kmeans_workspace_bytes refused (N=%d, K=%d, D=%d)' % (N, K, D))
+        self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.assign = [torch.empty(N, dtype=torch.int32, device=dev) for _ in range(2)]
+        self.score = torch.empty(N, dtype=torch.float32, device=dev)
+        self.centers = [torch.empty((K, D), dtype=torch.float32, device=dev) for _ in range(2)]
+        self.c_aux = [torch.empty(K, dtype=torch.float32, device=dev) for _ in range(2)]
+        self.sums = torch.empty((K, D), dtype=torch.float32, device=dev)
+        self.counts = torch.empty(K, dtype=torch.int32, device=dev)
+        self.inertia = torch.empty(1, dtype=torch.float64, device=dev)
+        self.empty = torch.empty(1, dtype=torch.int32, device=dev)
+        self.changed = torch.empty(max(1, slots), dtype=torch.int32, device=dev)
+
+    def step(self, C, cs, c_aux, prev, out, it):
+        """One iteration from centres ``C`` (row stride ``cs``) into buffer set ``out``, ``changed[it]`` included."""
+        lib = self.lib
+        with torch.cuda.device(self.X.device):
+            check(lib.sgnn_kmeans_step(_ptr(self.X), self.xs, self.N, _ptr(C), cs, self.K, self.D, self.code, _ptr(self.x_aux),
+                                       _ptr(c_aux), _ptr(prev), _ptr(self.assign[out]), _ptr(self.score), _ptr(self.ws),
+                                       self.nbytes, _stream()), 'sgnn_kmeans_step')
+            check(lib.sgnn_kmeans_finish(_ptr(self.ws), self.nbytes, self.N, self.K, self.D, self.code, _ptr(C), cs,
+                                         _ptr(self.sums), _ptr(self.counts), _ptr(self.inertia), _ptr(self.empty),
+                                         _ptr(self.centers[out]), _ptr(self.c_aux[out]), _ptr(self.changed), it, _stream()),
+                  'sgnn_kmeans_finish')
+
+
+def kmeans_step(X, C, metric='l2', x_aux=None, c_aux=None, prev_assign=None):
+    """One Lloyd iteration of ``X`` (N, D) against the centres ``C`` (K, D) -> dict of device tensors: ``assign`` (N) int32 and
+    ``score`` (N), bit for bit ``topk_rows(X, C, 1, metric, q_aux=x_aux, b_aux=c_aux)``; ``sums`` (K, D), ``counts`` (K) int32,
+    ``inertia`` (1) float64 = the sum of the scores, ``changed`` (1) int32 = the rows whose cluster differs from ``prev_assign``
+    (None: N), ``centers`` (K, D) = sums / counts (a cluster without rows keeps its row of ``C``), ``c_aux`` (K) the next
+    centres' aux vector and ``empty`` (1) int32.  'cosine' expects rows the caller has normalised.  Two launches, no (N, K)
+    matrix, no float atomics; a call repeats bit for bit."""
+    N, K, D, xs, cs = _kmeans_check(X, C, metric)
+    x_aux = topk_aux(X, metric) if x_aux is None else x_aux
+    c_aux = topk_aux(C, metric) if c_aux is None else c_aux
+    for name, a, n, dt in (('x_aux', x_aux, N, torch.float32), ('c_aux', c_aux, K, torch.float32),
+                           ('prev_assign', prev_assign, N, torch.int32)):
+        _req(a, dt, name)
+        if a is not None and a.shape != (n,):
+            raise ValueError('%s must have shape (%d,)' % (name, n))
+    st = _KMeansState(X, K, metric, x_aux, 1)
+    st.step(C, cs, c_aux, prev_assign, 0, 0)
+    return {'assign': st.assign[0], 'score': st.score, 'sums': st.sums, 'counts': st.counts, 'inertia': st.inertia,
+            'changed': st.changed, 'centers': st.centers[0], 'c_aux': st.c_aux[0], 'empty': st.empty}
+
+
+def kmeans_unit_rows(X):
+    """The rows times rsqrt(max(sum of squares, tiny)): what spherical k-means ('cosine') runs on."""
+    return X * torch.rsqrt((X * X).sum(dim=1, keepdim=True, dtype=torch.float32).clamp_min(_TOPK_TINY))
+
+
+def kmeans_init_rows(X, n_clusters, init, seed):
+    """The rows of ``X`` the initial centres are, as a list: see ``kmeans``.  'k-means++' reads one float64 cumulative sum
+    per centre back to the host (N doubles); the squared distances come from topk_rows."""
+    N = X.shape[0]
+    rng = np.random.default_rng(seed)
+    if init == 'random':
+        return [int(r) for r in rng.choice(N, n_clusters, replace=False)]
+    u = rng.random(n_clusters)
+    picks = [min(int(np.floor(u[0] * N)), N - 1)]
+    x_aux = topk_aux(X, 'l2')
+    d2 = None
+    for j in range(1, n_clusters):
+        c = X[picks[-1]][None].contiguous()
+        s = topk_rows(X, c, 1, 'l2', q_aux=x_aux)[0][:, 0].clamp_min(0.0)
+        d2 = s if d2 is None else torch.minimum(d2, s)
+        p = torch.cumsum(d2.double(), 0).cpu().numpy()
+        if p[-1] == 0:
+            chosen = set(picks)
+            pick = next(r for r in range(N) if r not in chosen)
+        else:
+            pick = min(int(np.searchsorted(p, u[j] * p[-1], side='right')), N - 1)
+        picks.append(pick)
+    return picks
+
+
+def kmeans(X, n_clusters, metric='l2', init='k-means++', n_init=1, max_iter=100, seed=0, check_every=8):
+    """Lloyd's k-means of the rows of ``X`` (N, D) float32 on the device -> dict: ``centers`` (K, D), ``assign`` (N) int32,
+    ``score`` (N), ``sizes`` (K) int32, ``inertia`` (float), ``n_iter``, ``converged``, ``empty`` (int) and ``c_aux`` (K), the
+    centres' aux vector as the last iteration used it.
+
+    'cosine' is spherical k-means: the rows are normalised once (torch) and the kernel runs on those rows.  ``check_every``
+    iterations are enqueued at a time, then the ``changed`` array is read once; ``n_iter`` is the first iteration with no
+    changed row, and since an iteration whose assignment repeats reproduces its centres bit for bit, the result has the bits
+    of a run stopped exactly there.  ``init``: 'k-means++' or 'random' from ``numpy.random.default_rng(seed + run)`` (see
+    DESIGN 8o: u = rng.random(K); first centre row floor(u[0] N); then by the float64 cumulative sum of the clamped squared
+    distances), or a (K, D) tensor.  ``n_init`` runs keep the one of lowest inertia (highest for 'cosine', whose score is a
+    similarity), ties to the earlier."""
+    if metric not in KMEANS_METRICS:
+        raise ValueError('metric must be one of %s, got %r' % (KMEANS_METRICS, metric))
+    if not isinstance(X, torch.Tensor) or X.dim() != 2 or X.dtype != torch.float32 or not X.is_cuda:
+        raise ValueError('X must be a 2-d float32 CUDA/HIP tensor')
+    N, D = X.shape
+    K = int(n_clusters)
+    if isinstance(init, torch.Tensor):
+        if init.shape != (K, D) or init.dtype != torch.float32:
+            raise ValueError('init must be a (%d, %d) float32 tensor' % (K, D))
+    elif init not in KMEANS_INITS:
+        raise ValueError('init must be one of %s or a (K, D) tensor, got %r' % (KMEANS_INITS, init))
+    if K < 1 or K > N:
+        raise ValueError('n_clusters must be in 1 .. N = %d, got %d' % (N, K))
+    if int(n_init) < 1 or int(max_iter) < 1 or int(check_every) < 1:
+        raise ValueError('n_init, max_iter and check_every must be at least 1')
+    if not bool(torch.isfinite(X).all()):
+        raise ValueError('X holds NaN or infinity')
+    if metric == 'cosine':
+        X = kmeans_unit_rows(X)
+    _kmeans_check(X, X[:K], metric)
+    x_aux = topk_aux(X, metric)
+    higher = metric == 'cosine'
+    best = None
+    for run in range(1 if isinstance(init, torch.Tensor) else int(n_init)):
+        if isinstance(init, torch.Tensor):
+            C0 = init.to(X.device).contiguous()
+        else:
+            rows = kmeans_init_rows(X, K, init, seed + run)
+            C0 = X[torch.as_tensor(rows, dtype=torch.int64, device=X.device)].contiguous()
+        st = _KMeansState(X, K, metric, x_aux, int(max_iter))
+        C, c_aux, prev, n_iter, it = C0, topk_aux(C0, metric), None, None, 0
+        while it < max_iter and n_iter is None:
+            first = it
+            for _ in range(min(int(check_every), max_iter - it)):
+                st.step(C, D, c_aux, prev, it & 1, it)
+                C, c_aux, prev = st.centers[it & 1], st.c_aux[it & 1], st.assign[it & 1]
+                it += 1
+            ch = st.changed[first:it].cpu().numpy()
+            zero = np.nonzero(ch == 0)[0]
+            if len(zero):
+                n_iter = first + int(zero[0]) + 1
+        inertia = float(st.inertia.item())
+        res = {'centers': C, 'assign': prev, 'score': st.score, 'sizes': st.counts, 'inertia': inertia,
+               'n_iter': n_iter if n_iter is not None else it, 'converged': n_iter is not None,
+               'empty': int(st.empty.item()), 'c_aux': c_aux}
+        if best is None or (inertia > best['inertia'] if higher else inertia < best['inertia']):
+            best = res
+    return best
