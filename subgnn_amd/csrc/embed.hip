@@ -30,18 +30,25 @@ __global__ __launch_bounds__(256) void cc_embed_fwd_kernel(
             }
         } else {
             // PAD rows (zeros) take part in the max whenever the padded row is longer than the
-            // component (SubGNN.py:622); an empty row is all PAD.
+            // component (SubGNN.py:622); an empty row is all PAD.  x.max(dim) names the FIRST maximal entry and the
+            // padding stands behind the members: PAD joins after them, so a member that is exactly 0 keeps its
+            // gradient.  The first NaN stays, as torch.max keeps it (a diverged table must reach the loss).
             const bool with_pad = (n < padded_len) || (n == 0);
-            const float init = with_pad ? 0.f : -INFINITY;
-            acc = make_float4(init, init, init, init);
+            acc = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
 #pragma unroll 4
             for (int i = 0; i < n; ++i) {
                 const int32_t id = set_nodes[beg + i];
                 const float4 x = sgnn_load4<T>(E, (int64_t)id, D4, dv);
-                if (x.x > acc.x) { acc.x = x.x; arg.x = id; }
-                if (x.y > acc.y) { acc.y = x.y; arg.y = id; }
-                if (x.z > acc.z) { acc.z = x.z; arg.z = id; }
-                if (x.w > acc.w) { acc.w = x.w; arg.w = id; }
+                if (x.x > acc.x || (x.x != x.x && acc.x == acc.x)) { acc.x = x.x; arg.x = id; }
+                if (x.y > acc.y || (x.y != x.y && acc.y == acc.y)) { acc.y = x.y; arg.y = id; }
+                if (x.z > acc.z || (x.z != x.z && acc.z == acc.z)) { acc.z = x.z; arg.z = id; }
+                if (x.w > acc.w || (x.w != x.w && acc.w == acc.w)) { acc.w = x.w; arg.w = id; }
+            }
+            if (with_pad) {
+                if (0.f > acc.x) { acc.x = 0.f; arg.x = 0; }
+                if (0.f > acc.y) { acc.y = 0.f; arg.y = 0; }
+                if (0.f > acc.z) { acc.z = 0.f; arg.z = 0; }
+                if (0.f > acc.w) { acc.w = 0.f; arg.w = 0; }
             }
             if (out_arg) reinterpret_cast<int4*>(out_arg)[t] = arg;
         }

@@ -934,8 +934,8 @@ def test_clip_adam_fused_tail_replays_from_a_hipgraph():
 @pytest.mark.parametrize('D', [8, 64, 128, 200])
 def test_scatter_add_rows_sorted_matches_index_add_and_is_reproducible(D):
     """sgnn_scatter_add_rows_sorted against a float64 index_add: PAD keys, a hub target with thousands of
-    edges (a chain over hundreds of 64-edge runs), both coefficient terms, explicit and implicit source rows;
-    two runs give the same bits."""
+    edges (a chain over hundreds of 16-edge runs: 9100 edges are a batch-sized launch), both coefficient terms, explicit and
+    implicit source rows; two runs give the same bits.  tests/test_gpu_scatter.py holds the cases per launch form."""
     from subgnn_amd import ops
     g = torch.Generator().manual_seed(D)
     n_rows, R, A = 5000, 700, 13
