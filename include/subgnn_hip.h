@@ -479,6 +479,33 @@ int sgnn_triangular_walks_both(const int64_t* rowptr, const int32_t* col, const 
                                const int32_t* inb_nodes, int64_t n_items, int64_t walks_per_patch, int64_t walk_len,
                                double beta, uint64_t seed, uint64_t stream_id_int, uint64_t stream_id_bor,
                                int64_t item_base, int64_t max_id, int64_t* out, void* stream);
+/* The same walks by a workgroup-per-walk kernel that keeps NO bitmap over node ids (no id-range limit, a few KB of LDS per
+ * walk, several walks per CU).  Adjacency to the previous node: its neighbour list staged in LDS when it has fewer than 512
+ * entries; else bit hub_index[prev] of row w of the hub tables (hub_index / hub_bits / hub_words as for
+ * sgnn_degree_sequence_hub_bitmaps; both NULL: no tables); else a binary search in col_sorted.  kernel: 0 = this kernel,
+ * 1 = the wavefront-per-walk kernel.  variant: 0 = the launch rule -- launches of up to 256 walks (a CU for every walk) on a
+ * graph whose id bitmap fits LDS (max_id, the largest id; 0 = unknown) go to the bitmap kernel of sgnn_triangular_walks,
+ * which is faster there; all others to this kernel with 512 threads; 1 .. sgnn_triangular_walks_variants() - 1 = this
+ * kernel always, at 256 / 512 / 1024 threads with a 256-chunk ballot cache, 512 threads with 1024 chunks (same walks; for
+ * tests and measurements).  sgnn_triangular_walks_both_lists: the internal and the border walks in one launch, on every graph. */
+int sgnn_triangular_walks_variants(void);
+/* 1 = variant 0 sends a launch of n_walks walks (internal + border counted together) to the bitmap kernel: the caller need
+ * not have hub tables.  Tuned on the benchmark's hub-heavy graph. */
+int sgnn_triangular_walks_rule(int64_t n_walks, int64_t max_id);
+int sgnn_triangular_walks_lists(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
+                                const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
+                                const int32_t* node_order, int64_t n_nodes,
+                                const int64_t* patch_ptr, const int32_t* patch_nodes,
+                                const int64_t* inb_ptr, const int32_t* inb_nodes,
+                                int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta,
+                                uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t max_id, int kernel, int variant,
+                                int64_t* out, void* stream);
+int sgnn_triangular_walks_both_lists(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
+                                     const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
+                                     const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr,
+                                     const int32_t* inb_nodes, int64_t n_items, int64_t walks_per_patch, int64_t walk_len,
+                                     double beta, uint64_t seed, uint64_t stream_id_int, uint64_t stream_id_bor,
+                                     int64_t item_base, int64_t max_id, int variant, int64_t* out, void* stream);
 
 /* in-border nodes of a patch (subgraph_utils.get_border_nodes, subgraph_utils.py:126-144, with
  * its id-1 / node-order indexing quirk): out_flag[i] = 1 iff patch_nodes[i] is a border node.

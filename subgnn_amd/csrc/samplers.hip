@@ -481,13 +481,15 @@ __device__ static inline void wkb_bits(uint32_t* bm, const int32_t* __restrict__
     }
 }
 
-// workgroup-cooperative build of a membership hash; returns the longest probe chain (uniform)
+// workgroup-cooperative build of a membership hash by T threads; returns the longest probe chain (uniform).  s_red: a word of
+// the hash's OWN -- the result is read after the last barrier, so a second build must not reset the word of the first
+template <int T>
 __device__ static inline int wkb_build_hash(int32_t* h, const int32_t* a, int32_t n, int tid, int32_t* s_red) {
-    for (int i = tid; i < WK_HASH; i += WKB_THREADS) h[i] = 0;
+    for (int i = tid; i < WK_HASH; i += T) h[i] = 0;
     if (tid == 0) *s_red = 0;
     __syncthreads();
     int chain = 0;
-    for (int i = tid; i < n; i += WKB_THREADS) {
+    for (int i = tid; i < n; i += T) {
         const int32_t v = a[i];
         uint32_t b = sgnn_hash32((uint32_t)v) >> (32 - WK_HASH_BITS);
         int c = 0;
@@ -608,7 +610,7 @@ __global__ __launch_bounds__(WKB_THREADS) void triangular_walks_wg_kernel(
     extern __shared__ uint32_t s_adj[];                    // bitmap over node ids: N(prev)
     __shared__ uint64_t s_tri[WK_CHUNKS], s_non[WK_CHUNKS];
     __shared__ int32_t s_hp[WK_HASH], s_hi[WK_HASH];
-    __shared__ int32_t s_cnt[2], s_next, s_red;
+    __shared__ int32_t s_cnt[2], s_next, s_red[2];
     const int tid = threadIdx.x;
     for (int64_t i = tid; i < words; i += WKB_THREADS) s_adj[i] = 0;
     __syncthreads();
@@ -639,14 +641,14 @@ __global__ __launch_bounds__(WKB_THREADS) void triangular_walks_wg_kernel(
             c.patch = patch_nodes + patch_ptr[p];
             c.n_patch = (int32_t)(patch_ptr[p + 1] - patch_ptr[p]);
             if (c.n_patch == 0) continue;                                              // aps:134-135
-            if (c.n_patch <= WK_HASH_MAX) { c.pp = wkb_build_hash(s_hp, c.patch, c.n_patch, tid, &s_red); c.hpatch = s_hp; }
+            if (c.n_patch <= WK_HASH_MAX) { c.pp = wkb_build_hash<WKB_THREADS>(s_hp, c.patch, c.n_patch, tid, &s_red[0]); c.hpatch = s_hp; }
             if (mode == 1) {
                 prev = c.patch[sgnn_choice_index(h1, j++, (uint32_t)c.n_patch)];      // aps:70
             } else {
                 c.inb = inb_nodes + inb_ptr[p];
                 c.n_inb = (int32_t)(inb_ptr[p + 1] - inb_ptr[p]);
                 if (c.n_inb == 0) continue;        // reference raises ValueError here (aps:78)
-                if (c.n_inb <= WK_HASH_MAX) { c.pi = wkb_build_hash(s_hi, c.inb, c.n_inb, tid, &s_red); c.hinb = s_hi; }
+                if (c.n_inb <= WK_HASH_MAX) { c.pi = wkb_build_hash<WKB_THREADS>(s_hi, c.inb, c.n_inb, tid, &s_red[1]); c.hinb = s_hi; }
                 prev = c.inb[sgnn_choice_index(h1, j++, (uint32_t)c.n_inb)];          // aps:78
             }
         }
@@ -751,6 +753,373 @@ extern "C" int sgnn_triangular_walks_both(const int64_t* rowptr, const int32_t* 
                        sgnn_tape_h0(seed, stream_id_bor));
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Workgroup-per-walk kernel WITHOUT a bitmap over node ids: a walk owns a few KB of LDS, so several walks share a CU
+// (the bitmap kernel above: one walk per CU) and no pass over N(prev) sets or clears bits when the walk moves on.  "Is
+// candidate w adjacent to prev?" takes one of three forms, chosen per step by the length of N(prev):
+//   1  fewer than WKS_LIST_MAX entries: N(prev) lies in LDS as an open-addressing hash of WKS_SLOTS slots (at most half full;
+//      an empty slot ends a probe) -- the count pass of the step BEFORE entered it when prev was its `curr`, from the very
+//      entries it classified: no second fetch.  Three tables rotate: one is read, one is filled, one is emptied for the
+//      step after (the barriers the step has anyway separate the three uses)
+//   2  longer, and the graph has hub tables (DeviceGraph.hub_tables, the degree sequence's): bit hub_index[prev] of row w --
+//      one load per candidate, all candidates independent
+//   3  longer, no tables: binary search in the global col_sorted, as the wavefront kernel does
+// Same tape, same draws, same order of candidates, same early exits as the two kernels above: same walks.
+// T threads (T / 64 wavefronts share a neighbour list, chunks of 64 dealt round-robin, WKS_UNROLL chunks of a wavefront in
+// flight at once); CH chunks of cached ballots.
+// ---------------------------------------------------------------------------------------------
+#define WKS_LIST_MAX 512        // == DS_SEARCH (degree_sequence.hip): the lists that have a row in the hub tables are at least this long
+#define WKS_SLOTS 1024          // slots of a list's hash (2 * WKS_LIST_MAX: an empty slot always exists)
+#define WKS_UNROLL 4
+
+struct WksAdj {
+    int form;                   // 0: no previous node; 1 / 2 / 3: see above
+    int32_t n;                  // form 3: entries of N(prev)
+    const int32_t* lds;         // form 1: the hash of N(prev) in LDS
+    const int32_t* sorted;      // form 3: col_sorted + rowptr[prev]
+    const uint32_t* bits;       // form 2: hub_bits + (hub number >> 5); row w is W words further
+    int64_t W;
+    uint32_t bit;               // form 2: hub number & 31
+};
+
+__device__ static inline uint32_t wks_slot(int32_t v) { return sgnn_hash32((uint32_t)v) >> 22; }      // 32 - log2(WKS_SLOTS)
+
+__device__ static inline bool wks_in_list_hash(const int32_t* h, int32_t w) {
+    uint32_t b = wks_slot(w);
+    while (true) {
+        const int32_t x = h[b];
+        if (x == w) return true;
+        if (x == 0) return false;                          // ids are >= 1: 0 = empty
+        b = (b + 1) & (WKS_SLOTS - 1);
+    }
+}
+
+__device__ static inline void wks_list_hash_insert(int32_t* h, int32_t v) {
+    uint32_t b = wks_slot(v);
+    while (true) {
+        const int32_t old = atomicCAS(&h[b], 0, v);
+        if (old == 0 || old == v) break;
+        b = (b + 1) & (WKS_SLOTS - 1);
+    }
+}
+
+__device__ static inline bool wks_adjacent(const WksAdj& a, int32_t w) {
+    if (a.form == 2) return ((a.bits[(int64_t)w * a.W] >> a.bit) & 1u) != 0;
+    if (a.form == 1) return wks_in_list_hash(a.lds, w);
+    return sgnn_sorted_contains(a.sorted, a.n, w);
+}
+
+// how the NEXT step tests adjacency to v, whose row is [r0, r1), whose hub number is hub (-1: none) and whose list the
+// count pass entered into the hash `staged` if it is short
+__device__ static inline WksAdj wks_adj_of(const int32_t* col_sorted, int64_t r0, int64_t r1, int32_t hub, const uint32_t* hub_bits,
+                                           int64_t W, const int32_t* staged) {
+    WksAdj a;
+    a.n = (int32_t)(r1 - r0); a.lds = staged; a.sorted = col_sorted + r0; a.bits = nullptr; a.W = W; a.bit = 0;
+    if (r1 - r0 < WKS_LIST_MAX) a.form = 1;
+    else if (hub >= 0) { a.form = 2; a.bits = hub_bits + (hub >> 5); a.bit = (uint32_t)hub & 31u; }
+    else a.form = 3;
+    return a;
+}
+
+// pass 1 on the whole workgroup: classify the valid neighbours of the node whose row is [r0, r1), keep the per-chunk
+// ballots, enter the row into the hash `stage` when it is short (it is N(prev) of the next step) and empty `clear`, the
+// hash the step after fills
+template <int T, int CH>
+__device__ static inline void wks_count(const WalkCtx& c, int64_t r0, int64_t r1, const WksAdj& a, int32_t* stage, int32_t* clear,
+                                        int tid, int32_t& nt, int32_t& nn, uint64_t* s_tri, uint64_t* s_non, int32_t* s_cnt) {
+    constexpr int NW = T / 64, U = WKS_UNROLL;
+    const int lane = tid & 63, wave = tid >> 6;
+    const int64_t n_chunks = (r1 - r0 + 63) / 64;
+    const bool short_row = r1 - r0 < WKS_LIST_MAX;
+    for (int i = tid; i < WKS_SLOTS; i += T) clear[i] = 0;
+    int32_t lt = 0, ln = 0;
+    for (int64_t ch0 = wave; ch0 < n_chunks; ch0 += U * NW) {
+        // U independent loads of col[] in flight per wavefront: issued unconditionally (a lane past the row's end re-reads its
+        // first entry) and fenced, so that none is moved down to its first use behind a branch -- a list of thousands of
+        // entries costs U times fewer round trips
+        int32_t w[U];
+        bool ok[U], tri[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t e = r0 + (ch0 + u * NW) * 64 + lane;
+            ok[u] = e < r1;
+            w[u] = c.col[ok[u] ? e : r0];
+        }
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (short_row && ok[u]) wks_list_hash_insert(stage, w[u]);
+            ok[u] = ok[u] && walk_valid(c, w[u]);
+        }
+        if (a.form == 2) {                                  // and U independent loads of hub-table words (row 0 for a lane without a candidate)
+            uint32_t word[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) word[u] = a.bits[(int64_t)(ok[u] ? w[u] : 0) * a.W];
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int u = 0; u < U; ++u) tri[u] = ((word[u] >> a.bit) & 1u) != 0;
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; ++u) tri[u] = ok[u] && a.form && wks_adjacent(a, w[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t ch = ch0 + u * NW;
+            if (ch < n_chunks) {                            // wave-uniform
+                const uint64_t mt = __ballot(ok[u] && tri[u]), mn = __ballot(ok[u] && !tri[u]);
+                if (ch < CH && lane == 0) { s_tri[ch] = mt; s_non[ch] = mn; }
+                lt += __popcll(mt);
+                ln += __popcll(mn);
+            }
+        }
+    }
+    if (lane == 0) { s_cnt[2 * wave] = lt; s_cnt[2 * wave + 1] = ln; }
+    __syncthreads();
+    nt = 0; nn = 0;
+#pragma unroll
+    for (int k = 0; k < NW; ++k) { nt += s_cnt[2 * k]; nn += s_cnt[2 * k + 1]; }
+}
+
+// pass 2: the pick-th valid neighbour (adjacency order) in the wanted class of the row [r0, r1) -> *s_next
+template <int CH>
+__device__ static inline int32_t wks_pick(const WalkCtx& c, int64_t r0, int64_t r1, const WksAdj& a, bool want_tri, int32_t pick,
+                                          int tid, const uint64_t* s_tri, const uint64_t* s_non, int32_t* s_next) {
+    const int lane = tid & 63;
+    const int64_t n_chunks = (r1 - r0 + 63) / 64;
+    if (tid < 64) {
+        if (n_chunks <= CH) {
+            // lane l owns chunks [l*per, (l+1)*per): popcount them, scan over the wave, the owner of the crossing walks its chunks
+            const uint64_t* s = want_tri ? s_tri : s_non;
+            const int per = (int)((n_chunks + 63) / 64);
+            const int c0 = lane * per, c1 = (c0 + per < n_chunks) ? c0 + per : (int)n_chunks;
+            int32_t mine = 0;
+            for (int ch = c0; ch < c1; ++ch) mine += __popcll(s[ch]);
+            int32_t incl = mine;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) { const int32_t t = __shfl_up(incl, d); if (lane >= d) incl += t; }
+            const int32_t excl = incl - mine;
+            if (pick >= excl && pick < incl) {
+                int32_t seen = excl;
+                for (int ch = c0; ch < c1; ++ch) {
+                    uint64_t m = s[ch];
+                    const int32_t cnt = __popcll(m);
+                    if (seen + cnt > pick) {
+                        int k = pick - seen;
+                        while (k-- > 0) m &= m - 1;
+                        *s_next = c.col[r0 + (int64_t)ch * 64 + (__ffsll((unsigned long long)m) - 1)];
+                        break;
+                    }
+                    seen += cnt;
+                }
+            }
+        } else {
+            // list longer than the ballot cache: wavefront 0 re-classifies it in order
+            int32_t seen = 0, res = 0;
+            bool done = false;
+            for (int64_t base = r0; base < r1 && !done; base += 64) {
+                const int64_t e = base + lane;
+                bool hit = false;
+                int32_t w = 0;
+                if (e < r1) {
+                    w = c.col[e];
+                    if (walk_valid(c, w)) {
+                        const bool tri = a.form ? wks_adjacent(a, w) : false;
+                        hit = (tri == want_tri);
+                    }
+                }
+                const uint64_t m = __ballot(hit);
+                const int32_t cnt = __popcll(m);
+                if (seen + cnt > pick) {
+                    const int32_t rank = __popcll(m & ((1ull << lane) - 1ull));
+                    const uint64_t sel = __ballot(hit && (seen + rank == pick));
+                    res = __shfl(w, __ffsll((unsigned long long)sel) - 1);
+                    done = true;
+                }
+                seen += cnt;
+            }
+            if (lane == 0) *s_next = res;
+        }
+    }
+    __syncthreads();
+    return *s_next;
+}
+
+template <int T, int CH>
+__global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8))) void triangular_walks_lists_kernel(
+    const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ col_sorted,
+    const int32_t* __restrict__ hub_index, const uint32_t* __restrict__ hub_bits, int64_t hub_words,
+    const int32_t* __restrict__ node_order, int64_t n_nodes,
+    const int64_t* __restrict__ patch_ptr, const int32_t* __restrict__ patch_nodes,
+    const int64_t* __restrict__ inb_ptr, const int32_t* __restrict__ inb_nodes,
+    int mode_all, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta,
+    uint64_t h0_all, int64_t item_base, int64_t* __restrict__ out, uint64_t h0_border)
+{
+    __shared__ uint64_t s_tri[CH], s_non[CH];
+    __shared__ int32_t s_list[3][WKS_SLOTS];               // hashes of N(prev) (read), N(curr) (filled), and one being emptied
+    __shared__ int32_t s_hp[WK_HASH], s_hi[WK_HASH];
+    __shared__ int32_t s_cnt[2 * (T / 64)], s_next, s_red[2];
+    const int tid = threadIdx.x;
+    for (int64_t item_all = blockIdx.x; item_all < n_items; item_all += gridDim.x) {
+        int64_t* o = out + item_all * walk_len;
+        for (int64_t t = tid; t < walk_len; t += T) o[t] = 0;
+        // mode 3: the internal walks (items [0, n / 2): mode 1) and the border walks (items [n / 2, n): mode 2) of the same
+        // patches in ONE launch -- each side draws from its own tape stream under its own walk numbers, as two launches would
+        int mode = mode_all;
+        int64_t item = item_all;
+        uint64_t h0 = h0_all;
+        if (mode_all == 3) {
+            const int64_t half = n_items >> 1;
+            if (item_all >= half) { mode = 2; item = item_all - half; h0 = h0_border; } else mode = 1;
+        }
+        WalkCtx c;
+        c.rowptr = rowptr; c.col = col; c.col_sorted = col_sorted; c.mode = mode;
+        c.patch = nullptr; c.n_patch = 0; c.inb = nullptr; c.n_inb = 0;
+        c.hpatch = nullptr; c.hinb = nullptr; c.pp = 0; c.pi = 0;
+        const uint64_t h1 = sgnn_tape_h1(h0, (uint64_t)(item_base + item));   // the walk's GLOBAL number: a dealt share draws what the whole launch would
+        uint64_t j = 0;
+        int32_t prev;
+        __syncthreads();                            // previous item's LDS tables are no longer read
+        if (mode == 0) {
+            prev = node_order[sgnn_choice_index(h1, j++, (uint32_t)n_nodes)];          // aps:70
+        } else {
+            const int64_t p = item / walks_per_patch;
+            c.patch = patch_nodes + patch_ptr[p];
+            c.n_patch = (int32_t)(patch_ptr[p + 1] - patch_ptr[p]);
+            if (c.n_patch == 0) continue;                                              // aps:134-135
+            if (c.n_patch <= WK_HASH_MAX) { c.pp = wkb_build_hash<T>(s_hp, c.patch, c.n_patch, tid, &s_red[0]); c.hpatch = s_hp; }
+            if (mode == 1) {
+                prev = c.patch[sgnn_choice_index(h1, j++, (uint32_t)c.n_patch)];      // aps:70
+            } else {
+                c.inb = inb_nodes + inb_ptr[p];
+                c.n_inb = (int32_t)(inb_ptr[p + 1] - inb_ptr[p]);
+                if (c.n_inb == 0) continue;        // reference raises ValueError here (aps:78)
+                if (c.n_inb <= WK_HASH_MAX) { c.pi = wkb_build_hash<T>(s_hi, c.inb, c.n_inb, tid, &s_red[1]); c.hinb = s_hi; }
+                prev = c.inb[sgnn_choice_index(h1, j++, (uint32_t)c.n_inb)];          // aps:78
+            }
+        }
+        if (walk_len < 1) continue;
+        prev = __builtin_amdgcn_readfirstlane(prev);
+        for (int i = tid; i < WKS_SLOTS; i += T) s_list[0][i] = 0;      // the first hash to be filled
+        __syncthreads();                            // zero fill above precedes the thread-0 writes
+        if (tid == 0) o[0] = prev;
+        int64_t r0 = rowptr[prev], r1 = rowptr[prev + 1];
+        int32_t hub = hub_index ? hub_index[prev] : -1;
+        int buf = 0;
+        WksAdj a;
+        a.form = 0; a.n = 0; a.lds = nullptr; a.sorted = nullptr; a.bits = nullptr; a.W = 0; a.bit = 0;
+        int32_t nt, nn;
+        wks_count<T, CH>(c, r0, r1, a, s_list[0], s_list[1], tid, nt, nn, s_tri, s_non, s_cnt);   // aps:72,79
+        if (nn == 0 || walk_len < 2) continue;                                          // aps:83-84
+        int32_t curr = wks_pick<CH>(c, r0, r1, a, false, (int32_t)sgnn_choice_index(h1, j++, (uint32_t)nn), tid,
+                                    s_tri, s_non, &s_next);                              // aps:74,80
+        if (tid == 0) o[1] = curr;
+        for (int64_t step = 2; step < walk_len; ++step) {
+            // prev's list is in s_list[buf] if it is short; curr's goes into the next hash while it is counted, the third is emptied
+            a = wks_adj_of(col_sorted, r0, r1, hub, hub_bits, hub_words, s_list[buf]);
+            curr = __builtin_amdgcn_readfirstlane(curr);
+            r0 = rowptr[curr]; r1 = rowptr[curr + 1];
+            hub = hub_index ? hub_index[curr] : -1;
+            buf = buf == 2 ? 0 : buf + 1;
+            wks_count<T, CH>(c, r0, r1, a, s_list[buf], s_list[buf == 2 ? 0 : buf + 1], tid, nt, nn, s_tri, s_non, s_cnt);   // aps:35-45
+            if (nt + nn == 0) break;                                                     // aps:94
+            bool want_tri;
+            if (nt == 0) want_tri = false;                                               // aps:97-98
+            else if (nn == 0) want_tri = true;                                           // aps:99-100
+            else want_tri = (sgnn_uniform01(h1, j++) <= beta);                           // aps:102
+            const int32_t pick = (int32_t)sgnn_choice_index(h1, j++, (uint32_t)(want_tri ? nt : nn));
+            curr = wks_pick<CH>(c, r0, r1, a, want_tri, pick, tid, s_tri, s_non, &s_next);
+            if (tid == 0) o[step] = curr;
+        }
+    }
+}
+
+#define WKS_VARIANTS 5
+static int wks_launch(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, const int32_t* hub_index,
+                      const uint32_t* hub_bits, int64_t hub_words, const int32_t* node_order, int64_t n_nodes,
+                      const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr, const int32_t* inb_nodes,
+                      int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta, uint64_t h0,
+                      int64_t item_base, int64_t* out, uint64_t h0_border, int variant, hipStream_t stream)
+{
+    const dim3 grid((unsigned)(n_items < 0x7fffffff ? n_items : 0x7fffffff));       // one workgroup per walk
+#define WKS_GO(T, CH)                                                                                                         \
+    hipLaunchKernelGGL((triangular_walks_lists_kernel<T, CH>), grid, dim3(T), 0, stream, rowptr, col, col_sorted, hub_index,  \
+                       hub_bits, hub_words, node_order, n_nodes, patch_ptr, patch_nodes, inb_ptr, inb_nodes, mode, n_items,    \
+                       walks_per_patch, walk_len, beta, h0, item_base, out, h0_border)
+    switch (variant) {                              // 0 (the launch rule's choice) == 2
+    case 1: WKS_GO(256, 256); break;
+    case 3: WKS_GO(1024, 256); break;
+    case 4: WKS_GO(512, 1024); break;
+    default: WKS_GO(512, 256); break;
+    }
+#undef WKS_GO
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
+extern "C" int sgnn_triangular_walks_variants(void) { return WKS_VARIANTS; }
+
+// The launch rule (variant 0).  A launch of at most WKS_FEW_WALKS walks on a graph whose id bitmap fits LDS stays with the
+// bitmap kernel: every walk has a CU to itself there whatever the kernel, nothing waits for a free one, and the bitmap's
+// bit test in LDS beats a gathered hub-table word where walks sit among the hubs (the benchmark's 210 graph walks of 50:
+// 150 us against 234 - 346 us at 1024 - 256 threads, profiles/walks_probe.json).  More walks than that queue for CUs, and
+// the list kernel runs several per CU (2 x 1050 patch walks of 10: 264 -> 164 us).  Tuned on that one hub-heavy graph:
+// between 210 and 2100 walks, and on graphs without hubs: not measured.
+#define WKS_FEW_WALKS 256
+static bool wks_bitmap_kernel_wins(int variant, int64_t n_walks, int64_t max_id) {
+    return variant == 0 && n_walks <= WKS_FEW_WALKS && max_id > 0 && ((max_id + 32) / 32) * 4 <= WKB_LDS_BYTES;
+}
+// what variant 0 does with a launch of n_walks walks (both sides counted): 1 = the bitmap kernel (the hub tables are not read)
+extern "C" int sgnn_triangular_walks_rule(int64_t n_walks, int64_t max_id) { return wks_bitmap_kernel_wins(0, n_walks, max_id) ? 1 : 0; }
+
+extern "C" int sgnn_triangular_walks_lists(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
+                                           const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
+                                           const int32_t* node_order, int64_t n_nodes,
+                                           const int64_t* patch_ptr, const int32_t* patch_nodes,
+                                           const int64_t* inb_ptr, const int32_t* inb_nodes,
+                                           int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta,
+                                           uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t max_id, int kernel,
+                                           int variant, int64_t* out, void* stream)
+{
+    if (!rowptr || !col || !col_sorted || !out || n_items < 0 || walk_len < 0 || mode < 0 || mode > 2 || kernel < 0 || kernel > 1 || item_base < 0)
+        return SGNN_ERR_BAD_ARG;
+    if (variant < 0 || variant >= WKS_VARIANTS || (hub_index != nullptr) != (hub_bits != nullptr) || (hub_index && hub_words < 1))
+        return SGNN_ERR_BAD_ARG;
+    if (mode == 0 && (!node_order || n_nodes <= 0)) return SGNN_ERR_BAD_ARG;
+    if (mode >= 1 && (!patch_ptr || !patch_nodes || walks_per_patch <= 0)) return SGNN_ERR_BAD_ARG;
+    if (mode == 2 && (!inb_ptr || !inb_nodes)) return SGNN_ERR_BAD_ARG;
+    if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
+    if (n_items == 0 || walk_len == 0) return SGNN_OK;
+    if (kernel == 1 || wks_bitmap_kernel_wins(variant, n_items, max_id))
+        return sgnn_triangular_walks(rowptr, col, col_sorted, nnz, node_order, n_nodes, patch_ptr, patch_nodes, inb_ptr, inb_nodes, mode,
+                                     n_items, walks_per_patch, walk_len, beta, seed, stream_id, item_base, kernel == 1 ? 0 : max_id,
+                                     kernel, out, stream);
+    return wks_launch(rowptr, col, col_sorted, hub_index, hub_bits, hub_words, node_order, n_nodes, patch_ptr, patch_nodes, inb_ptr,
+                      inb_nodes, mode, n_items, walks_per_patch, walk_len, beta, sgnn_tape_h0(seed, stream_id), item_base, out,
+                      (uint64_t)0, variant, (hipStream_t)stream);
+}
+
+extern "C" int sgnn_triangular_walks_both_lists(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
+                                                const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
+                                                const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr,
+                                                const int32_t* inb_nodes, int64_t n_items, int64_t walks_per_patch, int64_t walk_len,
+                                                double beta, uint64_t seed, uint64_t stream_id_int, uint64_t stream_id_bor,
+                                                int64_t item_base, int64_t max_id, int variant, int64_t* out, void* stream)
+{
+    if (!rowptr || !col || !col_sorted || !out || !patch_ptr || !patch_nodes || !inb_ptr || !inb_nodes || n_items < 0 || walk_len < 0
+        || walks_per_patch <= 0 || item_base < 0)
+        return SGNN_ERR_BAD_ARG;
+    if (variant < 0 || variant >= WKS_VARIANTS || (hub_index != nullptr) != (hub_bits != nullptr) || (hub_index && hub_words < 1))
+        return SGNN_ERR_BAD_ARG;
+    if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
+    if (n_items == 0 || walk_len == 0) return SGNN_OK;
+    if (wks_bitmap_kernel_wins(variant, 2 * n_items, max_id))
+        return sgnn_triangular_walks_both(rowptr, col, col_sorted, nnz, patch_ptr, patch_nodes, inb_ptr, inb_nodes, n_items, walks_per_patch,
+                                          walk_len, beta, seed, stream_id_int, stream_id_bor, item_base, max_id, out, stream);
+    return wks_launch(rowptr, col, col_sorted, hub_index, hub_bits, hub_words, nullptr, 0, patch_ptr, patch_nodes, inb_ptr, inb_nodes, 3,
+                      2 * n_items, walks_per_patch, walk_len, beta, sgnn_tape_h0(seed, stream_id_int), item_base, out,
+                      sgnn_tape_h0(seed, stream_id_bor), variant, (hipStream_t)stream);
 }
 
 SGNN_DEFINE_WARM(samplers)

@@ -79,7 +79,6 @@ def _hand_over(stream, *objs):
 
 
 BFS_LEVEL_MARGIN = 2
-WALKS_ON_SIDE_MAX_SETS = 16384      # component rows up to which the structure walks run on the side stream ahead of the position search
 
 
 def _bfs_levels(model, key, max_hops):
@@ -519,7 +518,7 @@ def _structure_walks(cx):
         int_w = st.attrs['int_structure_anchor_random_walks'] = walks[:, 1].contiguous()
     elif cx.new_patches:
         views = aps.patch_node_views(structure_anchors)
-        # (internal and border walks in ONE launch: 1050 + 1050 one-workgroup-per-CU walks fill the chip's rounds better)
+        # (internal and border walks in ONE launch: 1050 + 1050 walks, four 512-thread workgroups to a CU, fill the chip better)
         int_w, bor_w = aps.perform_random_walks_both(hp, g, structure_anchors, views)
         st.attrs['bor_structure_anchor_random_walks'], st.attrs['int_structure_anchor_random_walks'] = bor_w, int_w
     if pool is not None:
@@ -674,16 +673,17 @@ def prepare_pass(model, split='train', timer=None, shard=None, defer_dtw=False, 
     t.mark('start')
     # ---- components (main) ---------------------------------------------------------------
     _components(cx)
-    # Where the walks run (decided here, not above: by the number of component rows).  For shards of up to
-    # WALKS_ON_SIDE_MAX_SETS component rows (round 6): on the SIDE stream, right behind the patches and AHEAD of the position
-    # search.  Nothing on the main chain reads the walks -- the DTW launches read the patches' degree sequences only -- so they leave it; and they no longer run BESIDE the search: a walk is one
-    # 1024-thread workgroup around a 125 KB LDS bitmap, it needs 16 free wavefront slots on one CU at once, and the search's
-    # small workgroups kept every CU's slots busy -- at 6 250 subgraphs the walks' stage took 1.3-1.45 ms on the main chain
-    # for 0.27 ms of kernel: the pass 3.08 -> 2.79 ms (same box, back to back).  At the benchmark's 50k subgraphs the main
-    # chain is the long one either way and the walks hide better there (8.82 vs 8.87 ms pipelined, 9.31 vs 9.60 sequential):
-    # they stay on the main chain, as rounds 3-5 had them.  hparams['walks_on_side_stream'] = True / False forces either.
-    wos = hp.get('walks_on_side_stream')            # None: by size; True / False: forced
-    walks_on_side = (bool(wos) if wos is not None else cx.cc_sets.n <= WALKS_ON_SIDE_MAX_SETS) and two and structure
+    # Where the walks run: on the SIDE stream, right behind the patches and AHEAD of the position search, at every size.
+    # Nothing on the main chain reads the walks -- the DTW launches read the patches' degree sequences only -- so they leave
+    # it.  Round 6 did this for shards of up to 16 384 component rows only, and kept the walks of the benchmark's 50k subgraphs
+    # on the main chain: a walk was one 1024-thread workgroup around a 125 KB LDS bitmap then, which needs 16 free wavefront
+    # slots on one CU at once, and at 50k the main chain hid that wait better (8.82 vs 8.87 ms pipelined).  The patch walks now
+    # run on the list kernel (512-thread workgroups with 18 KB of LDS, four to a CU) and the reason is gone -- re-measured
+    # with hparams['walks_on_side_stream'] forced True / False in fresh alternating bench.py processes
+    # (profiles/walks_probe.json): 50k subgraphs 6.41, 6.43 ms on the side stream against 6.57, 6.68 on the main chain;
+    # 6 250 subgraphs 2.16-2.20 against 2.20-2.22.  hparams['walks_on_side_stream'] = True / False still forces either.
+    wos = hp.get('walks_on_side_stream')            # None: the side stream; True / False: forced
+    walks_on_side = (bool(wos) if wos is not None else True) and two and structure
     # ---- side stream: structure patches, position channel (+ the walks, see above) ------------
     side.wait_stream(main)
     if two and cx.keep_facts and cx.rec.cc_ids is not None:

@@ -285,6 +285,11 @@ class DeviceGraph:
                 # (no id twice in a row -- simple_rows -- so the bits of a word are distinct powers of two: their sum is their OR)
                 words.index_add_(0, x * W + (owner >> 5), torch.ones_like(owner) << (owner & 31))
                 out = (hub_index, words.to(torch.int32).view(rows_n, W).contiguous(), W)
+                # The tables are handed to callers on ANY stream from here on (the walks of a pass run on the side stream, the
+                # degree sequences on the main one) with no event between them: the stream that built them is drained once,
+                # here, before they are published (a host wait of the first use per graph, next to the hub count's above).
+                if words.is_cuda:
+                    torch.cuda.current_stream(words.device).synchronize()
         self.__dict__['_hub_tables'] = out
         return out
 
@@ -304,6 +309,8 @@ class DeviceGraph:
             z = ((sl.to(torch.int64) << 24) | torch.where(hub[0] >= 0, hub[0], torch.full_like(hub[0], 0xffffff)).to(torch.int64)).to(torch.int32)
             full = self.full_degree if self.full_degree is not None else deg + sl
             out = torch.stack([self.rowptr[:-1].to(torch.int32), deg, z, full.to(torch.int32)], 1).contiguous()
+            if out.is_cuda:                              # published to every stream, like the hub tables: drained once
+                torch.cuda.current_stream(out.device).synchronize()
         self.__dict__['_node_records'] = out
         return out
 
@@ -1091,40 +1098,51 @@ def draw_border_anchors_keyed(borders, hops, keys, row_has_pad, n_slots, seed, s
     return anchor, sims
 
 
+def _walk_hub_args(g, hub_tables, n_walks, variant):
+    """(hub_index, hub_bits, W) pointers of the walk kernel's adjacency test against long lists, or (None, None, 0) -- also for
+    a launch the rule (variant 0) sends to the bitmap kernel, which does not read them: such a launch builds no tables."""
+    if not hub_tables or not hasattr(g, 'hub_tables'):
+        return None, None, 0
+    if int(variant) == 0 and _lib.load().sgnn_triangular_walks_rule(int(n_walks), g.max_id):
+        return None, None, 0
+    hub = g.hub_tables()
+    return (_ptr(hub[0]), _ptr(hub[1]), int(hub[2])) if hub is not None else (None, None, 0)
+
+
 def triangular_walks(g, mode, n_items, walk_len, beta, seed, stream_id, patches=None, in_border=None,
-                     walks_per_patch=1, kernel=0, item_base=0):
+                     walks_per_patch=1, kernel=0, item_base=0, hub_tables=True, variant=0):
     """mode 0 'graph' / 1 'inside' / 2 'border' -> (n_items, walk_len) int64, PAD filled.
-    kernel: 0 = pick by graph size, 1 = the wavefront-per-walk kernel (same walks).
-    item_base: global number of this call's first walk (a share of a larger launch: same draws)."""
+    kernel: 0 = a workgroup per walk (variant 0: up to 256 walks on a graph whose id bitmap fits LDS run on the bitmap kernel,
+    a walk per CU; more walks, or larger graphs, on the list kernel, several walks per CU -- adjacency to the previous node:
+    its list in LDS, its bit of the graph's hub tables, or a search), 1 = the wavefront-per-walk kernel (same walks).
+    item_base: global number of this call's first walk (a share of a larger launch: same draws).
+    hub_tables = False: long lists are searched even where the graph has the tables; variant >= 1: the list kernel always, at
+    the launch shapes sgnn_triangular_walks_lists knows (same walks -- both for tests and measurements)."""
     lib = _lib.load()
     out = torch.empty((n_items, walk_len), dtype=torch.int64, device=g.device)
-    check(lib.sgnn_triangular_walks(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, _ptr(g.node_order),
-                                    g.n_nodes, _ptr(patches.ptr) if patches else None,
-                                    _ptr(patches.nodes) if patches else None,
-                                    _ptr(in_border.ptr) if in_border else None,
-                                    _ptr(in_border.nodes) if in_border else None,
-                                    mode, n_items, walks_per_patch, walk_len, float(beta), seed, stream_id, int(item_base),
-                                    g.max_id, int(kernel), _ptr(out), _stream()), 'sgnn_triangular_walks')
+    hi, hb, hw = _walk_hub_args(g, hub_tables and int(kernel) == 0, n_items, variant)
+    check(lib.sgnn_triangular_walks_lists(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, hi, hb, hw, _ptr(g.node_order),
+                                          g.n_nodes, _ptr(patches.ptr) if patches else None,
+                                          _ptr(patches.nodes) if patches else None,
+                                          _ptr(in_border.ptr) if in_border else None,
+                                          _ptr(in_border.nodes) if in_border else None,
+                                          mode, n_items, walks_per_patch, walk_len, float(beta), seed, stream_id, int(item_base),
+                                          g.max_id, int(kernel), int(variant), _ptr(out), _stream()), 'sgnn_triangular_walks_lists')
     return out
 
 
 def triangular_walks_both(g, n_items, walk_len, beta, seed, stream_id_int, stream_id_bor, patches, in_border, walks_per_patch,
-                          item_base=0):
+                          item_base=0, hub_tables=True, variant=0):
     """The internal and the border walks over the same patches in ONE launch -> (2, n_items, walk_len) int64, [0] internal,
-    [1] border: what triangular_walks(mode 1) and triangular_walks(mode 2) return.  Falls back to those two calls where the
-    graph's id bitmap does not fit LDS."""
+    [1] border: what triangular_walks(mode 1) and triangular_walks(mode 2) return, on every graph."""
     lib = _lib.load()
     out = torch.empty((2, n_items, walk_len), dtype=torch.int64, device=g.device)
-    rc = lib.sgnn_triangular_walks_both(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, _ptr(patches.ptr), _ptr(patches.nodes),
-                                        _ptr(in_border.ptr), _ptr(in_border.nodes), n_items, walks_per_patch, walk_len, float(beta),
-                                        seed, stream_id_int, stream_id_bor, int(item_base), g.max_id, _ptr(out), _stream())
-    if rc == -2:                                                        # SGNN_ERR_SET_TOO_LARGE: no LDS bitmap for this graph
-        out[0] = triangular_walks(g, 1, n_items, walk_len, beta, seed, stream_id_int, patches=patches,
-                                  walks_per_patch=walks_per_patch, item_base=item_base)
-        out[1] = triangular_walks(g, 2, n_items, walk_len, beta, seed, stream_id_bor, patches=patches, in_border=in_border,
-                                  walks_per_patch=walks_per_patch, item_base=item_base)
-        return out
-    check(rc, 'sgnn_triangular_walks_both')
+    hi, hb, hw = _walk_hub_args(g, hub_tables, 2 * n_items, variant)
+    check(lib.sgnn_triangular_walks_both_lists(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, hi, hb, hw, _ptr(patches.ptr),
+                                               _ptr(patches.nodes), _ptr(in_border.ptr), _ptr(in_border.nodes), n_items,
+                                               walks_per_patch, walk_len, float(beta), seed, stream_id_int, stream_id_bor,
+                                               int(item_base), g.max_id, int(variant), _ptr(out), _stream()),
+          'sgnn_triangular_walks_both_lists')
     return out
 
 
