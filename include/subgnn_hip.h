@@ -976,6 +976,34 @@ int sgnn_bce_logits_fwd_weighted(const float* logits, const int64_t* targets, in
 int sgnn_bce_logits_bwd_weighted(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K,
                                  float* grad_logits, void* stream, const float* weight, const float* pos_weight);
 
+/* Shaped losses: label smoothing and focal loss on the two pairs above.  The argument lists are those of the _weighted entries
+ * plus `float label_smoothing, float focal_gamma` (the bce entries: focal_gamma only).  With both 0 the call IS the _weighted
+ * entry (and with null rows the bare one).  label_smoothing outside [0, 1), a negative or non-finite focal_gamma, or both
+ * non-zero: SGNN_ERR_BAD_ARG before any launch, nothing is written.  Otherwise kernels of their own run; an absent weight row
+ * stands as ones.  With w the class weights (W their sum), p = softmax(x_i), y the label, D = sum_i w[y_i] over counted rows:
+ *   smoothing eps  (F.cross_entropy(weight=, label_smoothing=), mean)
+ *                  loss = sum_i [(1 - eps) w_y (lse_i - x_iy) + (eps / K) sum_k w_k (lse_i - x_ik)] / D;
+ *                  grad_logits[i, k] = [(1 - eps) w_y (p_k - [k == y]) + (eps / K) (W p_k - w_k)] grad_loss[0] / D
+ *   focal gamma    lp = x_iy - lse_i, p_t = exp(lp), q = -expm1(lp): loss = sum_i w_y q^gamma (-lp) / D;
+ *                  grad_logits[i, k] = w_y f_i (p_k - [k == y]) grad_loss[0] / D, f_i = q^gamma - gamma p_t q^(gamma - 1) lp;
+ *                  a row with q = 0 has loss and f_i exactly 0
+ *   focal gamma, multi-label   s = +1 for a target, -1 otherwise, z = s x, e = exp(-|z|), l = log1p(e) + max(-z, 0),
+ *                  q = sigmoid(-z), p_t = sigmoid(z) (both from e), c = weight_k, L = pos_weight_k for a target, else 1:
+ *                  element loss c L q^gamma l, mean over B K; grad_logits = -s c L q^gamma (q + gamma p_t l) grad_loss[0] / (B K)
+ * lse[B] stays the divisor D; labels of -100 are ignored and any other label outside [0, K) makes the loss NaN, as before;
+ * the accuracy is unweighted and unchanged.  Workspaces, partials and summation orders are the bare entries': bit-reproducible. */
+int sgnn_cross_entropy_fwd_shaped(const float* logits, const int64_t* labels, int64_t B, int64_t K, float* lse, float* loss,
+                                  float* accuracy, void* workspace, int64_t workspace_bytes, void* stream,
+                                  const float* class_weight, float label_smoothing, float focal_gamma);
+int sgnn_cross_entropy_bwd_shaped(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss,
+                                  int64_t B, int64_t K, float* grad_logits, void* stream, const float* class_weight,
+                                  float label_smoothing, float focal_gamma);
+int sgnn_bce_logits_fwd_shaped(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
+                               void* workspace, int64_t workspace_bytes, void* stream, const float* weight,
+                               const float* pos_weight, float focal_gamma);
+int sgnn_bce_logits_bwd_shaped(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K,
+                               float* grad_logits, void* stream, const float* weight, const float* pos_weight, float focal_gamma);
+
 /* Column sums of a row-major matrix x (R rows of A floats, row stride ld): out[a] = sum_r x[r, a] -- the bias gradients of the
  * head's Linear layers over a shard's rows (autograd of SubGNN/SubGNN.py:304-312).  Row-block partials added in block order:
  * bit-reproducible.  workspace: sgnn_column_sum_workspace_bytes. */
@@ -1239,6 +1267,30 @@ int sgnn_head_bwd_ml_weighted(const float* logits, const int64_t* targets, const
                               const float* rows, const float* a1, const float* a2, const float* W2, const float* W3, int64_t B,
                               int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream,
                               const float* weight, const float* pos_weight);
+
+/* The head's four launches with a shaped loss (label smoothing / focal loss; semantics as stated at
+ * sgnn_cross_entropy_fwd_shaped).  The argument lists are those of the four _weighted entries plus `float label_smoothing, float
+ * focal_gamma` (the _ml entries: focal_gamma only).  With both 0 -- or without labels / grad_loss -- the call IS the _weighted entry;
+ * a value outside its domain or both non-zero: SGNN_ERR_BAD_ARG before any launch.  Otherwise kernels of their own run, with the
+ * weight rows in LDS (an absent row stands as ones) and {label_smoothing, focal_gamma} passed by value, so a recorded step replays
+ * them.  The backward recomputes what it needs from logits and lse: nothing more is saved.  out[2] = lse[B] stays the divisor;
+ * accuracy, logits, saved activations, dropout masks and the {seed, step} state do not depend on the loss mode. */
+int sgnn_head_fwd_shaped(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                         const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1, float* a2,
+                         float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream,
+                         const float* class_weight, float label_smoothing, float focal_gamma);
+int sgnn_head_bwd_shaped(const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,
+                         const float* grad_logits, const float* rows, const float* a1, const float* a2, const float* W2,
+                         const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial,
+                         void* stream, const float* class_weight, float label_smoothing, float focal_gamma);
+int sgnn_head_fwd_ml_shaped(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                            const float* W3, const float* b3, const int64_t* targets, float p, int64_t* rng, float* a1,
+                            float* a2, float* logits, float* out, void* workspace, int64_t workspace_bytes, void* stream,
+                            const float* weight, const float* pos_weight, float focal_gamma);
+int sgnn_head_bwd_ml_shaped(const float* logits, const int64_t* targets, const float* grad_loss, const float* grad_logits,
+                            const float* rows, const float* a1, const float* a2, const float* W2, const float* W3, int64_t B,
+                            int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream,
+                            const float* weight, const float* pos_weight, float focal_gamma);
 
 /* A^T B for tall operands (the weight gradients of Linear / LSTM layers: outputs of a few thousand elements contracted over
  * thousands of rows -- a library GEMM runs them on a handful of workgroups): job k contracts A[k] (R[k], M[k]) with B[k]

@@ -167,7 +167,10 @@ class SubGNN(nn.Module):
         # hparams['class_weight'] / ['pos_weight'] (None, K numbers, {label: number} or 'balanced' from the training split):
         # the module carries them as non-persistent buffers, so the kernels of a training step, the library path and the
         # validation loss all apply the same weights and the state_dict keeps its keys
-        self.loss = loss_weights.make_loss(self.multilabel, *self._loss_weights())
+        # hparams['label_smoothing'] / ['focal_gamma'] (default 0.0; they exclude each other, smoothing is single-label only): a
+        # loss_weights.ShapedLoss carrying the same rows; with both 0 the nn module it always was
+        self.loss = loss_weights.make_loss(self.multilabel, *self._loss_weights(), label_smoothing=hp.get('label_smoothing', 0.0),
+                                           focal_gamma=hp.get('focal_gamma', 0.0))
         loss_weights.refuse_multi_rank(self.loss)
         self.lstm = LSTM(D, D, dropout=hp['lstm_dropout'], num_layers=hp['lstm_n_layers'],
                          aggregator=hp['lstm_aggregator'])
@@ -910,7 +913,7 @@ class SubGNN(nn.Module):
         hp = self.hparams
         labels = self.__dict__.pop('_head_labels', None)
         targets = self.__dict__.pop('_head_targets', None)
-        class_weight, pos_weight = self.__dict__.pop('_head_weights', None) or (None, None)
+        class_weight, pos_weight, smoothing, gamma = self.__dict__.pop('_head_weights', None) or (None, None, 0.0, 0.0)
         x = subgraph_embedding
         keep = self.__dict__.get('_head_inputs')        # (predict.Predictor: the subgraph embeddings of a request, per chunk)
         if keep is not None:
@@ -926,8 +929,10 @@ class SubGNN(nn.Module):
                 targets = None
             if labels is None and targets is None:
                 class_weight = pos_weight = None
+                smoothing = gamma = 0.0
             logits, loss, acc = ops.fused_head(x, self.lin, self.lin2, self.lin3, labels, p, self._dropout_rng() if p > 0 else None,
-                                               targets=targets, class_weight=class_weight, pos_weight=pos_weight)
+                                               targets=targets, class_weight=class_weight, pos_weight=pos_weight,
+                                               label_smoothing=smoothing, focal_gamma=gamma)
             if labels is not None or targets is not None:
                 self.__dict__['_head_result'] = (loss, acc)
             return logits
@@ -968,10 +973,11 @@ class SubGNN(nn.Module):
 
     def training_step(self, train_batch, batch_idx):
         labels = train_batch['label'].squeeze(-1)
-        # what the loss kernels can compute of self.loss (loss_weights.kernel_plan): its weight rows, (None, None) for a bare
-        # module -- or None: a module with another reduction / ignore_index / label_smoothing, a subclass, or weights of another
-        # shape, dtype or device go through the library.  Weights the user assigned to self.loss count like the hyper-parameters'.
-        plan = loss_weights.kernel_plan(self.loss, self.multilabel, self.lin3.out_features, labels.device) \
+        # what the loss kernels can compute of self.loss (loss_weights.plan): its weight rows ((None, None) for a bare module) and
+        # the (label_smoothing, focal_gamma) of a loss_weights.ShapedLoss -- or None: an nn module with another reduction /
+        # ignore_index / label_smoothing, a subclass, or weights of another shape, dtype or device go through the library.  A
+        # module the user assigned to self.loss counts like the hyper-parameters'.
+        plan = loss_weights.plan(self.loss, self.multilabel, self.lin3.out_features, labels.device) \
             if self.hparams.get('fused_forward', True) else None
         fusable = plan is not None and not self.multilabel and labels.is_cuda and labels.dim() == 1
         # multi-label (HPO-NEURO): BCE with logits + exact-match accuracy in the head's launch too, straight from the int64 (B, K)
@@ -997,13 +1003,13 @@ class SubGNN(nn.Module):
             return {'loss': loss, 'log': {'train_loss': loss, 'train_acc': acc}}
         if fusable_ml and logits.is_cuda and logits.dtype == torch.float32 and logits.shape == labels.shape:
             # a head the fused kernel does not take (widths above 128, K above 32, fused_head: false): one pass over the logits
-            loss, acc = ops.bce_with_logits_and_accuracy(logits, labels, weight=plan[0], pos_weight=plan[1])
+            loss, acc = ops.bce_with_logits_and_accuracy(logits, labels, weight=plan[0], pos_weight=plan[1], focal_gamma=plan[3])
             return {'loss': loss, 'log': {'train_loss': loss, 'train_acc': acc}}
         if not self.multilabel and logits.is_cuda and logits.dim() == 2 and labels.dim() == 1 and logits.dtype == torch.float32 \
                 and plan is not None:
             # cross entropy + accuracy in one pass over the logits (ops.cross_entropy_with_accuracy): the library's nll
             # reduction runs on one workgroup (48 us at 50k rows) and the pair is 12 launches
-            loss, acc = ops.cross_entropy_with_accuracy(logits, labels, weight=plan[0])
+            loss, acc = ops.cross_entropy_with_accuracy(logits, labels, weight=plan[0], label_smoothing=plan[2], focal_gamma=plan[3])
             return {'loss': loss, 'log': {'train_loss': loss, 'train_acc': acc}}
         loss, labels = self._loss(logits, labels)
         acc = subgraph_utils.calc_accuracy(logits, labels, multilabel_binarizer=self.multilabel_binarizer)

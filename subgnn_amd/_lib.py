@@ -182,6 +182,12 @@ SIGNATURES = {
     'sgnn_cross_entropy_bwd_weighted': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
     'sgnn_bce_logits_fwd_weighted': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     'sgnn_bce_logits_bwd_weighted': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    # the shaped forms (label smoothing / focal loss): the weighted lists + float label_smoothing, float focal_gamma (bce: gamma only)
+    'sgnn_cross_entropy_fwd_shaped': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, ctypes.c_float,
+                                              ctypes.c_float]),
+    'sgnn_cross_entropy_bwd_shaped': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, ctypes.c_float, ctypes.c_float]),
+    'sgnn_bce_logits_fwd_shaped': (c_int, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, ctypes.c_float]),
+    'sgnn_bce_logits_bwd_shaped': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float]),
     'sgnn_column_sum_workspace_bytes': (c_i64, [c_i64, c_i64]),
     'sgnn_column_sum': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_i64, c_ptr]),
     'sgnn_gather_rows_many_max': (c_i64, []),
@@ -216,6 +222,14 @@ SIGNATURES = {
                                           c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr]),
     'sgnn_head_bwd_ml_weighted': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64,
                                           ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sgnn_head_fwd_shaped': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float, c_ptr, c_ptr,
+                                     c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, ctypes.c_float, ctypes.c_float]),
+    'sgnn_head_bwd_shaped': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64,
+                                     ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float, ctypes.c_float]),
+    'sgnn_head_fwd_ml_shaped': (c_int, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float, c_ptr, c_ptr,
+                                        c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, ctypes.c_float]),
+    'sgnn_head_bwd_ml_shaped': (c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64,
+                                        ctypes.c_float, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, ctypes.c_float]),
     'sgnn_contract_rows_max_jobs': (c_i64, []),
     'sgnn_contract_rows_blocks': (c_i64, [c_i64, c_i64, c_i64]),
     'sgnn_contract_rows_partial': (c_int, [c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),

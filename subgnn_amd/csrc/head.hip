@@ -36,6 +36,13 @@
 // 1.0 reproduce the bare launch bit for bit); w[y] is read only for y in [0, K).  Multi-label: the element loss is
 // c_k [(1 - y) x + L (log1p(exp(-|x|)) + max(-x, 0))] with L = 1 + (p_k - 1) y, its gradient c_k [(1 - y) - L sigmoid(-x)] g / (B K);
 // out[2] stays B K.  The accuracy is unweighted in both modes, and the dropout masks do not depend on the mode.
+//
+// Shaped losses (label smoothing, focal loss: DESIGN 8p): one more compile-time axis SH on the same two bodies -- 0: as above, 1:
+// label smoothing eps (single-label), 2: focal gamma -- again kernels of their own (heads_fwd_kernel<ML, SH>, heads_bwd_kernel<NB, ML,
+// SH>) that always take the weight rows (an absent row stands as ones, as with WT = 1) and a by-value HeadShape {eps, gamma}: a
+// recorded step replays them.  The formulas are those stated in csrc/loss.hip; the backward recomputes p_t, f and q^gamma from the
+// logits and lse (nothing more is saved), smoothing adds W = sum_j w_j once per workgroup from the LDS rows.  out[2] / lse[B] stay the
+// divisor, the partials, the ticket and the summation orders are unchanged.
 #include "common.h"
 
 #define HEAD_RB 32
@@ -53,6 +60,7 @@ struct HeadFwd {
 };
 
 struct HeadWeights { const float* w; const float* pw; };     // the weighted launches' class weight rows (either nullable)
+struct HeadShape { float eps, gamma; };                      // the shaped launches': label smoothing | focal exponent (SH picks one)
 
 struct HeadBwd {
     const float* logits; const float* lse; const int64_t* labels; const float* g_loss; const float* g_logits; const float* rows;
@@ -87,8 +95,11 @@ __device__ __forceinline__ float head_sigmoid(float x)
     return e / (1.f + e);
 }
 
-template <int ML, int WT>
-__device__ __forceinline__ void head_fwd_body(const HeadFwd A, const HeadWeights Wt)
+// q^gamma of the focal losses, q in [0, 1]: exactly 0 at q = 0
+__device__ __forceinline__ float head_qpow(float q, float gamma) { return q > 0.f ? powf(q, gamma) : 0.f; }
+
+template <int ML, int WT, int SH = 0>
+__device__ __forceinline__ void head_fwd_body(const HeadFwd A, const HeadWeights Wt, const HeadShape Sp = HeadShape{0.f, 0.f})
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H1 = A.H1, H2 = A.H2, K = A.K, tid = threadIdx.x;
@@ -190,7 +201,10 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwd A, const HeadWeights
                 for (int k = 0; k < K; ++k) {
                     const float v = x[k];
                     const bool t = y[k] != 0;
-                    if (WT) l += wts[k] * ((t ? 0.f : v) + (t ? wts[K + k] : 1.f) * (log1pf(expf(-fabsf(v))) + fmaxf(-v, 0.f)));
+                    if (SH == 2) {
+                        const float z = t ? v : -v, e = expf(-fabsf(v)), inv = 1.f / (1.f + e);
+                        l += wts[k] * (t ? wts[K + k] : 1.f) * head_qpow(z >= 0.f ? e * inv : inv, Sp.gamma) * (log1pf(e) + fmaxf(-z, 0.f));
+                    } else if (WT) l += wts[k] * ((t ? 0.f : v) + (t ? wts[K + k] : 1.f) * (log1pf(expf(-fabsf(v))) + fmaxf(-v, 0.f)));
                     else l += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
                     all = all && ((1.f / (1.f + expf(-v)) > 0.5f) == t);           // torch.sigmoid(x) > 0.5 in float32
                 }
@@ -208,7 +222,14 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwd A, const HeadWeights
             const int64_t y = A.labels[row0 + tid];
             if (y >= 0 && y < K) {
                 const float wy = WT ? wts[y] : 1.f;
-                if (WT) loss += wy * (l - x[y]); else loss += l - x[y];
+                if (SH == 1) {
+                    float s = 0.f;
+                    for (int k = 0; k < K; ++k) s += wts[k] * (l - x[k]);
+                    loss += (1.f - Sp.eps) * wy * (l - x[y]) + (Sp.eps / (float)K) * s;
+                } else if (SH == 2) {
+                    const float lp = x[y] - l;
+                    loss += wy * head_qpow(fmaxf(-expm1f(lp), 0.f), Sp.gamma) * (-lp);
+                } else if (WT) loss += wy * (l - x[y]); else loss += l - x[y];
                 hit += (am == (int)y) ? 1.f : 0.f; cnt += wy;
             }
             else if (y != -100ll) { loss = __builtin_nanf(""); cnt += 1.f; }
@@ -256,13 +277,14 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const HeadFwd A)
 __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_ml_kernel(const HeadFwd A) { head_fwd_body<1, 0>(A, HeadWeights{nullptr, nullptr}); }
 __global__ __launch_bounds__(HEAD_THREADS) void headw_fwd_kernel(const HeadFwd A, const HeadWeights Wt) { head_fwd_body<0, 1>(A, Wt); }
 __global__ __launch_bounds__(HEAD_THREADS) void headw_fwd_ml_kernel(const HeadFwd A, const HeadWeights Wt) { head_fwd_body<1, 1>(A, Wt); }
+template <int ML, int SH> __global__ __launch_bounds__(HEAD_THREADS) void heads_fwd_kernel(const HeadFwd A, const HeadWeights Wt, const HeadShape Sp) { head_fwd_body<ML, 1, SH>(A, Wt, Sp); }
 
 // partial layout of one workgroup: [gW3 (K H2) | gb3 (K) | gW2 (H2 H1) | gb2 (H2) | gb1 (H1)]
 __host__ __device__ static inline int64_t head_partial_floats(int H1, int H2, int K) { return (int64_t)K * H2 + K + (int64_t)H2 * H1 + H2 + H1; }
 
 // NB: 4 x 4 blocks of gW2 a thread keeps in registers (1: up to 64 x 64 weights, 2: 128 x 64, 4: 128 x 128)
-template <int NB, int ML, int WT>
-__device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights Wt)
+template <int NB, int ML, int WT, int SH = 0>
+__device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights Wt, const HeadShape Sp = HeadShape{0.f, 0.f})
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H1 = A.H1, H2 = A.H2, K = A.K, tid = threadIdx.x;
@@ -301,6 +323,8 @@ __device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights
         for (int v = 0; v < 16; ++v) accW[nb][v] = 0.f;
     bool first = true;
     __syncthreads();
+    float Wsum = 0.f;                                    // (SH = 1) the sum of the class weights, in class order
+    if (SH == 1) { for (int k = 0; k < K; ++k) Wsum += wts[k]; }
     for (int64_t chunk = blockIdx.x; chunk < n_chunks; chunk += gridDim.x) {
         const int64_t row0 = chunk * HEAD_RB;
         const int nr = (int)(A.B - row0 < HEAD_RB ? A.B - row0 : HEAD_RB);
@@ -308,7 +332,16 @@ __device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights
             const int r = idx / K, c = idx - r * K;
             float v = 0.f;
             if (ML) {
-                if (WT) {
+                if (SH == 2) {
+                    if (A.labels && A.g_loss) {
+                        const bool t = A.labels[row0 * K + idx] != 0;
+                        const float xv = A.logits[row0 * K + idx], z = t ? xv : -xv, e = expf(-fabsf(xv)), inv = 1.f / (1.f + e);
+                        const float q = z >= 0.f ? e * inv : inv, pt = z >= 0.f ? inv : e * inv;
+                        const float gq = wts[c] * (t ? wts[K + c] : 1.f) * head_qpow(q, Sp.gamma)
+                                         * (q + Sp.gamma * pt * (log1pf(e) + fmaxf(-z, 0.f))) * gscale;
+                        v = t ? -gq : gq;
+                    }
+                } else if (WT) {
                     if (A.labels && A.g_loss) {
                         const bool t = A.labels[row0 * K + idx] != 0;
                         v = wts[c] * ((t ? 0.f : 1.f) - (t ? wts[K + c] : 1.f) * head_sigmoid(-A.logits[row0 * K + idx])) * gscale;
@@ -318,8 +351,18 @@ __device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights
             } else if (A.labels && A.g_loss) {
                 const int64_t y = A.labels[row0 + r];
                 if (y >= 0 && y < K) {
-                    v = (expf(A.logits[row0 * K + idx] - A.lse[row0 + r]) - (c == (int)y ? 1.f : 0.f)) * gscale;
-                    if (WT) v *= wts[y];
+                    if (SH == 1) {
+                        const float pc = expf(A.logits[row0 * K + idx] - A.lse[row0 + r]);
+                        v = ((1.f - Sp.eps) * wts[y] * (pc - (c == (int)y ? 1.f : 0.f)) + (Sp.eps / (float)K) * (Wsum * pc - wts[c])) * gscale;
+                    } else if (SH == 2) {
+                        const float ls = A.lse[row0 + r], pc = expf(A.logits[row0 * K + idx] - ls);
+                        const float lp = A.logits[(row0 + r) * K + y] - ls, q = fmaxf(-expm1f(lp), 0.f);
+                        const float f = q > 0.f ? powf(q, Sp.gamma) * (1.f - Sp.gamma * expf(lp) * (lp / q)) : 0.f;
+                        v = wts[y] * f * (pc - (c == (int)y ? 1.f : 0.f)) * gscale;
+                    } else {
+                        v = (expf(A.logits[row0 * K + idx] - A.lse[row0 + r]) - (c == (int)y ? 1.f : 0.f)) * gscale;
+                        if (WT) v *= wts[y];
+                    }
                 }
             }
             if (A.g_logits) v += A.g_logits[row0 * K + idx];
@@ -424,6 +467,7 @@ template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kerne
 template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_ml_kernel(const HeadBwd A) { head_bwd_body<NB, 1, 0>(A, HeadWeights{nullptr, nullptr}); }
 template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void headw_bwd_kernel(const HeadBwd A, const HeadWeights Wt) { head_bwd_body<NB, 0, 1>(A, Wt); }
 template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void headw_bwd_ml_kernel(const HeadBwd A, const HeadWeights Wt) { head_bwd_body<NB, 1, 1>(A, Wt); }
+template <int NB, int ML, int SH> __global__ __launch_bounds__(HEAD_THREADS) void heads_bwd_kernel(const HeadBwd A, const HeadWeights Wt, const HeadShape Sp) { head_bwd_body<NB, ML, 1, SH>(A, Wt, Sp); }
 
 // ---- A^T B for tall operands: partial sums over row blocks (fp32 MFMA) ----------------------------------------------------------
 // part[blk][m][n] = sum over the block's rows r of A[r][m] B[r][n].  blockIdx.x = row block (four wavefronts of `wr` rows each),
@@ -582,18 +626,29 @@ static int head_set_lds(const void* kernel, size_t bytes)
 
 // ml: `labels` is the (B, K) indicator matrix and the launch is head_fwd_ml_kernel (no lse).  cw / pw: DEVICE rows of K class
 // weights, nullable; with labels and either of them the launch is the weighted kernel (pw: multi-label only)
+// label_smoothing in [0, 1) (single-label only), focal_gamma finite and >= 0, at most one of them non-zero
+static inline bool head_shape_ok(bool ml, float eps, float gamma)
+{
+    return eps >= 0.f && eps < 1.f && gamma >= 0.f && gamma <= 3.0e38f && !(eps > 0.f && gamma > 0.f) && !(ml && eps > 0.f);
+}
+
+// eps / gamma: with labels and either of them non-zero the launch is the shaped kernel (heads_fwd_kernel<ML, SH>)
 static int head_fwd_launch(bool ml, const float* cw, const float* pw, const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
                            const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1, float* a2,
-                           float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream)
+                           float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream,
+                           float eps = 0.f, float gamma = 0.f)
 {
+    if (!head_shape_ok(ml, eps, gamma)) return SGNN_ERR_BAD_ARG;
     if (!z1 || !W2 || !W3 || !a1 || !a2 || !logits || B < 1 || !(p >= 0.f && p < 1.f)) return SGNN_ERR_BAD_ARG;
     if (!sgnn_head_supported(H1, H2, K)) return SGNN_ERR_UNSUPPORTED_D;
     if (labels && ((!ml && !lse) || !out)) return SGNN_ERR_BAD_ARG;
     if (pw && !ml) return SGNN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < sgnn_head_fwd_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
-    const bool weighted = labels && (cw || pw);
+    const bool shaped = labels && (eps > 0.f || gamma > 0.f);
+    const bool weighted = shaped || (labels && (cw || pw));
     HeadWeights Wt;
     Wt.w = cw; Wt.pw = pw;
+    const HeadShape Sp{eps, gamma};
     HeadFwd A;
     A.z1 = z1; A.W2 = W2; A.b2 = b2; A.W3 = W3; A.b3 = b3; A.labels = labels; A.rng = (p > 0.f) ? rng : nullptr;
     A.B = B; A.H1 = (int)H1; A.H2 = (int)H2; A.K = (int)K; A.p = p;
@@ -603,7 +658,11 @@ static int head_fwd_launch(bool ml, const float* cw, const float* pw, const floa
     A.ticket = (unsigned*)((char*)workspace + 3 * nb * 4);
     const int64_t H1p = (H1 + 3) & ~3ll, H2p = (H2 + 3) & ~3ll, H2e = (H2 + 1) & ~1ll;
     const size_t lds = (size_t)(H2e * (H1p + 4) + K * (H2p + 4) + HEAD_RB * (H1p + H2p + K) + (weighted ? 2 * K : 0)) * 4;
-    if (weighted && ml) {
+#define HEAD_FWD_S(ML_, SH_) do { if (head_set_lds((const void*)heads_fwd_kernel<ML_, SH_>, lds) != 0) return SGNN_ERR_LAUNCH; \
+                                  hipLaunchKernelGGL((heads_fwd_kernel<ML_, SH_>), dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt, Sp); } while (0)
+    if (shaped) {
+        if (ml) HEAD_FWD_S(1, 2); else if (eps > 0.f) HEAD_FWD_S(0, 1); else HEAD_FWD_S(0, 2);
+    } else if (weighted && ml) {
         if (head_set_lds((const void*)headw_fwd_ml_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
         hipLaunchKernelGGL(headw_fwd_ml_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt);
     } else if (weighted) {
@@ -616,6 +675,7 @@ static int head_fwd_launch(bool ml, const float* cw, const float* pw, const floa
         if (head_set_lds((const void*)head_fwd_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
         hipLaunchKernelGGL(head_fwd_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A);
     }
+#undef HEAD_FWD_S
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
@@ -637,6 +697,15 @@ extern "C" int sgnn_head_fwd_weighted(const float* z1, int64_t B, int64_t H1, in
                            workspace, workspace_bytes, stream);
 }
 
+extern "C" int sgnn_head_fwd_shaped(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
+                                    const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1,
+                                    float* a2, float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes,
+                                    void* stream, const float* class_weight, float label_smoothing, float focal_gamma)
+{
+    return head_fwd_launch(false, class_weight, nullptr, z1, B, H1, H2, K, W2, b2, W3, b3, labels, p, rng, a1, a2, logits, lse, out,
+                           workspace, workspace_bytes, stream, label_smoothing, focal_gamma);
+}
+
 extern "C" int sgnn_head_fwd_ml(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
                                 const float* W3, const float* b3, const int64_t* targets, float p, int64_t* rng, float* a1, float* a2,
                                 float* logits, float* out, void* workspace, int64_t workspace_bytes, void* stream)
@@ -656,18 +725,32 @@ extern "C" int sgnn_head_fwd_ml_weighted(const float* z1, int64_t B, int64_t H1,
                            workspace, workspace_bytes, stream);
 }
 
+extern "C" int sgnn_head_fwd_ml_shaped(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2,
+                                       const float* b2, const float* W3, const float* b3, const int64_t* targets, float p,
+                                       int64_t* rng, float* a1, float* a2, float* logits, float* out, void* workspace,
+                                       int64_t workspace_bytes, void* stream, const float* weight, const float* pos_weight,
+                                       float focal_gamma)
+{
+    if (!targets) return SGNN_ERR_BAD_ARG;
+    return head_fwd_launch(true, weight, pos_weight, z1, B, H1, H2, K, W2, b2, W3, b3, targets, p, rng, a1, a2, logits, nullptr, out,
+                           workspace, workspace_bytes, stream, 0.f, focal_gamma);
+}
+
 static int head_bwd_launch(bool ml, const float* cw, const float* pw, const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,
                            const float* grad_logits, const float* rows, const float* a1, const float* a2, const float* W2,
                            const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial,
-                           void* stream)
+                           void* stream, float eps = 0.f, float gamma = 0.f)
 {
+    if (!head_shape_ok(ml, eps, gamma)) return SGNN_ERR_BAD_ARG;
     if (!a1 || !a2 || !W2 || !W3 || !dz1 || !partial || B < 1 || !(p >= 0.f && p < 1.f)) return SGNN_ERR_BAD_ARG;
     if (!sgnn_head_supported(H1, H2, K)) return SGNN_ERR_UNSUPPORTED_D;
     if (grad_loss && (!labels || !logits || (!ml && !lse) || !rows)) return SGNN_ERR_BAD_ARG;
     if (pw && !ml) return SGNN_ERR_BAD_ARG;
-    const bool weighted = grad_loss && (cw || pw);
+    const bool shaped = grad_loss && (eps > 0.f || gamma > 0.f);
+    const bool weighted = shaped || (grad_loss && (cw || pw));
     HeadWeights Wt;
     Wt.w = cw; Wt.pw = pw;
+    const HeadShape Sp{eps, gamma};
     HeadBwd A;
     A.logits = logits; A.lse = lse; A.labels = labels; A.g_loss = grad_loss; A.g_logits = grad_logits; A.rows = rows;
     A.a1 = a1; A.a2 = a2; A.W2 = W2; A.W3 = W3; A.B = B; A.H1 = (int)H1; A.H2 = (int)H2; A.K = (int)K;
@@ -680,7 +763,12 @@ static int head_bwd_launch(bool ml, const float* cw, const float* pw, const floa
                                   hipLaunchKernelGGL(KERNEL<NB>, dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A); } while (0)
 #define HEAD_BWD_W(KERNEL, NB) do { if (head_set_lds((const void*)KERNEL<NB>, lds) != 0) return SGNN_ERR_LAUNCH; \
                                     hipLaunchKernelGGL(KERNEL<NB>, dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt); } while (0)
-    if (weighted && ml) {
+#define HEAD_BWD_S(NB, ML_, SH_) do { if (head_set_lds((const void*)heads_bwd_kernel<NB, ML_, SH_>, lds) != 0) return SGNN_ERR_LAUNCH; \
+                                      hipLaunchKernelGGL((heads_bwd_kernel<NB, ML_, SH_>), dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt, Sp); } while (0)
+#define HEAD_BWD_S3(ML_, SH_) do { if (nblocks <= HEAD_THREADS) HEAD_BWD_S(1, ML_, SH_); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD_S(2, ML_, SH_); else HEAD_BWD_S(4, ML_, SH_); } while (0)
+    if (shaped) {
+        if (ml) HEAD_BWD_S3(1, 2); else if (eps > 0.f) HEAD_BWD_S3(0, 1); else HEAD_BWD_S3(0, 2);
+    } else if (weighted && ml) {
         if (nblocks <= HEAD_THREADS) HEAD_BWD_W(headw_bwd_ml_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD_W(headw_bwd_ml_kernel, 2); else HEAD_BWD_W(headw_bwd_ml_kernel, 4);
     } else if (weighted) {
         if (nblocks <= HEAD_THREADS) HEAD_BWD_W(headw_bwd_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD_W(headw_bwd_kernel, 2); else HEAD_BWD_W(headw_bwd_kernel, 4);
@@ -691,6 +779,8 @@ static int head_bwd_launch(bool ml, const float* cw, const float* pw, const floa
     }
 #undef HEAD_BWD
 #undef HEAD_BWD_W
+#undef HEAD_BWD_S
+#undef HEAD_BWD_S3
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
@@ -713,6 +803,16 @@ extern "C" int sgnn_head_bwd_weighted(const float* logits, const float* lse, con
                            dz1, partial, stream);
 }
 
+extern "C" int sgnn_head_bwd_shaped(const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,
+                                    const float* grad_logits, const float* rows, const float* a1, const float* a2, const float* W2,
+                                    const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1,
+                                    float* partial, void* stream, const float* class_weight, float label_smoothing,
+                                    float focal_gamma)
+{
+    return head_bwd_launch(false, class_weight, nullptr, logits, lse, labels, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K, p,
+                           dz1, partial, stream, label_smoothing, focal_gamma);
+}
+
 extern "C" int sgnn_head_bwd_ml(const float* logits, const int64_t* targets, const float* grad_loss, const float* grad_logits,
                                 const float* rows, const float* a1, const float* a2, const float* W2, const float* W3, int64_t B,
                                 int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream)
@@ -728,6 +828,15 @@ extern "C" int sgnn_head_bwd_ml_weighted(const float* logits, const int64_t* tar
 {
     return head_bwd_launch(true, weight, pos_weight, logits, nullptr, targets, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K,
                            p, dz1, partial, stream);
+}
+
+extern "C" int sgnn_head_bwd_ml_shaped(const float* logits, const int64_t* targets, const float* grad_loss, const float* grad_logits,
+                                       const float* rows, const float* a1, const float* a2, const float* W2, const float* W3,
+                                       int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial, void* stream,
+                                       const float* weight, const float* pos_weight, float focal_gamma)
+{
+    return head_bwd_launch(true, weight, pos_weight, logits, nullptr, targets, grad_loss, grad_logits, rows, a1, a2, W2, W3, B, H1, H2, K,
+                           p, dz1, partial, stream, 0.f, focal_gamma);
 }
 
 // rows per wavefront of a job: enough row blocks that blocks x output tiles fill the chip twice (~512 workgroups), no more -- every

@@ -10,15 +10,33 @@
 // counted row's loss and count are multiplied by w[y] -- the third partial becomes the sum of weights, which the finish writes
 // to lse[B] as before; w[y] is read only for y in [0, K).  Multi-label: c_k [(1 - y) x + L (log1p(exp(-|x|)) + max(-x, 0))] with
 // L = 1 + (p_k - 1) y; the mean stays over B K.
+//
+// Shaped losses (label smoothing and focal loss): a further compile-time axis SH on the same bodies (0: as above; 1:
+// label smoothing eps, single-label only; 2: focal gamma).  The SH = 0 instantiations are the kernels above; SH > 0 are kernels of
+// their own (ce_fwd_shaped_kernel<SH>, ce_bwd_shaped_kernel<SH>, bce_fwd_focal_kernel, bce_bwd_focal_kernel) that always take the
+// weight rows (an absent one stands as ones) and a by-value LossShape {eps, gamma}.
+//   smoothing  row loss (1 - eps) w_y (lse - x_y) + (eps / K) sum_k w_k (lse - x_k); gradient [(1 - eps) w_y (p_k - [k == y]) +
+//              (eps / K) (W p_k - w_k)] g / D with W = sum_j w_j (added once per workgroup in a fixed order) and D = sum w_y
+//   focal      lp = x_y - lse, q = -expm1(lp): row loss w_y q^gamma (-lp); gradient w_y f (p_k - [k == y]) g / D with
+//              f = q^gamma (1 - gamma p_t lp / q), and loss = f = 0 at q = 0 (lp / q is of order 1: nothing overflows)
+//   focal, multi-label   z = x for a positive, -x for a negative, e = exp(-|x|), l = log1p(e) + max(-z, 0), q = sigmoid(-z), p_t =
+//              sigmoid(z), both from e: element loss c L q^gamma l, gradient -+ c L q^gamma (q + gamma p_t l) g / (B K)
+// Partials, the finish kernels and the summation orders are those of the bare kernels.
 #include "common.h"
 
 #define SGNN_CE_IGNORE_INDEX (-100ll)
 
+struct LossShape { float eps, gamma; };                     // label smoothing | focal exponent (SH picks which one is read)
+
+// q^gamma of the focal losses, q in [0, 1]: exactly 0 at q = 0
+__device__ __forceinline__ float loss_qpow(float q, float gamma) { return q > 0.f ? powf(q, gamma) : 0.f; }
+
 // thread per row; per-workgroup partial sums added in a fixed order (bit-reproducible)
-template <int WT>
+template <int WT, int SH = 0>
 __device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, const int64_t* __restrict__ labels, int64_t B, int32_t K,
                                             const float* __restrict__ weight, float* __restrict__ lse, float* __restrict__ partial_loss,
-                                            float* __restrict__ partial_hits, float* __restrict__ partial_rows)
+                                            float* __restrict__ partial_hits, float* __restrict__ partial_rows,
+                                            const LossShape Sp = LossShape{0.f, 0.f})
 {
     __shared__ float sh_l[256], sh_h[256], sh_n[256];
     const int64_t r = blockIdx.x * 256ll + threadIdx.x;
@@ -35,7 +53,16 @@ __device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, co
         const int64_t y = labels[r];
         if (y >= 0 && y < K) {
             hit = (am == (int32_t)y) ? 1.f : 0.f;
-            if (WT) { cnt = weight[y]; loss = cnt * (l - x[y]); } else { loss = l - x[y]; cnt = 1.f; }
+            if (SH == 1) {                                // (weight: nullable, an absent row stands as ones)
+                cnt = weight ? weight[y] : 1.f;
+                float s = 0.f;
+                for (int32_t k = 0; k < K; ++k) s += (weight ? weight[k] : 1.f) * (l - x[k]);
+                loss = (1.f - Sp.eps) * cnt * (l - x[y]) + (Sp.eps / (float)K) * s;
+            } else if (SH == 2) {
+                cnt = weight ? weight[y] : 1.f;
+                const float lp = x[y] - l, q = fmaxf(-expm1f(lp), 0.f);
+                loss = cnt * loss_qpow(q, Sp.gamma) * (-lp);
+            } else if (WT) { cnt = weight[y]; loss = cnt * (l - x[y]); } else { loss = l - x[y]; cnt = 1.f; }
         }
         else if (y != SGNN_CE_IGNORE_INDEX) { loss = __builtin_nanf(""); cnt = 1.f; }
     }
@@ -68,6 +95,16 @@ __global__ __launch_bounds__(256) void ce_fwd_weighted_kernel(const float* __res
     ce_fwd_body<1>(logits, labels, B, K, weight, lse, partial_loss, partial_hits, partial_rows);
 }
 
+template <int SH>
+__global__ __launch_bounds__(256) void ce_fwd_shaped_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                            int64_t B, int32_t K, const float* __restrict__ weight,
+                                                            float* __restrict__ lse, float* __restrict__ partial_loss,
+                                                            float* __restrict__ partial_hits, float* __restrict__ partial_rows,
+                                                            const LossShape Sp)
+{
+    ce_fwd_body<1, SH>(logits, labels, B, K, weight, lse, partial_loss, partial_hits, partial_rows, Sp);
+}
+
 __global__ __launch_bounds__(64) void ce_finish_kernel(const float* __restrict__ partial_loss, const float* __restrict__ partial_hits,
                                                        const float* __restrict__ partial_rows, int64_t nblk, int64_t B,
                                                        float* __restrict__ loss, float* __restrict__ accuracy, float* __restrict__ rows)
@@ -84,12 +121,26 @@ __global__ __launch_bounds__(64) void ce_finish_kernel(const float* __restrict__
 }
 
 // d loss / d logits[r, k] = (softmax(r)[k] - [k == label r]) * grad_loss / (rows not ignored)   [WT: * w[label r] / (sum of weights)]
-template <int WT>
+template <int WT, int SH = 0>
 __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                             const float* __restrict__ lse, const float* __restrict__ grad_loss, int64_t B, int32_t K,
-                                            const float* __restrict__ weight, float* __restrict__ grad_logits)
+                                            const float* __restrict__ weight, float* __restrict__ grad_logits,
+                                            const LossShape Sp = LossShape{0.f, 0.f})
 {
     const int64_t t = blockIdx.x * 256ll + threadIdx.x;
+    float W = 0.f;
+    if (SH == 1) {                                          // W = sum of the class weights: strided sums, then a fixed tree
+        __shared__ float sh_w[256];
+        float s = 0.f;
+        for (int32_t k = threadIdx.x; k < K; k += 256) s += weight ? weight[k] : 1.f;
+        sh_w[threadIdx.x] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) sh_w[threadIdx.x] += sh_w[threadIdx.x + o];
+            __syncthreads();
+        }
+        W = sh_w[0];
+    }
     if (t >= B * K) return;
     const int64_t r = t / K;
     const int32_t k = (int32_t)(t - r * K);
@@ -97,8 +148,18 @@ __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, co
     const float scale = grad_loss[0] / lse[B];
     float v = 0.f;
     if (y >= 0 && y < K) {
-        v = (expf(logits[t] - lse[r]) - (k == (int32_t)y ? 1.f : 0.f)) * scale;
-        if (WT) v *= weight[y];
+        if (SH == 1) {
+            const float pk = expf(logits[t] - lse[r]), wy = weight ? weight[y] : 1.f, wk = weight ? weight[k] : 1.f;
+            v = ((1.f - Sp.eps) * wy * (pk - (k == (int32_t)y ? 1.f : 0.f)) + (Sp.eps / (float)K) * (W * pk - wk)) * scale;
+        } else if (SH == 2) {
+            const float pk = expf(logits[t] - lse[r]), wy = weight ? weight[y] : 1.f;
+            const float lp = logits[r * K + y] - lse[r], q = fmaxf(-expm1f(lp), 0.f);
+            const float f = q > 0.f ? powf(q, Sp.gamma) * (1.f - Sp.gamma * expf(lp) * (lp / q)) : 0.f;
+            v = wy * f * (pk - (k == (int32_t)y ? 1.f : 0.f)) * scale;
+        } else {
+            v = (expf(logits[t] - lse[r]) - (k == (int32_t)y ? 1.f : 0.f)) * scale;
+            if (WT) v *= weight[y];
+        }
     }
     grad_logits[t] = v;
 }
@@ -118,7 +179,22 @@ __global__ __launch_bounds__(256) void ce_bwd_weighted_kernel(const float* __res
     ce_bwd_body<1>(logits, labels, lse, grad_loss, B, K, weight, grad_logits);
 }
 
+template <int SH>
+__global__ __launch_bounds__(256) void ce_bwd_shaped_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
+                                                            const float* __restrict__ lse, const float* __restrict__ grad_loss,
+                                                            int64_t B, int32_t K, const float* __restrict__ weight,
+                                                            float* __restrict__ grad_logits, const LossShape Sp)
+{
+    ce_bwd_body<1, SH>(logits, labels, lse, grad_loss, B, K, weight, grad_logits, Sp);
+}
+
 static inline int64_t ce_blocks(int64_t B) { return (B + 255) / 256; }
+
+// label_smoothing in [0, 1), focal_gamma finite and >= 0, at most one of them non-zero
+static inline bool loss_shape_ok(float eps, float gamma)
+{
+    return eps >= 0.f && eps < 1.f && gamma >= 0.f && gamma <= 3.0e38f && !(eps > 0.f && gamma > 0.f);
+}
 
 extern "C" int64_t sgnn_cross_entropy_workspace_bytes(int64_t B)
 {
@@ -128,8 +204,9 @@ extern "C" int64_t sgnn_cross_entropy_workspace_bytes(int64_t B)
 
 // weight: DEVICE row of K class weights, nullable (null: the bare kernel)
 static int ce_fwd_launch(const float* logits, const int64_t* labels, int64_t B, int64_t K, float* lse, float* loss, float* accuracy,
-                         void* workspace, int64_t workspace_bytes, void* stream, const float* weight)
+                         void* workspace, int64_t workspace_bytes, void* stream, const float* weight, float eps = 0.f, float gamma = 0.f)
 {
+    if (!loss_shape_ok(eps, gamma)) return SGNN_ERR_BAD_ARG;
     if (!logits || !labels || !lse || !loss || B < 1 || K < 1 || K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < sgnn_cross_entropy_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
     const int64_t nblk = ce_blocks(B);
@@ -138,7 +215,10 @@ static int ce_fwd_launch(const float* logits, const int64_t* labels, int64_t B, 
     float* ph = pl + nblk;
     float* pn = ph + nblk;
     hipStream_t st = (hipStream_t)stream;
-    if (weight) hipLaunchKernelGGL(ce_fwd_weighted_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, weight, lse, pl, ph, pn);
+    const LossShape Sp{eps, gamma};
+    if (eps > 0.f) hipLaunchKernelGGL(ce_fwd_shaped_kernel<1>, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, weight, lse, pl, ph, pn, Sp);
+    else if (gamma > 0.f) hipLaunchKernelGGL(ce_fwd_shaped_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, weight, lse, pl, ph, pn, Sp);
+    else if (weight) hipLaunchKernelGGL(ce_fwd_weighted_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, weight, lse, pl, ph, pn);
     else hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, lse, pl, ph, pn);
     SGNN_CHECK_LAUNCH();
     hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, st, pl, ph, pn, nblk, B, loss, accuracy, lse + B);
@@ -159,12 +239,26 @@ extern "C" int sgnn_cross_entropy_fwd_weighted(const float* logits, const int64_
     return ce_fwd_launch(logits, labels, B, K, lse, loss, accuracy, workspace, workspace_bytes, stream, class_weight);
 }
 
-static int ce_bwd_launch(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss, int64_t B, int64_t K,
-                         float* grad_logits, void* stream, const float* weight)
+extern "C" int sgnn_cross_entropy_fwd_shaped(const float* logits, const int64_t* labels, int64_t B, int64_t K, float* lse, float* loss,
+                                             float* accuracy, void* workspace, int64_t workspace_bytes, void* stream,
+                                             const float* class_weight, float label_smoothing, float focal_gamma)
 {
+    return ce_fwd_launch(logits, labels, B, K, lse, loss, accuracy, workspace, workspace_bytes, stream, class_weight, label_smoothing,
+                         focal_gamma);
+}
+
+static int ce_bwd_launch(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss, int64_t B, int64_t K,
+                         float* grad_logits, void* stream, const float* weight, float eps = 0.f, float gamma = 0.f)
+{
+    if (!loss_shape_ok(eps, gamma)) return SGNN_ERR_BAD_ARG;
     if (!logits || !labels || !lse || !grad_loss || !grad_logits || B < 1 || K < 1 || K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
     if ((B * K + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-    if (weight) hipLaunchKernelGGL(ce_bwd_weighted_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits,
+    const LossShape Sp{eps, gamma};
+    if (eps > 0.f) hipLaunchKernelGGL(ce_bwd_shaped_kernel<1>, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits,
+                                      labels, lse, grad_loss, B, (int32_t)K, weight, grad_logits, Sp);
+    else if (gamma > 0.f) hipLaunchKernelGGL(ce_bwd_shaped_kernel<2>, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                                             logits, labels, lse, grad_loss, B, (int32_t)K, weight, grad_logits, Sp);
+    else if (weight) hipLaunchKernelGGL(ce_bwd_weighted_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits,
                                    labels, lse, grad_loss, B, (int32_t)K, weight, grad_logits);
     else hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, labels, lse,
                             grad_loss, B, (int32_t)K, grad_logits);
@@ -184,14 +278,22 @@ extern "C" int sgnn_cross_entropy_bwd_weighted(const float* logits, const int64_
     return ce_bwd_launch(logits, labels, lse, grad_loss, B, K, grad_logits, stream, class_weight);
 }
 
+extern "C" int sgnn_cross_entropy_bwd_shaped(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss,
+                                             int64_t B, int64_t K, float* grad_logits, void* stream, const float* class_weight,
+                                             float label_smoothing, float focal_gamma)
+{
+    return ce_bwd_launch(logits, labels, lse, grad_loss, B, K, grad_logits, stream, class_weight, label_smoothing, focal_gamma);
+}
+
 // ---- multi-label: nn.BCEWithLogitsLoss() (mean over B x K, SubGNN.py:133 with several labels per subgraph) + the exact-match
 // accuracy of su:108-124, for any K.  targets: int64 (B, K) indicator matrix, non-zero counts as 1.  A thread walks its row in k
 // order: l = max(x, 0) - x y + log1p(exp(-|x|)); the row is a hit when 1 / (1 + exp(-x)) > 0.5 (float32, as torch.sigmoid(x) >
 // 0.5 evaluates it -- not x > 0) equals y in every column.  Same partials and the same fixed order as the single-label pair.
-template <int WT>
+template <int WT, int SH = 0>
 __device__ __forceinline__ void bce_fwd_body(const float* __restrict__ logits, const int64_t* __restrict__ targets, int64_t B, int32_t K,
                                              const float* __restrict__ weight, const float* __restrict__ pos_weight,
-                                             float* __restrict__ partial_loss, float* __restrict__ partial_hits)
+                                             float* __restrict__ partial_loss, float* __restrict__ partial_hits,
+                                             const LossShape Sp = LossShape{0.f, 0.f})
 {
     __shared__ float sh_l[256], sh_h[256];
     const int64_t r = blockIdx.x * 256ll + threadIdx.x;
@@ -203,7 +305,11 @@ __device__ __forceinline__ void bce_fwd_body(const float* __restrict__ logits, c
         for (int32_t k = 0; k < K; ++k) {
             const float v = x[k];
             const bool t = y[k] != 0;
-            if (WT) {                                     // (either row may be absent: it stands as ones)
+            if (SH == 2) {
+                const float c = weight ? weight[k] : 1.f, L = (t && pos_weight) ? pos_weight[k] : 1.f;
+                const float z = t ? v : -v, e = expf(-fabsf(v)), inv = 1.f / (1.f + e);
+                loss += c * L * loss_qpow(z >= 0.f ? e * inv : inv, Sp.gamma) * (log1pf(e) + fmaxf(-z, 0.f));
+            } else if (WT) {                              // (either row may be absent: it stands as ones)
                 const float c = weight ? weight[k] : 1.f, L = (t && pos_weight) ? pos_weight[k] : 1.f;
                 loss += c * ((t ? 0.f : v) + L * (log1pf(expf(-fabsf(v))) + fmaxf(-v, 0.f)));
             } else loss += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
@@ -237,6 +343,14 @@ __global__ __launch_bounds__(256) void bce_fwd_weighted_kernel(const float* __re
     bce_fwd_body<1>(logits, targets, B, K, weight, pos_weight, partial_loss, partial_hits);
 }
 
+__global__ __launch_bounds__(256) void bce_fwd_focal_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                            int64_t B, int32_t K, const float* __restrict__ weight,
+                                                            const float* __restrict__ pos_weight, float* __restrict__ partial_loss,
+                                                            float* __restrict__ partial_hits, const LossShape Sp)
+{
+    bce_fwd_body<1, 2>(logits, targets, B, K, weight, pos_weight, partial_loss, partial_hits, Sp);
+}
+
 __global__ __launch_bounds__(64) void bce_finish_kernel(const float* __restrict__ partial_loss, const float* __restrict__ partial_hits,
                                                         int64_t nblk, int64_t B, int64_t K, float* __restrict__ loss,
                                                         float* __restrict__ accuracy)
@@ -253,14 +367,24 @@ __global__ __launch_bounds__(64) void bce_finish_kernel(const float* __restrict_
 
 // d loss / d logits[r, k] = (sigmoid(x) - y) * grad_loss / (B K); the sigmoid takes exp of a non-positive argument only
 // WT: c_k [(1 - y) - L (1 - sigmoid(x))] * grad_loss / (B K), L = 1 + (p_k - 1) y; 1 - sigmoid(x) = sigmoid(-x), from the same exp
-template <int WT>
+template <int WT, int SH = 0>
 __device__ __forceinline__ void bce_bwd_body(const float* __restrict__ logits, const int64_t* __restrict__ targets,
                                              const float* __restrict__ grad_loss, int64_t n, int32_t K, const float* __restrict__ weight,
-                                             const float* __restrict__ pos_weight, float* __restrict__ grad_logits)
+                                             const float* __restrict__ pos_weight, float* __restrict__ grad_logits,
+                                             const LossShape Sp = LossShape{0.f, 0.f})
 {
     const int64_t t = blockIdx.x * 256ll + threadIdx.x;
     if (t >= n) return;
     const float x = logits[t], e = expf(-fabsf(x));
+    if (SH == 2) {
+        const int32_t k = (int32_t)(t % K);
+        const bool y = targets[t] != 0;
+        const float c = weight ? weight[k] : 1.f, L = (y && pos_weight) ? pos_weight[k] : 1.f;
+        const float z = y ? x : -x, inv = 1.f / (1.f + e), q = z >= 0.f ? e * inv : inv, pt = z >= 0.f ? inv : e * inv;
+        const float g = c * L * loss_qpow(q, Sp.gamma) * (q + Sp.gamma * pt * (log1pf(e) + fmaxf(-z, 0.f))) * (grad_loss[0] / (float)n);
+        grad_logits[t] = y ? -g : g;
+        return;
+    }
     if (WT) {
         const int32_t k = (int32_t)(t % K);
         const bool y = targets[t] != 0;
@@ -287,6 +411,14 @@ __global__ __launch_bounds__(256) void bce_bwd_weighted_kernel(const float* __re
     bce_bwd_body<1>(logits, targets, grad_loss, n, K, weight, pos_weight, grad_logits);
 }
 
+__global__ __launch_bounds__(256) void bce_bwd_focal_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
+                                                            const float* __restrict__ grad_loss, int64_t n, int32_t K,
+                                                            const float* __restrict__ weight, const float* __restrict__ pos_weight,
+                                                            float* __restrict__ grad_logits, const LossShape Sp)
+{
+    bce_bwd_body<1, 2>(logits, targets, grad_loss, n, K, weight, pos_weight, grad_logits, Sp);
+}
+
 extern "C" int64_t sgnn_bce_logits_workspace_bytes(int64_t B)
 {
     if (B < 0) return -1;
@@ -295,8 +427,10 @@ extern "C" int64_t sgnn_bce_logits_workspace_bytes(int64_t B)
 
 // weight / pos_weight: DEVICE rows of K floats, either nullable (both null: the bare kernel)
 static int bce_fwd_launch(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
-                          void* workspace, int64_t workspace_bytes, void* stream, const float* weight, const float* pos_weight)
+                          void* workspace, int64_t workspace_bytes, void* stream, const float* weight, const float* pos_weight,
+                          float gamma = 0.f)
 {
+    if (!loss_shape_ok(0.f, gamma)) return SGNN_ERR_BAD_ARG;
     if (!logits || !targets || !loss || B < 1 || K < 1 || K > 0x7fffffff || B > (int64_t)0x7fffffffffffffffll / K) return SGNN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < sgnn_bce_logits_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
     const int64_t nblk = ce_blocks(B);
@@ -304,7 +438,10 @@ static int bce_fwd_launch(const float* logits, const int64_t* targets, int64_t B
     float* pl = (float*)workspace;
     float* ph = pl + nblk;
     hipStream_t st = (hipStream_t)stream;
-    if (weight || pos_weight)
+    if (gamma > 0.f)
+        hipLaunchKernelGGL(bce_fwd_focal_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, weight, pos_weight, pl, ph,
+                           LossShape{0.f, gamma});
+    else if (weight || pos_weight)
         hipLaunchKernelGGL(bce_fwd_weighted_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, weight, pos_weight, pl, ph);
     else hipLaunchKernelGGL(bce_fwd_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, pl, ph);
     SGNN_CHECK_LAUNCH();
@@ -326,12 +463,24 @@ extern "C" int sgnn_bce_logits_fwd_weighted(const float* logits, const int64_t* 
     return bce_fwd_launch(logits, targets, B, K, loss, accuracy, workspace, workspace_bytes, stream, weight, pos_weight);
 }
 
-static int bce_bwd_launch(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K, float* grad_logits,
-                          void* stream, const float* weight, const float* pos_weight)
+extern "C" int sgnn_bce_logits_fwd_shaped(const float* logits, const int64_t* targets, int64_t B, int64_t K, float* loss, float* accuracy,
+                                          void* workspace, int64_t workspace_bytes, void* stream, const float* weight,
+                                          const float* pos_weight, float focal_gamma)
 {
+    return bce_fwd_launch(logits, targets, B, K, loss, accuracy, workspace, workspace_bytes, stream, weight, pos_weight, focal_gamma);
+}
+
+static int bce_bwd_launch(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K, float* grad_logits,
+                          void* stream, const float* weight, const float* pos_weight, float gamma = 0.f)
+{
+    if (!loss_shape_ok(0.f, gamma)) return SGNN_ERR_BAD_ARG;
     if (!logits || !targets || !grad_loss || !grad_logits || B < 1 || K < 1 || B > (int64_t)0x7fffffffffffffffll / K) return SGNN_ERR_BAD_ARG;
     if ((B * K + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-    if (weight || pos_weight) {
+    if (gamma > 0.f) {
+        if (K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
+        hipLaunchKernelGGL(bce_bwd_focal_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, targets,
+                           grad_loss, B * K, (int32_t)K, weight, pos_weight, grad_logits, LossShape{0.f, gamma});
+    } else if (weight || pos_weight) {
         if (K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
         hipLaunchKernelGGL(bce_bwd_weighted_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, targets,
                            grad_loss, B * K, (int32_t)K, weight, pos_weight, grad_logits);
@@ -352,6 +501,13 @@ extern "C" int sgnn_bce_logits_bwd_weighted(const float* logits, const int64_t* 
                                             float* grad_logits, void* stream, const float* weight, const float* pos_weight)
 {
     return bce_bwd_launch(logits, targets, grad_loss, B, K, grad_logits, stream, weight, pos_weight);
+}
+
+extern "C" int sgnn_bce_logits_bwd_shaped(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K,
+                                          float* grad_logits, void* stream, const float* weight, const float* pos_weight,
+                                          float focal_gamma)
+{
+    return bce_bwd_launch(logits, targets, grad_loss, B, K, grad_logits, stream, weight, pos_weight, focal_gamma);
 }
 
 SGNN_DEFINE_WARM(loss)

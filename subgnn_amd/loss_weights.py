@@ -1,11 +1,13 @@
 """Class weights of the training loss: hparams['class_weight'] / hparams['pos_weight'] -> torch's ``weight`` / ``pos_weight`` of
-the two loss modules the model builds (nn.CrossEntropyLoss / nn.BCEWithLogitsLoss, reference SubGNN.py:133), and the decision
-which route a loss module takes through a training step (the kernels of csrc/head.hip and csrc/loss.hip, or the library).
+the two loss modules the model builds (nn.CrossEntropyLoss / nn.BCEWithLogitsLoss, reference SubGNN.py:133), the shaped losses
+(hparams['label_smoothing'] / hparams['focal_gamma'] -> ShapedLoss), and the decision which route a loss module takes through a
+training step (the kernels of csrc/head.hip and csrc/loss.hip, or the library).
 Host code only: nothing here touches a device."""
 import math
 
 import numpy as np
 import torch
+import torch.nn.functional as F
 from torch import nn
 
 KINDS = ('class_weight', 'pos_weight')
@@ -91,10 +93,91 @@ def resolve(spec, kind, K, multilabel, labels=None, names=None):
     return out
 
 
-def make_loss(multilabel, class_weight=None, pos_weight=None):
+def check_shape(label_smoothing, focal_gamma, multilabel, where='loss'):
+    """(label_smoothing, focal_gamma) as two floats.  ValueError for a label_smoothing outside [0, 1), a negative or non-finite
+    focal_gamma, both non-zero (no definition of a smoothed focal loss is torch's), or label smoothing of a multi-label loss
+    (torch has none for BCE)."""
+    out = []
+    for name, v in (('label_smoothing', label_smoothing), ('focal_gamma', focal_gamma)):
+        if v is None:
+            v = 0.0
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+            raise ValueError('%s: %s = %r is not a number' % (where, name, v))
+        out.append(float(v))
+    eps, gamma = out
+    if not (0.0 <= eps < 1.0):
+        raise ValueError('%s: label_smoothing = %r must lie in [0, 1)' % (where, eps))
+    if not (math.isfinite(gamma) and gamma >= 0.0):
+        raise ValueError('%s: focal_gamma = %r must be finite and non-negative' % (where, gamma))
+    if eps != 0.0 and gamma != 0.0:
+        raise ValueError('%s: label_smoothing and focal_gamma exclude each other' % where)
+    if eps != 0.0 and multilabel:
+        raise ValueError('%s: label_smoothing belongs to a single-label dataset (torch has none for BCE); use focal_gamma or pos_weight'
+                         % where)
+    return eps, gamma
+
+
+class ShapedLoss(nn.Module):
+    """Label smoothing or focal loss with per-class weights, mean reduction: the torch expression of what the shaped kernels of
+    csrc/head.hip and csrc/loss.hip compute -- the validation loss, the library route and the tests' reference.
+      single-label, label_smoothing eps   F.cross_entropy(logits, target, weight=weight, label_smoothing=eps)
+      single-label, focal_gamma g         sum_i w[y_i] (1 - p_t)^g (-log p_t) / sum_i w[y_i] over the rows with y_i != -100 (p_t the
+                                          softmax probability of the label; the class weights play alpha's role)
+      multi-label, focal_gamma g          mean over B K of weight_k L (1 - p_t)^g (-log p_t), p_t = sigmoid(x) for a target and
+                                          sigmoid(-x) otherwise, L = pos_weight_k for a target, else 1 (pos_weight is alpha)
+    With both 0 it is the weighted nn.CrossEntropyLoss / nn.BCEWithLogitsLoss.  ``weight`` / ``pos_weight``: None or K numbers, kept
+    as NON-persistent float32 buffers (no state_dict keys, as make_loss keeps them).  (1 - p_t)^g is formed from a clamped 1 - p_t
+    and is exactly 0 where 1 - p_t is: loss and gradient are 0 and finite there, also for g < 1."""
+
+    def __init__(self, multilabel, label_smoothing=0.0, focal_gamma=0.0, weight=None, pos_weight=None):
+        super().__init__()
+        self.multilabel = bool(multilabel)
+        self.label_smoothing, self.focal_gamma = check_shape(label_smoothing, focal_gamma, self.multilabel, 'ShapedLoss')
+        if pos_weight is not None and not self.multilabel:
+            raise ValueError('ShapedLoss: pos_weight belongs to a multi-label loss')
+        for name, w in (('weight', weight), ('pos_weight', pos_weight)):
+            self.register_buffer(name, None if w is None else torch.as_tensor(w, dtype=torch.float32).detach().clone(), persistent=False)
+
+    def extra_repr(self):
+        return 'multilabel=%s, label_smoothing=%g, focal_gamma=%g' % (self.multilabel, self.label_smoothing, self.focal_gamma)
+
+    @staticmethod
+    def _qpow(q, gamma):
+        """q^gamma for q in [0, 1] with a finite gradient: 0 (value and gradient) at q = 0."""
+        return torch.where(q > 0, q.clamp_min(torch.finfo(q.dtype).tiny).pow(gamma), torch.zeros_like(q))
+
+    def forward(self, logits, target):
+        w = None if self.weight is None else self.weight.to(logits.dtype)
+        if self.multilabel:
+            pw = None if self.pos_weight is None else self.pos_weight.to(logits.dtype)
+            t = target != 0
+            if self.focal_gamma == 0.0:
+                return F.binary_cross_entropy_with_logits(logits, t.to(logits.dtype), weight=w, pos_weight=pw)
+            z = torch.where(t, logits, -logits)
+            el = -F.logsigmoid(z) * self._qpow(torch.sigmoid(-z), self.focal_gamma)
+            if pw is not None:
+                el = el * torch.where(t, pw.expand_as(el), torch.ones_like(el))
+            if w is not None:
+                el = el * w
+            return el.mean()
+        if self.focal_gamma == 0.0:
+            return F.cross_entropy(logits, target, weight=w, label_smoothing=self.label_smoothing)
+        counted = target != -100
+        y = torch.where(counted, target, torch.zeros_like(target))
+        lp = F.log_softmax(logits, 1).gather(1, y.unsqueeze(1)).squeeze(1)
+        wy = torch.ones_like(lp) if w is None else w[y]
+        wy = torch.where(counted, wy, torch.zeros_like(wy))
+        return (wy * self._qpow(-torch.expm1(lp), self.focal_gamma) * -lp).sum() / wy.sum()
+
+
+def make_loss(multilabel, class_weight=None, pos_weight=None, label_smoothing=0.0, focal_gamma=0.0):
     """The model's loss module (reference SubGNN.py:133) carrying the weights as NON-persistent buffers: they follow the module
     across devices but are no state_dict keys -- a checkpoint has the same keys with and without weights, which are rebuilt from
-    the hyper-parameters and the training split."""
+    the hyper-parameters and the training split.  With label_smoothing or focal_gamma non-zero: a ShapedLoss carrying the same
+    rows; with both 0 exactly the nn module this returned before."""
+    eps, gamma = check_shape(label_smoothing, focal_gamma, multilabel, 'hparams')
+    if eps != 0.0 or gamma != 0.0:
+        return ShapedLoss(multilabel, eps, gamma, weight=class_weight, pos_weight=pos_weight)
     cw = None if class_weight is None else torch.tensor(class_weight, dtype=torch.float32)
     pw = None if pos_weight is None else torch.tensor(pos_weight, dtype=torch.float32)
     loss = nn.BCEWithLogitsLoss() if multilabel else nn.CrossEntropyLoss()
@@ -142,12 +225,28 @@ def kernel_plan(loss, multilabel, K, device=None):
     return w, pw
 
 
+def plan(loss, multilabel, K, device=None):
+    """What the loss kernels take of ``loss`` -> (weight, pos_weight, label_smoothing, focal_gamma) or None: the library path.  A
+    module whose type is exactly ShapedLoss (of this kind of dataset, its rows K float32 values on ``device``): its parameters;
+    anything else: kernel_plan's answer with (0.0, 0.0) appended -- a hand-assigned nn.CrossEntropyLoss(label_smoothing=) stays
+    the library's."""
+    if type(loss) is ShapedLoss:
+        if loss.multilabel != bool(multilabel):
+            return None
+        for row in (loss.weight, loss.pos_weight):
+            if row is not None and not _row_ok(row, K, device):
+                return None
+        return loss.weight, loss.pos_weight, loss.label_smoothing, loss.focal_gamma
+    kp = kernel_plan(loss, multilabel, K, device)
+    return None if kp is None else kp + (0.0, 0.0)
+
+
 def route(loss, hparams, multilabel, K, head_ok, device=None):
     """Which route a training step's loss takes: 'fused_head' (inside the head's launches, ops.fused_head), 'standalone' (one pass
     over the logits: ops.cross_entropy_with_accuracy / ops.bce_with_logits_and_accuracy -- a head the fused kernel does not take,
     or fused_head: false) or 'library' (the torch module itself).  ``head_ok``: ops.head_supported of the head's widths.  What
     SubGNN.training_step decides for device tensors of the expected shapes."""
-    if kernel_plan(loss, multilabel, K, device) is None or not hparams.get('fused_forward', True):
+    if plan(loss, multilabel, K, device) is None or not hparams.get('fused_forward', True):
         return 'library'
     if multilabel and not hparams.get('fused_multilabel_loss', True):
         return 'library'

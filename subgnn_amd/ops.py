@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from ._lib import MpnArgs, check
+from .loss_weights import check_shape as _loss_shape      # (label_smoothing, focal_gamma) as floats, or ValueError
 
 PAD = 0
 
@@ -2753,10 +2754,11 @@ def _class_weights(w, K, like, name):
 
 class _CrossEntropy(torch.autograd.Function):
     """(mean cross entropy, accuracy) of logits (B, K) against int64 labels (sgnn_cross_entropy_fwd / _bwd; with a class weight
-    row their ``_weighted`` forms: the mean is over the sum of the counted rows' weights, the accuracy stays unweighted)."""
+    row their ``_weighted`` forms: the mean is over the sum of the counted rows' weights, the accuracy stays unweighted; with label
+    smoothing or a focal exponent their ``_shaped`` forms)."""
 
     @staticmethod
-    def forward(ctx, logits, labels, weight):
+    def forward(ctx, logits, labels, weight, eps=0.0, gamma=0.0):
         lib = _lib.load()
         _req(logits, torch.float32, 'logits')
         _req(labels, torch.int64, 'labels')
@@ -2765,7 +2767,12 @@ class _CrossEntropy(torch.autograd.Function):
         res = torch.empty(2, dtype=torch.float32, device=logits.device)
         wsb = lib.sgnn_cross_entropy_workspace_bytes(B)
         ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=logits.device)
-        if weight is None:
+        ctx.shape = (float(eps), float(gamma))
+        if eps or gamma:
+            check(lib.sgnn_cross_entropy_fwd_shaped(_ptr(logits), _ptr(labels), B, K, _ptr(lse), _ptr(res),
+                                                    ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb, _stream(), _ptr(weight),
+                                                    float(eps), float(gamma)), 'sgnn_cross_entropy_fwd_shaped')
+        elif weight is None:
             check(lib.sgnn_cross_entropy_fwd(_ptr(logits), _ptr(labels), B, K, _ptr(lse), _ptr(res), ctypes.c_void_p(res.data_ptr() + 4),
                                              _ptr(ws), wsb, _stream()), 'sgnn_cross_entropy_fwd')
         else:
@@ -2783,21 +2790,28 @@ class _CrossEntropy(torch.autograd.Function):
         logits, labels, lse, weight = ctx.saved_tensors
         B, K = logits.shape
         g = torch.empty_like(logits)
-        if weight is None:
+        eps, gamma = ctx.shape
+        if eps or gamma:
+            check(lib.sgnn_cross_entropy_bwd_shaped(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss.reshape(1).contiguous().float()),
+                                                    B, K, _ptr(g), _stream(), _ptr(weight), eps, gamma), 'sgnn_cross_entropy_bwd_shaped')
+        elif weight is None:
             check(lib.sgnn_cross_entropy_bwd(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss.reshape(1).contiguous().float()), B, K,
                                              _ptr(g), _stream()), 'sgnn_cross_entropy_bwd')
         else:
             check(lib.sgnn_cross_entropy_bwd_weighted(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss.reshape(1).contiguous().float()),
                                                       B, K, _ptr(g), _stream(), _ptr(weight)), 'sgnn_cross_entropy_bwd_weighted')
-        return g, None, None
+        return g, None, None, None, None
 
 
-def cross_entropy_with_accuracy(logits, labels, weight=None):
+def cross_entropy_with_accuracy(logits, labels, weight=None, label_smoothing=0.0, focal_gamma=0.0):
     """nn.CrossEntropyLoss(weight=weight)(logits, labels) and calc_accuracy(logits, labels) -> (0-d loss, (1,) accuracy) in one
     pass.  ``weight``: None or a float32 device tensor of K class weights (torch's semantics: the mean is taken over the sum of the
-    counted rows' weights; the accuracy is over all rows, unweighted)."""
-    return _CrossEntropy.apply(logits.contiguous(), labels.contiguous(),
-                               _class_weights(weight, logits.shape[-1], logits, 'cross_entropy_with_accuracy: weight'))
+    counted rows' weights; the accuracy is over all rows, unweighted).  ``label_smoothing`` in [0, 1): nn.CrossEntropyLoss's;
+    ``focal_gamma`` >= 0: the focal loss w_y (1 - p_t)^gamma (-log p_t) over the same divisor (loss_weights.ShapedLoss); at most
+    one of the two is non-zero, and at the defaults the call is the one it was."""
+    eps, gamma = _loss_shape(label_smoothing, focal_gamma, False, 'cross_entropy_with_accuracy')
+    weight = _class_weights(weight, logits.shape[-1], logits, 'cross_entropy_with_accuracy: weight')
+    return _CrossEntropy.apply(logits.contiguous(), labels.contiguous(), weight, eps, gamma)
 
 
 class _BCEWithLogits(torch.autograd.Function):
@@ -2805,7 +2819,7 @@ class _BCEWithLogits(torch.autograd.Function):
     (sgnn_bce_logits_fwd / _bwd).  Nothing but the two inputs is saved: the backward recomputes the sigmoid."""
 
     @staticmethod
-    def forward(ctx, logits, targets, weight, pos_weight):
+    def forward(ctx, logits, targets, weight, pos_weight, gamma=0.0):
         lib = _lib.load()
         _req(logits, torch.float32, 'logits')
         _req(targets, torch.int64, 'targets')
@@ -2816,7 +2830,12 @@ class _BCEWithLogits(torch.autograd.Function):
         res = torch.empty(2, dtype=torch.float32, device=logits.device)
         wsb = lib.sgnn_bce_logits_workspace_bytes(B)
         ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=logits.device)
-        if weight is None and pos_weight is None:
+        ctx.gamma = float(gamma)
+        if gamma:
+            check(lib.sgnn_bce_logits_fwd_shaped(_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4),
+                                                 _ptr(ws), wsb, _stream(), _ptr(weight), _ptr(pos_weight), float(gamma)),
+                  'sgnn_bce_logits_fwd_shaped')
+        elif weight is None and pos_weight is None:
             check(lib.sgnn_bce_logits_fwd(_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb,
                                           _stream()), 'sgnn_bce_logits_fwd')
         else:
@@ -2834,24 +2853,31 @@ class _BCEWithLogits(torch.autograd.Function):
         logits, targets, weight, pos_weight = ctx.saved_tensors
         B, K = logits.shape
         g = torch.empty_like(logits)
-        if weight is None and pos_weight is None:
+        if ctx.gamma:
+            check(lib.sgnn_bce_logits_bwd_shaped(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K,
+                                                 _ptr(g), _stream(), _ptr(weight), _ptr(pos_weight), ctx.gamma), 'sgnn_bce_logits_bwd_shaped')
+        elif weight is None and pos_weight is None:
             check(lib.sgnn_bce_logits_bwd(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K, _ptr(g),
                                           _stream()), 'sgnn_bce_logits_bwd')
         else:
             check(lib.sgnn_bce_logits_bwd_weighted(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K,
                                                    _ptr(g), _stream(), _ptr(weight), _ptr(pos_weight)), 'sgnn_bce_logits_bwd_weighted')
-        return g, None, None, None
+        return g, None, None, None, None
 
 
-def bce_with_logits_and_accuracy(logits, targets, weight=None, pos_weight=None):
+def bce_with_logits_and_accuracy(logits, targets, weight=None, pos_weight=None, focal_gamma=0.0):
     """nn.BCEWithLogitsLoss(weight=, pos_weight=)(logits, targets.float()) and the exact-match accuracy calc_accuracy logs for a
     multi-label batch (every sigmoid(x) > 0.5 of a row equal to its target) -> (0-d loss, (1,) accuracy) in one pass.  ``targets``:
     int64 (B, K) indicator matrix, as the data loader keeps it (no float copy is made); any K.  ``weight`` / ``pos_weight``: None
-    or float32 device tensors of K per-class factors (torch's: weight scales a column's loss, pos_weight its positive term)."""
+    or float32 device tensors of K per-class factors (torch's: weight scales a column's loss, pos_weight its positive term).
+    ``focal_gamma`` >= 0: every element's loss times (1 - p_t)^gamma, p_t the probability of its target (loss_weights.ShapedLoss);
+    at 0 the call is the one it was."""
+    _, gamma = _loss_shape(0.0, focal_gamma, True, 'bce_with_logits_and_accuracy')
     logits = logits.contiguous()
     K = logits.shape[-1]
-    return _BCEWithLogits.apply(logits, targets.contiguous(), _class_weights(weight, K, logits, 'bce_with_logits_and_accuracy: weight'),
-                                _class_weights(pos_weight, K, logits, 'bce_with_logits_and_accuracy: pos_weight'))
+    weight = _class_weights(weight, K, logits, 'bce_with_logits_and_accuracy: weight')
+    pos_weight = _class_weights(pos_weight, K, logits, 'bce_with_logits_and_accuracy: pos_weight')
+    return _BCEWithLogits.apply(logits, targets.contiguous(), weight, pos_weight, gamma)
 
 
 # ---------------------------------------------------------------------------------------
@@ -2960,7 +2986,7 @@ class _FusedHead(torch.autograd.Function):
     every weight and bias gradient of the head.  9 + 22 launches -> 2 + 4."""
 
     @staticmethod
-    def forward(ctx, x, W1, b1, W2, b2, W3, b3, labels, p, rng, ml, class_weight=None, pos_weight=None):
+    def forward(ctx, x, W1, b1, W2, b2, W3, b3, labels, p, rng, ml, class_weight=None, pos_weight=None, eps=0.0, gamma=0.0):
         lib = _lib.load()
         for t, nm in ((x, 'x'), (W1, 'W1'), (b1, 'b1'), (W2, 'W2'), (b2, 'b2'), (W3, 'W3'), (b3, 'b3')):
             _req(t, torch.float32, nm)
@@ -2977,8 +3003,18 @@ class _FusedHead(torch.autograd.Function):
         lse = torch.empty(B + 1, dtype=torch.float32, device=dev) if (labels is not None and not ml) else None
         out = torch.empty(3, dtype=torch.float32, device=dev) if labels is not None else None
         ws = _head_workspace(dev, B)
-        weighted = labels is not None and (class_weight is not None or pos_weight is not None)
-        if weighted and ml:                                  # the weighted launches (headw_*): the bare ones below stay as they are
+        shaped = labels is not None and bool(eps or gamma)
+        weighted = shaped or (labels is not None and (class_weight is not None or pos_weight is not None))
+        ctx.shape = (float(eps), float(gamma)) if shaped else (0.0, 0.0)
+        if shaped and ml:                                    # the shaped launches (heads_*): label smoothing / focal loss
+            check(lib.sgnn_head_fwd_ml_shaped(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p),
+                                              _ptr(rng), _ptr(a1), _ptr(a2), _ptr(logits), _ptr(out), _ptr(ws), ws.numel() * 4,
+                                              _stream(), _ptr(class_weight), _ptr(pos_weight), float(gamma)), 'sgnn_head_fwd_ml_shaped')
+        elif shaped:
+            check(lib.sgnn_head_fwd_shaped(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p),
+                                           _ptr(rng), _ptr(a1), _ptr(a2), _ptr(logits), _ptr(lse), _ptr(out), _ptr(ws),
+                                           ws.numel() * 4, _stream(), _ptr(class_weight), float(eps), float(gamma)), 'sgnn_head_fwd_shaped')
+        elif weighted and ml:                                # the weighted launches (headw_*): the bare ones below stay as they are
             check(lib.sgnn_head_fwd_ml_weighted(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p),
                                                 _ptr(rng), _ptr(a1), _ptr(a2), _ptr(logits), _ptr(out), _ptr(ws), ws.numel() * 4,
                                                 _stream(), _ptr(class_weight), _ptr(pos_weight)), 'sgnn_head_fwd_ml_weighted')
@@ -3012,7 +3048,7 @@ class _FusedHead(torch.autograd.Function):
         B, H1, H2, K = ctx.dims
         dev = x.device
         if g_logits is None and g_loss is None:
-            return (None,) * 13
+            return (None,) * 15
         g_logits = g_logits.contiguous() if g_logits is not None else None
         g_loss = g_loss.reshape(1).contiguous().float() if g_loss is not None else None
         P = int(lib.sgnn_head_partial_floats(H1, H2, K))
@@ -3021,7 +3057,16 @@ class _FusedHead(torch.autograd.Function):
         partial = torch.empty((nb, P), dtype=torch.float32, device=dev)
         rows = ctypes.c_void_p(out.data_ptr() + 8) if out is not None else None
         weighted = class_weight is not None or pos_weight is not None
-        if weighted and ctx.ml:
+        eps, gamma = ctx.shape
+        if (eps or gamma) and ctx.ml:
+            check(lib.sgnn_head_bwd_ml_shaped(_ptr(logits), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2),
+                                              _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream(),
+                                              _ptr(class_weight), _ptr(pos_weight), gamma), 'sgnn_head_bwd_ml_shaped')
+        elif eps or gamma:
+            check(lib.sgnn_head_bwd_shaped(_ptr(logits), _ptr(lse), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1),
+                                           _ptr(a2), _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream(),
+                                           _ptr(class_weight), eps, gamma), 'sgnn_head_bwd_shaped')
+        elif weighted and ctx.ml:
             check(lib.sgnn_head_bwd_ml_weighted(_ptr(logits), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2),
                                                 _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream(),
                                                 _ptr(class_weight), _ptr(pos_weight)), 'sgnn_head_bwd_ml_weighted')
@@ -3065,10 +3110,11 @@ class _FusedHead(torch.autograd.Function):
         need = ctx.needs_input_grad
         dx = dz1 @ W1 if need[0] else None
         return (dx, gW1, gb1 if (hb[0] and need[2]) else None, gW2 if need[3] else None, gb2 if (hb[1] and need[4]) else None,
-                gW3 if need[5] else None, gb3 if (hb[2] and need[6]) else None, None, None, None, None, None, None)
+                gW3 if need[5] else None, gb3 if (hb[2] and need[6]) else None, None, None, None, None, None, None, None, None)
 
 
-def fused_head(x, lin, lin2, lin3, labels=None, p=0.0, rng=None, targets=None, class_weight=None, pos_weight=None):
+def fused_head(x, lin, lin2, lin3, labels=None, p=0.0, rng=None, targets=None, class_weight=None, pos_weight=None,
+               label_smoothing=0.0, focal_gamma=0.0):
     """The head's three Linear layers with relu + dropout(p) between them, and -- with ``labels`` (int64 (B,)) -- the mean cross
     entropy and the accuracy of the logits, or -- with ``targets`` (int64 (B, K) indicator matrix, multi-label) -- the mean binary
     cross entropy with logits and the exact-match accuracy (``lin*``: nn.Linear modules).
@@ -3076,7 +3122,11 @@ def fused_head(x, lin, lin2, lin3, labels=None, p=0.0, rng=None, targets=None, c
     ``rng``: int64 (2,) device tensor {seed, step} when p > 0 (the launch advances step).
     ``class_weight``: float32 device tensor of K class weights -- nn.CrossEntropyLoss's ``weight`` with ``labels`` (the mean is over
     the sum of the counted rows' weights), nn.BCEWithLogitsLoss's ``weight`` with ``targets``; ``pos_weight`` (``targets`` only):
-    nn.BCEWithLogitsLoss's.  Either selects the weighted launches; no gradient flows to them; the accuracy is unweighted."""
+    nn.BCEWithLogitsLoss's.  Either selects the weighted launches; no gradient flows to them; the accuracy is unweighted.
+    ``label_smoothing`` in [0, 1) (``labels`` only: nn.CrossEntropyLoss's) / ``focal_gamma`` >= 0 (the focal loss of
+    loss_weights.ShapedLoss, with ``labels`` or ``targets``): at most one non-zero; either selects the shaped launches, which
+    take the weight rows too; at the defaults the call is the one it was."""
+    eps, gamma = _loss_shape(label_smoothing, focal_gamma, targets is not None, 'fused_head')
     if labels is not None and targets is not None:
         raise ValueError('fused_head: labels (single-label) and targets (multi-label) exclude each other')
     if p > 0 and rng is None:
@@ -3092,10 +3142,10 @@ def fused_head(x, lin, lin2, lin3, labels=None, p=0.0, rng=None, targets=None, c
     pos_weight = _class_weights(pos_weight, K, x, 'fused_head: pos_weight')
     if targets is not None:
         return _FusedHead.apply(x, lin.weight, lin.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias, targets.contiguous(),
-                                float(p), rng if p > 0 else None, True, class_weight, pos_weight)
+                                float(p), rng if p > 0 else None, True, class_weight, pos_weight, eps, gamma)
     return _FusedHead.apply(x, lin.weight, lin.bias, lin2.weight, lin2.bias, lin3.weight, lin3.bias,
                             labels.contiguous() if labels is not None else None, float(p), rng if p > 0 else None, False,
-                            class_weight, None)
+                            class_weight, None, eps, gamma)
 
 
 class _GatherRows(torch.autograd.Function):
