@@ -1188,6 +1188,33 @@ int sgnn_optim_adam_lr_table(float* const* params, float* const* grads, float* c
                              const int64_t* step_counters, const int64_t* counter_slots, const int64_t* row_lens,
                              unsigned char* const* row_seen, const float* partial, int64_t n_partial, float max_norm,
                              float* coef_out, void* stream);
+/*   sgnn_optim_adam_ema(...)                sgnn_optim_adam that also moves a weight average: ema (HOST array of DEVICE
+ *   sgnn_optim_adam_ema_lr_table(...)       pointers, one float32 tensor per parameter, 4-byte aligned at least) after the
+ *                                           update of every element it steps: e = fma(w, p_new - e, e), w = 1 - d_s (formed once
+ *                                           per workgroup, in double), d_s = ema_decay (in [0, 1)), or with ema_warmup != 0
+ *                                           min(ema_decay, (1 + s) / (10 + s)) at the step count s the tensor reads above.
+ *                                           Parameters, moments and the coefficient are sgnn_optim_adam's bit for bit.  The
+ *                                           average advances with the tensor's OWN steps: a tensor outside the call keeps its
+ *                                           average, and so does a table row the update skips -- with the average initialised to
+ *                                           the parameter such a row has e == p bit for bit, which e + w (p - e) leaves as it
+ *                                           is, so skipping needs no catch-up.  A NaN coefficient steps every row and the
+ *                                           averages turn NaN with the parameters.  56 tensors per launch (the fifth pointer).
+ *   sgnn_optim_swap(a, b, numels, n, ...)   a[i] <-> b[i] in place (HOST arrays of DEVICE pointers, numels[i] floats, 4-byte
+ *                                           aligned at least; float4 where both are 16-byte aligned), no temporary, one launch
+ *                                           per 128 tensors; empty tensors and a[i] == b[i] are skipped, a partial overlap is
+ *                                           a bad argument. */
+int sgnn_optim_adam_ema(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                        const int64_t* numels, const int32_t* zero_grad, int64_t n_tensors, float lr, float beta1, float beta2,
+                        float eps, const int64_t* steps, const int64_t* step_counters, const int64_t* counter_slots,
+                        const int64_t* row_lens, unsigned char* const* row_seen, const float* partial, int64_t n_partial,
+                        float max_norm, float* coef_out, float* const* ema, float ema_decay, int ema_warmup, void* stream);
+int sgnn_optim_adam_ema_lr_table(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                 const int64_t* numels, const int32_t* zero_grad, int64_t n_tensors, const float* lr_table,
+                                 int64_t lr_len, float beta1, float beta2, float eps, const int64_t* steps,
+                                 const int64_t* step_counters, const int64_t* counter_slots, const int64_t* row_lens,
+                                 unsigned char* const* row_seen, const float* partial, int64_t n_partial, float max_norm,
+                                 float* coef_out, float* const* ema, float ema_decay, int ema_warmup, void* stream);
+int sgnn_optim_swap(float* const* a, float* const* b, const int64_t* numels, int64_t n_tensors, void* stream);
 
 
 /* A batch's rows of up to sgnn_gather_rows_many_max() per-split tensors in ONE launch (the row gathers of _pad_collate,

@@ -23,7 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.nn.parameter import Parameter
 
-from . import config, gamma, loss_weights, ops, subgraph_utils
+from . import config, gamma, loss_weights, ops, schedule, subgraph_utils
 from . import anchor_patch_samplers as aps
 from .datasets import SubgraphDataset
 from .graph import load_graph
@@ -172,6 +172,11 @@ class SubGNN(nn.Module):
         self.loss = loss_weights.make_loss(self.multilabel, *self._loss_weights(), label_smoothing=hp.get('label_smoothing', 0.0),
                                            focal_gamma=hp.get('focal_gamma', 0.0))
         loss_weights.refuse_multi_rank(self.loss)
+        # hparams['ema_decay'] / ['lr_schedule'] / ['early_stop_patience'] and their companions (schedule.py; read by
+        # train_config.Trainer.fit): checked here so that a bad value fails before the data is prepared; a multi-rank run, whose
+        # table is stepped by dist.ShardedTableAdam, is refused a weight average and a learning-rate table
+        schedule.check_hparams(hp)
+        schedule.refuse_multi_rank(hp)
         self.lstm = LSTM(D, D, dropout=hp['lstm_dropout'], num_layers=hp['lstm_n_layers'],
                          aggregator=hp['lstm_aggregator'])
         if hp.get('ff_attn', False):                                   # S.py:179-183

@@ -163,21 +163,62 @@ def load(path, weights_only=False):
     return torch.load(path, map_location='cpu', weights_only=weights_only)
 
 
-def load_checkpoint(model, path_or_dict):
+def ema_tensors(ck):
+    """{parameter name: averaged tensor} of a checkpoint written by a run with ``ema_decay`` > 0, or None.  The average travels
+    as the ``'ema'`` entry of each parameter's optimizer state; the file's info names the parameters in the optimizer's order
+    (``'ema_params'``), so reading it does not depend on rebuilding the optimizer."""
+    info = ck.get(INFO_KEY) or {}
+    names = info.get('ema_params')
+    if not info.get('ema_decay') or not names:
+        return None
+    states = ck.get('optimizer_states') or []
+    state = states[0].get('state') if states and isinstance(states[0], dict) else None
+    if not state:
+        return None
+    out = {}
+    for i, name in enumerate(names):
+        ent = state.get(i)
+        if ent is None or ent.get('ema') is None:
+            return None
+        out[name] = ent['ema']
+    return out
+
+
+def load_checkpoint(model, path_or_dict, weights='auto'):
     """Load a checkpoint's ``state_dict`` into ``model`` as the reference does (train.py:265-271): keys the model lacks are
     dropped, a key the checkpoint lacks raises (``load_state_dict``'s strict check), tensors go to the model's device.  The
     values are COPIED into the model's existing tensors, never rebound, so a training step already recorded in a hipGraph
     (graph_step.CapturedTrainStep) reads the loaded weights.  Works before or after ``prepare_data`` / ``hotpath.prepare_sparse``.
     A file of this project also names the anchor draw its epoch was validated with: a prepared model with
     ``resample_anchor_patches`` draws those anchors again, so that testing it does not depend on how many epochs ran since.
+    ``weights``: a run with ``ema_decay`` > 0 validated, ranked and kept its epochs by the AVERAGED weights; its files hold
+    the raw weights in ``state_dict`` (what a resume and the reference's loader read) and the averages beside the moments.
+    'auto' (the default, what the tools call) copies the averages over the parameters when the file says the run validated
+    with them and they are there; 'raw' never does (``fit(resume_from=)``); 'ema' raises when the file has none.  The model then
+    carries ``_loaded_weights`` = 'ema' or 'raw' (``Trainer.test`` does not exchange the weights of a loaded model again).
     Returns the checkpoint dict."""
+    if weights not in ('auto', 'raw', 'ema'):
+        raise ValueError("load_checkpoint: weights must be 'auto', 'raw' or 'ema', not %r" % (weights,))
     ck = load(path_or_dict) if isinstance(path_or_dict, (str, os.PathLike)) else path_or_dict
     if 'state_dict' not in ck:
         raise KeyError("checkpoint has no 'state_dict'")
     own = model.state_dict()
     sd = {k: v for k, v in ck['state_dict'].items() if k in own}
+    avg = ema_tensors(ck) if weights != 'raw' else None
+    if weights == 'ema' and avg is None:
+        raise ValueError("load_checkpoint(weights='ema'): the checkpoint holds no averaged weights (its run had ema_decay = 0, or "
+                         "it was not written by this project)")
+    if avg is not None:
+        named = dict(model.named_parameters())
+        for name, t in avg.items():
+            if name not in named or tuple(named[name].shape) != tuple(t.shape):
+                raise ValueError('load_checkpoint: the averaged %r of the checkpoint does not match the model' % (name,))
     with torch.no_grad():
         model.load_state_dict(sd)                       # (copy_ into the existing parameters and buffers; strict on missing keys)
+        if avg is not None:
+            for name, t in avg.items():
+                named[name].copy_(t)
+    model.__dict__['_loaded_weights'] = 'ema' if avg is not None else 'raw'
     if hasattr(model, 'invalidate_half_table'):
         model.invalidate_half_table()
     info = ck.get(INFO_KEY) or {}

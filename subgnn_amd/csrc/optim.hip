@@ -71,15 +71,17 @@ extern "C" int sgnn_adam_step(float* param, const float* grad, float* exp_avg, f
 // of them), forms the coefficient and updates its chunk.  Tensors travel as kernel arguments (pointers of gradients change from
 // step to step in eager mode and are frozen into a recorded step), OPT_MAXT per launch.
 #define OPT_MAXT 72
+#define OPT_EMA_MAXT 56                   // tensors per launch of the updates that also move a weight average (a fifth pointer each)
 #define OPT_CHUNK 4096                    // floats per workgroup iteration: 256 lanes x 4 float4
 #define OPT_MAX_BLOCKS 2048               // per tensor; larger tensors stride
 
-struct OptTensors {
-    float* p[OPT_MAXT]; float* g[OPT_MAXT]; float* m[OPT_MAXT]; float* v[OPT_MAXT];
-    long long n[OPT_MAXT];
-    int blk[OPT_MAXT + 1];                // first workgroup of tensor t inside this launch
-    int zero[OPT_MAXT];
-    int slot[OPT_MAXT];                   // which device step count belongs to tensor t
+template <int MAXT>
+struct OptTensorsT {
+    float* p[MAXT]; float* g[MAXT]; float* m[MAXT]; float* v[MAXT];
+    long long n[MAXT];
+    int blk[MAXT + 1];                    // first workgroup of tensor t inside this launch
+    int zero[MAXT];
+    int slot[MAXT];                       // which device step count belongs to tensor t
     int count;
     // one tensor of the launch may be a table of rows with a per-row "ever had a gradient" byte: a row whose gradient is all
     // zero and that never had one has m = v = 0, so Adam leaves it exactly as it is (update = step_size * 0 / (0 + eps)) --
@@ -89,8 +91,23 @@ struct OptTensors {
     int row_lanes;                        // float4 lanes per row: a power of two <= 64
     unsigned char* seen;
 };
+typedef OptTensorsT<OPT_MAXT> OptTensors;
+// the same with the weight averages: e += (1 - d_s) (p_new - e) inside the update, d_s = ema_decay, or with ema_warmup
+// min(ema_decay, (1 + s) / (10 + s)) at the tensor's step count s.  Kernel arguments end at 4 KB and OptTensors takes 3.7 of
+// them: a fifth pointer per tensor does not fit beside 72 tensors, so these launches hold OPT_EMA_MAXT.
+struct OptTensorsEma : OptTensorsT<OPT_EMA_MAXT> {
+    float* e[OPT_EMA_MAXT];
+    float ema_decay;
+    int ema_warmup;
+};
+template <bool EMA> struct OptArgs { typedef OptTensors type; };
+template <> struct OptArgs<true> { typedef OptTensorsEma type; };
+// (the launch's other arguments take 72 bytes and the hidden ones 256)
+static_assert(sizeof(OptTensors) == 3768 && sizeof(OptTensors) + 72 + 256 <= 4096, "OptTensors outgrew the kernel-argument segment");
+static_assert(sizeof(OptTensorsEma) == 3392 && sizeof(OptTensorsEma) + 72 + 256 <= 4096, "OptTensorsEma outgrew the kernel-argument segment");
 
-__device__ __forceinline__ int opt_find(const OptTensors& T, int b)
+template <class TT>
+__device__ __forceinline__ int opt_find(const TT& T, int b)
 {
     int lo = 0, hi = T.count - 1;         // largest t with blk[t] <= b
     while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (T.blk[mid] <= b) lo = mid; else hi = mid - 1; }
@@ -129,8 +146,12 @@ __global__ __launch_bounds__(256) void optim_sumsq_kernel(const OptTensors T, fl
 #ifndef OPT_ROW_SLICES
 #define OPT_ROW_SLICES 2
 #endif
-__global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, const float* __restrict__ partial, int n_partial, float max_norm,
-                                                         float* __restrict__ coef_out, float lr, float b1, float b2, float eps,
+// EMA: the launch also moves the weight averages T.e (OptTensorsEma) of every element it steps -- one more read and one more
+// write beside the parameter's, which is in registers here; an element that is not stepped (a skipped row, a tensor outside
+// the launch) keeps its average: it advances with the tensor's own steps.  <false> is the update as it always was.
+template <bool EMA>
+__global__ __launch_bounds__(256) void optim_adam_kernel(const typename OptArgs<EMA>::type T, const float* __restrict__ partial, int n_partial,
+                                                         float max_norm, float* __restrict__ coef_out, float lr, float b1, float b2, float eps,
                                                          long long host_step, const int64_t* __restrict__ counters,
                                                          const float* __restrict__ lr_table, long long lr_len)
 {
@@ -160,11 +181,19 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
     const float step_size = (float)((double)lr_s / (1.0 - pow((double)b1, st)));
     const float rsqrt_bc2 = (float)(1.0 / sqrt(1.0 - pow((double)b2, st)));
     float* __restrict__ p = T.p[t]; float* __restrict__ g = T.g[t]; float* __restrict__ m = T.m[t]; float* __restrict__ v = T.v[t];
+    float* __restrict__ e = nullptr;
+    float w = 0.f;                        // 1 - d_s, formed once per workgroup, in double (as step_size)
+    if constexpr (EMA) {
+        e = T.e[t];
+        double d = (double)T.ema_decay;
+        if (T.ema_warmup) { const double dw = (1.0 + st) / (10.0 + st); d = dw < d ? dw : d; }
+        w = (float)(1.0 - d);
+    }
     const int64_t n = T.n[t];
     const int zero = T.zero[t];
-    if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0) {
+    if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)e)) & 15) == 0) {
         const int64_t n4 = n >> 2;
-        float4* p4 = (float4*)p; float4* g4 = (float4*)g; float4* m4 = (float4*)m; float4* v4 = (float4*)v;
+        float4* p4 = (float4*)p; float4* g4 = (float4*)g; float4* m4 = (float4*)m; float4* v4 = (float4*)v; float4* e4 = (float4*)e;
         if (t == T.rows_t) {
             // (n = rows * 4 L and a wavefront's 64 consecutive float4 start at a multiple of 64: a row's lanes share a wavefront)
             const int L = T.row_lanes, lane = threadIdx.x & 63, sh = 31 - __builtin_clz(L);
@@ -193,11 +222,12 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
                     was[u] = in[u] ? seen[idx[u] >> sh] != 0 : false;
                     act[u] = in[u] && (any[u] || was[u] || gs != gs);        // a NaN coefficient poisons every row
                 }
-                float4 pp[U], mm[U], vv[U];
+                float4 pp[U], mm[U], vv[U], ee[EMA ? U : 1];
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const int64_t j = act[u] ? idx[u] : 0;
                     pp[u] = p4[j]; mm[u] = m4[j]; vv[u] = v4[j];
+                    if constexpr (EMA) ee[u] = e4[j];
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
@@ -209,8 +239,10 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
                             M[k] = M[k] + (1.f - b1) * (gk - M[k]);
                             V[k] = b2 * V[k] + (1.f - b2) * gk * gk;
                             P[k] -= step_size * M[k] / (sqrtf(V[k]) * rsqrt_bc2 + eps);
+                            if constexpr (EMA) { float* E = &ee[u].x; E[k] = fmaf(w, P[k] - E[k], E[k]); }
                         }
                         p4[idx[u]] = pp[u]; m4[idx[u]] = mm[u]; v4[idx[u]] = vv[u];
+                        if constexpr (EMA) e4[idx[u]] = ee[u];
                         if (zero && any[u]) g4[idx[u]] = make_float4(0.f, 0.f, 0.f, 0.f);
                         if (!was[u] && (lane & (L - 1)) == 0) seen[idx[u] >> sh] = 1;
                     }
@@ -219,7 +251,8 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
             return;
         }
         for (int64_t i = (int64_t)(b - T.blk[t]) * 256 + threadIdx.x; i < n4; i += (int64_t)nb * 256) {
-            float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
+            float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i], ee;
+            if constexpr (EMA) ee = e4[i];
             float* P = &pp.x; float* G = &gg.x; float* M = &mm.x; float* V = &vv.x;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -227,8 +260,10 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
                 M[k] = M[k] + (1.f - b1) * (gk - M[k]);
                 V[k] = b2 * V[k] + (1.f - b2) * gk * gk;
                 P[k] -= step_size * M[k] / (sqrtf(V[k]) * rsqrt_bc2 + eps);
+                if constexpr (EMA) { float* E = &ee.x; E[k] = fmaf(w, P[k] - E[k], E[k]); }
             }
             p4[i] = pp; m4[i] = mm; v4[i] = vv;
+            if constexpr (EMA) e4[i] = ee;
             if (zero) g4[i] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         if (b == T.blk[t] && (int64_t)threadIdx.x < n - n4 * 4) {
@@ -237,7 +272,9 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
             const float mk = m[i] + (1.f - b1) * (gk - m[i]);
             const float vk = b2 * v[i] + (1.f - b2) * gk * gk;
             m[i] = mk; v[i] = vk;
-            p[i] -= step_size * mk / (sqrtf(vk) * rsqrt_bc2 + eps);
+            const float pk = p[i] - step_size * mk / (sqrtf(vk) * rsqrt_bc2 + eps);
+            p[i] = pk;
+            if constexpr (EMA) e[i] = fmaf(w, pk - e[i], e[i]);
             if (zero) g[i] = 0.f;
         }
     } else {
@@ -246,7 +283,9 @@ __global__ __launch_bounds__(256) void optim_adam_kernel(const OptTensors T, con
             const float mk = m[i] + (1.f - b1) * (gk - m[i]);
             const float vk = b2 * v[i] + (1.f - b2) * gk * gk;
             m[i] = mk; v[i] = vk;
-            p[i] -= step_size * mk / (sqrtf(vk) * rsqrt_bc2 + eps);
+            const float pk = p[i] - step_size * mk / (sqrtf(vk) * rsqrt_bc2 + eps);
+            p[i] = pk;
+            if constexpr (EMA) e[i] = fmaf(w, pk - e[i], e[i]);
             if (zero) g[i] = 0.f;
         }
     }
@@ -270,7 +309,8 @@ extern "C" int64_t sgnn_optim_partials(const int64_t* numels, int64_t n_tensors)
 }
 
 // one launch group = tensors [from, to): fills T, returns its workgroup count
-static int opt_fill(OptTensors& T, float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+template <class TT>
+static int opt_fill(TT& T, float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                     const int64_t* numels, const int32_t* zero_grad, const int64_t* slots, int64_t from, int64_t to)
 {
     int blocks = 0;
@@ -317,33 +357,43 @@ extern "C" int sgnn_optim_count(int64_t* step_counters, const int64_t* counter_s
     return SGNN_OK;
 }
 
+template <bool EMA>
 static int optim_adam(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
                       const int64_t* numels, const int32_t* zero_grad, int64_t n_tensors, float lr, const float* lr_table,
                       int64_t lr_len, float beta1, float beta2, float eps, const int64_t* steps, const int64_t* step_counters,
                       const int64_t* counter_slots, const int64_t* row_lens, unsigned char* const* row_seen,
-                      const float* partial, int64_t n_partial, float max_norm, float* coef_out, void* stream)
+                      const float* partial, int64_t n_partial, float max_norm, float* coef_out, float* const* ema, float ema_decay,
+                      int ema_warmup, void* stream)
 {
+    constexpr int MAXT = EMA ? OPT_EMA_MAXT : OPT_MAXT;
     if (n_tensors < 0 || (n_tensors && (!params || !grads || !exp_avg || !exp_avg_sq || !numels))) return SGNN_ERR_BAD_ARG;
+    if (EMA && ((n_tensors && !ema) || !(ema_decay >= 0.f && ema_decay < 1.f))) return SGNN_ERR_BAD_ARG;
     if ((steps == nullptr) == (step_counters == nullptr) && n_tensors) return SGNN_ERR_BAD_ARG;      // exactly one of the two
     if (max_norm > 0.f && (!partial || n_partial < 0 || n_partial > 0x7fffffffll)) return SGNN_ERR_BAD_ARG;
     for (int64_t i = 0; i < n_tensors; ++i) {
         if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || numels[i] < 0 || (steps && steps[i] < 1)) return SGNN_ERR_BAD_ARG;
         if ((((uintptr_t)params[i]) | ((uintptr_t)grads[i]) | ((uintptr_t)exp_avg[i]) | ((uintptr_t)exp_avg_sq[i])) & 3) return SGNN_ERR_BAD_ARG;
+        if (EMA && (!ema[i] || (((uintptr_t)ema[i]) & 3))) return SGNN_ERR_BAD_ARG;
     }
     int64_t from = 0;
     bool first = true;
     while (from < n_tensors) {
-        int64_t to = from + 1;                     // a launch = up to OPT_MAXT consecutive tensors with the same host step count
-        while (to < n_tensors && to - from < OPT_MAXT && (!steps || steps[to] == steps[from])) ++to;
-        OptTensors T;
+        int64_t to = from + 1;                     // a launch = up to MAXT consecutive tensors with the same host step count
+        while (to < n_tensors && to - from < MAXT && (!steps || steps[to] == steps[from])) ++to;
+        typename OptArgs<EMA>::type T;
         const int blocks = opt_fill(T, params, grads, exp_avg, exp_avg_sq, numels, zero_grad, counter_slots, from, to);
+        if constexpr (EMA) {
+            for (int64_t i = from; i < to; ++i) T.e[i - from] = ema[i];
+            T.ema_decay = ema_decay; T.ema_warmup = ema_warmup;
+        }
         for (int64_t i = from; i < to && row_lens && row_seen && T.rows_t < 0; ++i) {
             const int64_t D = row_lens[i];
             if (!row_seen[i] || D < 4 || D > 256 || (D & (D - 1)) != 0 || numels[i] % D != 0) continue;      // 1..64 float4 lanes per row
             if ((((uintptr_t)params[i]) | ((uintptr_t)grads[i]) | ((uintptr_t)exp_avg[i]) | ((uintptr_t)exp_avg_sq[i])) & 15) continue;
+            if (EMA && (((uintptr_t)ema[i]) & 15)) continue;
             T.rows_t = (int)(i - from); T.row_lanes = (int)(D / 4); T.seen = row_seen[i];
         }
-        hipLaunchKernelGGL(optim_adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, T, partial, (int)n_partial, max_norm,
+        hipLaunchKernelGGL(optim_adam_kernel<EMA>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, T, partial, (int)n_partial, max_norm,
                            first ? coef_out : nullptr, lr, beta1, beta2, eps, (long long)(steps ? steps[from] : 0), step_counters,
                            lr_table, (long long)lr_len);
         SGNN_CHECK_LAUNCH();
@@ -359,8 +409,9 @@ extern "C" int sgnn_optim_adam(float* const* params, float* const* grads, float*
                                const int64_t* row_lens, unsigned char* const* row_seen,
                                const float* partial, int64_t n_partial, float max_norm, float* coef_out, void* stream)
 {
-    return optim_adam(params, grads, exp_avg, exp_avg_sq, numels, zero_grad, n_tensors, lr, nullptr, 0, beta1, beta2, eps, steps,
-                      step_counters, counter_slots, row_lens, row_seen, partial, n_partial, max_norm, coef_out, stream);
+    return optim_adam<false>(params, grads, exp_avg, exp_avg_sq, numels, zero_grad, n_tensors, lr, nullptr, 0, beta1, beta2, eps, steps,
+                             step_counters, counter_slots, row_lens, row_seen, partial, n_partial, max_norm, coef_out, nullptr, 0.f, 0,
+                             stream);
 }
 
 extern "C" int sgnn_optim_adam_lr_table(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
@@ -371,8 +422,95 @@ extern "C" int sgnn_optim_adam_lr_table(float* const* params, float* const* grad
                                         float* coef_out, void* stream)
 {
     if (!lr_table || lr_len < 1 || (((uintptr_t)lr_table) & 3)) return SGNN_ERR_BAD_ARG;
-    return optim_adam(params, grads, exp_avg, exp_avg_sq, numels, zero_grad, n_tensors, 0.f, lr_table, lr_len, beta1, beta2, eps,
-                      steps, step_counters, counter_slots, row_lens, row_seen, partial, n_partial, max_norm, coef_out, stream);
+    return optim_adam<false>(params, grads, exp_avg, exp_avg_sq, numels, zero_grad, n_tensors, 0.f, lr_table, lr_len, beta1, beta2, eps,
+                             steps, step_counters, counter_slots, row_lens, row_seen, partial, n_partial, max_norm, coef_out, nullptr,
+                             0.f, 0, stream);
+}
+
+extern "C" int sgnn_optim_adam_ema(float* const* params, float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                                   const int64_t* numels, const int32_t* zero_grad, int64_t n_tensors, float lr, float beta1,
+                                   float beta2, float eps, const int64_t* steps, const int64_t* step_counters,
+                                   const int64_t* counter_slots, const int64_t* row_lens, unsigned char* const* row_seen,
+                                   const float* partial, int64_t n_partial, float max_norm, float* coef_out, float* const* ema,
+                                   float ema_decay, int ema_warmup, void* stream)
+{
+    return optim_adam<true>(params, grads, exp_avg, exp_avg_sq, numels, zero_grad, n_tensors, lr, nullptr, 0, beta1, beta2, eps, steps,
+                            step_counters, counter_slots, row_lens, row_seen, partial, n_partial, max_norm, coef_out, ema, ema_decay,
+                            ema_warmup, stream);
+}
+
+extern "C" int sgnn_optim_adam_ema_lr_table(float* const* params, float* const* grads, float* const* exp_avg,
+                                            float* const* exp_avg_sq, const int64_t* numels, const int32_t* zero_grad,
+                                            int64_t n_tensors, const float* lr_table, int64_t lr_len, float beta1, float beta2,
+                                            float eps, const int64_t* steps, const int64_t* step_counters,
+                                            const int64_t* counter_slots, const int64_t* row_lens, unsigned char* const* row_seen,
+                                            const float* partial, int64_t n_partial, float max_norm, float* coef_out,
+                                            float* const* ema, float ema_decay, int ema_warmup, void* stream)
+{
+    if (!lr_table || lr_len < 1 || (((uintptr_t)lr_table) & 3)) return SGNN_ERR_BAD_ARG;
+    return optim_adam<true>(params, grads, exp_avg, exp_avg_sq, numels, zero_grad, n_tensors, 0.f, lr_table, lr_len, beta1, beta2, eps,
+                            steps, step_counters, counter_slots, row_lens, row_seen, partial, n_partial, max_norm, coef_out, ema,
+                            ema_decay, ema_warmup, stream);
+}
+
+
+// ---- exchange two lists of tensors in place ---------------------------------------------------------------------------------
+// a[i] <-> b[i], numels[i] floats each: how the weight averages get under a recorded validation forward, which reads the
+// parameters' own storage (optim.ClipAdam.swap_ema).  No temporary: every element is read from both sides and written to both
+// by the one lane that owns it.  float4 where both pointers of a pair are 16-byte aligned (+ a scalar tail), scalar otherwise.
+#define SWAP_MAXT 128
+struct SwapTensors {
+    float* a[SWAP_MAXT]; float* b[SWAP_MAXT];
+    long long n[SWAP_MAXT];
+    int blk[SWAP_MAXT + 1];
+    int count;
+};
+static_assert(sizeof(SwapTensors) + 256 <= 4096, "SwapTensors outgrew the kernel-argument segment");
+
+__global__ __launch_bounds__(256) void optim_swap_kernel(const SwapTensors T)
+{
+    const int b = blockIdx.x, t = opt_find(T, b), nb = T.blk[t + 1] - T.blk[t];
+    float* __restrict__ x = T.a[t]; float* __restrict__ y = T.b[t];
+    const int64_t n = T.n[t];
+    const int64_t first = (int64_t)(b - T.blk[t]) * 256 + threadIdx.x, stride = (int64_t)nb * 256;
+    if (((((uintptr_t)x) | ((uintptr_t)y)) & 15) == 0) {
+        const int64_t n4 = n >> 2;
+        float4* x4 = (float4*)x; float4* y4 = (float4*)y;
+        for (int64_t i = first; i < n4; i += stride) { const float4 u = x4[i], w = y4[i]; x4[i] = w; y4[i] = u; }
+        if (b == T.blk[t] && (int64_t)threadIdx.x < n - n4 * 4) {
+            const int64_t i = n4 * 4 + threadIdx.x;
+            const float u = x[i], w = y[i]; x[i] = w; y[i] = u;
+        }
+    } else {
+        for (int64_t i = first; i < n; i += stride) { const float u = x[i], w = y[i]; x[i] = w; y[i] = u; }
+    }
+}
+
+extern "C" int sgnn_optim_swap(float* const* a, float* const* b, const int64_t* numels, int64_t n_tensors, void* stream)
+{
+    if (n_tensors < 0 || (n_tensors && (!a || !b || !numels))) return SGNN_ERR_BAD_ARG;
+    for (int64_t i = 0; i < n_tensors; ++i) {
+        if (numels[i] < 0 || (numels[i] && (!a[i] || !b[i])) || ((((uintptr_t)a[i]) | ((uintptr_t)b[i])) & 3)) return SGNN_ERR_BAD_ARG;
+        // (two tensors that overlap without being the same one cannot be exchanged; the same one is its own exchange)
+        const uintptr_t lo = (uintptr_t)a[i], hi = (uintptr_t)b[i], len = (uintptr_t)numels[i] * 4;
+        if (lo != hi && lo < hi + len && hi < lo + len) return SGNN_ERR_BAD_ARG;
+    }
+    for (int64_t from = 0; from < n_tensors; from += SWAP_MAXT) {
+        const int64_t to = from + SWAP_MAXT < n_tensors ? from + SWAP_MAXT : n_tensors;
+        SwapTensors T;
+        int blocks = 0, k = 0;
+        for (int64_t i = from; i < to; ++i) {
+            if (numels[i] == 0 || a[i] == b[i]) continue;
+            T.a[k] = a[i]; T.b[k] = b[i]; T.n[k] = numels[i]; T.blk[k] = blocks;
+            blocks += opt_blocks(numels[i]);
+            ++k;
+        }
+        if (k == 0) continue;
+        T.count = k; T.blk[k] = blocks;
+        hipLaunchKernelGGL(optim_swap_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, T);
+        SGNN_CHECK_LAUNCH();
+    }
+    return SGNN_OK;
 }
 
 SGNN_DEFINE_WARM(optim)

@@ -2338,12 +2338,16 @@ class OptimTail:
                 self.seen[i] = torch.zeros(p.shape[0], dtype=torch.uint8, device=p.device)
                 self.row_len[i], self.seen_ptr[i] = D, self.seen[i].data_ptr()
 
-    def step(self, which, grads, lr, betas, eps, max_norm, steps=None, step_counters=None, lr_table=None):
+    def step(self, which, grads, lr, betas, eps, max_norm, steps=None, step_counters=None, lr_table=None, ema=None,
+             ema_decay=0.0, ema_warmup=False):
         """``which``: indices (ascending) of the parameters that have a gradient this step, ``grads`` theirs (float32,
         contiguous).  ``steps``: host step numbers per listed parameter -- or ``step_counters``: int64 device tensor over ALL
         parameters of the list (those of ``which`` advance).  ``lr_table``: a float32 device tensor read in place of ``lr`` --
-        step s takes entry min(s, len) - 1 (sgnn_optim_adam_lr_table).  Returns the (2,) device tensor [coefficient, total
-        norm] when clipping, else None."""
+        step s takes entry min(s, len) - 1 (sgnn_optim_adam_lr_table).  ``ema``: one float32 tensor per parameter of the list
+        (ALL of them, shaped like the parameters): the update also moves the average of every element it steps,
+        e += (1 - d_s) (p_new - e), d_s = ``ema_decay`` or with ``ema_warmup`` min(ema_decay, (1 + s) / (10 + s)) at the tensor's
+        step count s (sgnn_optim_adam_ema / _ema_lr_table); the average of a parameter outside ``which`` stays as it is.
+        Returns the (2,) device tensor [coefficient, total norm] when clipping, else None."""
         lib = _lib.load()
         empty = [j for j, p_i in enumerate(which) if self.numels[p_i] == 0]
         if empty:
@@ -2405,14 +2409,61 @@ class OptimTail:
                 slots, row_len.ctypes.data if self.seen else None, seen_ptr.ctypes.data if self.seen else None, _ptr(partial),
                 n_partial, float(max_norm) if partial is not None else 0.0, _ptr(out), st)
         head = (p_ptr.ctypes.data, g_ptr.ctypes.data, m_ptr.ctypes.data, v_ptr.ctypes.data, numels.ctypes.data, zero.ctypes.data, k)
-        if lr_table is None:
-            check(lib.sgnn_optim_adam(*head, float(lr), *tail), 'sgnn_optim_adam')
-        else:
+        if lr_table is not None:
             _req(lr_table, torch.float32, 'lr_table')
             if lr_table.numel() < 1 or lr_table.device != dev:
                 raise ValueError('lr_table must be a non-empty float32 tensor on the parameters\' device')
+        if ema is not None:
+            if not 0.0 <= float(ema_decay) < 1.0:
+                raise ValueError('ema_decay = %r must lie in [0, 1)' % (ema_decay,))
+            e_all = self._ema_ptrs(ema)
+            e_ptr = e_all if full else np.ascontiguousarray(e_all[idx])
+            avg = (e_ptr.ctypes.data, float(ema_decay), 1 if ema_warmup else 0)
+            if lr_table is None:
+                check(lib.sgnn_optim_adam_ema(*head, float(lr), *tail[:-1], *avg, st), 'sgnn_optim_adam_ema')
+            else:
+                check(lib.sgnn_optim_adam_ema_lr_table(*head, _ptr(lr_table), lr_table.numel(), *tail[:-1], *avg, st),
+                      'sgnn_optim_adam_ema_lr_table')
+        elif lr_table is None:
+            check(lib.sgnn_optim_adam(*head, float(lr), *tail), 'sgnn_optim_adam')
+        else:
             check(lib.sgnn_optim_adam_lr_table(*head, _ptr(lr_table), lr_table.numel(), *tail), 'sgnn_optim_adam_lr_table')
         return out
+
+    def _ema_ptrs(self, ema):
+        """The pointer table of the averages (they never move: built once per list), each checked against its parameter."""
+        kept = self.__dict__.get('_ema_kept')
+        if kept is not None and kept[0] is ema:
+            return kept[1]
+        if len(ema) != self.n:
+            raise ValueError('ema holds %d tensors for %d parameters' % (len(ema), self.n))
+        for i, e in enumerate(ema):
+            _req(e, torch.float32, 'ema')
+            if e.numel() != int(self.numels[i]) or e.device != self.params[i].device:
+                raise ValueError('ema of parameter %d does not match it' % i)
+        ptrs = np.array([e.data_ptr() for e in ema], dtype=np.uint64)
+        self._ema_kept = (ema, ptrs)
+        return ptrs
+
+    def swap(self, which, others):
+        """Exchange the contents of the parameters ``which`` (indices) and the tensors ``others`` (one per index, float32, same
+        sizes) in place (sgnn_optim_swap): no temporary, the storage of both stays where it is -- so a recorded forward that
+        reads the parameters' own storage reads what was in ``others``."""
+        pairs = [(self.params[i], o) for i, o in zip(which, others)]
+        if len(pairs) != len(list(which)):
+            raise ValueError('swap: one tensor per listed parameter')
+        for p, o in pairs:
+            _req(p, torch.float32, 'parameter')
+            _req(o, torch.float32, 'swap partner')
+            if o.numel() != p.numel() or o.device != p.device:
+                raise ValueError('swap: a partner does not match its parameter')
+        pairs = [(p, o) for p, o in pairs if p.numel() != 0]        # (an empty tensor has nothing to exchange and no address)
+        if not pairs:
+            return
+        a = np.array([p.data_ptr() for p, _ in pairs], dtype=np.uint64)
+        b = np.array([o.data_ptr() for _, o in pairs], dtype=np.uint64)
+        n = np.array([p.numel() for p, _ in pairs], dtype=np.int64)
+        check(_lib.load().sgnn_optim_swap(a.ctypes.data, b.ctypes.data, n.ctypes.data, len(pairs), _stream()), 'sgnn_optim_swap')
 
 
 _ZEROS = {}

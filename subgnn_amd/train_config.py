@@ -31,7 +31,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import checkpoint, config
+from . import checkpoint, config, schedule
 from . import lr_find as range_test
 from .SubGNN import SubGNN, dataset_paths
 from .graph_step import CapturedEvalStep, CapturedTrainStep, StepNotRecordable, make_capturable, make_eager, train_step
@@ -204,6 +204,11 @@ class Trainer:
         return stops training after that epoch (a pruned search trial) -- last.ckpt then names the next epoch to run."""
         if resume_from is not None and checkpoint.resume_blocker(model):
             raise ValueError(checkpoint.resume_blocker(model))
+        # the recipe around the step (schedule.py): hparams ema_decay / ema_warmup, lr_schedule / lr_warmup_steps / ..., and
+        # early_stop_patience / early_stop_min_delta -- all off by default
+        hp = model.hparams
+        schedule.check_hparams(hp)
+        schedule.refuse_multi_rank(hp)
         if not prepared:
             model.prepare_data()
         resume = None
@@ -219,7 +224,7 @@ class Trainer:
             if model.hparams.get('resample_anchor_patches') and model.__dict__.get('_resample_epoch', 0) != st['resample_epoch']:
                 model.__dict__['_resample_epoch'] = st['resample_epoch']
                 model._prepare_anchors_only()
-            checkpoint.load_checkpoint(model, resume)
+            checkpoint.load_checkpoint(model, resume, weights='raw')
         elif self.auto_lr_find:
             self._find_lr(model)
         if model.hparams.get('gc_freeze', True):
@@ -231,11 +236,31 @@ class Trainer:
             gc.freeze()
         # plain Adam over CUDA parameters (what configure_optimizers returns) becomes optim.ClipAdam: same update and clipping
         # rule, the embedding table in one HIP pass, the clip coefficient a device scalar (optim.accelerate)
-        opt = accelerate(model.configure_optimizers(), self.clip, capturable=self.hip_graph_step)
+        # hparams['lr_schedule'] / ['lr_warmup_steps']: the rate of every step of the run as a device table the (recorded) step
+        # indexes by its own count -- a host scheduler would be frozen into the recording.  Base rate: configure_optimizers'
+        # (auto_lr_find's suggestion on a fresh fit; on a resumed one the rate the interrupted fit trained at)
+        # hparams['ema_decay']: the update kernel also keeps an average of the weights, which is what the epoch is validated,
+        # ranked, checkpointed and tested with (exchanged in place around the validation, _swap_ema)
+        configured = model.configure_optimizers()
+        table = None
+        if schedule.scheduled(hp):
+            base = (resume['optimizer_states'][0]['param_groups'][0]['lr'] if resume is not None
+                    else getattr(configured, 'param_groups', [{}])[0].get('lr', hp.get('learning_rate')))
+            table = schedule.table_from_hparams(hp, float(base), len(model.train_dataloader()), self.max_epochs)
+            table = table.to(model.node_embeddings.weight.device)
+        opt = accelerate(configured, self.clip, capturable=self.hip_graph_step, lr_schedule=table,
+                         ema_decay=float(hp.get('ema_decay', 0) or 0), ema_warmup=bool(hp.get('ema_warmup') or False))
+        averaged = getattr(opt, 'ema', None) is not None
+        self._ema_run = (model, opt) if averaged else None
+        model.__dict__.pop('_loaded_weights', None)              # (the model holds this run's live weights from here on)
+        patience = hp.get('early_stop_patience')
+        stopper = schedule.EarlyStop(int(patience), hp.get('early_stop_min_delta') or 0, self.mode) if patience is not None else None
         start = 0
         if resume is not None:
             checkpoint.check_resumable(model, resume, opt)
             start = self._restore(model, opt, resume)
+            if stopper is not None and resume[checkpoint.RESUME_KEY].get('early_stop') is not None:
+                stopper.load(resume[checkpoint.RESUME_KEY]['early_stop'])     # (a checkpoint without the entry: a fresh counter)
             if self.auto_lr_find:                                # (the rate the interrupted fit found is the optimizer's)
                 model.hparams[range_test.lr_key(model.hparams, self.auto_lr_find)] = float(opt.param_groups[0]['lr'])
         captured = None
@@ -244,7 +269,11 @@ class Trainer:
         import time
         next_epoch = max(start, self.max_epochs)
         self.stopped_epoch = None
-        for epoch in range(start, self.max_epochs):
+        self._stopper = stopper
+        last = self.max_epochs
+        if stopper is not None and stopper.bad >= stopper.patience:          # a run that had stopped early stays stopped
+            self.stopped_epoch = next_epoch = last = start
+        for epoch in range(start, last):
             rec = None
             if self.phase_times is not None:
                 rec = {'replayed_steps': 0, 'eager_steps': 0, 'recordings': 0}
@@ -286,6 +315,8 @@ class Trainer:
                         rec['eager_steps'] += 1
             t_ph = self._phase(rec, 'train_steps_s', t_ph)
             model.eval()
+            if averaged:
+                self._swap_ema(model, opt)
             with torch.no_grad():
                 outs = self._validation_outputs(model)
                 t_ph = self._phase(rec, 'validation_steps_s', t_ph)
@@ -294,6 +325,8 @@ class Trainer:
                 drawn = model.__dict__.get('_resample_epoch', 0)      # (the anchor draw this epoch was validated with)
                 res = model.validation_epoch_end(outs)
                 t_ph = self._phase(rec, 'validation_epoch_end_s', t_ph)
+            if averaged:                                         # (before the epoch is kept: state_dict stays the raw weights)
+                self._swap_ema(model, opt)
             val = float(res['log'][self.monitor])
             if self.best is None or (val > self.best if self.mode == 'max' else val < self.best):
                 self.best = val
@@ -306,13 +339,28 @@ class Trainer:
             tl = float(torch.stack(losses).mean()) if losses else float('nan')
             self.history.append({'epoch': epoch, 'train_loss': tl, 'val_loss': float(res['avg_val_loss']), self.monitor: val})
             self.log('epoch %d  train_loss %.4f  val_loss %.4f  %s %.4f' % (epoch, tl, float(res['avg_val_loss']), self.monitor, val))
+            stop = stopper is not None and stopper.update(val)
             if epoch_callback is not None and epoch_callback(epoch, val):
                 self.stopped_epoch = next_epoch = epoch + 1
                 self.log('stopped after epoch %d by the epoch callback' % epoch)
                 break
+            if stop:
+                self.stopped_epoch = next_epoch = epoch + 1
+                self.log('stopped after epoch %d: %s has not improved by more than %g for %d epochs' % (
+                    epoch, self.monitor, stopper.min_delta, stopper.patience))
+                break
         if self.checkpoint_k > 0:
             self._write(model, opt, next_epoch)
         return self
+
+    def _swap_ema(self, model, opt):
+        """Parameters <-> their averages, in place (ClipAdam.swap_ema): the recorded eval forward reads the parameters' own
+        storage; what the model derived from the weights (the half-precision table) is refreshed by its next reader."""
+        if hasattr(model, 'invalidate_half_table'):
+            model.invalidate_half_table()
+        opt.swap_ema()
+        if hasattr(model, 'invalidate_half_table'):
+            model.invalidate_half_table()
 
     # -- checkpoints (checkpoint.py) ------------------------------------------------------------------------------------------
     def _state_tensors(self, model, opt):
@@ -350,8 +398,15 @@ class Trainer:
                                    'slot': free})
         return True
 
-    def _info(self, value, resample_epoch):
-        return {'monitor': self.monitor, 'mode': self.mode, 'value': value, 'resample_epoch': resample_epoch}
+    def _info(self, value, resample_epoch, model=None, opt=None):
+        """``ema_decay`` > 0: ``value`` is the AVERAGED model's, and ``ema_params`` names the parameters in the order of the
+        optimizer's state (whose 'ema' entries hold the averages): what checkpoint.load_checkpoint serves."""
+        info = {'monitor': self.monitor, 'mode': self.mode, 'value': value, 'resample_epoch': resample_epoch, 'ema_decay': 0.0}
+        if opt is not None and getattr(opt, 'ema', None) is not None:
+            names = {id(p): n for n, p in model.named_parameters()}
+            info['ema_decay'] = float(opt.ema_decay)
+            info['ema_params'] = [names[id(p)] for p in opt.param_groups[0]['params']]
+        return info
 
     def _write(self, model, opt, next_epoch):
         """The kept epochs' files and last.ckpt (the run's state now), written when fit returns."""
@@ -369,7 +424,7 @@ class Trainer:
             checkpoint.save({'epoch': meta['epoch'], 'global_step': meta['global_step'],
                              'state_dict': {k: t.cpu() for k, t in zip(keys, snap.bufs[:n])},
                              'optimizer_states': [checkpoint._optimizer_for_file(opt, refs, snap.bufs[n:])],
-                             checkpoint.INFO_KEY: self._info(e['value'], meta['resample_epoch'])}, d / e['file'])
+                             checkpoint.INFO_KEY: self._info(e['value'], meta['resample_epoch'], model, opt)}, d / e['file'])
             e['slot'] = None                                     # (on disk now)
         for f in self.__dict__.pop('_ck_stale', []):
             if (d / f).exists() and f not in {e['file'] for e in self.top_k.entries}:
@@ -383,9 +438,16 @@ class Trainer:
                   'metric_scores': list(model.metric_scores), 'history': list(self.history), 'best': self.best,
                   'top_k': [dict(e) for e in self.top_k.entries], 'k': self.checkpoint_k, 'monitor': self.monitor,
                   'mode': self.mode}
-        checkpoint.save({'epoch': int(next_epoch) - 1, 'global_step': self.global_step,
-                         'state_dict': checkpoint.to_cpu(model.state_dict()), 'optimizer_states': [checkpoint.to_cpu(opt.state_dict())],
-                         checkpoint.RESUME_KEY: resume}, d / checkpoint.LAST)
+        stopper = self.__dict__.get('_stopper')
+        if stopper is not None:
+            resume['early_stop'] = stopper.state()
+        last = {'epoch': int(next_epoch) - 1, 'global_step': self.global_step,
+                'state_dict': checkpoint.to_cpu(model.state_dict()), 'optimizer_states': [checkpoint.to_cpu(opt.state_dict())],
+                checkpoint.RESUME_KEY: resume}
+        if getattr(opt, 'ema', None) is not None:                # (the last epoch's averages can be served from it too)
+            last[checkpoint.INFO_KEY] = self._info(self.history[-1][self.monitor] if self.history else None,
+                                                   resume['resample_epoch'], model, opt)
+        checkpoint.save(last, d / checkpoint.LAST)
         self.checkpoint_write_s = time.perf_counter() - t0
 
     def _restore(self, model, opt, ck):
@@ -423,10 +485,20 @@ class Trainer:
         return self.checkpoint_dir / b['file'] if b is not None else None
 
     def test(self, model):
+        """After a fit with ``ema_decay`` > 0 the model this trainer trained is tested with its averaged weights (exchanged in
+        place and back) -- unless a checkpoint was loaded into it since: load_checkpoint has then put the weights to serve there."""
+        run = self.__dict__.get('_ema_run')
+        swap = run is not None and run[0] is model and model.__dict__.get('_loaded_weights') is None
+        if swap:
+            self._swap_ema(model, run[1])
         model.eval()
-        with torch.no_grad():
-            outs = [model.test_step(b, i) for i, b in enumerate(model.test_dataloader())]
-            return model.test_epoch_end(outs)
+        try:
+            with torch.no_grad():
+                outs = [model.test_step(b, i) for i, b in enumerate(model.test_dataloader())]
+                return model.test_epoch_end(outs)
+        finally:
+            if swap:
+                self._swap_ema(model, run[1])
 
 
 def write_hyperparams(results_dir, hp):
