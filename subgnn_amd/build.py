@@ -17,7 +17,7 @@ ARCH = 'gfx950'
 # of a row then copied the whole array (32 v_mov per row pair on the coarse levels)
 EXTRA_FLAGS = {'dtw.hip': ['-fno-honor-nans', '-mllvm', '-disable-promote-alloca-to-vector'],
                'dtw_exact.hip': ['-fno-honor-nans', '-mllvm', '-disable-promote-alloca-to-vector']}
-HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'dtw_cost.h'), os.path.join(CSRC, 'id_table.h'), os.path.join(CSRC, 'topk_order.h'), os.path.join(HERE, '..', 'include', 'subgnn_hip.h')]
+HEADERS = [os.path.join(CSRC, 'common.h'), os.path.join(CSRC, 'dtw_cost.h'), os.path.join(CSRC, 'id_table.h'), os.path.join(CSRC, 'loss_terms.h'), os.path.join(CSRC, 'topk_order.h'), os.path.join(HERE, '..', 'include', 'subgnn_hip.h')]
 
 
 def _hipcc():

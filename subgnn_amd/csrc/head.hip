@@ -24,26 +24,26 @@
 // Multi-label mode (HPO-NEURO: nn.BCEWithLogitsLoss, SubGNN.py:133, and the exact-match accuracy of su:108-124): the same two
 // bodies instantiated with ML = 1 as kernels of their own (head_fwd_ml_kernel, head_bwd_ml_kernel<NB>) -- the single-label
 // launches carry no argument and no branch for it.  `labels` is then the int64 (B, K) 0/1 indicator matrix (non-zero counts as
-// 1), a row's loss the sum over k of max(x, 0) - x y + log1p(exp(-|x|)), a row a hit when 1 / (1 + exp(-x)) > 0.5 (float32, as
-// torch.sigmoid(x) > 0.5 evaluates it: NOT x > 0) equals y in every column; out = [sum / (B K), hits / B, B K].  Nothing is saved
-// for the backward (no lse): dlogits = (sigmoid(x) - y) g / (B K) is recomputed from the logits.
+// 1), a row's loss the sum of its elements' terms, a row a hit when every column predicts its target; out = [sum / (B K), hits / B,
+// B K].  Nothing is saved for the backward (no lse): dlogits is recomputed from the logits.
 //
 // Class weights (torch's `weight` / `pos_weight` of the two loss modules built at SubGNN.py:133): the same two bodies with WT = 1,
 // again kernels of their own (headw_fwd_kernel, headw_fwd_ml_kernel, headw_bwd_kernel<NB>, headw_bwd_ml_kernel<NB>) that take the
 // weight rows as a SECOND argument -- the bare launches keep their argument block and their code.  The rows (K <= 32 floats each,
 // an absent one stands as ones) are loaded into LDS once per workgroup.  Single-label: a counted row's loss and its count are
 // multiplied by w[y], so out[2] = lse[B] = the sum of the counted rows' weights, which is what the backward divides by (weights of
-// 1.0 reproduce the bare launch bit for bit); w[y] is read only for y in [0, K).  Multi-label: the element loss is
-// c_k [(1 - y) x + L (log1p(exp(-|x|)) + max(-x, 0))] with L = 1 + (p_k - 1) y, its gradient c_k [(1 - y) - L sigmoid(-x)] g / (B K);
-// out[2] stays B K.  The accuracy is unweighted in both modes, and the dropout masks do not depend on the mode.
+// 1.0 reproduce the bare launch bit for bit); w[y] is read only for y in [0, K).  Multi-label: out[2] stays B K.  The accuracy is
+// unweighted in both modes, and the dropout masks do not depend on the mode.
 //
 // Shaped losses (label smoothing, focal loss: DESIGN 8p): one more compile-time axis SH on the same two bodies -- 0: as above, 1:
 // label smoothing eps (single-label), 2: focal gamma -- again kernels of their own (heads_fwd_kernel<ML, SH>, heads_bwd_kernel<NB, ML,
-// SH>) that always take the weight rows (an absent row stands as ones, as with WT = 1) and a by-value HeadShape {eps, gamma}: a
-// recorded step replays them.  The formulas are those stated in csrc/loss.hip; the backward recomputes p_t, f and q^gamma from the
-// logits and lse (nothing more is saved), smoothing adds W = sum_j w_j once per workgroup from the LDS rows.  out[2] / lse[B] stay the
-// divisor, the partials, the ticket and the summation orders are unchanged.
-#include "common.h"
+// SH>) that always take the weight rows (an absent row stands as ones, as with WT = 1) and a by-value LossShape {eps, gamma}: a
+// recorded step replays them.  The backward recomputes p_t, f and q^gamma from the logits and lse (nothing more is saved), smoothing
+// adds W = sum_j w_j once per workgroup from the LDS rows.  out[2] / lse[B] stay the divisor, the partials, the ticket and the
+// summation orders are unchanged.
+//
+// Every loss formula of every mode is written in loss_terms.h, which the stand-alone loss pairs (loss.hip) share.
+#include "loss_terms.h"
 
 #define HEAD_RB 32
 #define HEAD_THREADS 256
@@ -60,7 +60,6 @@ struct HeadFwd {
 };
 
 struct HeadWeights { const float* w; const float* pw; };     // the weighted launches' class weight rows (either nullable)
-struct HeadShape { float eps, gamma; };                      // the shaped launches': label smoothing | focal exponent (SH picks one)
 
 struct HeadBwd {
     const float* logits; const float* lse; const int64_t* labels; const float* g_loss; const float* g_logits; const float* rows;
@@ -87,19 +86,14 @@ __device__ __forceinline__ float head_dot4(const float4 a, const float4 b, float
     acc = fmaf(a.x, b.x, acc); acc = fmaf(a.y, b.y, acc); acc = fmaf(a.z, b.z, acc); return fmaf(a.w, b.w, acc);
 }
 
-// sigmoid that cannot overflow: exp of a non-positive argument only
-__device__ __forceinline__ float head_sigmoid(float x)
+// the weighted launches' rows into LDS, wts [2][K]: weight | pos_weight (an absent row stands as ones)
+__device__ __forceinline__ void head_stage_weights(float* wts, const HeadWeights Wt, int K)
 {
-    if (x >= 0.f) return 1.f / (1.f + expf(-x));
-    const float e = expf(x);
-    return e / (1.f + e);
+    for (int idx = threadIdx.x; idx < K; idx += HEAD_THREADS) { wts[idx] = Wt.w ? Wt.w[idx] : 1.f; wts[K + idx] = Wt.pw ? Wt.pw[idx] : 1.f; }
 }
 
-// q^gamma of the focal losses, q in [0, 1]: exactly 0 at q = 0
-__device__ __forceinline__ float head_qpow(float q, float gamma) { return q > 0.f ? powf(q, gamma) : 0.f; }
-
 template <int ML, int WT, int SH = 0>
-__device__ __forceinline__ void head_fwd_body(const HeadFwd A, const HeadWeights Wt, const HeadShape Sp = HeadShape{0.f, 0.f})
+__device__ __forceinline__ void head_fwd_body(const HeadFwd A, const HeadWeights Wt, const LossShape Sp = LossShape{0.f, 0.f})
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H1 = A.H1, H2 = A.H2, K = A.K, tid = threadIdx.x;
@@ -120,9 +114,8 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwd A, const HeadWeights
         W3s[idx] = k < H2 ? A.W3[c * H2 + k] : 0.f;
     }
     for (int idx = tid; idx < HEAD_RB * (H1p + H2p); idx += HEAD_THREADS) a1s[idx] = 0.f;      // (a1s and a2s are adjacent: pads stay zero)
-    if (WT) {
-        for (int idx = tid; idx < K; idx += HEAD_THREADS) { wts[idx] = Wt.w ? Wt.w[idx] : 1.f; wts[K + idx] = Wt.pw ? Wt.pw[idx] : 1.f; }
-    }
+    if (WT) head_stage_weights(wts, Wt, K);
+    const LossRow<false> cw{wts}, pw{wts + K};
     const bool drop = A.p > 0.f && A.rng != nullptr;
     uint64_t h01 = 0, h02 = 0;
     if (drop) {
@@ -201,38 +194,23 @@ __device__ __forceinline__ void head_fwd_body(const HeadFwd A, const HeadWeights
                 for (int k = 0; k < K; ++k) {
                     const float v = x[k];
                     const bool t = y[k] != 0;
-                    if (SH == 2) {
-                        const float z = t ? v : -v, e = expf(-fabsf(v)), inv = 1.f / (1.f + e);
-                        l += wts[k] * (t ? wts[K + k] : 1.f) * head_qpow(z >= 0.f ? e * inv : inv, Sp.gamma) * (log1pf(e) + fmaxf(-z, 0.f));
-                    } else if (WT) l += wts[k] * ((t ? 0.f : v) + (t ? wts[K + k] : 1.f) * (log1pf(expf(-fabsf(v))) + fmaxf(-v, 0.f)));
-                    else l += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
-                    all = all && ((1.f / (1.f + expf(-v)) > 0.5f) == t);           // torch.sigmoid(x) > 0.5 in float32
+                    l += loss_ml_term<WT, SH>(v, t, k, cw, pw, Sp);
+                    all = all && loss_ml_hit(v, t);
                 }
                 loss += l; hit += all ? 1.f : 0.f; cnt += (float)K;
             }
         } else if (A.labels && tid < nr) {
             const float* x = lgs + tid * K;
-            float m = x[0];
-            int am = 0;
-            for (int k = 1; k < K; ++k) { const float v = x[k]; if (v > m) { m = v; am = k; } }       // first maximum, as argmax
-            float sum = 0.f;
-            for (int k = 0; k < K; ++k) sum += expf(x[k] - m);
-            const float l = m + logf(sum);
+            int am;
+            const float l = loss_lse_argmax(x, K, am);
             A.lse[row0 + tid] = l;
             const int64_t y = A.labels[row0 + tid];
             if (y >= 0 && y < K) {
-                const float wy = WT ? wts[y] : 1.f;
-                if (SH == 1) {
-                    float s = 0.f;
-                    for (int k = 0; k < K; ++k) s += wts[k] * (l - x[k]);
-                    loss += (1.f - Sp.eps) * wy * (l - x[y]) + (Sp.eps / (float)K) * s;
-                } else if (SH == 2) {
-                    const float lp = x[y] - l;
-                    loss += wy * head_qpow(fmaxf(-expm1f(lp), 0.f), Sp.gamma) * (-lp);
-                } else if (WT) loss += wy * (l - x[y]); else loss += l - x[y];
+                const float wy = WT ? cw(y) : 1.f;
+                loss += loss_sl_row<WT, SH>(x, K, y, l, wy, cw, Sp);
                 hit += (am == (int)y) ? 1.f : 0.f; cnt += wy;
             }
-            else if (y != -100ll) { loss = __builtin_nanf(""); cnt += 1.f; }
+            else if (y != SGNN_CE_IGNORE_INDEX) { loss = __builtin_nanf(""); cnt += 1.f; }
         }
         __syncthreads();
     }
@@ -277,14 +255,14 @@ __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_kernel(const HeadFwd A)
 __global__ __launch_bounds__(HEAD_THREADS) void head_fwd_ml_kernel(const HeadFwd A) { head_fwd_body<1, 0>(A, HeadWeights{nullptr, nullptr}); }
 __global__ __launch_bounds__(HEAD_THREADS) void headw_fwd_kernel(const HeadFwd A, const HeadWeights Wt) { head_fwd_body<0, 1>(A, Wt); }
 __global__ __launch_bounds__(HEAD_THREADS) void headw_fwd_ml_kernel(const HeadFwd A, const HeadWeights Wt) { head_fwd_body<1, 1>(A, Wt); }
-template <int ML, int SH> __global__ __launch_bounds__(HEAD_THREADS) void heads_fwd_kernel(const HeadFwd A, const HeadWeights Wt, const HeadShape Sp) { head_fwd_body<ML, 1, SH>(A, Wt, Sp); }
+template <int ML, int SH> __global__ __launch_bounds__(HEAD_THREADS) void heads_fwd_kernel(const HeadFwd A, const HeadWeights Wt, const LossShape Sp) { head_fwd_body<ML, 1, SH>(A, Wt, Sp); }
 
 // partial layout of one workgroup: [gW3 (K H2) | gb3 (K) | gW2 (H2 H1) | gb2 (H2) | gb1 (H1)]
 __host__ __device__ static inline int64_t head_partial_floats(int H1, int H2, int K) { return (int64_t)K * H2 + K + (int64_t)H2 * H1 + H2 + H1; }
 
 // NB: 4 x 4 blocks of gW2 a thread keeps in registers (1: up to 64 x 64 weights, 2: 128 x 64, 4: 128 x 128)
 template <int NB, int ML, int WT, int SH = 0>
-__device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights Wt, const HeadShape Sp = HeadShape{0.f, 0.f})
+__device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights Wt, const LossShape Sp = LossShape{0.f, 0.f})
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int H1 = A.H1, H2 = A.H2, K = A.K, tid = threadIdx.x;
@@ -306,9 +284,8 @@ __device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights
         W3s[idx] = k < H2 ? A.W3[c * H2 + k] : 0.f;
     }
     for (int idx = tid; idx < HEAD_RB * (2 * H2p + 2 * H1p); idx += HEAD_THREADS) dz2s[idx] = 0.f;    // (adjacent: all pads zero)
-    if (WT) {
-        for (int idx = tid; idx < K; idx += HEAD_THREADS) { wts[idx] = Wt.w ? Wt.w[idx] : 1.f; wts[K + idx] = Wt.pw ? Wt.pw[idx] : 1.f; }
-    }
+    if (WT) head_stage_weights(wts, Wt, K);
+    const LossRow<false> cw{wts}, pw{wts + K};
     const int64_t P = head_partial_floats(H1, H2, K);
     float* part = A.partial + (int64_t)blockIdx.x * P;
     const float gscale = (A.labels && A.g_loss) ? A.g_loss[0] / A.rows[0] : 0.f;
@@ -331,38 +308,12 @@ __device__ __forceinline__ void head_bwd_body(const HeadBwd A, const HeadWeights
         for (int idx = tid; idx < nr * K; idx += HEAD_THREADS) {
             const int r = idx / K, c = idx - r * K;
             float v = 0.f;
-            if (ML) {
-                if (SH == 2) {
-                    if (A.labels && A.g_loss) {
-                        const bool t = A.labels[row0 * K + idx] != 0;
-                        const float xv = A.logits[row0 * K + idx], z = t ? xv : -xv, e = expf(-fabsf(xv)), inv = 1.f / (1.f + e);
-                        const float q = z >= 0.f ? e * inv : inv, pt = z >= 0.f ? inv : e * inv;
-                        const float gq = wts[c] * (t ? wts[K + c] : 1.f) * head_qpow(q, Sp.gamma)
-                                         * (q + Sp.gamma * pt * (log1pf(e) + fmaxf(-z, 0.f))) * gscale;
-                        v = t ? -gq : gq;
-                    }
-                } else if (WT) {
-                    if (A.labels && A.g_loss) {
-                        const bool t = A.labels[row0 * K + idx] != 0;
-                        v = wts[c] * ((t ? 0.f : 1.f) - (t ? wts[K + c] : 1.f) * head_sigmoid(-A.logits[row0 * K + idx])) * gscale;
-                    }
-                } else if (A.labels && A.g_loss)
-                    v = (head_sigmoid(A.logits[row0 * K + idx]) - (A.labels[row0 * K + idx] != 0 ? 1.f : 0.f)) * gscale;
-            } else if (A.labels && A.g_loss) {
-                const int64_t y = A.labels[row0 + r];
-                if (y >= 0 && y < K) {
-                    if (SH == 1) {
-                        const float pc = expf(A.logits[row0 * K + idx] - A.lse[row0 + r]);
-                        v = ((1.f - Sp.eps) * wts[y] * (pc - (c == (int)y ? 1.f : 0.f)) + (Sp.eps / (float)K) * (Wsum * pc - wts[c])) * gscale;
-                    } else if (SH == 2) {
-                        const float ls = A.lse[row0 + r], pc = expf(A.logits[row0 * K + idx] - ls);
-                        const float lp = A.logits[(row0 + r) * K + y] - ls, q = fmaxf(-expm1f(lp), 0.f);
-                        const float f = q > 0.f ? powf(q, Sp.gamma) * (1.f - Sp.gamma * expf(lp) * (lp / q)) : 0.f;
-                        v = wts[y] * f * (pc - (c == (int)y ? 1.f : 0.f)) * gscale;
-                    } else {
-                        v = (expf(A.logits[row0 * K + idx] - A.lse[row0 + r]) - (c == (int)y ? 1.f : 0.f)) * gscale;
-                        if (WT) v *= wts[y];
-                    }
+            if (A.labels && A.g_loss) {                  // (only a weighted multi-label term reads its column index)
+                if (ML) v = loss_ml_grad<WT, SH>(A.logits[row0 * K + idx], A.labels[row0 * K + idx] != 0, WT ? c : 0, cw, pw, Sp, gscale);
+                else {
+                    const int64_t y = A.labels[row0 + r];
+                    if (y >= 0 && y < K)
+                        v = loss_sl_grad<WT, SH>(A.logits[row0 * K + idx], A.logits + (row0 + r) * K + y, K, c, y, A.lse[row0 + r], cw, Wsum, Sp, gscale);
                 }
             }
             if (A.g_logits) v += A.g_logits[row0 * K + idx];
@@ -467,7 +418,7 @@ template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_kerne
 template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void head_bwd_ml_kernel(const HeadBwd A) { head_bwd_body<NB, 1, 0>(A, HeadWeights{nullptr, nullptr}); }
 template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void headw_bwd_kernel(const HeadBwd A, const HeadWeights Wt) { head_bwd_body<NB, 0, 1>(A, Wt); }
 template <int NB> __global__ __launch_bounds__(HEAD_THREADS) void headw_bwd_ml_kernel(const HeadBwd A, const HeadWeights Wt) { head_bwd_body<NB, 1, 1>(A, Wt); }
-template <int NB, int ML, int SH> __global__ __launch_bounds__(HEAD_THREADS) void heads_bwd_kernel(const HeadBwd A, const HeadWeights Wt, const HeadShape Sp) { head_bwd_body<NB, ML, 1, SH>(A, Wt, Sp); }
+template <int NB, int ML, int SH> __global__ __launch_bounds__(HEAD_THREADS) void heads_bwd_kernel(const HeadBwd A, const HeadWeights Wt, const LossShape Sp) { head_bwd_body<NB, ML, 1, SH>(A, Wt, Sp); }
 
 // ---- A^T B for tall operands: partial sums over row blocks (fp32 MFMA) ----------------------------------------------------------
 // part[blk][m][n] = sum over the block's rows r of A[r][m] B[r][n].  blockIdx.x = row block (four wavefronts of `wr` rows each),
@@ -624,21 +575,27 @@ static int head_set_lds(const void* kernel, size_t bytes)
     return 0;
 }
 
+// one launch of a head kernel on `blocks` workgroups with `lds` bytes of dynamic LDS
+struct HeadLaunch {
+    int64_t blocks; size_t lds; void* stream;
+    template <class... Args> int operator()(void (*kernel)(Args...), const Args&... args) const
+    {
+        if (head_set_lds((const void*)kernel, lds) != 0) return SGNN_ERR_LAUNCH;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(HEAD_THREADS), lds, (hipStream_t)stream, args...);
+        SGNN_CHECK_LAUNCH();
+        return SGNN_OK;
+    }
+};
+
 // ml: `labels` is the (B, K) indicator matrix and the launch is head_fwd_ml_kernel (no lse).  cw / pw: DEVICE rows of K class
 // weights, nullable; with labels and either of them the launch is the weighted kernel (pw: multi-label only)
-// label_smoothing in [0, 1) (single-label only), focal_gamma finite and >= 0, at most one of them non-zero
-static inline bool head_shape_ok(bool ml, float eps, float gamma)
-{
-    return eps >= 0.f && eps < 1.f && gamma >= 0.f && gamma <= 3.0e38f && !(eps > 0.f && gamma > 0.f) && !(ml && eps > 0.f);
-}
-
 // eps / gamma: with labels and either of them non-zero the launch is the shaped kernel (heads_fwd_kernel<ML, SH>)
 static int head_fwd_launch(bool ml, const float* cw, const float* pw, const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
                            const float* W3, const float* b3, const int64_t* labels, float p, int64_t* rng, float* a1, float* a2,
                            float* logits, float* lse, float* out, void* workspace, int64_t workspace_bytes, void* stream,
                            float eps = 0.f, float gamma = 0.f)
 {
-    if (!head_shape_ok(ml, eps, gamma)) return SGNN_ERR_BAD_ARG;
+    if (!loss_shape_ok(ml, eps, gamma)) return SGNN_ERR_BAD_ARG;
     if (!z1 || !W2 || !W3 || !a1 || !a2 || !logits || B < 1 || !(p >= 0.f && p < 1.f)) return SGNN_ERR_BAD_ARG;
     if (!sgnn_head_supported(H1, H2, K)) return SGNN_ERR_UNSUPPORTED_D;
     if (labels && ((!ml && !lse) || !out)) return SGNN_ERR_BAD_ARG;
@@ -648,7 +605,7 @@ static int head_fwd_launch(bool ml, const float* cw, const float* pw, const floa
     const bool weighted = shaped || (labels && (cw || pw));
     HeadWeights Wt;
     Wt.w = cw; Wt.pw = pw;
-    const HeadShape Sp{eps, gamma};
+    const LossShape Sp{eps, gamma};
     HeadFwd A;
     A.z1 = z1; A.W2 = W2; A.b2 = b2; A.W3 = W3; A.b3 = b3; A.labels = labels; A.rng = (p > 0.f) ? rng : nullptr;
     A.B = B; A.H1 = (int)H1; A.H2 = (int)H2; A.K = (int)K; A.p = p;
@@ -658,26 +615,11 @@ static int head_fwd_launch(bool ml, const float* cw, const float* pw, const floa
     A.ticket = (unsigned*)((char*)workspace + 3 * nb * 4);
     const int64_t H1p = (H1 + 3) & ~3ll, H2p = (H2 + 3) & ~3ll, H2e = (H2 + 1) & ~1ll;
     const size_t lds = (size_t)(H2e * (H1p + 4) + K * (H2p + 4) + HEAD_RB * (H1p + H2p + K) + (weighted ? 2 * K : 0)) * 4;
-#define HEAD_FWD_S(ML_, SH_) do { if (head_set_lds((const void*)heads_fwd_kernel<ML_, SH_>, lds) != 0) return SGNN_ERR_LAUNCH; \
-                                  hipLaunchKernelGGL((heads_fwd_kernel<ML_, SH_>), dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt, Sp); } while (0)
-    if (shaped) {
-        if (ml) HEAD_FWD_S(1, 2); else if (eps > 0.f) HEAD_FWD_S(0, 1); else HEAD_FWD_S(0, 2);
-    } else if (weighted && ml) {
-        if (head_set_lds((const void*)headw_fwd_ml_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
-        hipLaunchKernelGGL(headw_fwd_ml_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt);
-    } else if (weighted) {
-        if (head_set_lds((const void*)headw_fwd_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
-        hipLaunchKernelGGL(headw_fwd_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt);
-    } else if (ml) {
-        if (head_set_lds((const void*)head_fwd_ml_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
-        hipLaunchKernelGGL(head_fwd_ml_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A);
-    } else {
-        if (head_set_lds((const void*)head_fwd_kernel, lds) != 0) return SGNN_ERR_LAUNCH;
-        hipLaunchKernelGGL(head_fwd_kernel, dim3((unsigned)nb), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A);
-    }
-#undef HEAD_FWD_S
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
+    const HeadLaunch launch{nb, lds, stream};
+    if (shaped && eps > 0.f) return launch(heads_fwd_kernel<0, 1>, A, Wt, Sp);
+    if (shaped) return launch(ml ? heads_fwd_kernel<1, 2> : heads_fwd_kernel<0, 2>, A, Wt, Sp);
+    if (weighted) return launch(ml ? headw_fwd_ml_kernel : headw_fwd_kernel, A, Wt);
+    return launch(ml ? head_fwd_ml_kernel : head_fwd_kernel, A);
 }
 
 extern "C" int sgnn_head_fwd(const float* z1, int64_t B, int64_t H1, int64_t H2, int64_t K, const float* W2, const float* b2,
@@ -736,12 +678,22 @@ extern "C" int sgnn_head_fwd_ml_shaped(const float* z1, int64_t B, int64_t H1, i
                            workspace, workspace_bytes, stream, 0.f, focal_gamma);
 }
 
+// the backward kernel of a mode at NB blocks of gW2 per thread (sh: 0, or the shaped kernels' SH)
+template <int NB>
+static int head_bwd_pick(const HeadLaunch& launch, bool ml, bool weighted, int sh, const HeadBwd& A, const HeadWeights& Wt, const LossShape& Sp)
+{
+    if (sh == 1) return launch(heads_bwd_kernel<NB, 0, 1>, A, Wt, Sp);
+    if (sh == 2) return launch(ml ? heads_bwd_kernel<NB, 1, 2> : heads_bwd_kernel<NB, 0, 2>, A, Wt, Sp);
+    if (weighted) return launch(ml ? headw_bwd_ml_kernel<NB> : headw_bwd_kernel<NB>, A, Wt);
+    return launch(ml ? head_bwd_ml_kernel<NB> : head_bwd_kernel<NB>, A);
+}
+
 static int head_bwd_launch(bool ml, const float* cw, const float* pw, const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,
                            const float* grad_logits, const float* rows, const float* a1, const float* a2, const float* W2,
                            const float* W3, int64_t B, int64_t H1, int64_t H2, int64_t K, float p, float* dz1, float* partial,
                            void* stream, float eps = 0.f, float gamma = 0.f)
 {
-    if (!head_shape_ok(ml, eps, gamma)) return SGNN_ERR_BAD_ARG;
+    if (!loss_shape_ok(ml, eps, gamma)) return SGNN_ERR_BAD_ARG;
     if (!a1 || !a2 || !W2 || !W3 || !dz1 || !partial || B < 1 || !(p >= 0.f && p < 1.f)) return SGNN_ERR_BAD_ARG;
     if (!sgnn_head_supported(H1, H2, K)) return SGNN_ERR_UNSUPPORTED_D;
     if (grad_loss && (!labels || !logits || (!ml && !lse) || !rows)) return SGNN_ERR_BAD_ARG;
@@ -750,7 +702,7 @@ static int head_bwd_launch(bool ml, const float* cw, const float* pw, const floa
     const bool weighted = shaped || (grad_loss && (cw || pw));
     HeadWeights Wt;
     Wt.w = cw; Wt.pw = pw;
-    const HeadShape Sp{eps, gamma};
+    const LossShape Sp{eps, gamma};
     HeadBwd A;
     A.logits = logits; A.lse = lse; A.labels = labels; A.g_loss = grad_loss; A.g_logits = grad_logits; A.rows = rows;
     A.a1 = a1; A.a2 = a2; A.W2 = W2; A.W3 = W3; A.B = B; A.H1 = (int)H1; A.H2 = (int)H2; A.K = (int)K;
@@ -758,31 +710,12 @@ static int head_bwd_launch(bool ml, const float* cw, const float* pw, const floa
     A.dz1 = dz1; A.partial = partial;
     const int64_t H1p = (H1 + 3) & ~3ll, H2p = (H2 + 3) & ~3ll, H1e = (H1 + 1) & ~1ll;
     const size_t lds = (size_t)(H1e * (H2p + 4) + K * H2p + HEAD_RB * (K + 2 * H2p + 2 * H1p) + (weighted ? 2 * K : 0)) * 4;
-    const int64_t nblocks = (H2p / 4) * (H1p / 4);
-#define HEAD_BWD(KERNEL, NB) do { if (head_set_lds((const void*)KERNEL<NB>, lds) != 0) return SGNN_ERR_LAUNCH; \
-                                  hipLaunchKernelGGL(KERNEL<NB>, dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A); } while (0)
-#define HEAD_BWD_W(KERNEL, NB) do { if (head_set_lds((const void*)KERNEL<NB>, lds) != 0) return SGNN_ERR_LAUNCH; \
-                                    hipLaunchKernelGGL(KERNEL<NB>, dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt); } while (0)
-#define HEAD_BWD_S(NB, ML_, SH_) do { if (head_set_lds((const void*)heads_bwd_kernel<NB, ML_, SH_>, lds) != 0) return SGNN_ERR_LAUNCH; \
-                                      hipLaunchKernelGGL((heads_bwd_kernel<NB, ML_, SH_>), dim3((unsigned)head_blocks(B)), dim3(HEAD_THREADS), lds, (hipStream_t)stream, A, Wt, Sp); } while (0)
-#define HEAD_BWD_S3(ML_, SH_) do { if (nblocks <= HEAD_THREADS) HEAD_BWD_S(1, ML_, SH_); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD_S(2, ML_, SH_); else HEAD_BWD_S(4, ML_, SH_); } while (0)
-    if (shaped) {
-        if (ml) HEAD_BWD_S3(1, 2); else if (eps > 0.f) HEAD_BWD_S3(0, 1); else HEAD_BWD_S3(0, 2);
-    } else if (weighted && ml) {
-        if (nblocks <= HEAD_THREADS) HEAD_BWD_W(headw_bwd_ml_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD_W(headw_bwd_ml_kernel, 2); else HEAD_BWD_W(headw_bwd_ml_kernel, 4);
-    } else if (weighted) {
-        if (nblocks <= HEAD_THREADS) HEAD_BWD_W(headw_bwd_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD_W(headw_bwd_kernel, 2); else HEAD_BWD_W(headw_bwd_kernel, 4);
-    } else if (ml) {
-        if (nblocks <= HEAD_THREADS) HEAD_BWD(head_bwd_ml_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD(head_bwd_ml_kernel, 2); else HEAD_BWD(head_bwd_ml_kernel, 4);
-    } else {
-        if (nblocks <= HEAD_THREADS) HEAD_BWD(head_bwd_kernel, 1); else if (nblocks <= 2 * HEAD_THREADS) HEAD_BWD(head_bwd_kernel, 2); else HEAD_BWD(head_bwd_kernel, 4);
-    }
-#undef HEAD_BWD
-#undef HEAD_BWD_W
-#undef HEAD_BWD_S
-#undef HEAD_BWD_S3
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
+    const int64_t nblocks = (H2p / 4) * (H1p / 4);      // the 4 x 4 blocks of gW2: NB of them per thread
+    const HeadLaunch launch{head_blocks(B), lds, stream};
+    const int sh = !shaped ? 0 : (eps > 0.f ? 1 : 2);
+    if (nblocks <= HEAD_THREADS) return head_bwd_pick<1>(launch, ml, weighted, sh, A, Wt, Sp);
+    if (nblocks <= 2 * HEAD_THREADS) return head_bwd_pick<2>(launch, ml, weighted, sh, A, Wt, Sp);
+    return head_bwd_pick<4>(launch, ml, weighted, sh, A, Wt, Sp);
 }
 
 extern "C" int sgnn_head_bwd(const float* logits, const float* lse, const int64_t* labels, const float* grad_loss,

@@ -8,28 +8,15 @@
 // template on WT; the bare kernels are its WT = 0 instantiations under their old names and argument lists, the weighted ones
 // (ce_fwd_weighted_kernel, ...) kernels of their own that read the weight rows from global memory (any K).  Single-label: a
 // counted row's loss and count are multiplied by w[y] -- the third partial becomes the sum of weights, which the finish writes
-// to lse[B] as before; w[y] is read only for y in [0, K).  Multi-label: c_k [(1 - y) x + L (log1p(exp(-|x|)) + max(-x, 0))] with
-// L = 1 + (p_k - 1) y; the mean stays over B K.
+// to lse[B] as before; w[y] is read only for y in [0, K).  Multi-label: the mean stays over B K.
 //
 // Shaped losses (label smoothing and focal loss): a further compile-time axis SH on the same bodies (0: as above; 1:
 // label smoothing eps, single-label only; 2: focal gamma).  The SH = 0 instantiations are the kernels above; SH > 0 are kernels of
 // their own (ce_fwd_shaped_kernel<SH>, ce_bwd_shaped_kernel<SH>, bce_fwd_focal_kernel, bce_bwd_focal_kernel) that always take the
 // weight rows (an absent one stands as ones) and a by-value LossShape {eps, gamma}.
-//   smoothing  row loss (1 - eps) w_y (lse - x_y) + (eps / K) sum_k w_k (lse - x_k); gradient [(1 - eps) w_y (p_k - [k == y]) +
-//              (eps / K) (W p_k - w_k)] g / D with W = sum_j w_j (added once per workgroup in a fixed order) and D = sum w_y
-//   focal      lp = x_y - lse, q = -expm1(lp): row loss w_y q^gamma (-lp); gradient w_y f (p_k - [k == y]) g / D with
-//              f = q^gamma (1 - gamma p_t lp / q), and loss = f = 0 at q = 0 (lp / q is of order 1: nothing overflows)
-//   focal, multi-label   z = x for a positive, -x for a negative, e = exp(-|x|), l = log1p(e) + max(-z, 0), q = sigmoid(-z), p_t =
-//              sigmoid(z), both from e: element loss c L q^gamma l, gradient -+ c L q^gamma (q + gamma p_t l) g / (B K)
-// Partials, the finish kernels and the summation orders are those of the bare kernels.
-#include "common.h"
-
-#define SGNN_CE_IGNORE_INDEX (-100ll)
-
-struct LossShape { float eps, gamma; };                     // label smoothing | focal exponent (SH picks which one is read)
-
-// q^gamma of the focal losses, q in [0, 1]: exactly 0 at q = 0
-__device__ __forceinline__ float loss_qpow(float q, float gamma) { return q > 0.f ? powf(q, gamma) : 0.f; }
+// Every formula is written in loss_terms.h, which the fused head shares.  Partials, the finish kernels and the summation orders
+// are those of the bare kernels.
+#include "loss_terms.h"
 
 // thread per row; per-workgroup partial sums added in a fixed order (bit-reproducible)
 template <int WT, int SH = 0>
@@ -43,26 +30,15 @@ __device__ __forceinline__ void ce_fwd_body(const float* __restrict__ logits, co
     float loss = 0.f, hit = 0.f, cnt = 0.f;
     if (r < B) {
         const float* x = logits + r * K;
-        float m = x[0];
-        int32_t am = 0;
-        for (int32_t k = 1; k < K; ++k) { const float v = x[k]; if (v > m) { m = v; am = k; } }      // first maximum, as argmax
-        float sum = 0.f;
-        for (int32_t k = 0; k < K; ++k) sum += expf(x[k] - m);
-        const float l = m + logf(sum);
+        int am;
+        const float l = loss_lse_argmax(x, K, am);
         lse[r] = l;
         const int64_t y = labels[r];
         if (y >= 0 && y < K) {
+            const LossRow<SH != 0> w{weight};             // (the shaped kernels' row is nullable: an absent one stands as ones)
             hit = (am == (int32_t)y) ? 1.f : 0.f;
-            if (SH == 1) {                                // (weight: nullable, an absent row stands as ones)
-                cnt = weight ? weight[y] : 1.f;
-                float s = 0.f;
-                for (int32_t k = 0; k < K; ++k) s += (weight ? weight[k] : 1.f) * (l - x[k]);
-                loss = (1.f - Sp.eps) * cnt * (l - x[y]) + (Sp.eps / (float)K) * s;
-            } else if (SH == 2) {
-                cnt = weight ? weight[y] : 1.f;
-                const float lp = x[y] - l, q = fmaxf(-expm1f(lp), 0.f);
-                loss = cnt * loss_qpow(q, Sp.gamma) * (-lp);
-            } else if (WT) { cnt = weight[y]; loss = cnt * (l - x[y]); } else { loss = l - x[y]; cnt = 1.f; }
+            cnt = WT ? w(y) : 1.f;
+            loss = loss_sl_row<WT, SH>(x, K, y, l, cnt, w, Sp);
         }
         else if (y != SGNN_CE_IGNORE_INDEX) { loss = __builtin_nanf(""); cnt = 1.f; }
     }
@@ -120,7 +96,7 @@ __global__ __launch_bounds__(64) void ce_finish_kernel(const float* __restrict__
     }
 }
 
-// d loss / d logits[r, k] = (softmax(r)[k] - [k == label r]) * grad_loss / (rows not ignored)   [WT: * w[label r] / (sum of weights)]
+// thread per logit: d loss / d logits[r, k] (loss_sl_grad) at scale = grad_loss / lse[B], the divisor the finish left there
 template <int WT, int SH = 0>
 __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, const int64_t* __restrict__ labels,
                                             const float* __restrict__ lse, const float* __restrict__ grad_loss, int64_t B, int32_t K,
@@ -128,11 +104,12 @@ __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, co
                                             const LossShape Sp = LossShape{0.f, 0.f})
 {
     const int64_t t = blockIdx.x * 256ll + threadIdx.x;
+    const LossRow<SH != 0> w{weight};                       // (the shaped kernels' row is nullable: an absent one stands as ones)
     float W = 0.f;
     if (SH == 1) {                                          // W = sum of the class weights: strided sums, then a fixed tree
         __shared__ float sh_w[256];
         float s = 0.f;
-        for (int32_t k = threadIdx.x; k < K; k += 256) s += weight ? weight[k] : 1.f;
+        for (int32_t k = threadIdx.x; k < K; k += 256) s += w(k);
         sh_w[threadIdx.x] = s;
         __syncthreads();
         for (int o = 128; o > 0; o >>= 1) {
@@ -146,22 +123,7 @@ __device__ __forceinline__ void ce_bwd_body(const float* __restrict__ logits, co
     const int32_t k = (int32_t)(t - r * K);
     const int64_t y = labels[r];
     const float scale = grad_loss[0] / lse[B];
-    float v = 0.f;
-    if (y >= 0 && y < K) {
-        if (SH == 1) {
-            const float pk = expf(logits[t] - lse[r]), wy = weight ? weight[y] : 1.f, wk = weight ? weight[k] : 1.f;
-            v = ((1.f - Sp.eps) * wy * (pk - (k == (int32_t)y ? 1.f : 0.f)) + (Sp.eps / (float)K) * (W * pk - wk)) * scale;
-        } else if (SH == 2) {
-            const float pk = expf(logits[t] - lse[r]), wy = weight ? weight[y] : 1.f;
-            const float lp = logits[r * K + y] - lse[r], q = fmaxf(-expm1f(lp), 0.f);
-            const float f = q > 0.f ? powf(q, Sp.gamma) * (1.f - Sp.gamma * expf(lp) * (lp / q)) : 0.f;
-            v = wy * f * (pk - (k == (int32_t)y ? 1.f : 0.f)) * scale;
-        } else {
-            v = (expf(logits[t] - lse[r]) - (k == (int32_t)y ? 1.f : 0.f)) * scale;
-            if (WT) v *= weight[y];
-        }
-    }
-    grad_logits[t] = v;
+    grad_logits[t] = (y >= 0 && y < K) ? loss_sl_grad<WT, SH>(logits[t], logits + r * K + y, K, k, y, lse[r], w, W, Sp, scale) : 0.f;
 }
 
 __global__ __launch_bounds__(256) void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ labels,
@@ -190,12 +152,6 @@ __global__ __launch_bounds__(256) void ce_bwd_shaped_kernel(const float* __restr
 
 static inline int64_t ce_blocks(int64_t B) { return (B + 255) / 256; }
 
-// label_smoothing in [0, 1), focal_gamma finite and >= 0, at most one of them non-zero
-static inline bool loss_shape_ok(float eps, float gamma)
-{
-    return eps >= 0.f && eps < 1.f && gamma >= 0.f && gamma <= 3.0e38f && !(eps > 0.f && gamma > 0.f);
-}
-
 extern "C" int64_t sgnn_cross_entropy_workspace_bytes(int64_t B)
 {
     if (B < 0) return -1;
@@ -206,7 +162,7 @@ extern "C" int64_t sgnn_cross_entropy_workspace_bytes(int64_t B)
 static int ce_fwd_launch(const float* logits, const int64_t* labels, int64_t B, int64_t K, float* lse, float* loss, float* accuracy,
                          void* workspace, int64_t workspace_bytes, void* stream, const float* weight, float eps = 0.f, float gamma = 0.f)
 {
-    if (!loss_shape_ok(eps, gamma)) return SGNN_ERR_BAD_ARG;
+    if (!loss_shape_ok(false, eps, gamma)) return SGNN_ERR_BAD_ARG;
     if (!logits || !labels || !lse || !loss || B < 1 || K < 1 || K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < sgnn_cross_entropy_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
     const int64_t nblk = ce_blocks(B);
@@ -215,11 +171,13 @@ static int ce_fwd_launch(const float* logits, const int64_t* labels, int64_t B, 
     float* ph = pl + nblk;
     float* pn = ph + nblk;
     hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)nblk), block(256);
+    const int32_t k = (int32_t)K;
     const LossShape Sp{eps, gamma};
-    if (eps > 0.f) hipLaunchKernelGGL(ce_fwd_shaped_kernel<1>, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, weight, lse, pl, ph, pn, Sp);
-    else if (gamma > 0.f) hipLaunchKernelGGL(ce_fwd_shaped_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, weight, lse, pl, ph, pn, Sp);
-    else if (weight) hipLaunchKernelGGL(ce_fwd_weighted_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, weight, lse, pl, ph, pn);
-    else hipLaunchKernelGGL(ce_fwd_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, labels, B, (int32_t)K, lse, pl, ph, pn);
+    if (eps > 0.f) hipLaunchKernelGGL(ce_fwd_shaped_kernel<1>, grid, block, 0, st, logits, labels, B, k, weight, lse, pl, ph, pn, Sp);
+    else if (gamma > 0.f) hipLaunchKernelGGL(ce_fwd_shaped_kernel<2>, grid, block, 0, st, logits, labels, B, k, weight, lse, pl, ph, pn, Sp);
+    else if (weight) hipLaunchKernelGGL(ce_fwd_weighted_kernel, grid, block, 0, st, logits, labels, B, k, weight, lse, pl, ph, pn);
+    else hipLaunchKernelGGL(ce_fwd_kernel, grid, block, 0, st, logits, labels, B, k, lse, pl, ph, pn);
     SGNN_CHECK_LAUNCH();
     hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(64), 0, st, pl, ph, pn, nblk, B, loss, accuracy, lse + B);
     SGNN_CHECK_LAUNCH();
@@ -250,18 +208,17 @@ extern "C" int sgnn_cross_entropy_fwd_shaped(const float* logits, const int64_t*
 static int ce_bwd_launch(const float* logits, const int64_t* labels, const float* lse, const float* grad_loss, int64_t B, int64_t K,
                          float* grad_logits, void* stream, const float* weight, float eps = 0.f, float gamma = 0.f)
 {
-    if (!loss_shape_ok(eps, gamma)) return SGNN_ERR_BAD_ARG;
+    if (!loss_shape_ok(false, eps, gamma)) return SGNN_ERR_BAD_ARG;
     if (!logits || !labels || !lse || !grad_loss || !grad_logits || B < 1 || K < 1 || K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
     if ((B * K + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((B * K + 255) / 256)), block(256);
+    const int32_t k = (int32_t)K;
     const LossShape Sp{eps, gamma};
-    if (eps > 0.f) hipLaunchKernelGGL(ce_bwd_shaped_kernel<1>, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits,
-                                      labels, lse, grad_loss, B, (int32_t)K, weight, grad_logits, Sp);
-    else if (gamma > 0.f) hipLaunchKernelGGL(ce_bwd_shaped_kernel<2>, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                                             logits, labels, lse, grad_loss, B, (int32_t)K, weight, grad_logits, Sp);
-    else if (weight) hipLaunchKernelGGL(ce_bwd_weighted_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits,
-                                   labels, lse, grad_loss, B, (int32_t)K, weight, grad_logits);
-    else hipLaunchKernelGGL(ce_bwd_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, labels, lse,
-                            grad_loss, B, (int32_t)K, grad_logits);
+    if (eps > 0.f) hipLaunchKernelGGL(ce_bwd_shaped_kernel<1>, grid, block, 0, st, logits, labels, lse, grad_loss, B, k, weight, grad_logits, Sp);
+    else if (gamma > 0.f) hipLaunchKernelGGL(ce_bwd_shaped_kernel<2>, grid, block, 0, st, logits, labels, lse, grad_loss, B, k, weight, grad_logits, Sp);
+    else if (weight) hipLaunchKernelGGL(ce_bwd_weighted_kernel, grid, block, 0, st, logits, labels, lse, grad_loss, B, k, weight, grad_logits);
+    else hipLaunchKernelGGL(ce_bwd_kernel, grid, block, 0, st, logits, labels, lse, grad_loss, B, k, grad_logits);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }
@@ -287,8 +244,8 @@ extern "C" int sgnn_cross_entropy_bwd_shaped(const float* logits, const int64_t*
 
 // ---- multi-label: nn.BCEWithLogitsLoss() (mean over B x K, SubGNN.py:133 with several labels per subgraph) + the exact-match
 // accuracy of su:108-124, for any K.  targets: int64 (B, K) indicator matrix, non-zero counts as 1.  A thread walks its row in k
-// order: l = max(x, 0) - x y + log1p(exp(-|x|)); the row is a hit when 1 / (1 + exp(-x)) > 0.5 (float32, as torch.sigmoid(x) >
-// 0.5 evaluates it -- not x > 0) equals y in every column.  Same partials and the same fixed order as the single-label pair.
+// order, adding loss_ml_term; the row is a hit when loss_ml_hit holds in every column.  Either weight row may be absent: it stands
+// as ones.  Same partials and the same fixed order as the single-label pair.
 template <int WT, int SH = 0>
 __device__ __forceinline__ void bce_fwd_body(const float* __restrict__ logits, const int64_t* __restrict__ targets, int64_t B, int32_t K,
                                              const float* __restrict__ weight, const float* __restrict__ pos_weight,
@@ -301,19 +258,13 @@ __device__ __forceinline__ void bce_fwd_body(const float* __restrict__ logits, c
     if (r < B) {
         const float* x = logits + r * K;
         const int64_t* y = targets + r * K;
+        const LossRow<true> cw{weight}, pw{pos_weight};
         bool all = true;
         for (int32_t k = 0; k < K; ++k) {
             const float v = x[k];
             const bool t = y[k] != 0;
-            if (SH == 2) {
-                const float c = weight ? weight[k] : 1.f, L = (t && pos_weight) ? pos_weight[k] : 1.f;
-                const float z = t ? v : -v, e = expf(-fabsf(v)), inv = 1.f / (1.f + e);
-                loss += c * L * loss_qpow(z >= 0.f ? e * inv : inv, Sp.gamma) * (log1pf(e) + fmaxf(-z, 0.f));
-            } else if (WT) {                              // (either row may be absent: it stands as ones)
-                const float c = weight ? weight[k] : 1.f, L = (t && pos_weight) ? pos_weight[k] : 1.f;
-                loss += c * ((t ? 0.f : v) + L * (log1pf(expf(-fabsf(v))) + fmaxf(-v, 0.f)));
-            } else loss += fmaxf(v, 0.f) - (t ? v : 0.f) + log1pf(expf(-fabsf(v)));
-            all = all && ((1.f / (1.f + expf(-v)) > 0.5f) == t);
+            loss += loss_ml_term<WT, SH>(v, t, k, cw, pw, Sp);
+            all = all && loss_ml_hit(v, t);
         }
         hit = all ? 1.f : 0.f;
     }
@@ -365,8 +316,7 @@ __global__ __launch_bounds__(64) void bce_finish_kernel(const float* __restrict_
     }
 }
 
-// d loss / d logits[r, k] = (sigmoid(x) - y) * grad_loss / (B K); the sigmoid takes exp of a non-positive argument only
-// WT: c_k [(1 - y) - L (1 - sigmoid(x))] * grad_loss / (B K), L = 1 + (p_k - 1) y; 1 - sigmoid(x) = sigmoid(-x), from the same exp
+// thread per element: d loss / d logits[r, k] (loss_ml_grad) at scale = grad_loss / (B K); the bare kernel needs no column index
 template <int WT, int SH = 0>
 __device__ __forceinline__ void bce_bwd_body(const float* __restrict__ logits, const int64_t* __restrict__ targets,
                                              const float* __restrict__ grad_loss, int64_t n, int32_t K, const float* __restrict__ weight,
@@ -375,26 +325,9 @@ __device__ __forceinline__ void bce_bwd_body(const float* __restrict__ logits, c
 {
     const int64_t t = blockIdx.x * 256ll + threadIdx.x;
     if (t >= n) return;
-    const float x = logits[t], e = expf(-fabsf(x));
-    if (SH == 2) {
-        const int32_t k = (int32_t)(t % K);
-        const bool y = targets[t] != 0;
-        const float c = weight ? weight[k] : 1.f, L = (y && pos_weight) ? pos_weight[k] : 1.f;
-        const float z = y ? x : -x, inv = 1.f / (1.f + e), q = z >= 0.f ? e * inv : inv, pt = z >= 0.f ? inv : e * inv;
-        const float g = c * L * loss_qpow(q, Sp.gamma) * (q + Sp.gamma * pt * (log1pf(e) + fmaxf(-z, 0.f))) * (grad_loss[0] / (float)n);
-        grad_logits[t] = y ? -g : g;
-        return;
-    }
-    if (WT) {
-        const int32_t k = (int32_t)(t % K);
-        const bool y = targets[t] != 0;
-        const float nsig = x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);
-        const float c = weight ? weight[k] : 1.f, L = (y && pos_weight) ? pos_weight[k] : 1.f;
-        grad_logits[t] = c * ((y ? 0.f : 1.f) - L * nsig) * (grad_loss[0] / (float)n);
-        return;
-    }
-    const float sig = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
-    grad_logits[t] = (sig - (targets[t] != 0 ? 1.f : 0.f)) * (grad_loss[0] / (float)n);
+    const int32_t k = WT ? (int32_t)(t % K) : 0;
+    grad_logits[t] = loss_ml_grad<WT, SH>(logits[t], targets[t] != 0, k, LossRow<true>{weight}, LossRow<true>{pos_weight}, Sp,
+                                          grad_loss[0] / (float)n);
 }
 
 __global__ __launch_bounds__(256) void bce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ targets,
@@ -430,7 +363,7 @@ static int bce_fwd_launch(const float* logits, const int64_t* targets, int64_t B
                           void* workspace, int64_t workspace_bytes, void* stream, const float* weight, const float* pos_weight,
                           float gamma = 0.f)
 {
-    if (!loss_shape_ok(0.f, gamma)) return SGNN_ERR_BAD_ARG;
+    if (!loss_shape_ok(false, 0.f, gamma)) return SGNN_ERR_BAD_ARG;
     if (!logits || !targets || !loss || B < 1 || K < 1 || K > 0x7fffffff || B > (int64_t)0x7fffffffffffffffll / K) return SGNN_ERR_BAD_ARG;
     if (!workspace || workspace_bytes < sgnn_bce_logits_workspace_bytes(B)) return SGNN_ERR_BAD_ARG;
     const int64_t nblk = ce_blocks(B);
@@ -438,12 +371,11 @@ static int bce_fwd_launch(const float* logits, const int64_t* targets, int64_t B
     float* pl = (float*)workspace;
     float* ph = pl + nblk;
     hipStream_t st = (hipStream_t)stream;
-    if (gamma > 0.f)
-        hipLaunchKernelGGL(bce_fwd_focal_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, weight, pos_weight, pl, ph,
-                           LossShape{0.f, gamma});
-    else if (weight || pos_weight)
-        hipLaunchKernelGGL(bce_fwd_weighted_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, weight, pos_weight, pl, ph);
-    else hipLaunchKernelGGL(bce_fwd_kernel, dim3((unsigned)nblk), dim3(256), 0, st, logits, targets, B, (int32_t)K, pl, ph);
+    const dim3 grid((unsigned)nblk), block(256);
+    const int32_t k = (int32_t)K;
+    if (gamma > 0.f) hipLaunchKernelGGL(bce_fwd_focal_kernel, grid, block, 0, st, logits, targets, B, k, weight, pos_weight, pl, ph, LossShape{0.f, gamma});
+    else if (weight || pos_weight) hipLaunchKernelGGL(bce_fwd_weighted_kernel, grid, block, 0, st, logits, targets, B, k, weight, pos_weight, pl, ph);
+    else hipLaunchKernelGGL(bce_fwd_kernel, grid, block, 0, st, logits, targets, B, k, pl, ph);
     SGNN_CHECK_LAUNCH();
     hipLaunchKernelGGL(bce_finish_kernel, dim3(1), dim3(64), 0, st, pl, ph, nblk, B, K, loss, accuracy);
     SGNN_CHECK_LAUNCH();
@@ -473,20 +405,18 @@ extern "C" int sgnn_bce_logits_fwd_shaped(const float* logits, const int64_t* ta
 static int bce_bwd_launch(const float* logits, const int64_t* targets, const float* grad_loss, int64_t B, int64_t K, float* grad_logits,
                           void* stream, const float* weight, const float* pos_weight, float gamma = 0.f)
 {
-    if (!loss_shape_ok(0.f, gamma)) return SGNN_ERR_BAD_ARG;
+    if (!loss_shape_ok(false, 0.f, gamma)) return SGNN_ERR_BAD_ARG;
     if (!logits || !targets || !grad_loss || !grad_logits || B < 1 || K < 1 || B > (int64_t)0x7fffffffffffffffll / K) return SGNN_ERR_BAD_ARG;
     if ((B * K + 255) / 256 > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-    if (gamma > 0.f) {
-        if (K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-        hipLaunchKernelGGL(bce_bwd_focal_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, targets,
-                           grad_loss, B * K, (int32_t)K, weight, pos_weight, grad_logits, LossShape{0.f, gamma});
-    } else if (weight || pos_weight) {
-        if (K > 0x7fffffff) return SGNN_ERR_BAD_ARG;
-        hipLaunchKernelGGL(bce_bwd_weighted_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, targets,
-                           grad_loss, B * K, (int32_t)K, weight, pos_weight, grad_logits);
-    } else
-        hipLaunchKernelGGL(bce_bwd_kernel, dim3((unsigned)((B * K + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logits, targets,
-                           grad_loss, B * K, grad_logits);
+    const bool bare = !(gamma > 0.f) && !weight && !pos_weight;
+    if (!bare && K > 0x7fffffff) return SGNN_ERR_BAD_ARG;              // (only the bare kernel takes no column index)
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid((unsigned)((B * K + 255) / 256)), block(256);
+    const int64_t n = B * K;
+    const int32_t k = (int32_t)K;
+    if (gamma > 0.f) hipLaunchKernelGGL(bce_bwd_focal_kernel, grid, block, 0, st, logits, targets, grad_loss, n, k, weight, pos_weight, grad_logits, LossShape{0.f, gamma});
+    else if (!bare) hipLaunchKernelGGL(bce_bwd_weighted_kernel, grid, block, 0, st, logits, targets, grad_loss, n, k, weight, pos_weight, grad_logits);
+    else hipLaunchKernelGGL(bce_bwd_kernel, grid, block, 0, st, logits, targets, grad_loss, n, grad_logits);
     SGNN_CHECK_LAUNCH();
     return SGNN_OK;
 }

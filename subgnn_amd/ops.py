@@ -2803,6 +2803,25 @@ def _class_weights(w, K, like, name):
     return w.detach().contiguous()
 
 
+def _loss_call(lib, base, args, ml, weight, pos_weight, eps, gamma):
+    """Call the entry point of a loss mode: ``base`` bare, ``base_weighted`` with a class weight row, ``base_shaped`` with label
+    smoothing or a focal exponent; ``args`` are the bare entry's, the mode's own follow them (single-label: weight[, eps, gamma];
+    multi-label ``ml``: weight, pos_weight[, gamma])."""
+    rows = (_ptr(weight), _ptr(pos_weight)) if ml else (_ptr(weight),)
+    if eps or gamma:
+        name, tail = base + '_shaped', rows + ((float(gamma),) if ml else (float(eps), float(gamma)))
+    elif weight is not None or pos_weight is not None:
+        name, tail = base + '_weighted', rows
+    else:
+        name, tail = base, ()
+    check(getattr(lib, name)(*args, *tail), name)
+
+
+def _loss_grad(g_loss):
+    """The incoming gradient of the 0-d loss as the float32 (1,) device array the backward kernels read."""
+    return g_loss.reshape(1).contiguous().float()
+
+
 class _CrossEntropy(torch.autograd.Function):
     """(mean cross entropy, accuracy) of logits (B, K) against int64 labels (sgnn_cross_entropy_fwd / _bwd; with a class weight
     row their ``_weighted`` forms: the mean is over the sum of the counted rows' weights, the accuracy stays unweighted; with label
@@ -2819,17 +2838,9 @@ class _CrossEntropy(torch.autograd.Function):
         wsb = lib.sgnn_cross_entropy_workspace_bytes(B)
         ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=logits.device)
         ctx.shape = (float(eps), float(gamma))
-        if eps or gamma:
-            check(lib.sgnn_cross_entropy_fwd_shaped(_ptr(logits), _ptr(labels), B, K, _ptr(lse), _ptr(res),
-                                                    ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb, _stream(), _ptr(weight),
-                                                    float(eps), float(gamma)), 'sgnn_cross_entropy_fwd_shaped')
-        elif weight is None:
-            check(lib.sgnn_cross_entropy_fwd(_ptr(logits), _ptr(labels), B, K, _ptr(lse), _ptr(res), ctypes.c_void_p(res.data_ptr() + 4),
-                                             _ptr(ws), wsb, _stream()), 'sgnn_cross_entropy_fwd')
-        else:
-            check(lib.sgnn_cross_entropy_fwd_weighted(_ptr(logits), _ptr(labels), B, K, _ptr(lse), _ptr(res),
-                                                      ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb, _stream(), _ptr(weight)),
-                  'sgnn_cross_entropy_fwd_weighted')
+        _loss_call(lib, 'sgnn_cross_entropy_fwd', (_ptr(logits), _ptr(labels), B, K, _ptr(lse), _ptr(res),
+                                                   ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb, _stream()),
+                   False, weight, None, eps, gamma)
         ctx.save_for_backward(logits, labels, lse, weight)
         loss, acc = res[0], res[1:2]
         ctx.mark_non_differentiable(acc)
@@ -2842,15 +2853,9 @@ class _CrossEntropy(torch.autograd.Function):
         B, K = logits.shape
         g = torch.empty_like(logits)
         eps, gamma = ctx.shape
-        if eps or gamma:
-            check(lib.sgnn_cross_entropy_bwd_shaped(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss.reshape(1).contiguous().float()),
-                                                    B, K, _ptr(g), _stream(), _ptr(weight), eps, gamma), 'sgnn_cross_entropy_bwd_shaped')
-        elif weight is None:
-            check(lib.sgnn_cross_entropy_bwd(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss.reshape(1).contiguous().float()), B, K,
-                                             _ptr(g), _stream()), 'sgnn_cross_entropy_bwd')
-        else:
-            check(lib.sgnn_cross_entropy_bwd_weighted(_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss.reshape(1).contiguous().float()),
-                                                      B, K, _ptr(g), _stream(), _ptr(weight)), 'sgnn_cross_entropy_bwd_weighted')
+        g_loss = _loss_grad(g_loss)
+        _loss_call(lib, 'sgnn_cross_entropy_bwd', (_ptr(logits), _ptr(labels), _ptr(lse), _ptr(g_loss), B, K, _ptr(g), _stream()),
+                   False, weight, None, eps, gamma)
         return g, None, None, None, None
 
 
@@ -2882,17 +2887,8 @@ class _BCEWithLogits(torch.autograd.Function):
         wsb = lib.sgnn_bce_logits_workspace_bytes(B)
         ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=logits.device)
         ctx.gamma = float(gamma)
-        if gamma:
-            check(lib.sgnn_bce_logits_fwd_shaped(_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4),
-                                                 _ptr(ws), wsb, _stream(), _ptr(weight), _ptr(pos_weight), float(gamma)),
-                  'sgnn_bce_logits_fwd_shaped')
-        elif weight is None and pos_weight is None:
-            check(lib.sgnn_bce_logits_fwd(_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4), _ptr(ws), wsb,
-                                          _stream()), 'sgnn_bce_logits_fwd')
-        else:
-            check(lib.sgnn_bce_logits_fwd_weighted(_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4),
-                                                   _ptr(ws), wsb, _stream(), _ptr(weight), _ptr(pos_weight)),
-                  'sgnn_bce_logits_fwd_weighted')
+        _loss_call(lib, 'sgnn_bce_logits_fwd', (_ptr(logits), _ptr(targets), B, K, _ptr(res), ctypes.c_void_p(res.data_ptr() + 4),
+                                                _ptr(ws), wsb, _stream()), True, weight, pos_weight, 0.0, gamma)
         ctx.save_for_backward(logits, targets, weight, pos_weight)
         loss, acc = res[0], res[1:2]
         ctx.mark_non_differentiable(acc)
@@ -2904,15 +2900,9 @@ class _BCEWithLogits(torch.autograd.Function):
         logits, targets, weight, pos_weight = ctx.saved_tensors
         B, K = logits.shape
         g = torch.empty_like(logits)
-        if ctx.gamma:
-            check(lib.sgnn_bce_logits_bwd_shaped(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K,
-                                                 _ptr(g), _stream(), _ptr(weight), _ptr(pos_weight), ctx.gamma), 'sgnn_bce_logits_bwd_shaped')
-        elif weight is None and pos_weight is None:
-            check(lib.sgnn_bce_logits_bwd(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K, _ptr(g),
-                                          _stream()), 'sgnn_bce_logits_bwd')
-        else:
-            check(lib.sgnn_bce_logits_bwd_weighted(_ptr(logits), _ptr(targets), _ptr(g_loss.reshape(1).contiguous().float()), B, K,
-                                                   _ptr(g), _stream(), _ptr(weight), _ptr(pos_weight)), 'sgnn_bce_logits_bwd_weighted')
+        g_loss = _loss_grad(g_loss)
+        _loss_call(lib, 'sgnn_bce_logits_bwd', (_ptr(logits), _ptr(targets), _ptr(g_loss), B, K, _ptr(g), _stream()),
+                   True, weight, pos_weight, 0.0, ctx.gamma)
         return g, None, None, None, None
 
 
@@ -3057,32 +3047,14 @@ class _FusedHead(torch.autograd.Function):
         shaped = labels is not None and bool(eps or gamma)
         weighted = shaped or (labels is not None and (class_weight is not None or pos_weight is not None))
         ctx.shape = (float(eps), float(gamma)) if shaped else (0.0, 0.0)
-        if shaped and ml:                                    # the shaped launches (heads_*): label smoothing / focal loss
-            check(lib.sgnn_head_fwd_ml_shaped(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p),
-                                              _ptr(rng), _ptr(a1), _ptr(a2), _ptr(logits), _ptr(out), _ptr(ws), ws.numel() * 4,
-                                              _stream(), _ptr(class_weight), _ptr(pos_weight), float(gamma)), 'sgnn_head_fwd_ml_shaped')
-        elif shaped:
-            check(lib.sgnn_head_fwd_shaped(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p),
-                                           _ptr(rng), _ptr(a1), _ptr(a2), _ptr(logits), _ptr(lse), _ptr(out), _ptr(ws),
-                                           ws.numel() * 4, _stream(), _ptr(class_weight), float(eps), float(gamma)), 'sgnn_head_fwd_shaped')
-        elif weighted and ml:                                # the weighted launches (headw_*): the bare ones below stay as they are
-            check(lib.sgnn_head_fwd_ml_weighted(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p),
-                                                _ptr(rng), _ptr(a1), _ptr(a2), _ptr(logits), _ptr(out), _ptr(ws), ws.numel() * 4,
-                                                _stream(), _ptr(class_weight), _ptr(pos_weight)), 'sgnn_head_fwd_ml_weighted')
-        elif weighted:
-            check(lib.sgnn_head_fwd_weighted(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p),
-                                             _ptr(rng), _ptr(a1), _ptr(a2), _ptr(logits), _ptr(lse), _ptr(out), _ptr(ws),
-                                             ws.numel() * 4, _stream(), _ptr(class_weight)), 'sgnn_head_fwd_weighted')
-        elif ml:                                             # multi-label: ``labels`` is the (B, K) indicator matrix; no lse
-            check(lib.sgnn_head_fwd_ml(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p), _ptr(rng),
-                                       _ptr(a1), _ptr(a2), _ptr(logits), _ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
-                  'sgnn_head_fwd_ml')
-        else:
-            check(lib.sgnn_head_fwd(_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p), _ptr(rng),
-                                    _ptr(a1), _ptr(a2), _ptr(logits), _ptr(lse), _ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
-                  'sgnn_head_fwd')
-        ctx.save_for_backward(x, W1, W2, W3, a1, a2, logits, lse, labels, out, class_weight if weighted else None,
-                              pos_weight if weighted else None)
+        if not weighted:                                     # (without labels there is no loss: the bare launch, whatever was passed)
+            class_weight = pos_weight = None
+        # multi-label: ``labels`` is the (B, K) indicator matrix and the entry takes no lse
+        _loss_call(lib, 'sgnn_head_fwd_ml' if ml else 'sgnn_head_fwd',
+                   (_ptr(z1), B, H1, H2, K, _ptr(W2), _ptr(b2), _ptr(W3), _ptr(b3), _ptr(labels), float(p), _ptr(rng), _ptr(a1), _ptr(a2),
+                    _ptr(logits)) + (() if ml else (_ptr(lse),)) + (_ptr(out), _ptr(ws), ws.numel() * 4, _stream()),
+                   ml, class_weight, pos_weight, *ctx.shape)
+        ctx.save_for_backward(x, W1, W2, W3, a1, a2, logits, lse, labels, out, class_weight, pos_weight)
         ctx.p, ctx.dims, ctx.ml = float(p), (B, H1, H2, K), bool(ml)
         ctx.has_bias = (b1 is not None, b2 is not None, b3 is not None)
         ctx.set_materialize_grads(False)
@@ -3101,36 +3073,17 @@ class _FusedHead(torch.autograd.Function):
         if g_logits is None and g_loss is None:
             return (None,) * 15
         g_logits = g_logits.contiguous() if g_logits is not None else None
-        g_loss = g_loss.reshape(1).contiguous().float() if g_loss is not None else None
+        g_loss = _loss_grad(g_loss) if g_loss is not None else None
         P = int(lib.sgnn_head_partial_floats(H1, H2, K))
         nb = int(lib.sgnn_head_blocks(B))
         dz1 = torch.empty((B, H1), dtype=torch.float32, device=dev)
         partial = torch.empty((nb, P), dtype=torch.float32, device=dev)
         rows = ctypes.c_void_p(out.data_ptr() + 8) if out is not None else None
-        weighted = class_weight is not None or pos_weight is not None
-        eps, gamma = ctx.shape
-        if (eps or gamma) and ctx.ml:
-            check(lib.sgnn_head_bwd_ml_shaped(_ptr(logits), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2),
-                                              _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream(),
-                                              _ptr(class_weight), _ptr(pos_weight), gamma), 'sgnn_head_bwd_ml_shaped')
-        elif eps or gamma:
-            check(lib.sgnn_head_bwd_shaped(_ptr(logits), _ptr(lse), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1),
-                                           _ptr(a2), _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream(),
-                                           _ptr(class_weight), eps, gamma), 'sgnn_head_bwd_shaped')
-        elif weighted and ctx.ml:
-            check(lib.sgnn_head_bwd_ml_weighted(_ptr(logits), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2),
-                                                _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream(),
-                                                _ptr(class_weight), _ptr(pos_weight)), 'sgnn_head_bwd_ml_weighted')
-        elif weighted:
-            check(lib.sgnn_head_bwd_weighted(_ptr(logits), _ptr(lse), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1),
-                                             _ptr(a2), _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream(),
-                                             _ptr(class_weight)), 'sgnn_head_bwd_weighted')
-        elif ctx.ml:
-            check(lib.sgnn_head_bwd_ml(_ptr(logits), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2), _ptr(W2),
-                                       _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream()), 'sgnn_head_bwd_ml')
-        else:
-            check(lib.sgnn_head_bwd(_ptr(logits), _ptr(lse), _ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2),
-                                    _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1), _ptr(partial), _stream()), 'sgnn_head_bwd')
+        _loss_call(lib, 'sgnn_head_bwd_ml' if ctx.ml else 'sgnn_head_bwd',
+                   (_ptr(logits),) + (() if ctx.ml else (_ptr(lse),))
+                   + (_ptr(labels), _ptr(g_loss), _ptr(g_logits), rows, _ptr(a1), _ptr(a2), _ptr(W2), _ptr(W3), B, H1, H2, K, ctx.p, _ptr(dz1),
+                      _ptr(partial), _stream()),
+                   ctx.ml, class_weight, pos_weight, *ctx.shape)
         # gW1 = dz1^T x: block partials on the matrix cores; its blocks and the head kernel's partials are added by ONE launch
         flat = torch.empty(P, dtype=torch.float32, device=dev)
         jobs_part, jobs_nb, jobs_n, jobs_out = [partial], [nb], [P], [flat]

@@ -26,6 +26,19 @@ def test_library_exports_every_declared_symbol():
     assert lib.sgnn_abi_version() == 13
 
 
+def test_every_kernel_header_is_a_build_dependency():
+    """A csrc header missing from build.HEADERS leaves the objects that include it stale after an edit."""
+    import glob
+    from subgnn_amd import build
+    listed = {os.path.realpath(h) for h in build.HEADERS}
+    headers = glob.glob(os.path.join(build.CSRC, '*.h'))
+    assert len(headers) >= 5
+    for h in headers:
+        assert os.path.realpath(h) in listed, os.path.basename(h)
+    for h in build.HEADERS:
+        assert os.path.exists(h), h
+
+
 def test_workspace_queries_run_on_the_host():
     from subgnn_amd import _lib
     lib = _lib.load()
