@@ -38,7 +38,7 @@ extern "C" {
 #define SGNN_ERR_LAUNCH         -4   /* hipGetLastError() after a launch */
 #define SGNN_ERR_UNSUPPORTED_D  -5   /* embedding width not supported by the vector path */
 
-#define SGNN_ABI_VERSION 13
+#define SGNN_ABI_VERSION 14
 int sgnn_abi_version(void);
 /* Load the code objects of every translation unit of the library on the current device (one empty launch each on ``stream``):
  * what the first call of each kernel family would otherwise pay, 5-25 ms at a time, inside the reference's one-time
@@ -458,54 +458,43 @@ int sgnn_seeded_walk_sets(const int64_t* rowptr, const int32_t* col, int64_t max
  *                     restricted to in_border U (V \ patch) (aps:141-143)
  * out: (n_items, walk_len) int64, PAD filled.  One tape item per walk (item = item_base + walk index: a rank that runs a
  * share of a launch's walks -- with the patches of that share only, for modes 1 and 2 -- draws what the whole launch would).
- * max_id: largest node id (rowptr has max_id + 2 entries); when the id range fits an LDS bitmap
- * (~1.1 M ids) a workgroup-per-walk kernel is used (adjacency to the previous node = one bit
- * test), else a wavefront-per-walk kernel (binary search in the sorted list); max_id <= 0 or
- * kernel = 1 select the latter (kernel = 0: pick by graph size).  Both give the same walks.
+ * sgnn_triangular_walks_both: the internal AND the border walks over the same patches (aps:118-158, which the reference calls
+ * twice: inside = True / False) in ONE launch, on every graph: out (2, n_items, walk_len), [0] = internal walks (tape stream
+ * stream_id_int), [1] = border walks (stream_id_bor) -- the walks the two calls of sgnn_triangular_walks (modes 1, 2) produce.
+ *
+ * Three kernels give the same walks; they differ in how "is candidate w adjacent to the previous node?" is answered:
+ *   bitmap     a workgroup of 1024 threads and a CU per walk; an LDS bitmap over node ids holds N(prev): one bit test.  Only
+ *              where the bitmap fits (max_id, the largest id -- rowptr has max_id + 2 entries; 0 = unknown -- below ~1.1 M)
+ *   list       a workgroup per walk, a few KB of LDS, several walks per CU, no limit on ids.  N(prev) staged in LDS as a hash
+ *              when it has fewer than 512 entries; else bit hub_index[prev] of row w of the hub tables (hub_index / hub_bits /
+ *              hub_words as for sgnn_degree_sequence_hub_bitmaps; both NULL: no tables); else a binary search in col_sorted
+ *   wavefront  a wavefront per walk, binary search in col_sorted: the device-side reference of the other two
+ * kernel: 0 = the workgroup kernels, as variant says; 1 = the wavefront kernel (it has no combined launch:
+ * sgnn_triangular_walks_both returns SGNN_ERR_BAD_ARG); 2 = the bitmap kernel whatever the size of the launch, or
+ * SGNN_ERR_SET_TOO_LARGE, before any launch, where max_id <= 0 or the bitmap does not fit (tests and measurements).
+ * variant (kernel 0): 0 = the launch rule -- launches of up to 256 walks (a CU for every walk) on a graph whose bitmap fits go
+ * to the bitmap kernel, which is faster there; all others to the list kernel with 512 threads; 1 ..
+ * sgnn_triangular_walks_variants() - 1 = the list kernel always, at 256 / 512 / 1024 threads with a 256-chunk ballot cache,
+ * 512 threads with 1024 chunks (same walks; for tests and measurements).
  * ------------------------------------------------------------------------------------- */
-int sgnn_triangular_walks(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
-                          const int32_t* node_order, int64_t n_nodes,
-                          const int64_t* patch_ptr, const int32_t* patch_nodes,
-                          const int64_t* inb_ptr, const int32_t* inb_nodes,
-                          int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta,
-                          uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t max_id, int kernel, int64_t* out,
-                          void* stream);
-/* The internal AND the border walks over the same patches (aps:118-158, which the reference calls twice: inside = True / False)
- * in ONE launch: out (2, n_items, walk_len) int64, [0] = internal walks (tape stream stream_id_int), [1] = border walks
- * (stream_id_bor) -- the walks the two calls of sgnn_triangular_walks (modes 1 and 2) produce.  Only where the graph's id
- * bitmap fits LDS (max_id < ~1.1 M): SGNN_ERR_SET_TOO_LARGE otherwise, and the caller makes the two calls. */
-int sgnn_triangular_walks_both(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
-                               const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr,
-                               const int32_t* inb_nodes, int64_t n_items, int64_t walks_per_patch, int64_t walk_len,
-                               double beta, uint64_t seed, uint64_t stream_id_int, uint64_t stream_id_bor,
-                               int64_t item_base, int64_t max_id, int64_t* out, void* stream);
-/* The same walks by a workgroup-per-walk kernel that keeps NO bitmap over node ids (no id-range limit, a few KB of LDS per
- * walk, several walks per CU).  Adjacency to the previous node: its neighbour list staged in LDS when it has fewer than 512
- * entries; else bit hub_index[prev] of row w of the hub tables (hub_index / hub_bits / hub_words as for
- * sgnn_degree_sequence_hub_bitmaps; both NULL: no tables); else a binary search in col_sorted.  kernel: 0 = this kernel,
- * 1 = the wavefront-per-walk kernel.  variant: 0 = the launch rule -- launches of up to 256 walks (a CU for every walk) on a
- * graph whose id bitmap fits LDS (max_id, the largest id; 0 = unknown) go to the bitmap kernel of sgnn_triangular_walks,
- * which is faster there; all others to this kernel with 512 threads; 1 .. sgnn_triangular_walks_variants() - 1 = this
- * kernel always, at 256 / 512 / 1024 threads with a 256-chunk ballot cache, 512 threads with 1024 chunks (same walks; for
- * tests and measurements).  sgnn_triangular_walks_both_lists: the internal and the border walks in one launch, on every graph. */
 int sgnn_triangular_walks_variants(void);
 /* 1 = variant 0 sends a launch of n_walks walks (internal + border counted together) to the bitmap kernel: the caller need
  * not have hub tables.  Tuned on the benchmark's hub-heavy graph. */
 int sgnn_triangular_walks_rule(int64_t n_walks, int64_t max_id);
-int sgnn_triangular_walks_lists(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
-                                const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
-                                const int32_t* node_order, int64_t n_nodes,
-                                const int64_t* patch_ptr, const int32_t* patch_nodes,
-                                const int64_t* inb_ptr, const int32_t* inb_nodes,
-                                int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta,
-                                uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t max_id, int kernel, int variant,
-                                int64_t* out, void* stream);
-int sgnn_triangular_walks_both_lists(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
-                                     const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
-                                     const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr,
-                                     const int32_t* inb_nodes, int64_t n_items, int64_t walks_per_patch, int64_t walk_len,
-                                     double beta, uint64_t seed, uint64_t stream_id_int, uint64_t stream_id_bor,
-                                     int64_t item_base, int64_t max_id, int variant, int64_t* out, void* stream);
+int sgnn_triangular_walks(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
+                          const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
+                          const int32_t* node_order, int64_t n_nodes,
+                          const int64_t* patch_ptr, const int32_t* patch_nodes,
+                          const int64_t* inb_ptr, const int32_t* inb_nodes,
+                          int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta,
+                          uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t max_id, int kernel, int variant,
+                          int64_t* out, void* stream);
+int sgnn_triangular_walks_both(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
+                               const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
+                               const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr,
+                               const int32_t* inb_nodes, int64_t n_items, int64_t walks_per_patch, int64_t walk_len,
+                               double beta, uint64_t seed, uint64_t stream_id_int, uint64_t stream_id_bor,
+                               int64_t item_base, int64_t max_id, int kernel, int variant, int64_t* out, void* stream);
 
 /* in-border nodes of a patch (subgraph_utils.get_border_nodes, subgraph_utils.py:126-144, with
  * its id-1 / node-order indexing quirk): out_flag[i] = 1 iff patch_nodes[i] is a border node.

@@ -85,16 +85,12 @@ SIGNATURES = {
     'sgnn_choice_ragged_keyed': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
     'sgnn_sample_border_anchors_keyed': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr,
                                                  c_ptr]),
-    'sgnn_triangular_walks_both': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_dbl, c_u64,
-                                           c_u64, c_u64, c_i64, c_i64, c_ptr, c_ptr]),
-    'sgnn_triangular_walks': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_int,
-                                      c_i64, c_i64, c_i64, c_dbl, c_u64, c_u64, c_i64, c_i64, c_int, c_ptr, c_ptr]),
     'sgnn_triangular_walks_variants': (c_int, []),
     'sgnn_triangular_walks_rule': (c_int, [c_i64, c_i64]),
-    'sgnn_triangular_walks_lists': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
-                                            c_int, c_i64, c_i64, c_i64, c_dbl, c_u64, c_u64, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
-    'sgnn_triangular_walks_both_lists': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
-                                                 c_i64, c_i64, c_dbl, c_u64, c_u64, c_u64, c_i64, c_i64, c_int, c_ptr, c_ptr]),
+    'sgnn_triangular_walks': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
+                                      c_int, c_i64, c_i64, c_i64, c_dbl, c_u64, c_u64, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
+    'sgnn_triangular_walks_both': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_i64,
+                                           c_i64, c_i64, c_dbl, c_u64, c_u64, c_u64, c_i64, c_i64, c_int, c_int, c_ptr, c_ptr]),
     'sgnn_patch_in_border': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     'sgnn_sp_similarity_dense': (c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
     'sgnn_bfs_hops_workspace_bytes': (c_i64, [c_i64, c_i64, c_int]),
@@ -310,7 +306,7 @@ def load():
         fn = getattr(lib, name)          # AttributeError if the header and the library disagree
         fn.restype = res
         fn.argtypes = args
-    if lib.sgnn_abi_version() != 13:
+    if lib.sgnn_abi_version() != 14:
         raise SubgnnHipError('ABI version mismatch')
     _lib = lib
     return lib

@@ -255,6 +255,9 @@ extern "C" int sgnn_set_keys(const int64_t* set_ptr, const int32_t* set_nodes, i
 // wavefront ballots + popcounts give the triangle / non-triangle counts (pass 1) and the
 // position of the drawn candidate (pass 2).  The walk state (tape counter, prev, curr) is
 // wave-uniform.  Latency-bound integer work; the walks are few (patches x walks).
+// No launch rule chooses this kernel: it is the device-side reference the tests compare the workgroup kernels below against
+// (kernel = 1).  That is why it keeps its OWN copy of the walk (the body of triangular_walks_kernel, walk_count, walk_pick,
+// walk_build_hash) and shares only WalkCtx and walk_valid with them: sharing a body would compare that body with itself.
 // ---------------------------------------------------------------------------------------------
 #define WK_HASH_BITS 8
 #define WK_HASH (1 << WK_HASH_BITS)
@@ -534,16 +537,16 @@ __device__ static inline void wkb_count(const WalkCtx& c, int32_t v, bool has_pr
     nn = s_cnt[1];
 }
 
-// pass 2: the pick-th valid neighbour of v in the wanted class (adjacency order) -> *s_next
-__device__ static inline int32_t wkb_pick(const WalkCtx& c, int32_t v, bool has_prev, const uint32_t* bm, bool want_tri,
-                                          int32_t pick, int tid, const uint64_t* s_tri, const uint64_t* s_non, int32_t* s_next) {
+// pass 2 of both workgroup kernels: the pick-th valid neighbour (adjacency order) in the wanted class of the row [r0, r1)
+// -> *s_next.  CH: chunks of cached ballots; adjacent(w): the kernel's test "is w adjacent to prev?" (false without a prev)
+template <int CH, class Adjacent>
+__device__ static inline int32_t wk_pick(const WalkCtx& c, int64_t r0, int64_t r1, const Adjacent& adjacent, bool want_tri, int32_t pick,
+                                         int tid, const uint64_t* s_tri, const uint64_t* s_non, int32_t* s_next) {
     const int lane = tid & 63;
-    const int64_t r0 = c.rowptr[v], r1 = c.rowptr[v + 1];
     const int64_t n_chunks = (r1 - r0 + 63) / 64;
     if (tid < 64) {
-        if (n_chunks <= WK_CHUNKS) {
-            // lane l owns chunks [l*per, (l+1)*per): popcount them, scan over the wave, the owner of
-            // the crossing walks its chunks
+        if (n_chunks <= CH) {
+            // lane l owns chunks [l*per, (l+1)*per): popcount them, scan over the wave, the owner of the crossing walks its chunks
             const uint64_t* s = want_tri ? s_tri : s_non;
             const int per = (int)((n_chunks + 63) / 64);
             const int c0 = lane * per, c1 = (c0 + per < n_chunks) ? c0 + per : (int)n_chunks;
@@ -578,7 +581,7 @@ __device__ static inline int32_t wkb_pick(const WalkCtx& c, int32_t v, bool has_
                 if (e < r1) {
                     w = c.col[e];
                     if (walk_valid(c, w)) {
-                        const bool tri = has_prev ? (((bm[w >> 5] >> (w & 31)) & 1u) != 0) : false;
+                        const bool tri = adjacent(w);
                         hit = (tri == want_tri);
                     }
                 }
@@ -658,8 +661,8 @@ __global__ __launch_bounds__(WKB_THREADS) void triangular_walks_wg_kernel(
         int32_t nt, nn;
         wkb_count(c, prev, false, s_adj, tid, nt, nn, s_tri, s_non, s_cnt);             // aps:72,79
         if (nn == 0 || walk_len < 2) continue;                                          // aps:83-84
-        int32_t curr = wkb_pick(c, prev, false, s_adj, false, (int32_t)sgnn_choice_index(h1, j++, (uint32_t)nn), tid,
-                                s_tri, s_non, &s_next);                                  // aps:74,80
+        int32_t curr = wk_pick<WK_CHUNKS>(c, rowptr[prev], rowptr[prev + 1], [](int32_t) { return false; }, false,
+                                          (int32_t)sgnn_choice_index(h1, j++, (uint32_t)nn), tid, s_tri, s_non, &s_next);   // aps:74,80
         if (tid == 0) o[1] = curr;
         // the bitmap holds N(prev) from here on
         wkb_bits(s_adj, col + rowptr[prev], (int32_t)(rowptr[prev + 1] - rowptr[prev]), true, tid);
@@ -672,7 +675,9 @@ __global__ __launch_bounds__(WKB_THREADS) void triangular_walks_wg_kernel(
             else if (nn == 0) want_tri = true;                                           // aps:99-100
             else want_tri = (sgnn_uniform01(h1, j++) <= beta);                           // aps:102
             const int32_t pick = (int32_t)sgnn_choice_index(h1, j++, (uint32_t)(want_tri ? nt : nn));
-            const int32_t nxt = wkb_pick(c, curr, true, s_adj, want_tri, pick, tid, s_tri, s_non, &s_next);
+            const int32_t nxt = wk_pick<WK_CHUNKS>(c, rowptr[curr], rowptr[curr + 1],
+                                                   [&](int32_t w) { return ((s_adj[w >> 5] >> (w & 31)) & 1u) != 0; }, want_tri, pick, tid,
+                                                   s_tri, s_non, &s_next);
             if (tid == 0) o[step] = nxt;
             // N(prev) out, N(curr) in: curr becomes prev
             wkb_bits(s_adj, col + rowptr[prev], (int32_t)(rowptr[prev + 1] - rowptr[prev]), false, tid);
@@ -686,73 +691,6 @@ __global__ __launch_bounds__(WKB_THREADS) void triangular_walks_wg_kernel(
         if (prev) wkb_bits(s_adj, col + rowptr[prev], (int32_t)(rowptr[prev + 1] - rowptr[prev]), false, tid);
         __syncthreads();
     }
-}
-
-extern "C" int sgnn_triangular_walks(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
-                                     const int32_t* node_order, int64_t n_nodes,
-                                     const int64_t* patch_ptr, const int32_t* patch_nodes,
-                                     const int64_t* inb_ptr, const int32_t* inb_nodes,
-                                     int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta,
-                                     uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t max_id, int kernel, int64_t* out,
-                                     void* stream)
-{
-    if (!rowptr || !col || !col_sorted || !out || n_items < 0 || walk_len < 0 || mode < 0 || mode > 2 || kernel < 0 || kernel > 1 || item_base < 0)
-        return SGNN_ERR_BAD_ARG;
-    if (mode == 0 && (!node_order || n_nodes <= 0)) return SGNN_ERR_BAD_ARG;
-    if (mode >= 1 && (!patch_ptr || !patch_nodes || walks_per_patch <= 0)) return SGNN_ERR_BAD_ARG;
-    if (mode == 2 && (!inb_ptr || !inb_nodes)) return SGNN_ERR_BAD_ARG;
-    if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
-    if (n_items == 0 || walk_len == 0) return SGNN_OK;
-    const int64_t words = (max_id + 32) / 32;
-    if (max_id > 0 && words * 4 <= WKB_LDS_BYTES && kernel == 0) {
-        static bool attr_set = false;
-        if (!attr_set) {
-            (void)hipFuncSetAttribute((const void*)triangular_walks_wg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      WKB_LDS_BYTES);
-            attr_set = true;
-        }
-        hipLaunchKernelGGL(triangular_walks_wg_kernel, dim3((int)(n_items < 2048 ? n_items : 2048)), dim3(WKB_THREADS),
-                           (size_t)(words * 4), (hipStream_t)stream, rowptr, col, col_sorted, node_order, n_nodes, patch_ptr,
-                           patch_nodes, inb_ptr, inb_nodes, mode, n_items, walks_per_patch, walk_len, beta,
-                           sgnn_tape_h0(seed, stream_id), item_base, out, words, (uint64_t)0);
-        SGNN_CHECK_LAUNCH();
-        return SGNN_OK;
-    }
-    hipLaunchKernelGGL(triangular_walks_kernel, dim3((int)(n_items < 256 * 32 ? n_items : 256 * 32)), dim3(64), 0, (hipStream_t)stream,
-                       rowptr, col, col_sorted, node_order, n_nodes, patch_ptr, patch_nodes, inb_ptr, inb_nodes,
-                       mode, n_items, walks_per_patch, walk_len, beta, sgnn_tape_h0(seed, stream_id), item_base, out);
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
-}
-
-// Internal AND border walks over the same patches (aps:118-158 called twice by the reference: inside = True / False) in one
-// launch where the graph's id bitmap fits LDS: out (2, n_items, walk_len), [0] = internal (tape stream stream_id_int), [1] =
-// border (stream_id_bor).  Returns SGNN_ERR_SET_TOO_LARGE when it does not fit: the caller then makes the two launches.
-extern "C" int sgnn_triangular_walks_both(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
-                                          const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr,
-                                          const int32_t* inb_nodes, int64_t n_items, int64_t walks_per_patch, int64_t walk_len,
-                                          double beta, uint64_t seed, uint64_t stream_id_int, uint64_t stream_id_bor,
-                                          int64_t item_base, int64_t max_id, int64_t* out, void* stream)
-{
-    if (!rowptr || !col || !col_sorted || !out || !patch_ptr || !patch_nodes || !inb_ptr || !inb_nodes || n_items < 0 || walk_len < 0
-        || walks_per_patch <= 0 || item_base < 0)
-        return SGNN_ERR_BAD_ARG;
-    if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
-    if (n_items == 0 || walk_len == 0) return SGNN_OK;
-    const int64_t words = (max_id + 32) / 32;
-    if (max_id <= 0 || words * 4 > WKB_LDS_BYTES) return SGNN_ERR_SET_TOO_LARGE;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)triangular_walks_wg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WKB_LDS_BYTES);
-        attr_set = true;
-    }
-    const int64_t both = 2 * n_items;
-    hipLaunchKernelGGL(triangular_walks_wg_kernel, dim3((int)(both < 2048 ? both : 2048)), dim3(WKB_THREADS), (size_t)(words * 4),
-                       (hipStream_t)stream, rowptr, col, col_sorted, (const int32_t*)nullptr, (int64_t)0, patch_ptr, patch_nodes, inb_ptr,
-                       inb_nodes, 3, both, walks_per_patch, walk_len, beta, sgnn_tape_h0(seed, stream_id_int), item_base, out, words,
-                       sgnn_tape_h0(seed, stream_id_bor));
-    SGNN_CHECK_LAUNCH();
-    return SGNN_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -882,70 +820,6 @@ __device__ static inline void wks_count(const WalkCtx& c, int64_t r0, int64_t r1
     for (int k = 0; k < NW; ++k) { nt += s_cnt[2 * k]; nn += s_cnt[2 * k + 1]; }
 }
 
-// pass 2: the pick-th valid neighbour (adjacency order) in the wanted class of the row [r0, r1) -> *s_next
-template <int CH>
-__device__ static inline int32_t wks_pick(const WalkCtx& c, int64_t r0, int64_t r1, const WksAdj& a, bool want_tri, int32_t pick,
-                                          int tid, const uint64_t* s_tri, const uint64_t* s_non, int32_t* s_next) {
-    const int lane = tid & 63;
-    const int64_t n_chunks = (r1 - r0 + 63) / 64;
-    if (tid < 64) {
-        if (n_chunks <= CH) {
-            // lane l owns chunks [l*per, (l+1)*per): popcount them, scan over the wave, the owner of the crossing walks its chunks
-            const uint64_t* s = want_tri ? s_tri : s_non;
-            const int per = (int)((n_chunks + 63) / 64);
-            const int c0 = lane * per, c1 = (c0 + per < n_chunks) ? c0 + per : (int)n_chunks;
-            int32_t mine = 0;
-            for (int ch = c0; ch < c1; ++ch) mine += __popcll(s[ch]);
-            int32_t incl = mine;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) { const int32_t t = __shfl_up(incl, d); if (lane >= d) incl += t; }
-            const int32_t excl = incl - mine;
-            if (pick >= excl && pick < incl) {
-                int32_t seen = excl;
-                for (int ch = c0; ch < c1; ++ch) {
-                    uint64_t m = s[ch];
-                    const int32_t cnt = __popcll(m);
-                    if (seen + cnt > pick) {
-                        int k = pick - seen;
-                        while (k-- > 0) m &= m - 1;
-                        *s_next = c.col[r0 + (int64_t)ch * 64 + (__ffsll((unsigned long long)m) - 1)];
-                        break;
-                    }
-                    seen += cnt;
-                }
-            }
-        } else {
-            // list longer than the ballot cache: wavefront 0 re-classifies it in order
-            int32_t seen = 0, res = 0;
-            bool done = false;
-            for (int64_t base = r0; base < r1 && !done; base += 64) {
-                const int64_t e = base + lane;
-                bool hit = false;
-                int32_t w = 0;
-                if (e < r1) {
-                    w = c.col[e];
-                    if (walk_valid(c, w)) {
-                        const bool tri = a.form ? wks_adjacent(a, w) : false;
-                        hit = (tri == want_tri);
-                    }
-                }
-                const uint64_t m = __ballot(hit);
-                const int32_t cnt = __popcll(m);
-                if (seen + cnt > pick) {
-                    const int32_t rank = __popcll(m & ((1ull << lane) - 1ull));
-                    const uint64_t sel = __ballot(hit && (seen + rank == pick));
-                    res = __shfl(w, __ffsll((unsigned long long)sel) - 1);
-                    done = true;
-                }
-                seen += cnt;
-            }
-            if (lane == 0) *s_next = res;
-        }
-    }
-    __syncthreads();
-    return *s_next;
-}
-
 template <int T, int CH>
 __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8))) void triangular_walks_lists_kernel(
     const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, const int32_t* __restrict__ col_sorted,
@@ -1012,8 +886,9 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8))) void 
         int32_t nt, nn;
         wks_count<T, CH>(c, r0, r1, a, s_list[0], s_list[1], tid, nt, nn, s_tri, s_non, s_cnt);   // aps:72,79
         if (nn == 0 || walk_len < 2) continue;                                          // aps:83-84
-        int32_t curr = wks_pick<CH>(c, r0, r1, a, false, (int32_t)sgnn_choice_index(h1, j++, (uint32_t)nn), tid,
-                                    s_tri, s_non, &s_next);                              // aps:74,80
+        const auto adjacent = [&](int32_t w) { return a.form ? wks_adjacent(a, w) : false; };
+        int32_t curr = wk_pick<CH>(c, r0, r1, adjacent, false, (int32_t)sgnn_choice_index(h1, j++, (uint32_t)nn), tid,
+                                   s_tri, s_non, &s_next);                               // aps:74,80
         if (tid == 0) o[1] = curr;
         for (int64_t step = 2; step < walk_len; ++step) {
             // prev's list is in s_list[buf] if it is short; curr's goes into the next hash while it is counted, the third is emptied
@@ -1029,24 +904,48 @@ __global__ __launch_bounds__(T) __attribute__((amdgpu_waves_per_eu(8, 8))) void 
             else if (nn == 0) want_tri = true;                                           // aps:99-100
             else want_tri = (sgnn_uniform01(h1, j++) <= beta);                           // aps:102
             const int32_t pick = (int32_t)sgnn_choice_index(h1, j++, (uint32_t)(want_tri ? nt : nn));
-            curr = wks_pick<CH>(c, r0, r1, a, want_tri, pick, tid, s_tri, s_non, &s_next);
+            curr = wk_pick<CH>(c, r0, r1, adjacent, want_tri, pick, tid, s_tri, s_non, &s_next);
             if (tid == 0) o[step] = curr;
         }
     }
 }
 
-#define WKS_VARIANTS 5
-static int wks_launch(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, const int32_t* hub_index,
-                      const uint32_t* hub_bits, int64_t hub_words, const int32_t* node_order, int64_t n_nodes,
-                      const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr, const int32_t* inb_nodes,
-                      int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta, uint64_t h0,
-                      int64_t item_base, int64_t* out, uint64_t h0_border, int variant, hipStream_t stream)
+// a launch as the entry points describe it to the launches.  mode 3: the internal walks (items [0, n / 2): mode 1, tape h0) and the
+// border walks (items [n / 2, n): mode 2, tape h0_border) of the same patches in ONE launch
+struct WkArgs {
+    const int64_t* rowptr; const int32_t* col; const int32_t* col_sorted;
+    const int32_t* node_order; int64_t n_nodes;
+    const int64_t* patch_ptr; const int32_t* patch_nodes; const int64_t* inb_ptr; const int32_t* inb_nodes;
+    int mode; int64_t n_items, walks_per_patch, walk_len; double beta;
+    uint64_t h0; int64_t item_base; int64_t* out; uint64_t h0_border;
+};
+
+static int wkb_launch(const WkArgs& g, int64_t max_id, hipStream_t stream)
 {
-    const dim3 grid((unsigned)(n_items < 0x7fffffff ? n_items : 0x7fffffff));       // one workgroup per walk
+    static bool attr_set = false;
+    if (!attr_set) {
+        (void)hipFuncSetAttribute((const void*)triangular_walks_wg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WKB_LDS_BYTES);
+        attr_set = true;
+    }
+    const int64_t words = (max_id + 32) / 32;
+    hipLaunchKernelGGL(triangular_walks_wg_kernel, dim3((int)(g.n_items < 2048 ? g.n_items : 2048)), dim3(WKB_THREADS),
+                       (size_t)(words * 4), stream, g.rowptr, g.col, g.col_sorted, g.node_order, g.n_nodes, g.patch_ptr,
+                       g.patch_nodes, g.inb_ptr, g.inb_nodes, g.mode, g.n_items, g.walks_per_patch, g.walk_len, g.beta, g.h0,
+                       g.item_base, g.out, words, g.h0_border);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
+}
+
+#define WKS_VARIANTS 5
+static int wks_launch(const WkArgs& g, const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words, int variant,
+                      hipStream_t stream)
+{
+    const dim3 grid((unsigned)(g.n_items < 0x7fffffff ? g.n_items : 0x7fffffff));   // one workgroup per walk
 #define WKS_GO(T, CH)                                                                                                         \
-    hipLaunchKernelGGL((triangular_walks_lists_kernel<T, CH>), grid, dim3(T), 0, stream, rowptr, col, col_sorted, hub_index,  \
-                       hub_bits, hub_words, node_order, n_nodes, patch_ptr, patch_nodes, inb_ptr, inb_nodes, mode, n_items,    \
-                       walks_per_patch, walk_len, beta, h0, item_base, out, h0_border)
+    hipLaunchKernelGGL((triangular_walks_lists_kernel<T, CH>), grid, dim3(T), 0, stream, g.rowptr, g.col, g.col_sorted,       \
+                       hub_index, hub_bits, hub_words, g.node_order, g.n_nodes, g.patch_ptr, g.patch_nodes, g.inb_ptr,        \
+                       g.inb_nodes, g.mode, g.n_items, g.walks_per_patch, g.walk_len, g.beta, g.h0, g.item_base, g.out,       \
+                       g.h0_border)
     switch (variant) {                              // 0 (the launch rule's choice) == 2
     case 1: WKS_GO(256, 256); break;
     case 3: WKS_GO(1024, 256); break;
@@ -1067,59 +966,66 @@ extern "C" int sgnn_triangular_walks_variants(void) { return WKS_VARIANTS; }
 // the list kernel runs several per CU (2 x 1050 patch walks of 10: 264 -> 164 us).  Tuned on that one hub-heavy graph:
 // between 210 and 2100 walks, and on graphs without hubs: not measured.
 #define WKS_FEW_WALKS 256
+static bool wkb_fits(int64_t max_id) { return max_id > 0 && ((max_id + 32) / 32) * 4 <= WKB_LDS_BYTES; }
 static bool wks_bitmap_kernel_wins(int variant, int64_t n_walks, int64_t max_id) {
-    return variant == 0 && n_walks <= WKS_FEW_WALKS && max_id > 0 && ((max_id + 32) / 32) * 4 <= WKB_LDS_BYTES;
+    return variant == 0 && n_walks <= WKS_FEW_WALKS && wkb_fits(max_id);
 }
 // what variant 0 does with a launch of n_walks walks (both sides counted): 1 = the bitmap kernel (the hub tables are not read)
 extern "C" int sgnn_triangular_walks_rule(int64_t n_walks, int64_t max_id) { return wks_bitmap_kernel_wins(0, n_walks, max_id) ? 1 : 0; }
 
-extern "C" int sgnn_triangular_walks_lists(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
-                                           const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
-                                           const int32_t* node_order, int64_t n_nodes,
-                                           const int64_t* patch_ptr, const int32_t* patch_nodes,
-                                           const int64_t* inb_ptr, const int32_t* inb_nodes,
-                                           int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta,
-                                           uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t max_id, int kernel,
-                                           int variant, int64_t* out, void* stream)
+// Both entry points end here: g.mode 0 / 1 / 2, or 3 with g.n_items counting both sides.  kernel 0: the workgroup kernels (the
+// rule, or the list kernel at the shape `variant` names), 1: the wavefront kernel (no mode 3), 2: the bitmap kernel.
+static int wk_run(const WkArgs& g, int64_t nnz, const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words, int64_t max_id,
+                  int kernel, int variant, hipStream_t stream)
 {
-    if (!rowptr || !col || !col_sorted || !out || n_items < 0 || walk_len < 0 || mode < 0 || mode > 2 || kernel < 0 || kernel > 1 || item_base < 0)
+    if (!g.rowptr || !g.col || !g.col_sorted || !g.out || g.n_items < 0 || g.walk_len < 0 || g.item_base < 0 || g.mode < 0
+        || g.mode > 3 || kernel < 0 || kernel > 2 || (kernel == 1 && g.mode == 3))
         return SGNN_ERR_BAD_ARG;
     if (variant < 0 || variant >= WKS_VARIANTS || (hub_index != nullptr) != (hub_bits != nullptr) || (hub_index && hub_words < 1))
         return SGNN_ERR_BAD_ARG;
-    if (mode == 0 && (!node_order || n_nodes <= 0)) return SGNN_ERR_BAD_ARG;
-    if (mode >= 1 && (!patch_ptr || !patch_nodes || walks_per_patch <= 0)) return SGNN_ERR_BAD_ARG;
-    if (mode == 2 && (!inb_ptr || !inb_nodes)) return SGNN_ERR_BAD_ARG;
+    if (g.mode == 0 && (!g.node_order || g.n_nodes <= 0)) return SGNN_ERR_BAD_ARG;
+    if (g.mode >= 1 && (!g.patch_ptr || !g.patch_nodes || g.walks_per_patch <= 0)) return SGNN_ERR_BAD_ARG;
+    if (g.mode >= 2 && (!g.inb_ptr || !g.inb_nodes)) return SGNN_ERR_BAD_ARG;
     if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
-    if (n_items == 0 || walk_len == 0) return SGNN_OK;
-    if (kernel == 1 || wks_bitmap_kernel_wins(variant, n_items, max_id))
-        return sgnn_triangular_walks(rowptr, col, col_sorted, nnz, node_order, n_nodes, patch_ptr, patch_nodes, inb_ptr, inb_nodes, mode,
-                                     n_items, walks_per_patch, walk_len, beta, seed, stream_id, item_base, kernel == 1 ? 0 : max_id,
-                                     kernel, out, stream);
-    return wks_launch(rowptr, col, col_sorted, hub_index, hub_bits, hub_words, node_order, n_nodes, patch_ptr, patch_nodes, inb_ptr,
-                      inb_nodes, mode, n_items, walks_per_patch, walk_len, beta, sgnn_tape_h0(seed, stream_id), item_base, out,
-                      (uint64_t)0, variant, (hipStream_t)stream);
+    if (g.n_items == 0 || g.walk_len == 0) return SGNN_OK;
+    if (kernel == 2 && !wkb_fits(max_id)) return SGNN_ERR_SET_TOO_LARGE;
+    if (kernel == 2 || (kernel == 0 && wks_bitmap_kernel_wins(variant, g.n_items, max_id))) return wkb_launch(g, max_id, stream);
+    if (kernel == 0) return wks_launch(g, hub_index, hub_bits, hub_words, variant, stream);
+    hipLaunchKernelGGL(triangular_walks_kernel, dim3((int)(g.n_items < 256 * 32 ? g.n_items : 256 * 32)), dim3(64), 0, stream,
+                       g.rowptr, g.col, g.col_sorted, g.node_order, g.n_nodes, g.patch_ptr, g.patch_nodes, g.inb_ptr, g.inb_nodes,
+                       g.mode, g.n_items, g.walks_per_patch, g.walk_len, g.beta, g.h0, g.item_base, g.out);
+    SGNN_CHECK_LAUNCH();
+    return SGNN_OK;
 }
 
-extern "C" int sgnn_triangular_walks_both_lists(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
-                                                const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
-                                                const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr,
-                                                const int32_t* inb_nodes, int64_t n_items, int64_t walks_per_patch, int64_t walk_len,
-                                                double beta, uint64_t seed, uint64_t stream_id_int, uint64_t stream_id_bor,
-                                                int64_t item_base, int64_t max_id, int variant, int64_t* out, void* stream)
+extern "C" int sgnn_triangular_walks(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
+                                     const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
+                                     const int32_t* node_order, int64_t n_nodes,
+                                     const int64_t* patch_ptr, const int32_t* patch_nodes,
+                                     const int64_t* inb_ptr, const int32_t* inb_nodes,
+                                     int mode, int64_t n_items, int64_t walks_per_patch, int64_t walk_len, double beta,
+                                     uint64_t seed, uint64_t stream_id, int64_t item_base, int64_t max_id, int kernel,
+                                     int variant, int64_t* out, void* stream)
 {
-    if (!rowptr || !col || !col_sorted || !out || !patch_ptr || !patch_nodes || !inb_ptr || !inb_nodes || n_items < 0 || walk_len < 0
-        || walks_per_patch <= 0 || item_base < 0)
-        return SGNN_ERR_BAD_ARG;
-    if (variant < 0 || variant >= WKS_VARIANTS || (hub_index != nullptr) != (hub_bits != nullptr) || (hub_index && hub_words < 1))
-        return SGNN_ERR_BAD_ARG;
-    if (nnz >= (1ll << 31)) return SGNN_ERR_NNZ_TOO_LARGE;
-    if (n_items == 0 || walk_len == 0) return SGNN_OK;
-    if (wks_bitmap_kernel_wins(variant, 2 * n_items, max_id))
-        return sgnn_triangular_walks_both(rowptr, col, col_sorted, nnz, patch_ptr, patch_nodes, inb_ptr, inb_nodes, n_items, walks_per_patch,
-                                          walk_len, beta, seed, stream_id_int, stream_id_bor, item_base, max_id, out, stream);
-    return wks_launch(rowptr, col, col_sorted, hub_index, hub_bits, hub_words, nullptr, 0, patch_ptr, patch_nodes, inb_ptr, inb_nodes, 3,
-                      2 * n_items, walks_per_patch, walk_len, beta, sgnn_tape_h0(seed, stream_id_int), item_base, out,
-                      sgnn_tape_h0(seed, stream_id_bor), variant, (hipStream_t)stream);
+    if (mode > 2) return SGNN_ERR_BAD_ARG;          // the combined launch has its own entry
+    const WkArgs g = {rowptr, col, col_sorted, node_order, n_nodes, patch_ptr, patch_nodes, inb_ptr, inb_nodes, mode, n_items,
+                      walks_per_patch, walk_len, beta, sgnn_tape_h0(seed, stream_id), item_base, out, 0};
+    return wk_run(g, nnz, hub_index, hub_bits, hub_words, max_id, kernel, variant, (hipStream_t)stream);
+}
+
+// The internal AND the border walks over the same patches (aps:118-158 called twice by the reference: inside = True / False) in
+// one launch: out (2, n_items, walk_len), [0] = internal (tape stream stream_id_int), [1] = border (stream_id_bor)
+extern "C" int sgnn_triangular_walks_both(const int64_t* rowptr, const int32_t* col, const int32_t* col_sorted, int64_t nnz,
+                                          const int32_t* hub_index, const uint32_t* hub_bits, int64_t hub_words,
+                                          const int64_t* patch_ptr, const int32_t* patch_nodes, const int64_t* inb_ptr,
+                                          const int32_t* inb_nodes, int64_t n_items, int64_t walks_per_patch, int64_t walk_len,
+                                          double beta, uint64_t seed, uint64_t stream_id_int, uint64_t stream_id_bor,
+                                          int64_t item_base, int64_t max_id, int kernel, int variant, int64_t* out, void* stream)
+{
+    const WkArgs g = {rowptr, col, col_sorted, nullptr, 0, patch_ptr, patch_nodes, inb_ptr, inb_nodes, 3, 2 * n_items,
+                      walks_per_patch, walk_len, beta, sgnn_tape_h0(seed, stream_id_int), item_base, out,
+                      sgnn_tape_h0(seed, stream_id_bor)};
+    return wk_run(g, nnz, hub_index, hub_bits, hub_words, max_id, kernel, variant, (hipStream_t)stream);
 }
 
 SGNN_DEFINE_WARM(samplers)

@@ -1099,10 +1099,11 @@ def draw_border_anchors_keyed(borders, hops, keys, row_has_pad, n_slots, seed, s
     return anchor, sims
 
 
-def _walk_hub_args(g, hub_tables, n_walks, variant):
-    """(hub_index, hub_bits, W) pointers of the walk kernel's adjacency test against long lists, or (None, None, 0) -- also for
-    a launch the rule (variant 0) sends to the bitmap kernel, which does not read them: such a launch builds no tables."""
-    if not hub_tables or not hasattr(g, 'hub_tables'):
+def _walk_hub_args(g, hub_tables, n_walks, kernel, variant):
+    """(hub_index, hub_bits, W) pointers of the list kernel's adjacency test against long lists, or (None, None, 0) -- also for
+    the kernels that do not read them (kernel 1, 2, and a launch the rule, variant 0, sends to the bitmap kernel): such a launch
+    builds no tables."""
+    if not hub_tables or int(kernel) != 0 or not hasattr(g, 'hub_tables'):
         return None, None, 0
     if int(variant) == 0 and _lib.load().sgnn_triangular_walks_rule(int(n_walks), g.max_id):
         return None, None, 0
@@ -1115,35 +1116,36 @@ def triangular_walks(g, mode, n_items, walk_len, beta, seed, stream_id, patches=
     """mode 0 'graph' / 1 'inside' / 2 'border' -> (n_items, walk_len) int64, PAD filled.
     kernel: 0 = a workgroup per walk (variant 0: up to 256 walks on a graph whose id bitmap fits LDS run on the bitmap kernel,
     a walk per CU; more walks, or larger graphs, on the list kernel, several walks per CU -- adjacency to the previous node:
-    its list in LDS, its bit of the graph's hub tables, or a search), 1 = the wavefront-per-walk kernel (same walks).
+    its list in LDS, its bit of the graph's hub tables, or a search), 1 = the wavefront-per-walk kernel, 2 = the bitmap kernel
+    whatever the size of the launch (an error where the graph's ids do not fit it) -- same walks.
     item_base: global number of this call's first walk (a share of a larger launch: same draws).
     hub_tables = False: long lists are searched even where the graph has the tables; variant >= 1: the list kernel always, at
-    the launch shapes sgnn_triangular_walks_lists knows (same walks -- both for tests and measurements)."""
+    the launch shapes sgnn_triangular_walks knows (same walks -- both for tests and measurements)."""
     lib = _lib.load()
     out = torch.empty((n_items, walk_len), dtype=torch.int64, device=g.device)
-    hi, hb, hw = _walk_hub_args(g, hub_tables and int(kernel) == 0, n_items, variant)
-    check(lib.sgnn_triangular_walks_lists(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, hi, hb, hw, _ptr(g.node_order),
-                                          g.n_nodes, _ptr(patches.ptr) if patches else None,
-                                          _ptr(patches.nodes) if patches else None,
-                                          _ptr(in_border.ptr) if in_border else None,
-                                          _ptr(in_border.nodes) if in_border else None,
-                                          mode, n_items, walks_per_patch, walk_len, float(beta), seed, stream_id, int(item_base),
-                                          g.max_id, int(kernel), int(variant), _ptr(out), _stream()), 'sgnn_triangular_walks_lists')
+    hi, hb, hw = _walk_hub_args(g, hub_tables, n_items, kernel, variant)
+    check(lib.sgnn_triangular_walks(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, hi, hb, hw, _ptr(g.node_order),
+                                    g.n_nodes, _ptr(patches.ptr) if patches else None,
+                                    _ptr(patches.nodes) if patches else None,
+                                    _ptr(in_border.ptr) if in_border else None,
+                                    _ptr(in_border.nodes) if in_border else None,
+                                    mode, n_items, walks_per_patch, walk_len, float(beta), seed, stream_id, int(item_base),
+                                    g.max_id, int(kernel), int(variant), _ptr(out), _stream()), 'sgnn_triangular_walks')
     return out
 
 
 def triangular_walks_both(g, n_items, walk_len, beta, seed, stream_id_int, stream_id_bor, patches, in_border, walks_per_patch,
-                          item_base=0, hub_tables=True, variant=0):
+                          item_base=0, hub_tables=True, variant=0, kernel=0):
     """The internal and the border walks over the same patches in ONE launch -> (2, n_items, walk_len) int64, [0] internal,
-    [1] border: what triangular_walks(mode 1) and triangular_walks(mode 2) return, on every graph."""
+    [1] border: what triangular_walks(mode 1) and triangular_walks(mode 2) return, on every graph.  kernel: 0 or 2, as there."""
     lib = _lib.load()
     out = torch.empty((2, n_items, walk_len), dtype=torch.int64, device=g.device)
-    hi, hb, hw = _walk_hub_args(g, hub_tables, 2 * n_items, variant)
-    check(lib.sgnn_triangular_walks_both_lists(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, hi, hb, hw, _ptr(patches.ptr),
-                                               _ptr(patches.nodes), _ptr(in_border.ptr), _ptr(in_border.nodes), n_items,
-                                               walks_per_patch, walk_len, float(beta), seed, stream_id_int, stream_id_bor,
-                                               int(item_base), g.max_id, int(variant), _ptr(out), _stream()),
-          'sgnn_triangular_walks_both_lists')
+    hi, hb, hw = _walk_hub_args(g, hub_tables, 2 * n_items, kernel, variant)
+    check(lib.sgnn_triangular_walks_both(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, hi, hb, hw, _ptr(patches.ptr),
+                                         _ptr(patches.nodes), _ptr(in_border.ptr), _ptr(in_border.nodes), n_items,
+                                         walks_per_patch, walk_len, float(beta), seed, stream_id_int, stream_id_bor,
+                                         int(item_base), g.max_id, int(kernel), int(variant), _ptr(out), _stream()),
+          'sgnn_triangular_walks_both')
     return out
 
 

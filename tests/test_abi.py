@@ -23,7 +23,7 @@ def test_library_exports_every_declared_symbol():
     for n in names:
         assert hasattr(lib, n), n
     assert sorted(_lib.SIGNATURES) == names        # the ctypes table mirrors the header
-    assert lib.sgnn_abi_version() == 13
+    assert lib.sgnn_abi_version() == 14
 
 
 def test_every_kernel_header_is_a_build_dependency():
@@ -53,6 +53,15 @@ def test_argument_errors_are_reported_not_thrown():
     lib = _lib.load()
     assert lib.sgnn_degree_sequence(None, None, 0, None, None, None, None, 0, 1, 1, None, None, None, None) == -1
     assert lib.sgnn_mpn_fwd(None, None, None, None) == -1
+
+
+def test_the_walk_entries_report_null_pointers():
+    from subgnn_amd import _lib
+    lib = _lib.load()
+    assert lib.sgnn_triangular_walks(None, None, None, 0, None, None, 0, None, 0, None, None, None, None, 0, 1, 1, 1, 0.5, 0, 0, 0, 0,
+                                     0, 0, None, None) == -1
+    assert lib.sgnn_triangular_walks_both(None, None, None, 0, None, None, 0, None, None, None, None, 1, 1, 1, 0.5, 0, 0, 0, 0, 0,
+                                          0, 0, None, None) == -1
 
 
 def test_cpu_tensors_are_rejected():

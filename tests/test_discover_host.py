@@ -146,9 +146,9 @@ def test_the_new_symbols_are_declared_and_bound():
     txt = open(os.path.join(REPO, 'include', 'subgnn_hip.h')).read()
     assert re.search(r'\bint64_t sgnn_seeded_walk_max_size\s*\(void\)', txt) and re.search(r'\bint sgnn_seeded_walk_sets\s*\(', txt)
     assert 'sgnn_seeded_walk_max_size' in _lib.SIGNATURES and len(_lib.SIGNATURES['sgnn_seeded_walk_sets'][1]) == 20
-    assert '#define SGNN_ABI_VERSION 13' in txt
+    assert '#define SGNN_ABI_VERSION 14' in txt
     lib = _lib.load()
-    assert lib.sgnn_abi_version() == 13 and lib.sgnn_seeded_walk_max_size() == DC.MAX_SIZE
+    assert lib.sgnn_abi_version() == 14 and lib.sgnn_seeded_walk_max_size() == DC.MAX_SIZE
     # refused on the host, before any launch (no pointer is read): the arguments after the graph's are
     # (seeds, n_seeds, sizes, per_seed, width, restart_thr, max_steps, seed, stream, item_base, item_ids, n_items, outputs x 4, stream)
     call = lambda *a: lib.sgnn_seeded_walk_sets(None, None, 10, None, *a, None, None, None, None, None)

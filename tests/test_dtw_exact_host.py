@@ -88,7 +88,7 @@ def test_workspace_query_answers_on_the_host_and_null_arguments_are_errors():
     assert lib.sgnn_dtw_exact_workspace_bytes(0, 0, 0, 0) > 0
     assert lib.sgnn_dtw_exact_similarity(None, None, 1, 1, None, None, 1, 1, 0, None, None, None, 0, None) == -1
     assert lib.sgnn_dtw_exact_similarity_live(None, None, 1, 1, None, None, 1, 1, 0, None, None, None, None, 0, None) == -1
-    assert lib.sgnn_abi_version() == 13
+    assert lib.sgnn_abi_version() == 14
 
 
 def test_unknown_similarity_function_is_rejected_before_the_library_is_touched(monkeypatch):

@@ -83,7 +83,7 @@ def test_the_new_symbols_are_declared_and_bound():
         assert re.search(r'\b%s\s*\(' % name, txt), name
         assert name in _lib.SIGNATURES
     assert 'SGNN_OCC_NODE 0' in txt and 'SGNN_OCC_COMPONENT 1' in txt
-    assert '#define SGNN_ABI_VERSION 13' in txt
+    assert '#define SGNN_ABI_VERSION 14' in txt
     lib = _lib.load()
     assert lib.sgnn_occlusion_workspace_bytes(1000) == 16000 and lib.sgnn_occlusion_workspace_bytes(-1) == 0
     # refused on the host, before any launch: unknown mode, negative sizes, null pointers with non-zero counts

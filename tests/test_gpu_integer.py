@@ -665,17 +665,17 @@ def test_a_share_of_the_walks_draws_what_the_whole_launch_draws(walk_kernel):
 
 
 def test_walks_hubs_both_kernels_agree():
-    """Long walks over hubs (lists longer than one 64-entry chunk per wavefront, several workgroup
-    passes over the items): the two kernels return the same walks."""
+    """Long walks over hubs (lists longer than one 64-entry chunk per wavefront; on the bitmap kernel, kernel 2, several
+    workgroup passes over the items): the kernels return the same walks."""
     from subgnn_amd import synthetic
     ops = _ops()
     n = 30000
     rowptr, col = synthetic.sorted_csr(synthetic.barabasi_albert_edges(n, 12, seed=4), n)
     dg = ops.DeviceGraph(rowptr, col, np.arange(1, n + 1, dtype=np.int32), DEV)
     out = {}
-    for kernel in (0, 1):
+    for kernel in (0, 1, 2):
         out[kernel] = ops.triangular_walks(dg, 0, 3000, 40, 0.65, 5, T.stream_id(T.STREAM_STRUCT_PATCH), kernel=kernel)
-    assert torch.equal(out[0], out[1]) and int((out[0] != 0).sum()) > 3000 * 20
+    assert torch.equal(out[0], out[1]) and torch.equal(out[2], out[1]) and int((out[0] != 0).sum()) > 3000 * 20
 
 
 # ---- a9 shortest-path similarities --------------------------------------------------------

@@ -1,6 +1,7 @@
-"""-m gpu: the workgroup-per-walk kernel without an id bitmap (``ops.triangular_walks(kernel=0)``, ``ops.triangular_walks_both``)
-against the wavefront kernel (``kernel=1``) and the oracle, element for element, on the cases of tests/walks_cases.py --
-tests/test_walks_cases_host.py shows that they reach the branches they are named for."""
+"""-m gpu: the two workgroup-per-walk kernels -- the list kernel and the launch rule (``ops.triangular_walks(kernel=0)``,
+``ops.triangular_walks_both``) and the bitmap kernel on its own (``kernel=2``) -- against the wavefront kernel (``kernel=1``) and
+the oracle, element for element, on the cases of tests/walks_cases.py -- tests/test_walks_cases_host.py shows that they reach
+the branches they are named for."""
 import functools
 
 import numpy as np
@@ -39,9 +40,10 @@ def _graph_walks(G, n, walk_len, **kw):
 
 def _check_graph_walks(G, n, walk_len, tables=(True, False), variants=(0, WC.LIST_KERNEL)):
     """variant 0 is the launch rule (the bitmap kernel for launches of up to WC.FEW_WALKS walks on these small graphs),
-    WC.LIST_KERNEL the list kernel whatever the size of the launch."""
+    WC.LIST_KERNEL the list kernel whatever the size of the launch; kernel 2 the bitmap kernel whatever the size."""
     ref = _ref(G, n, walk_len)
-    assert np.array_equal(_graph_walks(G, n, walk_len, kernel=1), ref)
+    for kernel in (1, 2):
+        assert np.array_equal(_graph_walks(G, n, walk_len, kernel=kernel), ref), kernel
     for hub_tables in tables:
         for variant in variants:
             got = _graph_walks(G, n, walk_len, hub_tables=hub_tables, variant=variant)
@@ -98,11 +100,11 @@ def test_patch_modes_and_the_combined_launch(walks_per_patch):
     n, L = len(views) * walks_per_patch, 6
     K = WC.LIST_KERNEL
     both = ops.triangular_walks_both(dg, n, L, WC.BETA, WC.SEED, SID_INT, SID_BOR, vr, ir, walks_per_patch, variant=K)
-    for kw in ({'variant': K, 'hub_tables': False}, {'variant': 0}):
+    for kw in ({'variant': K, 'hub_tables': False}, {'variant': 0}, {'kernel': 2}):
         assert torch.equal(both, ops.triangular_walks_both(dg, n, L, WC.BETA, WC.SEED, SID_INT, SID_BOR, vr, ir, walks_per_patch, **kw))
     for k, (inside, sid) in enumerate(((True, SID_INT), (False, SID_BOR))):
         ref = WC.patch_walks(G, views, inb, walks_per_patch, L, inside)
-        for kernel, variant in ((0, K), (0, 0), (1, 0)):
+        for kernel, variant in ((0, K), (0, 0), (1, 0), (2, 0)):
             got = ops.triangular_walks(dg, 1 if inside else 2, n, L, WC.BETA, WC.SEED, sid, patches=vr, in_border=ir,
                                        walks_per_patch=walks_per_patch, kernel=kernel, variant=variant)
             assert np.array_equal(got.cpu().numpy(), ref), (inside, kernel, variant)
@@ -127,6 +129,36 @@ def test_more_walks_than_the_chip_holds_at_once():
     got = _graph_walks(G, 5000, 3)
     assert np.array_equal(got, _graph_walks(G, 5000, 3, kernel=1))
     assert np.array_equal(got[:500], _ref(G, 500, 3))
+
+
+def test_the_bitmap_kernel_takes_several_items_per_workgroup_and_cleans_up_between_them():
+    """WC.BITMAP_GRID workgroups, 64 walks more: the first 64 workgroups take a second item, on the bitmap their first walk
+    used.  A bit left behind would turn a non-triangle candidate of the second walk into a triangle one
+    (test_walks_cases_host: some of those walks meet both classes at a step, after a first walk of full length)."""
+    G = WC.random_graph()
+    n = WC.BITMAP_GRID + 64
+    assert np.array_equal(_graph_walks(G, n, 6, kernel=2), _ref(G, n, 6))
+
+
+def test_the_kernel_argument_is_checked_on_the_host():
+    """Returns of the entry points, made before any launch."""
+    ops = _ops()
+    from subgnn_amd._lib import SubgnnHipError
+    rowptr, col, order = WC.sparse_ids_csr()
+    big = ops.DeviceGraph(rowptr, col, order, DEV)
+    one = ops.Ragged.from_lists([[int(order[0])]], DEV)
+    with pytest.raises(SubgnnHipError):                               # ids beyond the bitmap
+        ops.triangular_walks(big, 0, 10, 4, WC.BETA, WC.SEED, SID, kernel=2)
+    with pytest.raises(SubgnnHipError):
+        ops.triangular_walks_both(big, 1, 4, WC.BETA, WC.SEED, SID_INT, SID_BOR, one, one, 1, kernel=2)
+    G, views, inb = WC.patches()
+    dg = _dev(G)
+    vr, ir = ops.Ragged.from_lists(views, DEV), ops.Ragged.from_lists(inb, DEV)
+    for kernel in (1, 3):                                             # the wavefront kernel has no combined launch
+        with pytest.raises(SubgnnHipError):
+            ops.triangular_walks_both(dg, len(views), 4, WC.BETA, WC.SEED, SID_INT, SID_BOR, vr, ir, 1, kernel=kernel)
+    with pytest.raises(SubgnnHipError):
+        ops.triangular_walks(dg, 0, 10, 4, WC.BETA, WC.SEED, SID, kernel=3)
 
 
 def test_ids_beyond_any_lds_bitmap():

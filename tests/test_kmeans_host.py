@@ -25,14 +25,14 @@ def feature():
 NAMES = ('sgnn_kmeans_max_k', 'sgnn_kmeans_slots', 'sgnn_kmeans_workspace_bytes', 'sgnn_kmeans_step', 'sgnn_kmeans_finish')
 
 
-def test_the_header_and_the_signatures_carry_the_new_entries_and_the_abi_is_13():
+def test_the_header_and_the_signatures_carry_the_new_entries_and_agree_on_the_abi():
     txt = open(os.path.join(REPO, 'include', 'subgnn_hip.h')).read()
     from subgnn_amd import build, _lib, ops
     for name in NAMES:
         assert re.search(r'\b%s\s*\(' % name, txt), name
         assert name in _lib.SIGNATURES
     assert 'Replaces no reference function' in txt[txt.index('n2   k-means'):txt.index('sgnn_kmeans_max_k(void)')]
-    assert re.search(r'#define SGNN_ABI_VERSION 13\b', txt) and _lib.load().sgnn_abi_version() == 13
+    assert re.search(r'#define SGNN_ABI_VERSION 14\b', txt) and _lib.load().sgnn_abi_version() == 14
     assert 'kmeans.hip' in build.SOURCES
     assert callable(ops.kmeans_step) and callable(ops.kmeans)
 

@@ -117,9 +117,9 @@ def test_the_new_symbols_are_declared_and_bound():
     for name in ('sgnn_insertion_count', 'sgnn_insertion_write'):
         assert re.search(r'\bint %s\s*\(' % name, txt), name
         assert name in _lib.SIGNATURES
-    assert '#define SGNN_ABI_VERSION 13' in txt
+    assert '#define SGNN_ABI_VERSION 14' in txt
     lib = _lib.load()
-    assert lib.sgnn_abi_version() == 13
+    assert lib.sgnn_abi_version() == 14
     # refused on the host, before any launch: negative sizes, sizes past 2^31 - 1, shared outside {0, 1}, null pointers with work
     assert lib.sgnn_insertion_count(None, None, -1, 0, None, None, 0, None, None) == -1
     assert lib.sgnn_insertion_count(None, None, 2 ** 31, 0, None, None, 0, None, None) == -1

@@ -26,6 +26,7 @@ def test_constants_are_the_sources():
     shapes = {int(v): (int(t), int(c)) for v, t, c in re.findall(r'case (\d): WKS_GO\((\d+), (\d+)\)', src)}
     shapes[0] = shapes[WC.LIST_KERNEL] = tuple(int(x) for x in re.search(r'default: WKS_GO\((\d+), (\d+)\)', src).groups())
     assert [shapes[v] for v in range(len(WC.CHUNKS))] == list(zip(WC.THREADS, WC.CHUNKS))
+    assert re.search(r'dim3\(\(int\)\(g\.n_items < (\d+) \? g\.n_items : \1\)\), dim3\(WKB_THREADS\)', src).group(1) == str(WC.BITMAP_GRID)
     ds = open(os.path.join(REPO, 'subgnn_amd', 'csrc', 'degree_sequence.hip')).read()
     assert int(re.search(r'^#define DS_SEARCH (\d+)\b', ds, re.M).group(1)) == WC.LIST_MAX     # the hub tables' threshold
 
@@ -79,6 +80,16 @@ def test_dead_ends_and_walks_that_end_at_their_first_node():
     assert any(WC.stopped_at_start(G, w) for w in walks)                    # node 3: nn == 0 at the first step
     G = WC.random_graph()
     assert any(WC.stopped_at_start(G, w) for w in WC.graph_walks(G, 400, 3))
+
+
+def test_second_items_of_a_bitmap_workgroup_meet_both_classes_after_a_full_first_walk():
+    """Walk i >= BITMAP_GRID runs on the bitmap walk i - BITMAP_GRID used: a bit that one left set could only show at a step
+    of the later walk that has both candidate classes -- and a walk of full length is one that held bits to its end."""
+    G = WC.random_graph()
+    n, L = WC.BITMAP_GRID + 64, 6
+    walks = WC.graph_walks(G, n, L)
+    assert any((walks[i - WC.BITMAP_GRID] != 0).all() and any(s['nt'] > 0 and s['nn'] > 0 for s in WC.steps(G, walks[i]))
+               for i in range(WC.BITMAP_GRID, n))
 
 
 def test_patches_lie_on_both_sides_of_the_hash_limit():

@@ -92,7 +92,7 @@ def test_abi_entries_are_declared_mirrored_exported_and_refuse_nulls():
     build.build(verbose=False)
     lib = _lib.load()
     txt, decl = _header()
-    assert '#define SGNN_ABI_VERSION 13' in txt and lib.sgnn_abi_version() == 13
+    assert '#define SGNN_ABI_VERSION 14' in txt and lib.sgnn_abi_version() == 14
     for name in C.NEW_ENTRIES:
         base = name[:-len('_weighted')]
         assert name in decl and base in decl, name

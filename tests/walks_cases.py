@@ -1,13 +1,15 @@
-"""Test helpers of the triangular walks' workgroup-per-walk kernel (triangular_walks_lists_kernel in subgnn_amd/csrc/samplers.hip,
-through ``ops.triangular_walks(kernel=0)`` and ``ops.triangular_walks_both``): the graphs and calls tests/test_gpu_walks.py makes,
+"""Test helpers of the triangular walks' workgroup-per-walk kernels (triangular_walks_lists_kernel and triangular_walks_wg_kernel
+in subgnn_amd/csrc/samplers.hip, through ``ops.triangular_walks(kernel=0 / 2)`` and ``ops.triangular_walks_both``): the graphs and
+calls tests/test_gpu_walks.py makes,
 the oracle's walks for them, and a step-by-step reading of an oracle walk (``steps``) from which tests/test_walks_cases_host.py
 says without a GPU which adjacency form and which branch every case reaches.  numpy and the oracle only; nothing here reads the
 GPU or imports the package.
 
-The kernel answers "is candidate w adjacent to prev?" by the length of N(prev): fewer than LIST_MAX entries -- a hash of the
+The list kernel answers "is candidate w adjacent to prev?" by the length of N(prev): fewer than LIST_MAX entries -- a hash of the
 list in LDS; at least LIST_MAX -- one bit of the graph's hub tables, or, where the graph has none (``hub_tables=False`` in the tests, or
 rows with repeated ids), a binary search in global memory.  Lists of more than 64 * CHUNKS[variant] entries are classified twice
-(the ballots of the count pass are not kept)."""
+(the ballots of the count pass are not kept).  The bitmap kernel (``kernel=2``, and what variant 0 takes for small launches) keeps
+N(prev) as bits over node ids, WK_CHUNKS chunks of ballots, and takes further items per workgroup beyond BITMAP_GRID walks."""
 import functools
 
 import numpy as np
@@ -20,6 +22,7 @@ CHUNKS = (256, 256, 256, 256, 1024)     # ballot-cache chunks of launch variants
 THREADS = (512, 256, 512, 1024, 512)    # their workgroup sizes (variant 0: what the launch rule takes where it takes this kernel)
 LIST_KERNEL = 2                         # the variant that is variant 0's shape WITHOUT the rule: small launches stay on the list kernel
 FEW_WALKS = 256                         # WKS_FEW_WALKS: launches up to this size go to the bitmap kernel under variant 0
+BITMAP_GRID = 2048                      # workgroups of a bitmap-kernel launch at the most: walk i + BITMAP_GRID follows walk i on its bitmap
 HASH_MAX = 96                           # WK_HASH_MAX: patches / in-border sets up to this size are hashed, longer ones scanned
 BETA, SEED = 0.5, 31
 

@@ -1,9 +1,9 @@
-"""The benchmark's two triangular-walk launches between device events, on the benchmark graph: the 125 KB-bitmap kernel (the
-old entry points sgnn_triangular_walks / sgnn_triangular_walks_both), the list kernel (sgnn_triangular_walks_lists /
-_both_lists) at every launch variant, with and without the hub tables, and the wavefront kernel -- alternating in one process,
-``rounds`` times, median in microseconds; every form's walks are compared with the first's.  The walks of a pass do not depend
-on the number of subgraphs (n_anchor_patches_structure x n_layers x max_sim_epochs patches): a 6 250-subgraph shard makes the
-same two launches.  usage: python tools/walks_probe.py [rounds] [OUT.json] [bench.py options] -> one JSON object."""
+"""The benchmark's two triangular-walk launches between device events, on the benchmark graph: the 125 KB-bitmap kernel
+(``kernel=2``), the list kernel at every launch variant, with and without the hub tables, and the wavefront kernel (``kernel=1``)
+-- alternating in one process, ``rounds`` times, median in microseconds; every form's walks are compared with the first's.
+The walks of a pass do not depend on the number of subgraphs (n_anchor_patches_structure x n_layers x max_sim_epochs patches):
+a 6 250-subgraph shard makes the same two launches.
+usage: python tools/walks_probe.py [rounds] [OUT.json] [bench.py options] -> one JSON object."""
 import json
 import os
 import statistics
@@ -22,7 +22,6 @@ def main():
     sys.argv = sys.argv[:1] + ['--subgraphs', '64'] + sys.argv[3:]
     args = bench.parse()
     from subgnn_amd import _lib, anchor_patch_samplers as aps, ops
-    from subgnn_amd.ops import _ptr, _stream
     from oracle import tape
     lib = _lib.load()
     dev = torch.device('cuda', 0)
@@ -39,21 +38,8 @@ def main():
     inb = aps.in_border_sets(g, views)
     torch.cuda.synchronize()
 
-    def old_graph():
-        o = torch.empty((P, L), dtype=torch.int64, device=dev)
-        _lib.check(lib.sgnn_triangular_walks(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, _ptr(g.node_order), g.n_nodes,
-                                             None, None, None, None, 0, P, 1, L, float(beta), 0, sid_p, 0, g.max_id, 0, _ptr(o),
-                                             _stream()), 'old')
-        return o
-
-    def old_both():
-        o = torch.empty((2, P * W, T), dtype=torch.int64, device=dev)
-        _lib.check(lib.sgnn_triangular_walks_both(_ptr(g.rowptr), _ptr(g.col), _ptr(g.col_sorted), g.nnz, _ptr(views.ptr),
-                                                  _ptr(views.nodes), _ptr(inb.ptr), _ptr(inb.nodes), P * W, W, T, float(beta), 0, sid_i,
-                                                  sid_b, 0, g.max_id, _ptr(o), _stream()), 'old both')
-        return o
-
-    forms = {'bitmap_1024_threads': (old_graph, old_both)}
+    forms = {'bitmap_1024_threads': (lambda: ops.triangular_walks(g, 0, P, L, beta, 0, sid_p, kernel=2),
+                                     lambda: ops.triangular_walks_both(g, P * W, T, beta, 0, sid_i, sid_b, views, inb, W, kernel=2))}
     n_var = int(lib.sgnn_triangular_walks_variants())
     for v in range(n_var):
         for tables in (True, False):
