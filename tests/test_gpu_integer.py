@@ -32,7 +32,7 @@ def _rand_graph(n, m, seed):
     edges = list(Gx.edges())
     edges = [edges[i] for i in rng.permutation(len(edges))]
     edges += [(3, 3), (10, 10), (0, 0)]                   # self loops (one of them on a hub whose list is searched, not streamed)
-    edges += [(0, i) for i in range(1, min(n, 1300))] + [(7, i) for i in range(8, min(n, 700))]   # hubs (deg >= 256 path)
+    edges += [(0, i) for i in range(1, min(n, 1300))] + [(7, i) for i in range(8, min(n, 700))]   # hubs (deg >= 512 path)
     return OG.from_edge_pairs(edges)
 
 
