@@ -1209,27 +1209,21 @@ def bfs_min_hops_to_sets(g, sources, sets, max_hops=64, want_status=False, pull_
     ``until``: 'nodes' runs until no node gains a source; 'sets' is the closing form (sgnn_bfs_min_hops_to_sets_closing): it
     stops once every set has its hops -- the same values whenever status[1] == 0, status[0] is then the closing level.  It
     takes the graph as symmetric and uses g.component_labels()."""
+    if until not in ('nodes', 'sets'):
+        raise ValueError("until must be 'nodes' or 'sets', not %r" % (until,))
     lib = _lib.load()
     _req(sources, torch.int32, 'sources')
     ns = sources.numel()
+    name, query, extra = 'sgnn_bfs_min_hops_to_sets', lib.sgnn_bfs_min_hops_workspace_bytes, ()
+    if until == 'sets':
+        name, query, extra = name + '_closing', lib.sgnn_bfs_min_hops_closing_workspace_bytes, (_ptr(g.component_labels()),)
     out = torch.empty((sets.n, ns), dtype=torch.float32, device=g.device)
     status = torch.zeros(4, dtype=torch.int32, device=g.device) if want_status else None
-    if until == 'sets':
-        labels = g.component_labels()
-        wsb = lib.sgnn_bfs_min_hops_closing_workspace_bytes(g.max_id, ns, max_hops, sets.n)
-        ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=g.device)
-        check(lib.sgnn_bfs_min_hops_to_sets_closing(_ptr(g.rowptr), _ptr(g.col), g.nnz, g.max_id, _ptr(sources), ns, max_hops,
-                                                    int(pull_alpha), int(push_levels), _ptr(labels), _ptr(sets.ptr),
-                                                    _ptr(sets.nodes), sets.n, _ptr(out), _ptr(status), _ptr(ws), wsb, _stream()),
-              'sgnn_bfs_min_hops_to_sets_closing')
-        return (out, status) if want_status else out
-    if until != 'nodes':
-        raise ValueError("until must be 'nodes' or 'sets', not %r" % (until,))
-    wsb = lib.sgnn_bfs_min_hops_workspace_bytes(g.max_id, ns, max_hops, sets.n)
+    wsb = query(g.max_id, ns, max_hops, sets.n)
     ws = torch.empty(wsb // 8 + 1, dtype=torch.int64, device=g.device)
-    check(lib.sgnn_bfs_min_hops_to_sets(_ptr(g.rowptr), _ptr(g.col), g.nnz, g.max_id, _ptr(sources), ns, max_hops,
-                                        int(pull_alpha), int(push_levels), _ptr(sets.ptr), _ptr(sets.nodes), sets.n, _ptr(out), _ptr(status), _ptr(ws), wsb,
-                                        _stream()), 'sgnn_bfs_min_hops_to_sets')
+    check(getattr(lib, name)(_ptr(g.rowptr), _ptr(g.col), g.nnz, g.max_id, _ptr(sources), ns, max_hops, int(pull_alpha),
+                             int(push_levels), *extra, _ptr(sets.ptr), _ptr(sets.nodes), sets.n, _ptr(out), _ptr(status), _ptr(ws),
+                             wsb, _stream()), name)
     return (out, status) if want_status else out
 
 
