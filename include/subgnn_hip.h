@@ -448,6 +448,64 @@ int sgnn_seeded_walk_sets(const int64_t* rowptr, const int32_t* col, int64_t max
                           int32_t* out_nodes, int32_t* out_len, int32_t* out_steps, uint64_t* out_keys, void* stream_handle);
 
 /* ---------------------------------------------------------------------------------------
+ * Node overlap of ragged node sets.  The reference has no counterpart: it compares subgraphs through the model only.
+ *
+ * A SET is an ascending int32 array without repeats, ids >= 0; it may be empty.  A BANK is n_rows sets (bank_ptr: int64,
+ * n_rows + 1; only the sizes are read) with its POSTINGS: post_rows[post_ptr[v] .. post_ptr[v + 1]) (post_ptr int64,
+ * max_id + 2 entries; post_rows int32) are, ascending, the bank rows that hold node v.  A query id above max_id is held by no
+ * row.  The number of postings a set walks is P = sum over its members v <= max_id of post_ptr[v + 1] - post_ptr[v]; the
+ * caller passes it per set.  It decides where the set's counting table lives: P <= sgnn_overlap_lds_max() (2048) in LDS,
+ * beyond it in the workspace, in the region at the set's offset (q_ws_off[s], in postings: the exclusive prefix sums of the P
+ * of the sets beyond the LDS tier; ws_entries = their sum <= 2^28, workspace of sgnn_overlap_workspace_bytes(ws_entries)
+ * bytes, < 0 for a count the calls refuse).  A set beyond the LDS tier whose region the workspace does not hold gets fillers.
+ * Results never depend on the home.
+ *
+ * sgnn_overlap_topk: for every query q the k <= sgnn_overlap_max_k() (64) best bank rows b among those with i = |q n b| >= 1,
+ * best first.  The measure is a fraction num / den:
+ *     SGNN_OVL_JACCARD      i / (|q| + |b| - i)
+ *     SGNN_OVL_CONTAINMENT  i / |q|
+ *     SGNN_OVL_COVERAGE     i / |b|
+ *     SGNN_OVL_COUNT        i / 1
+ * The order is exact: the larger fraction first, compared by n1 * d2 against n2 * d1 in 64 bits (every factor < 2^31), never
+ * through a quotient; equal fractions by the smaller row.  It is strict and total.  exclude (nullable): per query a bank row to
+ * skip, or -1.  out_rows (Q, k) int64, fillers -1; out_inter (Q, k) int32, the i of those rows, fillers 0; out_touched (Q)
+ * int32: the number of bank rows with i >= 1, the excluded one included.  One workgroup per query.
+ *
+ * sgnn_overlap_diverse: greedy selection among n_sets sets given in rank order (row r is rank r) with their OWN postings (the
+ * bank is the sets themselves), the threshold tau = tau_num / tau_den (0 <= tau_num <= tau_den <= 2^20) and top >= 1:
+ *     accepted = []; by = [-1] * N
+ *     for r in 0 .. N-1:
+ *         if by[r] >= 0: continue
+ *         accepted.append(r)
+ *         if len(accepted) == top: break
+ *         for every c > r with by[c] < 0 and i(r,c) * tau_den > tau_num * (|r| + |c| - i(r,c)):
+ *             by[c] = r
+ * (a pair with an empty union shares nothing and is never too similar).  out_accepted (top) int64, fillers -1; out_n (1)
+ * int32 = len(accepted); out_suppressed_by (N) int32 = by.  ONE launch of one workgroup, which reads nothing back; its
+ * workspace holds one region: ws_entries >= the largest P beyond the LDS tier (0: none is).
+ *
+ * SGNN_ERR_BAD_ARG before any launch, with nothing written, for negative sizes, sizes or max_id above 2^31 - 1, k, measure,
+ * tau or top outside their ranges, a workspace smaller than its query says, and a NULL pointer that the call would read or
+ * write (q_ws_off and the workspace may be NULL with ws_entries = 0).  n_queries = 0 writes nothing.
+ * ------------------------------------------------------------------------------------- */
+#define SGNN_OVL_JACCARD     0
+#define SGNN_OVL_CONTAINMENT 1
+#define SGNN_OVL_COVERAGE    2
+#define SGNN_OVL_COUNT       3
+int64_t sgnn_overlap_max_k(void);
+int64_t sgnn_overlap_lds_max(void);
+int64_t sgnn_overlap_workspace_bytes(int64_t entries);
+int sgnn_overlap_topk(const int64_t* q_ptr, const int32_t* q_nodes, int64_t n_queries, const int64_t* q_postings,
+                      const int64_t* q_ws_off, const int64_t* bank_ptr, int64_t n_rows, const int64_t* post_ptr,
+                      const int32_t* post_rows, int64_t max_id, const int64_t* exclude, int64_t k, int measure,
+                      void* workspace, int64_t ws_entries, int64_t workspace_bytes, int64_t* out_rows, int32_t* out_inter,
+                      int32_t* out_touched, void* stream);
+int sgnn_overlap_diverse(const int64_t* set_ptr, const int32_t* set_nodes, int64_t n_sets, const int64_t* set_postings,
+                         const int64_t* post_ptr, const int32_t* post_rows, int64_t max_id, int64_t tau_num, int64_t tau_den,
+                         int64_t top, void* workspace, int64_t ws_entries, int64_t workspace_bytes, int64_t* out_accepted,
+                         int32_t* out_n, int32_t* out_suppressed_by, void* stream);
+
+/* ---------------------------------------------------------------------------------------
  * a1-a3  Triangular random walks.
  * Replaces anchor_patch_samplers.triangular_random_walk / perform_random_walks /
  * sample_structure_anchor_patches (anchor_patch_samplers.py:20-158, 210-243).

@@ -81,6 +81,13 @@ SIGNATURES = {
     'sgnn_seeded_walk_max_size': (c_i64, []),
     'sgnn_seeded_walk_sets': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_ptr, c_i64, c_i64, c_u64, c_i64, c_u64, c_u64, c_i64,
                                       c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sgnn_overlap_max_k': (c_i64, []),
+    'sgnn_overlap_lds_max': (c_i64, []),
+    'sgnn_overlap_workspace_bytes': (c_i64, [c_i64]),
+    'sgnn_overlap_topk': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_int, c_ptr,
+                                  c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    'sgnn_overlap_diverse': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr,
+                                     c_ptr, c_ptr, c_ptr]),
     'sgnn_sample_anchors_ragged_keyed': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
     'sgnn_choice_ragged_keyed': (c_int, [c_ptr, c_ptr, c_i64, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr]),
     'sgnn_sample_border_anchors_keyed': (c_int, [c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_u64, c_u64, c_ptr, c_ptr,

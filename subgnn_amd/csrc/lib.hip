@@ -38,6 +38,7 @@ extern "C" int sgnn_warm_occlusion(void*);
 extern "C" int sgnn_warm_insertion(void*);
 extern "C" int sgnn_warm_seeded_sets(void*);
 extern "C" int sgnn_warm_kmeans(void*);
+extern "C" int sgnn_warm_overlap(void*);
 extern "C" int sgnn_warm_up(void* stream)
 {
     int bad = 0;
@@ -65,5 +66,6 @@ extern "C" int sgnn_warm_up(void* stream)
     bad += sgnn_warm_insertion(stream) != 0;
     bad += sgnn_warm_seeded_sets(stream) != 0;
     bad += sgnn_warm_kmeans(stream) != 0;
+    bad += sgnn_warm_overlap(stream) != 0;
     return bad == 0 ? SGNN_OK : SGNN_ERR_LAUNCH;
 }

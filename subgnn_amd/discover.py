@@ -13,6 +13,10 @@ sampled again from their item numbers afterwards.
     python -m subgnn_amd.discover -config_path CONFIG -restoreModelPath DIR [-restoreModelName F] -seeds FILE|all -out FILE
                                   [-target LABEL] [-sizes 5,10,20] [-per_seed 16] [-restart 0.15] [-max_steps N] [-draws E]
                                   [-top N] [-top_per_seed N] [-novel] [-batch_size B] [-sample_seed S]
+                                  [-max_overlap T] [-overlap_pool M]
+
+``-max_overlap T`` makes the list diverse: of the ranked candidates (the first ``-overlap_pool`` of them) one is dropped when a
+better candidate that is kept shares more than T of their joint nodes with it (Jaccard; ops.overlap_diverse, csrc/overlap.hip).
 """
 import argparse
 from pathlib import Path
@@ -79,8 +83,25 @@ def select(order, seed_index, top=None, top_per_seed=None):
     return order if top is None else order[:top]
 
 
+def diverse(g, seeds_t, walk, c, pool, max_overlap, top):
+    """Of the ranked candidates ``pool`` (indices into the kept scalars ``c``) those the greedy selection accepts, in rank order
+    -> (index array, the number of pool candidates it suppressed).  Their node lists are sampled again from their item numbers
+    (and checked against the scored keys), then ops.overlap_diverse runs once."""
+    if pool.size == 0:
+        return pool, 0
+    sel = torch.from_numpy(pool).to(seeds_t.device)
+    again = ops.seeded_walk_sets(g, seeds_t, item_ids=c['item'][sel].contiguous(), **walk)
+    if not torch.equal(again.keys, c['keys'][sel]):
+        raise RuntimeError('discover: the regenerated candidates are not the scored ones')
+    if bool((again.lengths == 0).any()):
+        raise RuntimeError('discover: a regenerated candidate is empty')
+    accepted, n, by = ops.overlap_diverse(again.sets, max_overlap, pool.size if top is None else top)
+    n = int(n.item())
+    return pool[accepted[:n].cpu().numpy()], int((by >= 0).sum().item())
+
+
 def discover(p, seeds, sizes=(8,), per_seed=16, target=None, restart=0.15, max_steps=None, draws=1, top=100, top_per_seed=None,
-             novel=False, batch_size=None, max_variants=65536, sample_seed=None):
+             novel=False, batch_size=None, max_variants=65536, sample_seed=None, max_overlap=None, overlap_pool=4096):
     """``Predictor.discover``.  -> dict, for the returned candidates in rank order (device tensors unless said otherwise):
       ``subgraphs`` node lists in the dataset's numbering, ascending (Python lists); ``seed`` (N,) int64, dataset ids;
       ``item``      (N,) int64: seed index * per_seed + candidate, the number the candidate's draws are keyed by;
@@ -96,12 +117,19 @@ def discover(p, seeds, sizes=(8,), per_seed=16, target=None, restart=0.15, max_s
     Order: descending score, then ascending item; NaN last.  ``top_per_seed`` keeps that many of every seed, then ``top`` cuts
     the list (None: no cut).  Of a node set sampled more than once the smallest item stands for it.  The items are sampled and
     scored in chunks of at most ``max_variants``; ``sample_seed`` is the tape seed of the walks (default: the model's).  The
-    model's own splits stay as ``Predictor.prepare`` leaves them."""
+    model's own splits stay as ``Predictor.prepare`` leaves them.
+    ``max_overlap`` (None, or a Jaccard threshold in [0, 1]): the list is made diverse.  The candidates are ranked and
+    ``top_per_seed`` applied as above; of the first ``overlap_pool`` of them, in rank order, one is dropped when an earlier one that
+    is kept shares MORE than ``max_overlap`` of their joint nodes with it (ops.overlap_diverse: greedy, exact in integers), until
+    ``top`` are kept.  The result gains ``n_suppressed`` (int): the candidates of the pool that were dropped for it."""
     per_seed, E, max_variants = _positive(per_seed, 'per_seed'), _positive(draws, 'draws'), _positive(max_variants, 'max_variants')
     top = None if top is None else _positive(top, 'top')
     top_per_seed = None if top_per_seed is None else _positive(top_per_seed, 'top_per_seed')
     if batch_size is not None:
         batch_size = _positive(batch_size, 'batch_size')
+    if max_overlap is not None:
+        ops.overlap_threshold(max_overlap)
+        overlap_pool = _positive(overlap_pool, 'overlap_pool')
     m = p.model
     K, dev, g = m.num_classes, m.device, m.networkx_graph
     if target is not None:
@@ -149,7 +177,12 @@ def discover(p, seeds, sizes=(8,), per_seed=16, target=None, restart=0.15, max_s
         fresh = (~c['known']).nonzero().view(-1)
         c = {k: v[fresh] for k, v in c.items()}
     item = c['item'].cpu().numpy()
-    chosen = select(rank_order(c['score'].cpu().numpy(), item), item // per_seed, top, top_per_seed)
+    n_suppressed = None
+    if max_overlap is None:
+        chosen = select(rank_order(c['score'].cpu().numpy(), item), item // per_seed, top, top_per_seed)
+    else:
+        pool = select(rank_order(c['score'].cpu().numpy(), item), item // per_seed, overlap_pool, top_per_seed)
+        chosen, n_suppressed = diverse(g, seeds_t, walk, c, pool, max_overlap, top)
     sel = torch.from_numpy(chosen).to(dev)
     out = {k: v[sel] for k, v in c.items()}
     out['seed'] = seeds_t[out['item'] // per_seed].long() - 1
@@ -161,6 +194,8 @@ def discover(p, seeds, sizes=(8,), per_seed=16, target=None, restart=0.15, max_s
     nodes, lens = again.nodes.cpu().numpy(), again.lengths.cpu().numpy()
     out['subgraphs'] = [(nodes[i, :lens[i]] - 1).tolist() for i in range(nodes.shape[0])]
     out['n_sampled'], out['n_distinct'] = total, n_distinct
+    if n_suppressed is not None:
+        out['n_suppressed'] = n_suppressed
     return out
 
 
@@ -212,8 +247,11 @@ def parse_args(argv=None):
     ap.add_argument('-novel', action='store_true', help="leave out the dataset's own subgraphs")
     ap.add_argument('-batch_size', type=int, default=None, help='chunk the forward pass (default: one batch)')
     ap.add_argument('-sample_seed', type=int, default=None, help='tape seed of the walks (default: the run\'s seed)')
+    ap.add_argument('-max_overlap', type=float, default=None,
+                    help='drop a candidate that shares more than this Jaccard fraction of nodes with a better kept one (default: keep all)')
+    ap.add_argument('-overlap_pool', type=int, default=4096, help='ranked candidates that -max_overlap looks at (default 4096)')
     args = ap.parse_args(argv)
-    for name in ('per_seed', 'draws', 'top', 'top_per_seed', 'batch_size'):
+    for name in ('per_seed', 'draws', 'top', 'top_per_seed', 'batch_size', 'overlap_pool'):
         v = getattr(args, name)
         if v is not None and v <= 0:
             ap.error('-%s must be positive' % name)
@@ -221,6 +259,8 @@ def parse_args(argv=None):
         ap.error('-max_steps must not be negative')
     if not 0.0 <= args.restart <= 1.0:
         ap.error('-restart must be in [0, 1]')
+    if args.max_overlap is not None and not 0.0 <= args.max_overlap <= 1.0:
+        ap.error('-max_overlap must be in [0, 1]')
     try:
         args.sizes = parse_sizes(args.sizes)
     except ValueError as e:
@@ -245,7 +285,7 @@ def main(argv=None):
         target = p.label_names.index(args.target)
     res = p.discover(seeds, sizes=args.sizes, per_seed=args.per_seed, target=target, restart=args.restart, max_steps=args.max_steps,
                      draws=args.draws, top=args.top, top_per_seed=args.top_per_seed, novel=args.novel, batch_size=args.batch_size,
-                     sample_seed=args.sample_seed)
+                     sample_seed=args.sample_seed, max_overlap=args.max_overlap, overlap_pool=args.overlap_pool)
     with open(args.out, 'w') as f:
         f.write(HEADER + '\n')
         for line in lines_of(p, res):

@@ -51,6 +51,7 @@ class SubgraphIndex:
         self.metric = metric
         self.checkpoint = None if checkpoint is None else str(checkpoint)
         self._aux = None
+        self._bank = None
 
     def __len__(self):
         return self.embeddings.shape[0]
@@ -157,6 +158,42 @@ class SubgraphIndex:
         """Every row's nearest other rows (itself excluded): leave-one-out inspection of the index."""
         me = torch.arange(len(self), dtype=torch.int64, device=self.embeddings.device)
         return self.query_embeddings(self.embeddings, k, exclude=me)
+
+    # ------------------------------------------------------------------ node overlap -----
+    def _overlap_device(self):
+        E = self.embeddings
+        return E.device if E.is_cuda else torch.device('cuda', torch.cuda.current_device())
+
+    def _overlap_bank(self):
+        """The rows' node sets (ascending, repeats dropped) with their postings (ops.SetBank), built on first use and kept."""
+        if self._bank is None:
+            sets = ops.Ragged.from_lists([sorted(set(s)) for s in self.subgraphs], self._overlap_device())
+            self._bank = ops.SetBank(sets)
+        return self._bank
+
+    def overlaps(self, lists, k=10, measure='jaccard', exclude=None):
+        """Which rows share nodes with the requests (node lists in the index's numbering; repeats are dropped, a negative id is
+        an error, an empty request gives fillers) -> dict of device tensors: ``rows`` (Q, k) int64, best first, fillers -1;
+        ``inter`` (Q, k) int32, the shared nodes; ``touched`` (Q,) int32, the rows that share a node; ``scores`` (Q, k)
+        float32 of ``measure`` ('jaccard', 'containment', 'coverage', 'count').  The order is that of ops.overlap_topk: exact,
+        equal measures by the smaller row.  No model is needed."""
+        sets = []
+        for s in lists:
+            ids = sorted({int(v) for v in s})
+            if ids and (ids[0] < 0 or ids[-1] > 0x7fffffff):
+                raise ValueError('a request holds an id outside 0 .. 2^31 - 1')
+            sets.append(ids)
+        bank = self._overlap_bank()
+        q = ops.Ragged.from_lists(sets, bank.post_ptr.device)
+        rows, inter, touched, scores = ops.overlap_topk(q, bank, k, measure, exclude=exclude)
+        return {'rows': rows, 'inter': inter, 'touched': touched, 'scores': scores}
+
+    def self_overlaps(self, k=10, measure='jaccard'):
+        """Every row's best other rows by shared nodes, itself excluded (``touched`` still counts it): ``overlaps``."""
+        bank = self._overlap_bank()
+        me = torch.arange(len(self), dtype=torch.int64, device=bank.post_ptr.device)
+        rows, inter, touched, scores = ops.overlap_topk(bank.sets, bank, k, measure, exclude=me)
+        return {'rows': rows, 'inter': inter, 'touched': touched, 'scores': scores}
 
     def cluster(self, n_clusters, metric=None, medoids=5, **kmeans_args):
         """k-means of the index's rows on the device (ops.kmeans) -> ``subgnn_amd.cluster.Clustering``.  ``metric`` None: the

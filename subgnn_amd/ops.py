@@ -3719,6 +3719,9 @@ def __getattr__(name):
     if name == 'TOPK_MAX_K':                           # the largest k of topk_rows, asked of the library (sgnn_topk_max_k)
         value = globals()['TOPK_MAX_K'] = int(_lib.load().sgnn_topk_max_k())
         return value
+    if name == 'OVERLAP_MAX_K':                        # the largest k of overlap_topk (sgnn_overlap_max_k)
+        value = globals()['OVERLAP_MAX_K'] = int(_lib.load().sgnn_overlap_max_k())
+        return value
     raise AttributeError('module %r has no attribute %r' % (__name__, name))
 
 
@@ -3790,6 +3793,210 @@ def topk_rows(queries, bank, k, metric='cosine', exclude=None, splits=0, q_aux=N
                                  _ptr(b_aux) if N else None, _ptr(exclude), int(splits), _ptr(scores), _ptr(indices), _ptr(ws),
                                  nbytes, _stream()), 'sgnn_topk_rows')
     return scores, indices
+
+
+# ---------------------------------------------------------------------------------------
+# node overlap of ragged sets (csrc/overlap.hip)
+# ---------------------------------------------------------------------------------------
+OVERLAP_MEASURES = {'jaccard': 0, 'containment': 1, 'coverage': 2, 'count': 3}       # include/subgnn_hip.h SGNN_OVL_*
+OVERLAP_WS_BUDGET = 1 << 30            # bytes of counting tables in the workspace that one launch of overlap_topk may take
+
+
+def overlap_lds_max():
+    """Sets that walk up to this many postings count in LDS; beyond it in the workspace (sgnn_overlap_lds_max)."""
+    return int(_lib.load().sgnn_overlap_lds_max())
+
+
+def _check_sets(sets, name):
+    """Every set ascending, without repeats, ids >= 0 -- or ValueError.  One host round trip."""
+    _req(sets.ptr, torch.int64, name + '.ptr')
+    _req(sets.nodes, torch.int32, name + '.nodes')
+    total = sets.total if sets.n else 0
+    if total == 0:
+        return 0
+    v = sets.nodes[:total]
+    rising = v[1:] > v[:-1]
+    if sets.n > 1:
+        starts = sets.ptr[1:-1]
+        starts = starts[(starts > 0) & (starts < total)]
+        rising[starts - 1] = True                                                    # (a set's first entry answers to nothing)
+    if not bool((rising.all() & (v >= 0).all()).item()):
+        raise ValueError('%s: every set must be ascending, without repeats, of ids >= 0' % name)
+    return total
+
+
+def set_postings(sets, bank):
+    """The number P of postings of ``bank`` that every set of ``sets`` walks -> int64 (n), on the device."""
+    dev = sets.ptr.device
+    total = sets.total if sets.n else 0
+    if total == 0:
+        return torch.zeros(sets.n, dtype=torch.int64, device=dev)
+    v = sets.nodes[:total].long()
+    inside = (v >= 0) & (v <= bank.max_id)
+    vc = v.clamp(0, bank.max_id)
+    deg = torch.where(inside, bank.post_ptr[vc + 1] - bank.post_ptr[vc], torch.zeros_like(vc))
+    run = torch.zeros(total + 1, dtype=torch.int64, device=dev)
+    torch.cumsum(deg, 0, out=run[1:])
+    return (run[sets.ptr[1:]] - run[sets.ptr[:-1]]).contiguous()
+
+
+class SetBank:
+    """B node sets (a Ragged of ascending sets without repeats, ids >= 0) with what a search over them needs: ``sizes``
+    int64 (B) and the postings -- ``post_ptr`` int64 (max_id + 2), ``post_rows`` int32: for every node id the rows that hold it,
+    ascending (a stable sort of the entries by id, on the device)."""
+
+    def __init__(self, sets):
+        total = _check_sets(sets, 'sets')
+        dev = sets.ptr.device
+        self.sets, self.n = sets, sets.n
+        self.sizes = sets.lengths
+        if sets.n > 0x7fffffff:
+            raise ValueError('%d sets: more than 2^31 - 1' % sets.n)
+        if total == 0:
+            self.max_id = 0
+            self.post_ptr = torch.zeros(2, dtype=torch.int64, device=dev)
+            self.post_rows = torch.zeros(1, dtype=torch.int32, device=dev)
+            return
+        v = sets.nodes[:total].long()
+        row = torch.repeat_interleave(torch.arange(sets.n, dtype=torch.int32, device=dev), self.sizes, output_size=total)
+        self.max_id = int(v.max().item())
+        order = torch.sort(v, stable=True)[1]
+        self.post_rows = row[order].contiguous()
+        self.post_ptr = torch.zeros(self.max_id + 2, dtype=torch.int64, device=dev)
+        torch.cumsum(torch.bincount(v, minlength=self.max_id + 1), 0, out=self.post_ptr[1:])
+
+
+def _overlap_chunks(P, lds_max, max_entries, chunk_queries):
+    """Query ranges [lo, hi) whose workspace-tier postings stay within ``max_entries`` (a query beyond it goes alone) and that
+    hold at most ``chunk_queries`` queries."""
+    Q = P.shape[0]
+    big = np.where(P > lds_max, P, 0)
+    if chunk_queries is None and int(big.sum()) <= max_entries:
+        return [(0, Q)] if Q else []
+    run = np.concatenate([[0], np.cumsum(big)])
+    out, lo = [], 0
+    while lo < Q:
+        hi = int(np.searchsorted(run, run[lo] + max_entries, side='right')) - 1
+        hi = max(hi, lo + 1)
+        if chunk_queries is not None:
+            hi = min(hi, lo + chunk_queries)
+        out.append((lo, min(hi, Q)))
+        lo = min(hi, Q)
+    return out
+
+
+def overlap_scores(inter, q_sizes, b_sizes, measure):
+    """The measure of ``overlap_topk``'s results as numbers: the float64 quotient of the integer fraction, rounded to float32;
+    0 where ``inter`` is 0 (fillers).  ``q_sizes`` (Q, 1), ``b_sizes`` (Q, k) int64."""
+    i = inter.long()
+    den = {'jaccard': q_sizes + b_sizes - i, 'containment': q_sizes.expand_as(i), 'coverage': b_sizes, 'count': torch.ones_like(i)}[measure]
+    return torch.where(i > 0, i.double() / den.clamp_min(1).double(), torch.zeros_like(i, dtype=torch.float64)).float()
+
+
+def overlap_topk(queries, bank, k, measure='jaccard', exclude=None, chunk_queries=None, ws_budget=None):
+    """For every set of ``queries`` (a Ragged of ascending sets without repeats) the ``k`` rows of ``bank`` (a SetBank) that share
+    the most with it, among the rows that share at least one node -> (rows (Q, k) int64, fillers -1; inter (Q, k) int32, the
+    shared nodes; touched (Q,) int32, the bank rows that share a node, the excluded one included; scores (Q, k) float32), best
+    first.  ``measure``: 'jaccard' i / (|q| + |b| - i), 'containment' i / |q|, 'coverage' i / |b|, 'count' i.  The order compares
+    the fractions exactly (64-bit cross-multiplication), equal ones by the smaller row; the scores are formed afterwards (a
+    float64 division, then float32) and may tie where the order does not.  ``exclude`` (Q,) int64: a row each query skips, or
+    -1.  Sets that walk more than ``overlap_lds_max()`` postings count in a workspace of 48 bytes per posting: the queries go in
+    chunks that keep it under ``ws_budget`` bytes (default OVERLAP_WS_BUDGET; a query beyond it goes alone), or of
+    ``chunk_queries`` queries at most; the result does not depend on either.  One host round trip: the postings per query."""
+    max_k = globals().get('OVERLAP_MAX_K') or __getattr__('OVERLAP_MAX_K')
+    if measure not in OVERLAP_MEASURES:
+        raise ValueError('measure must be one of %s, got %r' % (sorted(OVERLAP_MEASURES), measure))
+    if not isinstance(k, int) or isinstance(k, bool) or k < 1 or k > max_k:
+        raise ValueError('k must be an integer in 1 .. %d (OVERLAP_MAX_K), got %r' % (max_k, k))
+    if not isinstance(bank, SetBank):
+        raise TypeError('bank must be an ops.SetBank')
+    if chunk_queries is not None:
+        chunk_queries = _count(chunk_queries, 'chunk_queries', 1)
+    budget = OVERLAP_WS_BUDGET if ws_budget is None else _count(ws_budget, 'ws_budget', 48)
+    _check_sets(queries, 'queries')
+    Q, dev = queries.n, queries.ptr.device
+    if dev != bank.post_ptr.device:
+        raise ValueError('queries and bank must be on one device')
+    if Q > 0x7fffffff:
+        raise ValueError('%d queries: more than 2^31 - 1' % Q)
+    if exclude is not None:
+        _req(exclude, torch.int64, 'exclude')
+        if exclude.shape != (Q,):
+            raise ValueError('exclude must have shape (%d,)' % Q)
+    lib = _lib.load()
+    rows = torch.empty((Q, k), dtype=torch.int64, device=dev)
+    inter = torch.empty((Q, k), dtype=torch.int32, device=dev)
+    touched = torch.empty(Q, dtype=torch.int32, device=dev)
+    lds_max = overlap_lds_max()
+    P = set_postings(queries, bank)
+    max_entries = min(budget // 48, 1 << 28)
+    P_host = P.cpu().numpy()                                                                # the one host round trip
+    chunks = _overlap_chunks(P_host, lds_max, max_entries, chunk_queries)
+    spare = torch.zeros(1, dtype=torch.int32, device=dev)                                   # (a tensor of no elements has no address)
+    q_nodes = queries.nodes if queries.nodes.numel() else spare
+    with torch.cuda.device(dev):
+        for lo, hi in chunks:
+            Pc = P[lo:hi]
+            big = torch.where(Pc > lds_max, Pc, torch.zeros_like(Pc))
+            off = (torch.cumsum(big, 0) - big).contiguous()
+            Ph = P_host[lo:hi]
+            entries = int(Ph[Ph > lds_max].sum())
+            if entries > (1 << 28):
+                raise ValueError('a query walks %d postings: more than 2^28' % entries)
+            nbytes = int(lib.sgnn_overlap_workspace_bytes(entries))
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev) if entries else None
+            check(lib.sgnn_overlap_topk(_ptr(queries.ptr[lo:hi + 1]), _ptr(q_nodes), hi - lo, _ptr(Pc), _ptr(off),
+                                        _ptr(bank.sets.ptr), bank.n, _ptr(bank.post_ptr), _ptr(bank.post_rows), bank.max_id,
+                                        _ptr(exclude[lo:hi]) if exclude is not None else None, k, OVERLAP_MEASURES[measure],
+                                        _ptr(ws), entries, nbytes if entries else 0, _ptr(rows[lo:hi]), _ptr(inter[lo:hi]),
+                                        _ptr(touched[lo:hi]), _stream()), 'sgnn_overlap_topk')
+    b_sizes = bank.sizes[rows.clamp_min(0)] if bank.n else torch.zeros_like(rows)
+    scores = overlap_scores(inter, queries.lengths.view(-1, 1), b_sizes, measure)
+    return rows, inter, touched, scores
+
+
+def overlap_threshold(max_overlap):
+    """A threshold in [0, 1] -> (numerator, denominator) of ``Fraction(t).limit_denominator(1 << 20)``."""
+    from fractions import Fraction
+    t = float(max_overlap)
+    if not 0.0 <= t <= 1.0:                                                                 # (NaN fails both)
+        raise ValueError('max_overlap must be in [0, 1], got %r' % (max_overlap,))
+    f = Fraction(t).limit_denominator(1 << 20)
+    return f.numerator, f.denominator
+
+
+def overlap_diverse(sets, max_overlap, top):
+    """Greedy selection among ``sets`` (a Ragged of ascending sets without repeats, in rank order): a set is accepted unless an
+    accepted set before it has a Jaccard overlap with it ABOVE ``max_overlap``; it stops at ``top`` accepted sets
+    (sgnn_overlap_diverse; include/subgnn_hip.h has the loop) -> (accepted (top,) int64, fillers -1; n, a one-element int32
+    tensor; suppressed_by (N,) int32: the accepted row that ruled a row out, or -1).  One launch; the threshold is the fraction
+    ``overlap_threshold(max_overlap)``."""
+    num, den = overlap_threshold(max_overlap)
+    top = _count(top, 'top', 1)
+    if top > 0x7fffffff:
+        raise ValueError('top: more than 2^31 - 1')
+    bank = SetBank(sets)
+    lib = _lib.load()
+    dev = sets.ptr.device
+    N = sets.n
+    accepted = torch.empty(top, dtype=torch.int64, device=dev)
+    n = torch.empty(1, dtype=torch.int32, device=dev)
+    by = torch.empty(N, dtype=torch.int32, device=dev)
+    P = set_postings(sets, bank)
+    lds_max = overlap_lds_max()
+    entries = int(P.max().item()) if N else 0
+    entries = entries if entries > lds_max else 0
+    if entries > (1 << 28):
+        raise ValueError('a set walks %d postings: more than 2^28' % entries)
+    nbytes = int(lib.sgnn_overlap_workspace_bytes(entries))
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev) if entries else None
+    spare = torch.zeros(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.sgnn_overlap_diverse(_ptr(sets.ptr), _ptr(sets.nodes if sets.nodes.numel() else spare), N, _ptr(P),
+                                       _ptr(bank.post_ptr), _ptr(bank.post_rows), bank.max_id, num, den, top, _ptr(ws), entries,
+                                       nbytes if entries else 0, _ptr(accepted), _ptr(n), _ptr(by) if N else None, _stream()),
+              'sgnn_overlap_diverse')
+    return accepted, n, by
 
 
 # ---------------------------------------------------------------------------------------

@@ -319,12 +319,14 @@ class Predictor:
                              draws=draws, batch_size=batch_size)
 
     def discover(self, seeds, sizes=(8,), per_seed=16, target=None, restart=0.15, max_steps=None, draws=1, top=100,
-                 top_per_seed=None, novel=False, batch_size=None, max_variants=65536, sample_seed=None):
+                 top_per_seed=None, novel=False, batch_size=None, max_variants=65536, sample_seed=None, max_overlap=None,
+                 overlap_pool=4096):
         """Connected candidate subgraphs sampled around seed nodes on the device, scored and ranked: ``discover.discover``."""
         from . import discover as _discover
         return _discover.discover(self, seeds, sizes=sizes, per_seed=per_seed, target=target, restart=restart, max_steps=max_steps,
                                   draws=draws, top=top, top_per_seed=top_per_seed, novel=novel, batch_size=batch_size,
-                                  max_variants=max_variants, sample_seed=sample_seed)
+                                  max_variants=max_variants, sample_seed=sample_seed, max_overlap=max_overlap,
+                                  overlap_pool=overlap_pool)
 
     def nearest(self, index, subgraphs, k=10):
         """The ``k`` rows of ``index`` (a neighbors.SubgraphIndex) nearest to each requested subgraph: ``index.query``."""
