@@ -13,13 +13,12 @@ and normalised mutual information against the first label string of each row.
 import argparse
 import json
 import os
-from pathlib import Path
 
 import numpy as np
 import torch
 
-from . import config, ops
-from .neighbors import LABEL_SEP, SPLITS, SubgraphIndex
+from . import cli, ops
+from .neighbors import LABEL_SEP, SPLITS
 
 METRICS = ('cosine', 'l2')
 INITS = ('k-means++', 'random')
@@ -216,11 +215,7 @@ def format_line(split, row, cluster, score, nodes, label_strings):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Cluster the subgraph embeddings of a checkpoint with k-means on the device')
-    ap.add_argument('-config_path', type=str, required=True)
-    ap.add_argument('-project_root', type=str, default=None, help='overrides subgnn_amd.config.PROJECT_ROOT')
-    ap.add_argument('-restoreModelPath', type=str, required=True, help='directory of a run: its hyperparams.json is used')
-    ap.add_argument('-restoreModelName', type=str, default=None,
-                    help='checkpoint file in -restoreModelPath (default: the best epoch*.ckpt, else last.ckpt)')
+    cli.add_run_arguments(ap)
     ap.add_argument('-n_clusters', type=int, required=True)
     ap.add_argument('-out', type=str, required=True, help='text file: a header, then %s per row' % HEADER.replace('\t', '<TAB>'))
     ap.add_argument('-summary', type=str, default=None, help='a .json file: per-cluster sizes, label counts, purity, medoids')
@@ -245,11 +240,8 @@ def parse_args(argv=None):
         ap.error('-n_init and -max_iter must be at least 1')
     if args.medoids < 0:
         ap.error('-medoids must not be negative')
-    args.splits = tuple(s for s in args.splits.split(',') if s)
-    if not args.splits or any(s not in SPLITS for s in args.splits):
-        ap.error('-splits takes a comma-separated list of %s' % ', '.join(SPLITS))
-    if args.batch_size is not None and args.batch_size <= 0:
-        ap.error('-batch_size must be positive')
+    args.splits = cli.parse_splits(ap, args.splits)
+    cli.require_positive(ap, args, ('batch_size',))
     if args.index is not None and not args.index.endswith('.npz'):
         ap.error('-index takes a .npz file name')
     if args.summary is not None and not args.summary.endswith('.json'):
@@ -262,33 +254,25 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    from .predict import Predictor, read_requests
-    from .train_config import read_json
-    if args.project_root:
-        config.PROJECT_ROOT = Path(args.project_root)
+    from .predict import read_requests
     requests = read_requests(args.subgraphs) if args.subgraphs is not None else None
-    p = Predictor.from_run(read_json(args.config_path), args.restoreModelPath, args.restoreModelName)
-    if args.index is not None and os.path.exists(args.index):
-        index = SubgraphIndex.load(args.index, p.model.device, predictor=p)
-        index.metric, index._aux = args.metric, None
-    else:
-        index = SubgraphIndex.from_predictor(p, args.splits, args.batch_size, args.metric)
-        if args.index is not None:
-            index.save(args.index)
+    p = cli.open_predictor(args)
+    index = cli.open_index(p, args)
     cl = index.cluster(args.n_clusters, metric=args.metric, medoids=args.medoids, init=args.init, n_init=args.n_init,
                        max_iter=args.max_iter, seed=args.seed)
     labels, scores = cl.labels.cpu().numpy(), cl.scores.cpu().numpy()
-    with open(args.out, 'w') as f:
-        f.write(HEADER + '\n')
+
+    def lines():                                                         # formed while -out is written: the rows, then the requests
         for j in range(len(index)):
             sp, row, nodes, ls = index.describe(j)
-            f.write(format_line(sp, row, labels[j], scores[j], nodes, ls) + '\n')
+            yield format_line(sp, row, labels[j], scores[j], nodes, ls)
         if requests is not None:
             res = p.predict(requests, batch_size=args.batch_size, return_embeddings=True)
             k, s = cl.assign(res['embeddings'].detach().float().contiguous())
             k, s = k.cpu().numpy(), s.cpu().numpy()
             for i, nodes in enumerate(requests):
-                f.write(format_line('request', i, k[i], s[i], nodes, []) + '\n')
+                yield format_line('request', i, k[i], s[i], nodes, [])
+    cli.write_lines(args.out, lines(), HEADER)
     if args.summary is not None:
         arguments = {k: (list(v) if isinstance(v, tuple) else v) for k, v in vars(args).items()}
         tmp = args.summary[:-5] + '.tmp%d.json' % os.getpid()

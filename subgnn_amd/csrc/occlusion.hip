@@ -38,15 +38,6 @@ __device__ __forceinline__ int occ_label(const int32_t* __restrict__ lab, int i)
     return (l >= 0 && l < i && lab[l] == l) ? l : i;
 }
 
-__device__ __forceinline__ uint64_t occ_wave_sum(uint64_t acc) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)acc, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(acc >> 32), d);
-        acc += ((uint64_t)hi << 32) | lo;
-    }
-    return acc;
-}
-
 template <int THREADS, int CAP, bool COMP, bool WRITE>
 __global__ __launch_bounds__(THREADS) void occ_kernel(const OccArgs a)
 {
@@ -107,7 +98,7 @@ __global__ __launch_bounds__(THREADS) void occ_kernel(const OccArgs a)
         if (WRITE) {
             uint64_t acc = 0;
             for (int i = tid; i < n; i += THREADS) acc += sgnn_mix64((uint64_t)(uint32_t)nd[i]);
-            acc = occ_wave_sum(acc);
+            acc = sgnn_wave_sum_u64(acc);
             if (lane == 0) atomicAdd(&s_tot, (unsigned long long)acc);
         }
         idt_sync<LDS>();

@@ -226,11 +226,7 @@ __global__ __launch_bounds__(256) void set_keys_kernel(const int64_t* __restrict
         const int64_t beg = set_ptr[s], n = set_ptr[s + 1] - beg;
         uint64_t acc = 0;
         for (int64_t i = lane; i < n; i += 64) acc += sgnn_mix64((uint64_t)(uint32_t)set_nodes[beg + i]);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)acc, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(acc >> 32), d);
-            acc += ((uint64_t)hi << 32) | lo;
-        }
+        acc = sgnn_wave_sum_u64(acc);
         if (lane == 0) out_keys[s] = sgnn_set_key_finish(acc, (uint64_t)(n > 0 ? n : 0));
     }
 }

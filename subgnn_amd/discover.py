@@ -19,13 +19,12 @@ sampled again from their item numbers afterwards.
 better candidate that is kept shares more than T of their joint nodes with it (Jaccard; ops.overlap_diverse, csrc/overlap.hip).
 """
 import argparse
-from pathlib import Path
 
 import numpy as np
 import torch
 
-from . import config, ops, tape
-from .suggest import _positive, read_pool
+from . import cli, ops, scoring, tape
+from .suggest import read_pool
 
 ALL = 'all'
 HEADER = 'rank\tseed\tscore\tscore_std\tprob\tsubgraph\tlabel\tknown'
@@ -122,14 +121,15 @@ def discover(p, seeds, sizes=(8,), per_seed=16, target=None, restart=0.15, max_s
     ``top_per_seed`` applied as above; of the first ``overlap_pool`` of them, in rank order, one is dropped when an earlier one that
     is kept shares MORE than ``max_overlap`` of their joint nodes with it (ops.overlap_diverse: greedy, exact in integers), until
     ``top`` are kept.  The result gains ``n_suppressed`` (int): the candidates of the pool that were dropped for it."""
-    per_seed, E, max_variants = _positive(per_seed, 'per_seed'), _positive(draws, 'draws'), _positive(max_variants, 'max_variants')
-    top = None if top is None else _positive(top, 'top')
-    top_per_seed = None if top_per_seed is None else _positive(top_per_seed, 'top_per_seed')
+    per_seed, E = scoring.positive(per_seed, 'per_seed'), scoring.positive(draws, 'draws')
+    max_variants = scoring.positive(max_variants, 'max_variants')
+    top = None if top is None else scoring.positive(top, 'top')
+    top_per_seed = None if top_per_seed is None else scoring.positive(top_per_seed, 'top_per_seed')
     if batch_size is not None:
-        batch_size = _positive(batch_size, 'batch_size')
+        batch_size = scoring.positive(batch_size, 'batch_size')
     if max_overlap is not None:
         ops.overlap_threshold(max_overlap)
-        overlap_pool = _positive(overlap_pool, 'overlap_pool')
+        overlap_pool = scoring.positive(overlap_pool, 'overlap_pool')
     m = p.model
     K, dev, g = m.num_classes, m.device, m.networkx_graph
     if target is not None:
@@ -156,19 +156,18 @@ def discover(p, seeds, sizes=(8,), per_seed=16, target=None, restart=0.15, max_s
         keys = res.keys[rows].contiguous()
         seen = torch.cat((seen, keys))
         packed = ops.Ragged.from_padded(res.nodes[rows].long())
-        chunk = ops.Ragged(packed.ptr, packed.nodes, max_len=int(res.lengths[rows].max()))
-        z = torch.stack([p.draw_logits(chunk, d, batch_size, sub_keys=keys) for d in range(E)])        # (E, n, K)
+        z = scoring.variant_logits(p, packed, keys, K, E, batch_size, rows.numel())                     # (E, n, K)
         mean = z.mean(dim=0)
         tgt = mean.argmax(dim=-1) if target is None else torch.full((rows.numel(),), int(target), dtype=torch.int64, device=dev)
-        pick = tgt.view(1, -1, 1).expand(E, -1, 1)
-        zt = z.gather(2, pick).squeeze(2)                                                               # (E, n)
+        zt, pt = scoring.target_columns(p, z, tgt)                                                      # (E, n)
+        score, score_std = scoring.mean_std(zt)
         kept['item'].append(rows + lo)
         kept['keys'].append(keys)
         kept['steps'].append(res.steps[rows])
         kept['logits'].append(mean)
-        kept['score'].append(zt.mean(dim=0))
-        kept['score_std'].append(zt.std(dim=0, unbiased=True) if E > 1 else torch.zeros_like(zt[0]))
-        kept['prob'].append(p._probabilities(z).gather(2, pick).squeeze(2).mean(dim=0))
+        kept['score'].append(score)
+        kept['score_std'].append(score_std)
+        kept['prob'].append(pt.mean(dim=0))
         kept['target'].append(tgt)
     c = {k: torch.cat(v) for k, v in kept.items()}
     c['known'] = torch.isin(c['keys'], known_sorted)
@@ -228,11 +227,7 @@ def parse_sizes(text):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Sample candidate subgraphs around seed nodes and rank them by a class, from a checkpoint')
-    ap.add_argument('-config_path', type=str, required=True)
-    ap.add_argument('-project_root', type=str, default=None, help='overrides subgnn_amd.config.PROJECT_ROOT')
-    ap.add_argument('-restoreModelPath', type=str, required=True, help='directory of a run: its hyperparams.json is used')
-    ap.add_argument('-restoreModelName', type=str, default=None,
-                    help='checkpoint file in -restoreModelPath (default: the best epoch*.ckpt, else last.ckpt)')
+    cli.add_run_arguments(ap)
     ap.add_argument('-seeds', type=str, required=True, help="a file of node ids (whitespace separated), or 'all': every node with an edge")
     ap.add_argument('-out', type=str, required=True, help='text file: a header, then ' + HEADER.replace('\t', '<TAB>'))
     ap.add_argument('-target', type=str, default=None,
@@ -251,10 +246,7 @@ def parse_args(argv=None):
                     help='drop a candidate that shares more than this Jaccard fraction of nodes with a better kept one (default: keep all)')
     ap.add_argument('-overlap_pool', type=int, default=4096, help='ranked candidates that -max_overlap looks at (default 4096)')
     args = ap.parse_args(argv)
-    for name in ('per_seed', 'draws', 'top', 'top_per_seed', 'batch_size', 'overlap_pool'):
-        v = getattr(args, name)
-        if v is not None and v <= 0:
-            ap.error('-%s must be positive' % name)
+    cli.require_positive(ap, args, ('per_seed', 'draws', 'top', 'top_per_seed', 'batch_size', 'overlap_pool'))
     if args.max_steps is not None and args.max_steps < 0:
         ap.error('-max_steps must not be negative')
     if not 0.0 <= args.restart <= 1.0:
@@ -272,24 +264,13 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    from .predict import Predictor
-    from .train_config import read_json
-    if args.project_root:
-        config.PROJECT_ROOT = Path(args.project_root)
     seeds = ALL if args.seeds == ALL else read_pool(args.seeds)
-    p = Predictor.from_run(read_json(args.config_path), args.restoreModelPath, args.restoreModelName)
-    target = None
-    if args.target is not None:
-        if p.label_names is None or args.target not in p.label_names:
-            raise SystemExit('-target: %r is no label of the dataset (%s)' % (args.target, p.label_names))
-        target = p.label_names.index(args.target)
-    res = p.discover(seeds, sizes=args.sizes, per_seed=args.per_seed, target=target, restart=args.restart, max_steps=args.max_steps,
-                     draws=args.draws, top=args.top, top_per_seed=args.top_per_seed, novel=args.novel, batch_size=args.batch_size,
-                     sample_seed=args.sample_seed, max_overlap=args.max_overlap, overlap_pool=args.overlap_pool)
-    with open(args.out, 'w') as f:
-        f.write(HEADER + '\n')
-        for line in lines_of(p, res):
-            f.write(line + '\n')
+    p = cli.open_predictor(args)
+    res = p.discover(seeds, sizes=args.sizes, per_seed=args.per_seed, target=cli.label_index(p, args.target), restart=args.restart,
+                     max_steps=args.max_steps, draws=args.draws, top=args.top, top_per_seed=args.top_per_seed, novel=args.novel,
+                     batch_size=args.batch_size, sample_seed=args.sample_seed, max_overlap=args.max_overlap,
+                     overlap_pool=args.overlap_pool)
+    cli.write_lines(args.out, lines_of(p, res), HEADER)
     return res
 
 

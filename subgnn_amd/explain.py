@@ -14,21 +14,13 @@ of that per-draw difference -- the anchor noise, reported instead of hidden.  A 
                                  [-unit node|component] [-target LABEL] [-draws E] [-top N] [-batch_size B]
 """
 import argparse
-from pathlib import Path
 
-import numpy as np
 import torch
 
-from . import config, ops
+from . import cli, ops, scoring
 
 UNITS = ('node', 'component')
 HEADER = 'request\tunit\tdelta_logit\tdelta_std\tdelta_prob\tlabel_without'
-
-
-def _positive(value, name):
-    if isinstance(value, bool) or int(value) != value or int(value) <= 0:
-        raise ValueError('%s must be a positive integer' % name)
-    return int(value)
 
 
 def component_members(sets, labels, n_units):
@@ -44,9 +36,7 @@ def component_members(sets, labels, n_units):
     unit_of_root = torch.cumsum((lab == pos).long(), 0) - 1            # units are numbered by set, then by root position
     unit = unit_of_root[start + lab]
     order = torch.sort(unit, stable=True).indices
-    ptr = torch.zeros(n_units + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(torch.bincount(unit, minlength=n_units), 0, out=ptr[1:])
-    return ptr, sets.nodes[:total].long()[order]
+    return ops.exclusive_scan(torch.bincount(unit, minlength=n_units)), sets.nodes[:total].long()[order]
 
 
 def explain(p, subgraphs, unit='node', target=None, draws=1, batch_size=None, max_variants=65536):
@@ -65,50 +55,32 @@ def explain(p, subgraphs, unit='node', target=None, draws=1, batch_size=None, ma
     number); ``batch_size`` chunks every forward pass.  The model's own splits stay as ``Predictor.prepare`` leaves them."""
     if unit not in UNITS:
         raise ValueError("unit must be 'node' or 'component', got %r" % (unit,))
-    E, max_variants = _positive(draws, 'draws'), _positive(max_variants, 'max_variants')
+    E, max_variants = scoring.positive(draws, 'draws'), scoring.positive(max_variants, 'max_variants')
     if batch_size is not None:
-        batch_size = _positive(batch_size, 'batch_size')
+        batch_size = scoring.positive(batch_size, 'batch_size')
     g = p.model.networkx_graph
     sets = p.request_sets(subgraphs)
     R, dev = sets.n, sets.ptr.device
     out, base = p._predict_sets(sets, batch_size, False, E)                           # base: (E, R, K)
     K = base.shape[2]
-    if target is None:
-        tgt = base.mean(dim=0).argmax(dim=-1)
-    else:
-        t = np.asarray(target)
-        if t.dtype.kind not in 'iu' or t.ndim > 1 or (t.ndim == 1 and t.shape[0] != R):
-            raise ValueError('target: an int or %d ints' % R)
-        t = np.broadcast_to(t.astype(np.int64), (R,)).copy()
-        if t.min() < 0 or t.max() >= K:
-            raise ValueError('target outside the classes 0 .. %d' % (K - 1))
-        tgt = torch.from_numpy(t).to(dev)
+    tgt = scoring.class_targets(target, base, R, K, dev)
 
+    # the variants: every request without one of its units
     labels = ops.cc_labels(g, sets) if unit == 'component' else None
     occ = ops.occlusion_sets(sets, unit, labels)
-    ptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(occ.units, 0, out=ptr[1:])
-    vptr = occ.sets.ptr.cpu().numpy()
-    U, V = int(ptr[-1].item()), occ.sets.n
+    ptr = ops.exclusive_scan(occ.units)
+    U = int(ptr[-1].item())
     out.update({'target': tgt, 'ptr': ptr})
     out['unit_nodes'] = sets.nodes[:U].long() if unit == 'node' else component_members(sets, labels, U)
 
-    var = torch.empty((E, V, K), dtype=torch.float32, device=dev)
-    for lo in range(0, V, max_variants):
-        hi = min(lo + max_variants, V)
-        a, b = int(vptr[lo]), int(vptr[hi])
-        chunk = ops.Ragged((occ.sets.ptr[lo:hi + 1] - a).contiguous(), occ.sets.nodes[a:b].contiguous(),
-                           max_len=int((vptr[lo + 1:hi + 1] - vptr[lo:hi]).max()))
-        keys = occ.keys[lo:hi].contiguous()
-        for d in range(E):
-            var[d, lo:hi] = p.draw_logits(chunk, d, batch_size, sub_keys=keys)
+    var = scoring.variant_logits(p, occ.sets, occ.keys, K, E, batch_size, max_variants)           # (E, V, K)
 
     # per-variant differences, reduced on the device and scattered to the variants' units
     parent = occ.parent.long()
     row = ptr[:-1][parent] + occ.unit.long()
-    t_base, t_var = tgt.view(1, R, 1).expand(E, R, 1), tgt[parent].view(1, V, 1).expand(E, V, 1)
-    d_logit = base.gather(2, t_base).squeeze(2)[:, parent] - var.gather(2, t_var).squeeze(2)                        # (E, V)
-    d_prob = p._probabilities(base).gather(2, t_base).squeeze(2)[:, parent] - p._probabilities(var).gather(2, t_var).squeeze(2)
+    z_base, p_base = scoring.target_columns(p, base, tgt)
+    z_var, p_var = scoring.target_columns(p, var, tgt[parent])
+    d_logit, d_std = scoring.mean_std(z_base[:, parent] - z_var)
 
     def per_unit(values, shape):
         full = torch.full(shape, float('nan'), dtype=torch.float32, device=dev)
@@ -117,9 +89,9 @@ def explain(p, subgraphs, unit='node', target=None, draws=1, batch_size=None, ma
 
     out['valid'] = torch.zeros(U, dtype=torch.bool, device=dev).index_fill_(0, row, True)
     out['variant_logits'] = per_unit(var.mean(dim=0), (U, K))
-    out['delta_logit'] = per_unit(d_logit.mean(dim=0), (U,))
-    out['delta_std'] = per_unit(d_logit.std(dim=0, unbiased=True) if E > 1 else torch.zeros(V, device=dev), (U,))
-    out['delta_prob'] = per_unit(d_prob.mean(dim=0), (U,))
+    out['delta_logit'] = per_unit(d_logit, (U,))
+    out['delta_std'] = per_unit(d_std, (U,))
+    out['delta_prob'] = per_unit((p_base[:, parent] - p_var).mean(dim=0), (U,))
     return out
 
 
@@ -148,27 +120,19 @@ def lines_of(p, res, top=None):
     else:
         ids = res['unit_nodes'].cpu().numpy()
         members = lambda u: ids[u:u + 1] - 1
-    multilabel = p.model.multilabel
     lines = []
     for r in range(ptr.shape[0] - 1):
         lo, hi = int(ptr[r]), int(ptr[r + 1])
         order = unit_order(dl[lo:hi], valid[lo:hi])
         for k in order[:top]:
             u = lo + k
-            names = []
-            if valid[u]:
-                names = p.names_of(torch.sigmoid(vl[u]) > 0.5 if multilabel else vl[u].argmax())
-            lines.append(format_line(r, members(u), dl[u], ds[u], dp[u], names))
+            lines.append(format_line(r, members(u), dl[u], ds[u], dp[u], cli.predicted_names(p, vl[u]) if valid[u] else []))
     return lines
 
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Leave-one-out attribution of predictions over nodes or components, from a checkpoint')
-    ap.add_argument('-config_path', type=str, required=True)
-    ap.add_argument('-project_root', type=str, default=None, help='overrides subgnn_amd.config.PROJECT_ROOT')
-    ap.add_argument('-restoreModelPath', type=str, required=True, help='directory of a run: its hyperparams.json is used')
-    ap.add_argument('-restoreModelName', type=str, default=None,
-                    help='checkpoint file in -restoreModelPath (default: the best epoch*.ckpt, else last.ckpt)')
+    cli.add_run_arguments(ap)
     ap.add_argument('-subgraphs', type=str, required=True, help='one subgraph per line: n1-n2-... (further columns ignored)')
     ap.add_argument('-out', type=str, required=True, help='text file: a header, then ' + HEADER.replace('\t', '<TAB>'))
     ap.add_argument('-unit', type=str, default='node', choices=UNITS, help='what is left out: single nodes or whole components')
@@ -178,10 +142,7 @@ def parse_args(argv=None):
     ap.add_argument('-top', type=int, default=None, help='at most this many lines per request')
     ap.add_argument('-batch_size', type=int, default=None, help='chunk the forward pass (default: one batch)')
     args = ap.parse_args(argv)
-    for name in ('draws', 'top', 'batch_size'):
-        v = getattr(args, name)
-        if v is not None and v <= 0:
-            ap.error('-%s must be positive' % name)
+    cli.require_positive(ap, args, ('draws', 'top', 'batch_size'))
     if args.out == args.subgraphs:
         ap.error('-subgraphs and -out must be different files')
     return args
@@ -189,22 +150,11 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    from .predict import Predictor, read_requests
-    from .train_config import read_json
-    if args.project_root:
-        config.PROJECT_ROOT = Path(args.project_root)
+    from .predict import read_requests
     requests = read_requests(args.subgraphs)
-    p = Predictor.from_run(read_json(args.config_path), args.restoreModelPath, args.restoreModelName)
-    target = None
-    if args.target is not None:
-        if p.label_names is None or args.target not in p.label_names:
-            raise SystemExit('-target: %r is no label of the dataset (%s)' % (args.target, p.label_names))
-        target = p.label_names.index(args.target)
-    res = p.explain(requests, unit=args.unit, target=target, draws=args.draws, batch_size=args.batch_size)
-    with open(args.out, 'w') as f:
-        f.write(HEADER + '\n')
-        for line in lines_of(p, res, args.top):
-            f.write(line + '\n')
+    p = cli.open_predictor(args)
+    res = p.explain(requests, unit=args.unit, target=cli.label_index(p, args.target), draws=args.draws, batch_size=args.batch_size)
+    cli.write_lines(args.out, lines_of(p, res, args.top), HEADER)
     return res
 
 

@@ -14,12 +14,11 @@ is a dataset subgraph then lands exactly on its row.
 """
 import argparse
 import os
-from pathlib import Path
 
 import numpy as np
 import torch
 
-from . import config, ops
+from . import cli, ops
 
 METRICS = ('cosine', 'dot', 'l2')
 SPLITS = ('train', 'val', 'test')
@@ -220,11 +219,7 @@ def format_line(request, rank, score, split, row, nodes, label_strings):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Nearest known subgraphs of requested subgraphs, by the embeddings of a checkpoint')
-    ap.add_argument('-config_path', type=str, required=True)
-    ap.add_argument('-project_root', type=str, default=None, help='overrides subgnn_amd.config.PROJECT_ROOT')
-    ap.add_argument('-restoreModelPath', type=str, required=True, help='directory of a run: its hyperparams.json is used')
-    ap.add_argument('-restoreModelName', type=str, default=None,
-                    help='checkpoint file in -restoreModelPath (default: the best epoch*.ckpt, else last.ckpt)')
+    cli.add_run_arguments(ap)
     ap.add_argument('-subgraphs', type=str, required=True, help='one subgraph per line: n1-n2-... (further columns ignored)')
     ap.add_argument('-out', type=str, required=True,
                     help='text file: request<TAB>rank<TAB>score<TAB>split<TAB>row<TAB>n1-n2-...<TAB>label[-label] per (request, rank)')
@@ -238,11 +233,8 @@ def parse_args(argv=None):
         ap.error('-k must be at least 1')
     if args.metric not in METRICS:
         ap.error('-metric must be one of %s' % ', '.join(METRICS))
-    args.splits = tuple(s for s in args.splits.split(',') if s)
-    if not args.splits or any(s not in SPLITS for s in args.splits):
-        ap.error('-splits takes a comma-separated list of %s' % ', '.join(SPLITS))
-    if args.batch_size is not None and args.batch_size <= 0:
-        ap.error('-batch_size must be positive')
+    args.splits = cli.parse_splits(ap, args.splits)
+    cli.require_positive(ap, args, ('batch_size',))
     if args.index is not None and not args.index.endswith('.npz'):
         ap.error('-index takes a .npz file name')
     if args.out == args.subgraphs or (args.index is not None and args.index in (args.out, args.subgraphs)):
@@ -252,29 +244,19 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    from .predict import Predictor, read_requests
-    from .train_config import read_json
-    if args.project_root:
-        config.PROJECT_ROOT = Path(args.project_root)
+    from .predict import read_requests
     requests = read_requests(args.subgraphs)
-    p = Predictor.from_run(read_json(args.config_path), args.restoreModelPath, args.restoreModelName)
-    if args.index is not None and os.path.exists(args.index):
-        index = SubgraphIndex.load(args.index, p.model.device, predictor=p)
-        index.metric, index._aux = args.metric, None
-    else:
-        index = SubgraphIndex.from_predictor(p, args.splits, args.batch_size, args.metric)
-        if args.index is not None:
-            index.save(args.index)
+    p = cli.open_predictor(args)
+    index = cli.open_index(p, args)
     res = index.query(p, requests, args.k, batch_size=args.batch_size)
     scores, indices = res['scores'].cpu().numpy(), res['indices'].cpu().numpy()
-    with open(args.out, 'w') as f:
+
+    def lines():                                                         # formed while -out is written
         for i in range(scores.shape[0]):
             for r in range(scores.shape[1]):
-                j = int(indices[i, r])
-                if j < 0:                                                # fewer than k rows in the index
-                    f.write(format_line(i, r, scores[i, r], '', -1, [], []) + '\n')
-                else:
-                    f.write(format_line(i, r, scores[i, r], *index.describe(j)) + '\n')
+                j = int(indices[i, r])                                   # (-1: fewer than k rows in the index)
+                yield format_line(i, r, scores[i, r], *(index.describe(j) if j >= 0 else ('', -1, [], [])))
+    cli.write_lines(args.out, lines())
     return res
 
 

@@ -858,6 +858,21 @@ def set_keys(sets):
     return out
 
 
+def exclusive_scan(counts):
+    """int64 counts (n) -> ``ptr`` (n + 1) int64 on their device: ptr[0] = 0, ptr[i + 1] = counts[0] + ... + counts[i]."""
+    ptr = torch.zeros(counts.numel() + 1, dtype=torch.int64, device=counts.device)
+    torch.cumsum(counts, 0, out=ptr[1:])
+    return ptr
+
+
+def _variant_buffers(V, T, dev):
+    """What the write phase of ``occlusion_sets`` / ``insertion_sets`` fills for V variants of T entries: the variants' ptr and
+    nodes (one entry at least: a tensor of no elements has no address), and per variant two int32 columns and the int64 key."""
+    return (torch.zeros(V + 1, dtype=torch.int64, device=dev), torch.empty(max(T, 1), dtype=torch.int32, device=dev),
+            torch.empty(V, dtype=torch.int32, device=dev), torch.empty(V, dtype=torch.int32, device=dev),
+            torch.empty(V, dtype=torch.int64, device=dev))
+
+
 OCCLUSION_MODES = {'node': 0, 'component': 1}          # include/subgnn_hip.h SGNN_OCC_*
 Occlusion = collections.namedtuple('Occlusion', 'sets parent unit keys units variants')
 
@@ -899,16 +914,9 @@ def occlusion_sets(sets, unit='node', labels=None):
     head = (_ptr(sets.ptr), _ptr(sets.nodes), n, max_len, mode, _ptr(labels) if mode == 1 else None)
     check(lib.sgnn_occlusion_count(*head, _ptr(units), _ptr(variants), _ptr(lens), total, _ptr(ws), wsb, _stream()),
           'sgnn_occlusion_count')
-    var_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(variants, 0, out=var_ptr[1:])
-    len_scan = torch.zeros(lens.numel() + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(lens, 0, out=len_scan[1:])
+    var_ptr, len_scan = exclusive_scan(variants), exclusive_scan(lens)
     V, T = torch.stack((var_ptr[-1], len_scan[-1])).tolist()                  # the one host round trip
-    out_ptr = torch.zeros(V + 1, dtype=torch.int64, device=dev)
-    out_nodes = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
-    parent = torch.empty(V, dtype=torch.int32, device=dev)
-    rank = torch.empty(V, dtype=torch.int32, device=dev)
-    keys = torch.empty(V, dtype=torch.int64, device=dev)
+    out_ptr, out_nodes, parent, rank, keys = _variant_buffers(V, T, dev)
     check(lib.sgnn_occlusion_write(*head, _ptr(var_ptr), _ptr(len_scan), V, _ptr(out_ptr), _ptr(out_nodes), _ptr(parent),
                                    _ptr(rank), _ptr(keys), total, _ptr(ws), wsb, _stream()), 'sgnn_occlusion_write')
     return Occlusion(Ragged(out_ptr, out_nodes, max_len=max(max_len - 1, 0)), parent, rank, keys, units, variants)
@@ -940,18 +948,11 @@ def insertion_sets(sets, candidates, shared=False):
     head = (_ptr(sets.ptr), _ptr(nodes), n, max_len, _ptr(candidates.ptr), _ptr(cand), 1 if shared else 0)
     variants = torch.zeros(n, dtype=torch.int64, device=dev)
     check(lib.sgnn_insertion_count(*head, _ptr(variants), _stream()), 'sgnn_insertion_count')
-    var_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(variants, 0, out=var_ptr[1:])
-    entry_ptr = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(variants * (sets.lengths + 1), 0, out=entry_ptr[1:])
+    var_ptr, entry_ptr = exclusive_scan(variants), exclusive_scan(variants * (sets.lengths + 1))
     V, T = torch.stack((var_ptr[-1], entry_ptr[-1])).tolist()                 # the one host round trip
     if V > 0x7fffffff:
         raise ValueError('%d variants: more than 2^31 - 1 (send fewer sets or candidates at a time)' % V)
-    out_ptr = torch.zeros(V + 1, dtype=torch.int64, device=dev)
-    out_nodes = torch.empty(max(T, 1), dtype=torch.int32, device=dev)
-    parent = torch.empty(V, dtype=torch.int32, device=dev)
-    inserted = torch.empty(V, dtype=torch.int32, device=dev)
-    keys = torch.empty(V, dtype=torch.int64, device=dev)
+    out_ptr, out_nodes, parent, inserted, keys = _variant_buffers(V, T, dev)
     check(lib.sgnn_insertion_write(*head, _ptr(var_ptr), _ptr(entry_ptr), V, _ptr(out_ptr), _ptr(out_nodes), _ptr(parent),
                                    _ptr(inserted), _ptr(keys), _stream()), 'sgnn_insertion_write')
     return Insertion(Ragged(out_ptr, out_nodes, max_len=max_len + 1), parent, inserted, keys, variants)

@@ -19,7 +19,7 @@ import os
 import numpy as np
 import torch
 
-from . import ops
+from . import cli, ops
 from .neighbors import LABEL_SEP, SPLITS, SubgraphIndex
 
 MEASURES = tuple(ops.OVERLAP_MEASURES)
@@ -145,10 +145,7 @@ def main(argv=None):
         res = index.overlaps(read_requests(args.subgraphs), args.k, args.measure)
     else:
         res = index.self_overlaps(args.k, args.measure)
-    with open(args.out, 'w') as f:
-        f.write(HEADER + '\n')
-        for line in lines_of(index, res):
-            f.write(line + '\n')
+    cli.write_lines(args.out, lines_of(index, res), HEADER)
     if args.summary is not None:
         with open(args.summary, 'w') as f:
             json.dump({'splits': list(args.splits), 'pairs': split_summary(index, args.splits)}, f, indent=1)

@@ -27,7 +27,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import checkpoint, config, gamma, hotpath, ops, subgraph_utils, tape
+from . import checkpoint, cli, config, gamma, hotpath, ops, subgraph_utils, tape
 
 SPLIT = 'predict'
 
@@ -361,18 +361,13 @@ def format_line(nodes, label_strings, probabilities):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Predict labels (and embeddings) of subgraphs outside the dataset from a checkpoint')
-    ap.add_argument('-config_path', type=str, required=True)
-    ap.add_argument('-project_root', type=str, default=None, help='overrides subgnn_amd.config.PROJECT_ROOT')
-    ap.add_argument('-restoreModelPath', type=str, required=True, help='directory of a run: its hyperparams.json is used')
-    ap.add_argument('-restoreModelName', type=str, default=None,
-                    help='checkpoint file in -restoreModelPath (default: the best epoch*.ckpt, else last.ckpt)')
+    cli.add_run_arguments(ap)
     ap.add_argument('-subgraphs', type=str, required=True, help='one subgraph per line: n1-n2-... (further columns ignored)')
     ap.add_argument('-out', type=str, required=True, help='text file: n1-n2-...<TAB>label[-label]<TAB>p_1,...,p_K per request')
     ap.add_argument('-embeddings', type=str, default=None, help='write the (R, H) subgraph embeddings to this .npy file')
     ap.add_argument('-batch_size', type=int, default=None, help='chunk the forward pass (default: one batch)')
     args = ap.parse_args(argv)
-    if args.batch_size is not None and args.batch_size <= 0:
-        ap.error('-batch_size must be positive')
+    cli.require_positive(ap, args, ('batch_size',))
     if args.embeddings is not None and not args.embeddings.endswith('.npy'):
         ap.error('-embeddings takes a .npy file name')
     if args.out == args.subgraphs or (args.embeddings is not None and args.embeddings in (args.out, args.subgraphs)):
@@ -382,16 +377,12 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    from .train_config import read_json
-    if args.project_root:
-        config.PROJECT_ROOT = Path(args.project_root)
     requests = read_requests(args.subgraphs)
-    p = Predictor.from_run(read_json(args.config_path), args.restoreModelPath, args.restoreModelName)
+    p = cli.open_predictor(args)
     res = p.predict(requests, batch_size=args.batch_size, return_embeddings=args.embeddings is not None)
     prob, labels = res['probabilities'].cpu().numpy(), res['labels'].cpu()
-    with open(args.out, 'w') as f:
-        for i, nodes in enumerate(res['subgraphs']):
-            f.write(format_line([n - 1 for n in nodes], p.names_of(labels[i]), prob[i]) + '\n')
+    cli.write_lines(args.out, (format_line([n - 1 for n in nodes], p.names_of(labels[i]), prob[i])
+                               for i, nodes in enumerate(res['subgraphs'])))
     if args.embeddings is not None:
         np.save(args.embeddings, res['embeddings'].cpu().numpy())
     return res

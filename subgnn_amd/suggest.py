@@ -15,35 +15,15 @@ of that per-draw difference.  Every candidate has a variant.  ``grow`` adds the 
                                  [-grow STEPS [-min_gain G]]
 """
 import argparse
-from pathlib import Path
 
 import numpy as np
 import torch
 
-from . import config, ops
+from . import cli, ops, scoring
 
 BORDER = 'border'
 HEADER = 'request\tcandidate\tgain_logit\tgain_std\tgain_prob\tlabel_with'
 GROW_HEADER = 'request\tstep\tadded\tgain_logit\tgain_std\tlabel_after'
-
-
-def _positive(value, name):
-    if isinstance(value, bool) or int(value) != value or int(value) <= 0:
-        raise ValueError('%s must be a positive integer' % name)
-    return int(value)
-
-
-def _targets(target, base, R, K, dev):
-    """The class per request: the argmax of the mean base logits, or the given int or sequence of R ints (as ``explain``)."""
-    if target is None:
-        return base.mean(dim=0).argmax(dim=-1)
-    t = np.asarray(target)
-    if t.dtype.kind not in 'iu' or t.ndim > 1 or (t.ndim == 1 and t.shape[0] != R):
-        raise ValueError('target: an int or %d ints' % R)
-    t = np.broadcast_to(t.astype(np.int64), (R,)).copy()
-    if t.min() < 0 or t.max() >= K:
-        raise ValueError('target outside the classes 0 .. %d' % (K - 1))
-    return torch.from_numpy(t).to(dev)
 
 
 def map_pool(p, candidates):
@@ -92,43 +72,30 @@ def suggest(p, subgraphs, candidates=BORDER, hops=1, target=None, draws=1, batch
     own splits stay as ``Predictor.prepare`` leaves them."""
     if isinstance(candidates, str) and candidates != BORDER:
         raise ValueError("candidates must be 'border' or a sequence of node ids, got %r" % (candidates,))
-    hops = _positive(hops, 'hops')
-    E, max_variants = _positive(draws, 'draws'), _positive(max_variants, 'max_variants')
+    hops = scoring.positive(hops, 'hops')
+    E, max_variants = scoring.positive(draws, 'draws'), scoring.positive(max_variants, 'max_variants')
     if batch_size is not None:
-        batch_size = _positive(batch_size, 'batch_size')
+        batch_size = scoring.positive(batch_size, 'batch_size')
     sets = p.request_sets(subgraphs)
     R, dev = sets.n, sets.ptr.device
     cand, shared = candidate_rows(p, sets, candidates, hops)
     out, base = p._predict_sets(sets, batch_size, False, E)                           # base: (E, R, K)
     K = base.shape[2]
-    tgt = _targets(target, base, R, K, dev)
+    tgt = scoring.class_targets(target, base, R, K, dev)
 
+    # the variants: every request with one of its candidates
     ins = ops.insertion_sets(sets, cand, shared)
-    ptr = torch.zeros(R + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(ins.variants, 0, out=ptr[1:])
-    vptr = ins.sets.ptr.cpu().numpy()
-    V = ins.sets.n
-    out.update({'target': tgt, 'ptr': ptr, 'candidate_nodes': ins.cand.long()})
+    out.update({'target': tgt, 'ptr': ops.exclusive_scan(ins.variants), 'candidate_nodes': ins.cand.long()})
 
-    var = torch.empty((E, V, K), dtype=torch.float32, device=dev)
-    for lo in range(0, V, max_variants):
-        hi = min(lo + max_variants, V)
-        a, b = int(vptr[lo]), int(vptr[hi])
-        chunk = ops.Ragged((ins.sets.ptr[lo:hi + 1] - a).contiguous(), ins.sets.nodes[a:b].contiguous(),
-                           max_len=int((vptr[lo + 1:hi + 1] - vptr[lo:hi]).max()))
-        keys = ins.keys[lo:hi].contiguous()
-        for d in range(E):
-            var[d, lo:hi] = p.draw_logits(chunk, d, batch_size, sub_keys=keys)
+    var = scoring.variant_logits(p, ins.sets, ins.keys, K, E, batch_size, max_variants)           # (E, V, K)
 
     # per-variant differences, reduced on the device (the variants are the candidates, in order)
     parent = ins.parent.long()
-    t_base, t_var = tgt.view(1, R, 1).expand(E, R, 1), tgt[parent].view(1, V, 1).expand(E, V, 1)
-    g_logit = var.gather(2, t_var).squeeze(2) - base.gather(2, t_base).squeeze(2)[:, parent]                        # (E, V)
-    g_prob = p._probabilities(var).gather(2, t_var).squeeze(2) - p._probabilities(base).gather(2, t_base).squeeze(2)[:, parent]
+    z_base, p_base = scoring.target_columns(p, base, tgt)
+    z_var, p_var = scoring.target_columns(p, var, tgt[parent])
     out['variant_logits'] = var.mean(dim=0)
-    out['gain_logit'] = g_logit.mean(dim=0)
-    out['gain_std'] = g_logit.std(dim=0, unbiased=True) if E > 1 and V > 0 else torch.zeros(V, dtype=torch.float32, device=dev)
-    out['gain_prob'] = g_prob.mean(dim=0)
+    out['gain_logit'], out['gain_std'] = scoring.mean_std(z_var - z_base[:, parent])
+    out['gain_prob'] = (p_var - p_base[:, parent]).mean(dim=0)
     return out
 
 
@@ -158,7 +125,7 @@ def grow(p, subgraphs, steps, target=None, min_gain=0.0, candidates=BORDER, hops
       ``step_logits`` the (K,) logits of the request after each step (the chosen variant's, mean over draws);
       ``subgraphs`` the final sets in the dataset's numbering, ascending; ``logits`` (R, K): ``predict``'s of those;
       ``target``    (R,) int64."""
-    steps = _positive(steps, 'steps')
+    steps = scoring.positive(steps, 'steps')
     min_gain = float(min_gain)
     R = len(subgraphs)
     current = [list(s) for s in subgraphs]
@@ -216,10 +183,6 @@ def format_grow_line(request, step, added, gain_logit, gain_std, label_strings):
                                        '-'.join(label_strings))
 
 
-def _names(p, logits_row):
-    return p.names_of(torch.sigmoid(logits_row) > 0.5 if p.model.multilabel else logits_row.argmax())
-
-
 def lines_of(p, res, top=None):
     """The output lines of a ``suggest`` result (without the header)."""
     ptr = res['ptr'].cpu().numpy()
@@ -231,13 +194,13 @@ def lines_of(p, res, top=None):
         lo, hi = int(ptr[r]), int(ptr[r + 1])
         for k in candidate_order(gl[lo:hi], ids[lo:hi])[:top]:
             u = lo + k
-            lines.append(format_line(r, ids[u] - 1, gl[u], gs[u], gp[u], _names(p, vl[u])))
+            lines.append(format_line(r, ids[u] - 1, gl[u], gs[u], gp[u], cli.predicted_names(p, vl[u])))
     return lines
 
 
 def grow_lines_of(p, res):
     """The output lines of a ``grow`` result (without the header): one per request and accepted step."""
-    return [format_grow_line(r, k, v, res['gain_logit'][r][k], res['gain_std'][r][k], _names(p, res['step_logits'][r][k]))
+    return [format_grow_line(r, k, v, res['gain_logit'][r][k], res['gain_std'][r][k], cli.predicted_names(p, res['step_logits'][r][k]))
             for r, steps in enumerate(res['added']) for k, v in enumerate(steps)]
 
 
@@ -255,11 +218,7 @@ def read_pool(path):
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='Score the nodes a subgraph could gain (or grow it greedily), from a checkpoint')
-    ap.add_argument('-config_path', type=str, required=True)
-    ap.add_argument('-project_root', type=str, default=None, help='overrides subgnn_amd.config.PROJECT_ROOT')
-    ap.add_argument('-restoreModelPath', type=str, required=True, help='directory of a run: its hyperparams.json is used')
-    ap.add_argument('-restoreModelName', type=str, default=None,
-                    help='checkpoint file in -restoreModelPath (default: the best epoch*.ckpt, else last.ckpt)')
+    cli.add_run_arguments(ap)
     ap.add_argument('-subgraphs', type=str, required=True, help='one subgraph per line: n1-n2-... (further columns ignored)')
     ap.add_argument('-out', type=str, required=True, help='text file: a header, then ' + HEADER.replace('\t', '<TAB>') +
                     ' (with -grow: ' + GROW_HEADER.replace('\t', '<TAB>') + ')')
@@ -274,10 +233,7 @@ def parse_args(argv=None):
     ap.add_argument('-grow', type=int, default=None, metavar='STEPS', help='add the best candidate, for up to STEPS rounds')
     ap.add_argument('-min_gain', type=float, default=None, help='with -grow: a candidate is taken if its gain_logit is above this (default 0)')
     args = ap.parse_args(argv)
-    for name in ('hops', 'draws', 'top', 'batch_size', 'grow'):
-        v = getattr(args, name)
-        if v is not None and v <= 0:
-            ap.error('-%s must be positive' % name)
+    cli.require_positive(ap, args, ('hops', 'draws', 'top', 'batch_size', 'grow'))
     if args.grow is None and args.min_gain is not None:
         ap.error('-min_gain applies to -grow')
     if args.grow is not None and args.top is not None:
@@ -293,18 +249,11 @@ def parse_args(argv=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    from .predict import Predictor, read_requests
-    from .train_config import read_json
-    if args.project_root:
-        config.PROJECT_ROOT = Path(args.project_root)
+    from .predict import read_requests
     requests = read_requests(args.subgraphs)
     pool = BORDER if args.candidates == BORDER else read_pool(args.candidates)
-    p = Predictor.from_run(read_json(args.config_path), args.restoreModelPath, args.restoreModelName)
-    target = None
-    if args.target is not None:
-        if p.label_names is None or args.target not in p.label_names:
-            raise SystemExit('-target: %r is no label of the dataset (%s)' % (args.target, p.label_names))
-        target = p.label_names.index(args.target)
+    p = cli.open_predictor(args)
+    target = cli.label_index(p, args.target)
     if args.grow is not None:
         res = p.grow(requests, args.grow, target=target, min_gain=args.min_gain, candidates=pool, hops=args.hops,
                      draws=args.draws, batch_size=args.batch_size)
@@ -312,10 +261,7 @@ def main(argv=None):
     else:
         res = p.suggest(requests, candidates=pool, hops=args.hops, target=target, draws=args.draws, batch_size=args.batch_size)
         header, lines = HEADER, lines_of(p, res, args.top)
-    with open(args.out, 'w') as f:
-        f.write(header + '\n')
-        for line in lines:
-            f.write(line + '\n')
+    cli.write_lines(args.out, lines, header)
     return res
 
 
